@@ -484,6 +484,24 @@ def timed_steps(step_fn, steps, warmup, world, rank, device):
     return elapsed, lat, img, allz
 
 
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+
+
+def dump_bytes(latent, world):
+    """bytes `--dump-outputs` writes over all ranks: per rank the latent (4 x latent^2) and the image (3 x (8 latent)^2), float32"""
+    return world * 4 * (4 * latent * latent + 3 * (8 * latent) ** 2)
+
+
+def dump_outputs(out_dir, arrays):
+    """`--dump-outputs DIR`: what the timed path returned in its last step, as DIR/<name>.npy in float32, so that two builds
+    can be compared output for output (inputs, weights and the global generators are seeded: the same arguments give the
+    same inputs)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, f'{name}.npy'), t.detach().float().cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -499,7 +517,15 @@ def main():
                     help='measure HBM bytes per launch with rocprofv3 PMC passes and write profiles/traffic_r06.json (then exit)')
     ap.add_argument('--traffic-out', default=None, help='second copy of the --traffic-pass JSON (e.g. under gpurun_out/)')
     ap.add_argument('--cpu-baseline-only', action='store_true', help='time only the CPU comparator (no GPU needed) and exit')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write the latent and the image of the last timed step as DIR/<name>.npy (float32)')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    if args.dump_outputs:
+        n_dump = dump_bytes(WORKLOADS[args.workload]['latent'], args.gpus)
+        if n_dump > DUMP_LIMIT_BYTES:
+            ap.error(f'--dump-outputs would write {n_dump} bytes at --gpus {args.gpus}, more than {DUMP_LIMIT_BYTES}')
     if args.traffic_pass:
         return traffic_pass(also=args.traffic_out)
     if args.cpu_baseline_only:
@@ -546,8 +572,14 @@ def main():
     else:
         step_fn = lambda step: one_image_img2img(sampler, vae, *inputs_for(step), steps=wl['steps'],
                                                  strength=wl['strength'], scale=wl['scale'])
+    # img2img draws noise from the global generators (the posterior sample of encode_first_stage, stochastic_encode): seeded
+    # per rank, so that the same arguments give the same outputs
+    torch.manual_seed(rank)
     elapsed, lat, img, allz = timed_steps(step_fn, args.steps, args.warmup, world, rank, device)
     assert torch.isfinite(img).all() and torch.isfinite(allz).all()
+    if args.dump_outputs:           # every rank its own image; names carry the rank when there is more than one
+        sfx = f'_rank{rank}' if world > 1 else ''
+        dump_outputs(args.dump_outputs, {'latent' + sfx: lat, 'image' + sfx: img})
     ranks = sd_dist.ranks_seen(device)          # (a collective: every rank calls it)
     assert ranks == world, f'{ranks} ranks answered, WORLD_SIZE = {world}'
 

@@ -198,24 +198,27 @@ def test_ldm_shim_schedule_equals_oracle():
     assert ld.num_timesteps == 1000 and float(ld.alphas_cumprod_prev[0]) == 1.0
 
 
-@pytest.mark.skipif(not os.path.isdir('/root/reference/ldm'), reason='reference checkout only exists in the build container')
-def test_plugin_seam_against_the_real_reference():
-    """The reference's own plugin mechanism (`instantiate_from_config`, ldm/util.py:78-93) resolves the patched
-    `unet_config.target` to UNetModelHIP with the yaml's params, and the resulting state_dict keys / shapes equal the
-    real reference UNetModel's (built on the meta device), so `load_state_dict(sd, strict=False)` fills everything."""
-    import sys
-    import yaml
-    sys.path.insert(0, '/root/reference')
+def test_plugin_seam_matches_the_recorded_reference(golden_dir):
+    """The reference's plugin mechanism (`instantiate_from_config`, ldm/util.py:78-93: import `target`, call it with `params`;
+    restated below) resolves the patched `unet_config.target` to UNetModelHIP with the yaml's params, and the resulting
+    state_dict keys / shapes equal the reference UNetModel's, so `load_state_dict(sd, strict=False)` fills everything.  The
+    yaml's nodes and the reference modules' keys / shapes are recorded from the reference by oracle/make_golden_seam.py
+    (tests/golden/plugin_seam.json)."""
+    import importlib
+    import json
     sys.path.insert(0, os.path.join(ROOT, 'tools'))
     import run_reference_script as launcher
-    launcher.install_stubs(have_gpu=True, offline_stubs=True)   # stand-ins only; nn.Module.cuda stays untouched
-    from ldm.util import instantiate_from_config
-    cfg = yaml.safe_load(open('/root/reference/configs/stable-diffusion/v1-inference.yaml'))
-    unet_cfg = cfg['model']['params']['unet_config']
+    # FrozenCLIPEmbedderHIP() loads its tokenizer with from_pretrained: where that finds nothing offline, a seeded stand-in
+    # (only names and shapes are checked here)
+    launcher.install_stubs(have_gpu=True, offline_stubs=True)
+    seam = json.load(open(os.path.join(golden_dir, 'plugin_seam.json')))
+
+    def instantiate_from_config(config):
+        module, cls = config['target'].rsplit('.', 1)
+        return getattr(importlib.import_module(module), cls)(**config.get('params', dict()))
+    unet_cfg = seam['unet_config']
     assert unet_cfg['target'] == 'ldm.modules.diffusionmodules.openaimodel.UNetModel'
-    with torch.device('meta'):
-        ref = instantiate_from_config(unet_cfg)
-    ref_keys = {k: tuple(v.shape) for k, v in ref.state_dict().items()}
+    ref_keys = {k: tuple(s) for k, s in seam['unet_state'].items()}
     unet_cfg = dict(unet_cfg, target='stable_diffusion_amd.unet.UNetModelHIP')
     with torch.device('meta'):
         mine = instantiate_from_config(unet_cfg)
@@ -224,14 +227,10 @@ def test_plugin_seam_against_the_real_reference():
     assert {k: tuple(v.shape) for k, v in mine.state_dict().items()} == ref_keys
     assert len(ref_keys) == 686
     # first stage: same mechanism (LatentDiffusion.instantiate_first_stage, ddpm.py:502-507); the reference class itself
-    # needs pytorch_lightning + taming (stand-ins installed above), its Encoder / Decoder are the real ones
-    fs_cfg = cfg['model']['params']['first_stage_config']
+    # needs pytorch_lightning + taming, its Encoder / Decoder are the real ones
+    fs_cfg = seam['first_stage_config']
     assert fs_cfg['target'] == 'ldm.models.autoencoder.AutoencoderKL'
-    import contextlib
-    import io
-    with torch.device('meta'), contextlib.redirect_stdout(io.StringIO()):
-        ref_vae = instantiate_from_config(fs_cfg)
-    ref_keys = {k: tuple(v.shape) for k, v in ref_vae.state_dict().items() if not k.startswith('loss.')}
+    ref_keys = {k: tuple(s) for k, s in seam['first_stage_state'].items()}
     with torch.device('meta'):
         mine = instantiate_from_config(dict(fs_cfg, target='stable_diffusion_amd.vae.AutoencoderKLHIP'))
     from stable_diffusion_amd import AutoencoderKLHIP
@@ -240,7 +239,7 @@ def test_plugin_seam_against_the_real_reference():
     assert len(ref_keys) == 248
     # cond stage: `instantiate_from_config(cond_stage_config)` (ddpm.py:509-520); the yaml passes no params, the class
     # defaults are the reference's (version / device / max_length, modules.py:139)
-    cs_cfg = cfg['model']['params']['cond_stage_config']
+    cs_cfg = seam['cond_stage_config']
     assert cs_cfg['target'] == 'ldm.modules.encoders.modules.FrozenCLIPEmbedder'
     with torch.device('meta'):
         mine = instantiate_from_config(dict(cs_cfg, target='stable_diffusion_amd.clip.FrozenCLIPEmbedderHIP'))
@@ -291,6 +290,28 @@ def test_cpu_baseline_kind_follows_the_visibility_of_the_reference(monkeypatch):
     assert bench.reference_unet() == (None, None)       # neither the sources nor the bytecode bundle: the oracle port is timed
     rec = json.load(open(os.path.join(ROOT, 'profiles', 'cpu_baseline_reference_r02.json')))['cpu_baseline']
     assert rec['kind'] == 'reference' and rec['unit'] == 'images/s' and 0 < rec['value'] < 0.1
+
+
+def test_bench_dump_outputs_writes_float32_arrays_within_the_bound(tmp_path, monkeypatch):
+    """`bench.py --dump-outputs DIR`: every array the timed path returned becomes DIR/<name>.npy in float32 with its values
+    unchanged; a run that would write more than 64 MB over all ranks is refused at argument parsing, before any GPU work."""
+    import bench
+    lat = torch.randn(1, 4, 8, 8, dtype=torch.float16)
+    img = torch.rand(1, 3, 64, 64)
+    bench.dump_outputs(str(tmp_path / 'out'), {'latent': lat, 'image': img})
+    for name, t in (('latent', lat), ('image', img)):
+        a = np.load(tmp_path / 'out' / f'{name}.npy')
+        assert a.dtype == np.float32 and a.shape == tuple(t.shape) and np.array_equal(a, t.float().numpy())
+    for wl in bench.WORKLOADS.values():        # the up-front count is what the timed path's latent + image take in float32
+        n = wl['latent']
+        assert bench.dump_bytes(n, 1) == 4 * (4 * n * n + 3 * (8 * n) ** 2)
+    assert bench.dump_bytes(96, 8) <= bench.DUMP_LIMIT_BYTES < bench.dump_bytes(96, 9)
+    for argv in (['--gpus', '9', '--workload', 'txt2img768', '--dump-outputs', str(tmp_path / 'big')], ['--steps', '0']):
+        monkeypatch.setattr(sys, 'argv', ['bench.py'] + argv)
+        with pytest.raises(SystemExit) as e:
+            bench.main()
+        assert e.value.code == 2
+    assert not os.path.exists(tmp_path / 'big')
 
 
 def test_gpu_side_never_reads_the_reference_tree():
@@ -449,12 +470,26 @@ def test_design_knob_table_matches_the_sources():
 def test_reference_bytecode_bundle_builds_and_imports_sourceless(tmp_path):
     """oracle/build_ref_bundle.py (the recipe behind tests/test_reference_script_gpu.py): compiles the reference's modules where
     they lie into sourceless .pyc files -- no source text in the bundle --, the manifest pins the source hashes, and a fresh
-    interpreter imports `ldm.util.instantiate_from_config` from the bundle alone."""
+    interpreter imports `ldm.util.instantiate_from_config` from the bundle alone.  Run on a stand-in tree in the reference's
+    layout (the files the bundle, the manifest and the launcher rely on), so that the recipe is checked wherever the suite runs."""
     import hashlib
     import json
-    ref = '/root/reference'
-    if not os.path.isdir(os.path.join(ref, 'ldm')):
-        pytest.skip('no reference checkout here (the bundle is built where /root/reference is visible)')
+    ref = str(tmp_path / 'reference')
+    stand_in = {
+        'ldm/__init__.py': '',
+        'ldm/util.py': 'def instantiate_from_config(config):\n    return config\n',
+        'ldm/models/__init__.py': '',
+        'ldm/models/diffusion/__init__.py': '',
+        'ldm/models/diffusion/plms.py': 'class PLMSSampler:\n    pass\n',
+        'scripts/txt2img.py': 'print("txt2img")\n',
+        'scripts/img2img.py': 'print("img2img")\n',
+        'configs/stable-diffusion/v1-inference.yaml':
+            'model:\n  params:\n    unet_config:\n      target: ldm.modules.diffusionmodules.openaimodel.UNetModel\n',
+    }
+    for rel, text in stand_in.items():
+        os.makedirs(os.path.dirname(os.path.join(ref, rel)), exist_ok=True)
+        with open(os.path.join(ref, rel), 'w') as f:
+            f.write(text)
     import importlib.util
     spec = importlib.util.spec_from_file_location('sdmi_ref_bundle_t', os.path.join(ROOT, 'oracle', 'build_ref_bundle.py'))
     rb = importlib.util.module_from_spec(spec)
