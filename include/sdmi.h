@@ -95,8 +95,9 @@ int sdmi_unet_cache_timesteps(sdmi_unet* h, const int64_t* t_host, int n, void* 
 int sdmi_unet_hint_timestep(sdmi_unet* h, int64_t t);
 /* Launch tapes (ABI 17; csrc/tape.h): sdmi_unet_forward records the launch list of a (B, H, W, Lctx, workspace, timestep mode, knobs) once and
  * replays it -- no dry pass, no table lookups, no descriptor fills -- patching only the caller's pointers (x, eps_out, timesteps, context, the
- * timestep-table row).  There is nothing to call: this reports how many forwards were replayed / recorded (tests, bench.py).  SDMI_REPLAY=0
- * turns the tapes off; SDMI_REPLAY_VERIFY=1 runs the executor on every would-be replay and fails if the patched tape differs from it.
+ * timestep-table row), at the argument words the executor declared for each of them while recording.  There is nothing to call: this
+ * reports how many forwards were replayed / recorded (tests, bench.py).  SDMI_REPLAY=0 turns the tapes off; SDMI_REPLAY_VERIFY=1 runs the
+ * executor on every would-be replay and fails if the patched tape differs from it.
  * No counterpart in the reference (pure Python, scripts/txt2img.py drives torch ops one by one). */
 int sdmi_unet_tape_stats(sdmi_unet* h, int64_t* replayed, int64_t* recorded);
 
@@ -105,7 +106,9 @@ int sdmi_unet_tape_stats(sdmi_unet* h, int64_t* replayed, int64_t* recorded);
  *   x        fp32 [B, in_channels, H, W] (NCHW, contiguous)
  *   t_i64 / t_f32   exactly one non-NULL: [B] timesteps (int64 as the samplers pass; fp32 for DPM-Solver)
  *   ctx      fp32 [B, Lctx, context_dim], or NULL to reuse sdmi_unet_cache_context()'s result
- *   eps_out  fp32 [B, out_channels, H, W] -- written fresh on every call */
+ *   eps_out  fp32 [B, out_channels, H, W] -- written fresh on every call; may be x itself (in place), and the other caller buffers
+ *            may overlap one another -- a replayed call behaves the same, whatever the buffers of the recorded call were.  None of them
+ *            may lie inside the workspace. */
 int sdmi_unet_forward(sdmi_unet* h, const float* x, const int64_t* t_i64, const float* t_f32, const float* ctx,
                       float* eps_out, int B, int H, int W, int Lctx, void* workspace, int64_t workspace_bytes,
                       void* stream);

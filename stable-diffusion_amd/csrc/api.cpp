@@ -129,7 +129,7 @@ int sdmi_unet_forward(sdmi_unet* h, const float* x, const int64_t* t_i64, const 
 int sdmi_sampler_step(const float* eps_model, int cfg, float scale, const float* x, int mode, const float* old0,
                       const float* old1, const float* old2, float a_t, float a_prev, float sigma, float sqrt_1m_at,
                       const float* noise, float* e_t_out, float* x_prev, float* pred_x0, int64_t n, void* stream) {
-  SamplerStepParams p;
+  SamplerStepParams p = SamplerStepParams();
   p.eps_model = eps_model; p.cfg = cfg; p.scale = scale; p.x = x; p.mode = mode;
   p.old0 = old0; p.old1 = old1; p.old2 = old2;
   p.a_t = a_t; p.a_prev = a_prev; p.sigma = sigma; p.sqrt_1m_at = sqrt_1m_at;
@@ -141,7 +141,7 @@ int sdmi_sampler_step(const float* eps_model, int cfg, float scale, const float*
 int sdmi_dpm_solver_step(const float* eps_model, int cfg, float scale, const float* x, const float* m_prev, float alpha_s,
                          float sigma_s, float cx, float a, float inv_r0, int order, float* m_out, float* x_next, int64_t n,
                          void* stream) {
-  DpmStepParams p;
+  DpmStepParams p = DpmStepParams();
   p.eps_model = eps_model; p.cfg = cfg; p.scale = scale; p.x = x; p.m_prev = m_prev; p.alpha_s = alpha_s; p.sigma_s = sigma_s;
   p.cx = cx; p.a = a; p.inv_r0 = inv_r0; p.order = order; p.m_out = m_out; p.x_next = x_next; p.n = n;
   return launch_dpm_step(p, (hipStream_t)stream);
@@ -243,7 +243,7 @@ int sdmi_clip_forward(sdmi_clip* h, const int64_t* ids, float* out, int B, int L
 }
 int sdmi_k_attention_causal(const void* q, const void* k, const void* vt, void* out, int BH, int heads, int n, int n_pad,
                             int d, float scale, void* stream) {
-  AttnParams a;
+  AttnParams a = AttnParams();
   a.q = (const f16*)q; a.k = (const f16*)k; a.vt = (const f16*)vt; a.out = (f16*)out;
   a.BH = BH; a.heads = heads; a.nq = n; a.nkv = n; a.nkv_pad = n_pad; a.d = d; a.scale = scale; a.causal = 1;
   return launch_attention(a, (hipStream_t)stream);
@@ -276,7 +276,7 @@ static int igemm_params_of(const sdmi_igemm_desc* d, IGemmParams& p) {
 }
 int sdmi_k_igemm(const sdmi_igemm_desc* d, void* stream) {
   SDMI_CHECK(d, "null descriptor");
-  IGemmParams p;
+  IGemmParams p = IGemmParams();
   if (igemm_params_of(d, p)) return -1;
   IGemmTune t; t.tile = d->tile; t.dma = d->dma;
   return launch_igemm(p, t, (hipStream_t)stream);
@@ -284,7 +284,7 @@ int sdmi_k_igemm(const sdmi_igemm_desc* d, void* stream) {
 int sdmi_k_ff_tail(const sdmi_igemm_desc* proj_out, const void* ln_f16, const float* lnp, float ln_eps, const float* csd,
                    const void* wgg_f16, const void* wff2_f16, const float* bff2, const float* t, void* stream) {
   SDMI_CHECK(proj_out, "null descriptor");
-  FfTailParams q;
+  FfTailParams q = FfTailParams();
   if (igemm_params_of(proj_out, q.epi)) return -1;
   SDMI_CHECK(proj_out->split16 && proj_out->ksize == 1, "ff_tail: the proj_out descriptor is a split-fp16 1x1 (w = sdmi_k_pack_split3)");
   q.ln = (const f16*)ln_f16; q.lnp = lnp; q.ln_eps = ln_eps; q.csd = csd; q.wgg = (const f16*)wgg_f16; q.wff2 = (const f16*)wff2_f16;
@@ -294,7 +294,7 @@ int sdmi_k_ff_tail(const sdmi_igemm_desc* proj_out, const void* ln_f16, const fl
 int sdmi_k_st_tail(const sdmi_igemm_desc* proj_out, const void* a_f16, const void* wo_f16, const float* bo, float* t, const float* ln_gamma,
                    float ln_eps, const float* csd, const void* wgg_f16, const void* wff2_f16, const float* bff2, void* stream) {
   SDMI_CHECK(proj_out && a_f16, "null argument");
-  FfTailParams q;
+  FfTailParams q = FfTailParams();
   if (igemm_params_of(proj_out, q.epi)) return -1;
   SDMI_CHECK(proj_out->split16 && proj_out->ksize == 1, "st_tail: the proj_out descriptor is a split-fp16 1x1 (w = sdmi_k_pack_split3)");
   q.a16 = (const f16*)a_f16; q.wo = (const f16*)wo_f16; q.bo = bo; q.ln_gamma = ln_gamma; q.ln_eps = ln_eps; q.csd = csd;
@@ -304,12 +304,12 @@ int sdmi_k_st_tail(const sdmi_igemm_desc* proj_out, const void* a_f16, const voi
 int sdmi_k_gn_conv3(const sdmi_igemm_desc* conv, const float* x0, const float* x1, int c0, int c1, float* gn_ws, int64_t gn_ws_floats,
                     const float* gn_gamma, const float* gn_beta, float gn_eps, void* stream) {
   SDMI_CHECK(conv && x0 && gn_ws && gn_gamma && gn_beta, "gn_conv3: null argument");
-  GnConvParams q;
+  GnConvParams q = GnConvParams();
   if (igemm_params_of(conv, q.epi)) return -1;
   const int B = q.epi.B;
   SDMI_CHECK(gn_ws_floats >= gn_acc_words(B) * 2, "groupnorm workspace too small");
   SDMI_HIP_OK(hipMemsetAsync(gn_ws, 0, gn_acc_words(B) * sizeof(long long), (hipStream_t)stream));
-  GroupNormParams g;
+  GroupNormParams g = GroupNormParams();
   g.x0 = x0; g.c0 = c0; g.x1 = x1; g.c1 = c1; g.B = B; g.HW = q.epi.Hout * q.epi.Wout; g.gamma = gn_gamma; g.beta = gn_beta; g.eps = gn_eps;
   g.stats_only = 1; g.acc = (long long*)gn_ws;
   if (launch_groupnorm(g, (hipStream_t)stream)) return -1;
@@ -324,10 +324,10 @@ int sdmi_k_st_head(const float* x, float* gn_ws, int64_t gn_ws_floats, const flo
   SDMI_CHECK(x && gn_ws && gn_gamma && gn_beta, "st_head: null argument");
   SDMI_CHECK(gn_ws_floats >= gn_acc_words(B) * 2, "groupnorm workspace too small");
   SDMI_HIP_OK(hipMemsetAsync(gn_ws, 0, gn_acc_words(B) * sizeof(long long), (hipStream_t)stream));
-  GroupNormParams g;
+  GroupNormParams g = GroupNormParams();
   g.x0 = x; g.c0 = C; g.B = B; g.HW = ntok; g.gamma = gn_gamma; g.beta = gn_beta; g.eps = gn_eps; g.stats_only = 1; g.acc = (long long*)gn_ws;
   if (launch_groupnorm(g, (hipStream_t)stream)) return -1;
-  StHeadParams p;
+  StHeadParams p = StHeadParams();
   p.x = x; p.gn_acc = (const long long*)gn_ws; p.gn_gamma = gn_gamma; p.gn_beta = gn_beta; p.gn_eps = gn_eps;
   p.w_in = (const f16*)w_in3; p.b_in = b_in; p.t = t; p.ln_gamma = ln_gamma; p.ln_eps = ln_eps; p.wqkv = (const f16*)wqkv_f16;
   p.lnf_cs = lnf_cs; p.lnf_d = lnf_d; p.q = (f16*)q; p.k = (f16*)k; p.vt = (f16*)vt;
@@ -336,7 +336,7 @@ int sdmi_k_st_head(const float* x, float* gn_ws, int64_t gn_ws_floats, const flo
 }
 int sdmi_k_st_mid(const void* a_f16, const void* wo_f16, const float* bo, float* t, const float* ln_gamma, float ln_eps, const void* wq_f16,
                   const float* lnf_cs, const float* lnf_d, void* q, int B, int ntok, int heads, int dh, int C, void* stream) {
-  StHeadParams p;
+  StHeadParams p = StHeadParams();
   p.a16 = (const f16*)a_f16; p.w_in = (const f16*)wo_f16; p.b_in = bo; p.t = t; p.ln_gamma = ln_gamma; p.ln_eps = ln_eps;
   p.wqkv = (const f16*)wq_f16; p.lnf_cs = lnf_cs; p.lnf_d = lnf_d; p.q = (f16*)q;
   p.M = B * ntok; p.B = B; p.ntok = ntok; p.ntok_pad = ntok; p.heads = heads; p.dh = dh; p.C = C;
@@ -345,7 +345,7 @@ int sdmi_k_st_mid(const void* a_f16, const void* wo_f16, const float* bo, float*
 int sdmi_k_st_mid_ctx(const void* a_f16, const void* wo_f16, const float* bo, float* t, const float* ln_gamma, float ln_eps, const void* wq_f16,
                       const float* lnf_cs, const float* lnf_d, const void* ctx_k, const void* ctx_vt, int nkv, int nkv_pad, float scale, void* ao_out,
                       int B, int ntok, int heads, int dh, int C, void* stream) {
-  StHeadParams p;
+  StHeadParams p = StHeadParams();
   p.a16 = (const f16*)a_f16; p.w_in = (const f16*)wo_f16; p.b_in = bo; p.t = t; p.ln_gamma = ln_gamma; p.ln_eps = ln_eps;
   p.wqkv = (const f16*)wq_f16; p.lnf_cs = lnf_cs; p.lnf_d = lnf_d;
   p.ctx_k = (const f16*)ctx_k; p.ctx_vt = (const f16*)ctx_vt; p.ctx_nkv = nkv; p.ctx_nkv_pad = nkv_pad; p.ctx_scale = scale; p.ao_out = (f16*)ao_out;
@@ -359,7 +359,7 @@ int sdmi_k_ln_fold_prep(const void* w_f16, int N, int K, int ldw, const float* g
 }
 int sdmi_k_attention(const void* q, const void* k, const void* vt, void* out, int BH, int heads, int nq, int nkv,
                      int nkv_pad, int d, float scale, void* stream) {
-  AttnParams a;
+  AttnParams a = AttnParams();
   a.q = (const f16*)q; a.k = (const f16*)k; a.vt = (const f16*)vt; a.out = (f16*)out;
   a.BH = BH; a.heads = heads; a.nq = nq; a.nkv = nkv; a.nkv_pad = nkv_pad; a.d = d; a.scale = scale;
   if (const char* e = getenv("SDMI_ATTN_NW")) a.nw = atoi(e);     // test / tuning knob
@@ -368,7 +368,7 @@ int sdmi_k_attention(const void* q, const void* k, const void* vt, void* out, in
 int sdmi_k_attention_ctx(const void* x, const void* wq, const void* k, const void* vt, void* out, int BH, int heads, int nq,
                          int nkv, int nkv_pad, int d, float scale, const float* lnf_part, float lnf_eps, const float* lnf_cs,
                          const float* lnf_d, void* stream) {
-  AttnCtxParams a;
+  AttnCtxParams a = AttnCtxParams();
   a.x = (const f16*)x; a.wq = (const f16*)wq; a.k = (const f16*)k; a.vt = (const f16*)vt; a.out = (f16*)out;
   a.BH = BH; a.heads = heads; a.nq = nq; a.nkv = nkv; a.nkv_pad = nkv_pad; a.d = d; a.C = heads * d; a.scale = scale;
   if (lnf_part) { a.lnf_part = lnf_part; a.lnf_npart = a.C / 32; a.lnf_eps = lnf_eps; a.M = (BH / heads) * nq; a.lnf_cs = lnf_cs; a.lnf_d = lnf_d; }
@@ -381,7 +381,7 @@ int sdmi_k_groupnorm(const float* x0, const float* x1, int c0, int c1, int B, in
   SDMI_CHECK(partial_floats >= gn_acc_words(B) * 2, "groupnorm workspace too small");
   // the workspace holds the fixed-point statistics accumulators; they must start at zero
   SDMI_HIP_OK(hipMemsetAsync(partial_ws, 0, gn_acc_words(B) * sizeof(long long), (hipStream_t)stream));
-  GroupNormParams g;
+  GroupNormParams g = GroupNormParams();
   g.x0 = x0; g.x1 = x1; g.c0 = c0; g.c1 = c1; g.B = B; g.HW = HW; g.gamma = gamma; g.beta = beta; g.eps = eps;
   g.silu = silu; g.out_f16 = (f16*)out_f16; g.out_f32 = out_f32; g.raw_f16 = (f16*)raw_f16; g.out_lo = (f16*)out_lo; g.raw_lo = (f16*)raw_lo;
   g.acc = (long long*)partial_ws;
@@ -394,11 +394,11 @@ int sdmi_k_conv3gn(const float* x0, const float* x1, int c0, int c1, int B, int 
                    void* stream) {
   SDMI_CHECK(gn_ws_floats >= gn_acc_words(B) * 2, "groupnorm workspace too small");
   SDMI_HIP_OK(hipMemsetAsync(gn_ws, 0, gn_acc_words(B) * sizeof(long long), (hipStream_t)stream));
-  GroupNormParams g;
+  GroupNormParams g = GroupNormParams();
   g.x0 = x0; g.x1 = x1; g.c0 = c0; g.c1 = c1; g.B = B; g.HW = H * W; g.gamma = gamma; g.beta = beta; g.eps = eps;
   g.stats_only = 1; g.acc = (long long*)gn_ws;
   if (launch_groupnorm(g, (hipStream_t)stream)) return -1;
-  IGemmParams p;                       // the 3x3 convolution that normalises its own input (conv3halo.hip)
+  IGemmParams p = IGemmParams();                       // the 3x3 convolution that normalises its own input (conv3halo.hip)
   p.xf0 = x0; p.xf1 = x1; p.c0 = c0; p.c1 = c1; p.lda0 = c0 + c1;
   p.gn_in_acc = (const long long*)gn_ws; p.gn_in_gamma = gamma; p.gn_in_beta = beta; p.gn_in_eps = eps; p.gn_in_silu = 1;
   p.raw_hi = (f16*)raw_hi; p.raw_lo = (f16*)raw_lo;

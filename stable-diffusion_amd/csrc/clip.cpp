@@ -161,7 +161,7 @@ int ClipText::forward(const int64_t* ids, float* out, int B, int L, void* worksp
         f.gemm(p);
       }
       if (!d && !f.rc) {
-        AttnParams a;
+        AttnParams a = AttnParams();
         a.q = q; a.k = k; a.vt = vt; a.out = ao; a.BH = B * H; a.heads = H; a.nq = L; a.nkv = L; a.nkv_pad = Lp; a.d = dh;
         a.scale = scale; a.causal = 1;
         f.ok(launch_attention(a, stream));

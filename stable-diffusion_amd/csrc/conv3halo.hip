@@ -856,7 +856,7 @@ bool gn_fold_conv_supported(int B, int H, int W, int c0, int c1, int N) {
   // fp32 through registers instead of fp16 by DMA.
   static const int env_on = env_int("SDMI_FUSE_GN_CONV", 0);
   if (!env_on) return false;
-  IGemmParams p;
+  IGemmParams p = IGemmParams();
   p.B = B; p.Hin = p.Hout = H; p.Win = p.Wout = W; p.ksize = 3; p.stride = 1; p.pad = 1; p.up = 0;
   p.c0 = c0; p.c1 = c1; p.M = B * H * W; p.N = N; p.K = 9 * (c0 + c1);
   for (int bm : {256, 128})

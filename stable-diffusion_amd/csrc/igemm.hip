@@ -940,7 +940,7 @@ int launch_igemm(const IGemmParams& p, const IGemmTune& tune, hipStream_t stream
   if (gn_fold && tile == SDMI_TILE_TWO_LAUNCH) {
     SDMI_CHECK(p.gn_scratch != nullptr, "two-launch GroupNorm + conv needs the fp16 scratch");
     if (ev0) SDMI_HIP_OK(hipEventRecord(ev0, stream));
-    GroupNormParams g;
+    GroupNormParams g = GroupNormParams();
     g.x0 = p.xf0; g.x1 = p.xf1; g.c0 = p.c0; g.c1 = p.c1; g.B = p.B; g.HW = p.Hout * p.Wout;
     g.gamma = p.gn_in_gamma; g.beta = p.gn_in_beta; g.eps = p.gn_in_eps; g.silu = p.gn_in_silu;
     g.skip_stats = 1; g.acc = (long long*)p.gn_in_acc;                   // (complete: see IGemmParams::gn_in_acc)

@@ -527,7 +527,7 @@ int launch_small_linear(const float* in, int ld_in, const float* w, const float*
 int launch_conv_in(const float* x, const float* w, const float* bias, float* out, int B, int Cin, int H, int W, int Cout,
                    hipStream_t s, int gn_n, long long* const* gn_acc, const int* gn_cpg, const int* gn_cbase) {
   SDMI_CHECK(Cin * 9 <= CI_MAXK, "conv_in: in_channels <= 16");
-  ConvInStats st;
+  ConvInStats st = ConvInStats();
   if (gn_n > 0) {
     SDMI_CHECK(gn_n <= 2 && (H * W) % CI_PIX == 0, "conv_in statistics: at most two GroupNorm targets, H * W % 16 == 0");
     st.n = gn_n;

@@ -14,6 +14,7 @@ extern "C" char** environ;       // (the launch tapes hash the SDMI_* knobs)
 #include "prof.h"
 
 #include <math.h>
+#include <stdio.h>
 #include <string.h>
 
 #include <algorithm>
@@ -530,6 +531,7 @@ struct Fwd : FwdBase {
   bool gn_proj_fold = false;
   float* emb_all = nullptr;     // [B][emb_total] (emb_ld = emb_total), or one row of the timestep table shared by every sample (emb_ld = 0)
   int emb_ld = 0;
+  bool emb_caller = false;      // emb_all is that table row: a caller pointer of a launch tape (Tape::R_EMB)
   const f16* ctx16 = nullptr;   // [B*L][context_dim], null when the cached K/V are used
   const f16* ctx16_lo = nullptr; // ... its split-fp16 low half fp16(ctx - fp16(ctx)) (precise K / V projections)
 
@@ -576,13 +578,15 @@ struct Fwd : FwdBase {
     float* h = S<float>((size_t)M * Cout);
     Act out = make_act(P<float>((size_t)M * Cout), Cout, H, W, true);
     Act hact = make_act(h, Cout, H, W, true);
-    f16* a2 = nullptr; int gn2_applied = 0;
+    f16* a2 = nullptr;
+    int& gn2_applied = u->gn2_applied_;     // (its address rides in the recorded parameter bytes: the same on every call)
+    gn2_applied = 0;
     // in_layers / out_layers as ONE launch each (gnconv.hip: 32 pixels x all 320 output channels per workgroup, the halo normalised once):
     // the 64 x 64 level of SD v1.  (in_layers only without a skip convolution: that one reads raw fp16 copies the GroupNorm launch writes.)
     const bool gc1 = gn_conv_on && !L.precise3 && !fold1 && Cin == Cout && gn_conv3_supported(B, H, W, x0.C, x1 ? x1->C : 0, Cout);
     const bool gc2 = gn_conv_on && !L.precise3 && !fold2 && gn_conv3_supported(B, H, W, Cout, 0, Cout);
     auto gn_conv = [&](const Act& a0, const Act* a1, const float* gamma, const float* beta, const f16* w, IGemmParams& e) {
-      GnConvParams g;
+      GnConvParams g = GnConvParams();
       g.gn_acc = groupnorm(a0, a1, gamma, beta, 1e-5f, 1, nullptr, nullptr, nullptr, nullptr, nullptr, /*stats_only=*/true);
       g.x0 = a0.p; g.c0 = a0.C; g.x1 = a1 ? a1->p : nullptr; g.c1 = a1 ? a1->C : 0;
       g.gn_gamma = gamma; g.gn_beta = beta; g.gn_eps = 1e-5f; g.w = w; g.epi = e;
@@ -593,9 +597,10 @@ struct Fwd : FwdBase {
       p.bias = L.f32[2]; p.rowvec = emb_all + L.emb_off; p.ld_rowvec = emb_ld;
       p.out_f32 = h; p.ldo = Cout;
       attach_gn_targets(p, hact);
+      TapeCaller tc(Tape::R_EMB, emb_caller ? p.rowvec : nullptr);
       gn_conv(x0, x1, L.f32[0], L.f32[1], L.w16[0], p);
     } else {
-      IGemmParams p;
+      IGemmParams p = IGemmParams();
       if (fold1) {
         p = conv3_gn(x0, x1, L.f32[0], L.f32[1], L.w16[0], Cout, raw, raw_lo);    // (+ the skip conv's raw hi | lo operand)
       } else {
@@ -615,6 +620,7 @@ struct Fwd : FwdBase {
         a2 = S<f16>((size_t)M * Cout);
         p.pgn_gamma = L.f32[3]; p.pgn_beta = L.f32[4]; p.pgn_eps = 1e-5f; p.pgn_silu = 1; p.pgn_out = a2; p.pgn_applied = &gn2_applied;
       }
+      TapeCaller tc(Tape::R_EMB, emb_caller ? p.rowvec : nullptr);
       gemm(p);
     }
     const float* residual = x0.p;
@@ -632,7 +638,7 @@ struct Fwd : FwdBase {
       attach_f16_copy(p, out);
       gn_conv(hact, nullptr, L.f32[3], L.f32[4], L.w16[1], p);
     } else {
-      IGemmParams p;
+      IGemmParams p = IGemmParams();
       if (fold2) {
         p = conv3_gn(hact, nullptr, L.f32[3], L.f32[4], L.w16[1], Cout, nullptr, nullptr);
       } else {
@@ -680,7 +686,7 @@ struct Fwd : FwdBase {
     f16* xn_lo = p1 ? S<f16>((size_t)M * C) : nullptr;
     // proj_in(norm(x)), attention.py:254-255: the GroupNorm either as its own launch (fp32 stream -> split-fp16 hi | lo operands) or
     // applied inside the GEMM while it stages its A operand (gemm_split16_gn_kernel: same operand bits, same products, one launch less)
-    IGemmParams pin;
+    IGemmParams pin = IGemmParams();
     pin.M = M; pin.N = C; pin.K = C; pin.ksize = 1; pin.Hout = N; pin.Wout = 1; pin.B = B;
     const bool fold_ln = ln_fold_on && C % 64 == 0 && C <= 1280 && N % 64 == 0 && M % 64 == 0 && M >= u->ln_fold_min_rows_;
     const bool gn_in_gemm = gn_proj_fold && fold_ln && p1 && M >= 512 && split16_gn_supported(pin);
@@ -713,7 +719,7 @@ struct Fwd : FwdBase {
     };
     if (chain_head) {
       TBlock& T = L.tb[0];
-      StHeadParams h;
+      StHeadParams h = StHeadParams();
       h.x = x.p; h.gn_acc = gn_stats; h.gn_gamma = L.f32[0]; h.gn_beta = L.f32[1]; h.gn_eps = 1e-6f;
       h.w_in = L.w16[0]; h.b_in = L.f32[2]; h.t = t; h.ln_gamma = T.ln[0]; h.ln_eps = 1e-5f;
       h.wqkv = T.wqkv; h.lnf_cs = T.lnf[0]; h.lnf_d = T.lnf[1]; h.q = q; h.k = k; h.vt = vt;
@@ -764,7 +770,7 @@ struct Fwd : FwdBase {
       bool chain_ctx = false;
       const bool chain_mid = st_mid_on && fold_ln && !ctx_fused_here && T.lnf[2] != nullptr && st_head_supported(C, M, N, Np, L.heads, L.dh);
       if (chain_mid) {
-        StHeadParams h;
+        StHeadParams h = StHeadParams();
         h.a16 = ao; h.w_in = T.wo1; h.b_in = T.bo1; h.t = t; h.ln_gamma = T.ln[2]; h.ln_eps = 1e-5f;
         h.wqkv = T.wq2; h.lnf_cs = T.lnf[2]; h.lnf_d = T.lnf[3]; h.q = q;
         h.M = M; h.B = B; h.ntok = N; h.ntok_pad = Np; h.heads = L.heads; h.dh = L.dh; h.C = C;
@@ -785,7 +791,7 @@ struct Fwd : FwdBase {
         if (!chain_ctx) attention(q, T.ck, T.cvt, ao, L, N, Lctx, Lp, scale);       // (q = to_q(norm2(t)) came out of the chain launch)
       } else if (fuse_ctx_q && L.dh <= fuse_ctx_maxd && attention_ctx_supported(L.dh, C, Lctx) && !(fold_ln && C > 640)) {
         // to_q inside the attention kernel (attn_ctx.hip): one launch for q = norm2(x) Wq^T and softmax(q K^T) V
-        AttnCtxParams a;
+        AttnCtxParams a = AttnCtxParams();
         a.x = ln; a.wq = T.wq2; a.k = T.ck; a.vt = T.cvt; a.out = ao;
         a.BH = B * L.heads; a.heads = L.heads; a.nq = N; a.nkv = Lctx; a.nkv_pad = Lp; a.d = L.dh; a.C = C; a.scale = scale;
         if (fold_ln) { a.lnf_part = lnp; a.lnf_npart = C / 32; a.lnf_eps = 1e-5f; a.M = M; a.lnf_cs = T.lnf[2]; a.lnf_d = T.lnf[3]; }
@@ -835,7 +841,7 @@ struct Fwd : FwdBase {
       if (chain_ff) {
         // out = x + proj_out(t + FF(norm3(t))): one row-strip chain launch (rowchain.hip); `ln` / `lnp` are what attn2's out-projection stored
         TBlock& T = L.tb[0];
-        FfTailParams q;
+        FfTailParams q = FfTailParams();
         q.ln = ln; q.lnp = lnp; q.ln_eps = 1e-5f; q.csd = T.lnf_csd; q.wgg = T.wgg; q.wff2 = T.wff2; q.bff2 = T.bff2; q.t = t; q.wpo = L.w16[1];
         if (chain_tail) { q.a16 = ao; q.wo = T.wo2; q.bo = T.bo2; q.ln_gamma = T.ln[4]; }     // t += ao Wo2^T + bo2 first (attention.py:213)
         q.epi = p;
@@ -849,7 +855,7 @@ struct Fwd : FwdBase {
   }
 
   void attention(const f16* q, const f16* k, const f16* vt, f16* out, Layer& L, int nq, int nkv, int nkv_pad, float scale) {
-    AttnParams a;
+    AttnParams a = AttnParams();
     a.q = q; a.k = k; a.vt = vt; a.out = out; a.BH = B * L.heads; a.heads = L.heads; a.nq = nq; a.nkv = nkv;
     a.nkv_pad = nkv_pad; a.d = L.dh; a.scale = scale;
     if (!dry && !rc) ok(launch_attention(a, s));
@@ -995,8 +1001,15 @@ int UNet::run(const float* x, const int64_t* t_i64, const float* t_f32, const fl
   const bool replay_on = !(e_rp && atoi(e_rp) == 0);
   const bool replay_verify = e_rv && atoi(e_rv) != 0;
   const bool hinted = t_i64 != nullptr && hint_row >= 0 && hint_row < (int)emb_tab_t_.size();
+  // (a caller buffer inside the workspace is undefined input: such a call runs the executor, untaped)
+  auto in_ws = [&](const void* p, size_t bytes) {
+    return p && (uintptr_t)p < (uintptr_t)workspace + (uint64_t)ws_bytes && (uintptr_t)workspace < (uintptr_t)p + bytes;
+  };
+  const size_t img = (size_t)B * H * W * sizeof(float);
   const bool tape_ok = replay_on && !dry && !ctx_only && !side_stream_ && !prof_enabled() && !tune_collecting() && !range_check_enabled() &&
-                       workspace != nullptr && (t_i64 || t_f32);
+                       workspace != nullptr && (t_i64 || t_f32) && !in_ws(x, img * cfg_.in_channels) && !in_ws(eps_out, img * cfg_.out_channels) &&
+                       !in_ws(t_i64 ? (const void*)t_i64 : t_f32, (size_t)B * (t_i64 ? 8 : 4)) &&
+                       !in_ws(ctx, (size_t)B * Lctx * cfg_.context_dim * sizeof(float));
   TapeKey tkey;
   uintptr_t caller[Tape::R_COUNT] = {0, 0, 0, 0, 0};
   Tape* rec = nullptr;
@@ -1005,6 +1018,8 @@ int UNet::run(const float* x, const int64_t* t_i64, const float* t_f32, const fl
     tkey.B = B; tkey.H = H; tkey.W = W; tkey.Lctx = Lctx; tkey.mode = hinted ? 0 : (t_i64 ? 1 : 2);
     tkey.ws = workspace; tkey.ws_bytes = ws_bytes; tkey.have_ctx = ctx != nullptr;
     tkey.env = sdmi_env_hash() ^ (tune_generation() * 0x9e3779b97f4a7c15ull); tkey.weights_gen = weights_gen_; tkey.ctx_gen = ctx_gen_;
+    auto low4 = [](const void* p, int shift) { return (unsigned)((uintptr_t)p & 15) << shift; };
+    tkey.align = low4(x, 0) | low4(eps_out, 4) | low4(ctx, 8) | low4(t_i64 ? (const void*)t_i64 : t_f32, 12);
     caller[Tape::R_X] = (uintptr_t)x; caller[Tape::R_OUT] = (uintptr_t)eps_out;
     caller[Tape::R_T] = hinted ? 0 : (t_i64 ? (uintptr_t)t_i64 : (uintptr_t)t_f32);
     caller[Tape::R_CTX] = (uintptr_t)ctx;
@@ -1030,7 +1045,11 @@ int UNet::run(const float* x, const int64_t* t_i64, const float* t_f32, const fl
     }
   }
   std::unique_ptr<Tape> fresh;
-  if (tape_ok) { fresh.reset(new Tape()); rec = fresh.get(); }
+  if (tape_ok) {
+    fresh.reset(new Tape());
+    memcpy(fresh->caller, caller, sizeof(caller));
+    rec = fresh.get();
+  }
 
   Fwd f;
   f.u = this; f.s = stream; f.dry = dry; f.B = B; f.Lctx = Lctx; f.zero = zero_; f.precise_1x1 = precise_1x1_;
@@ -1091,7 +1110,11 @@ int UNet::run(const float* x, const int64_t* t_i64, const float* t_f32, const fl
     f16* ctx16_lo = precise_kv_ ? f.P<f16>((size_t)B * Lctx * cfg_.context_dim) : nullptr;
     const bool have_ctx = (ctx != nullptr) || d;
     if (have_ctx) {
-      if (!d) { int r = launch_cast_f16(ctx, ctx16, ctx16_lo, (int64_t)B * Lctx * cfg_.context_dim, stream); if (r) return r; }
+      if (!d) {
+        TapeCaller tc(Tape::R_CTX, ctx);
+        int r = launch_cast_f16(ctx, ctx16, ctx16_lo, (int64_t)B * Lctx * cfg_.context_dim, stream);
+        if (r) return r;
+      }
       f.ctx16 = ctx16; f.ctx16_lo = ctx16_lo;
     } else {
       SDMI_CHECK(ctx_valid_, "ctx == NULL but no cached context for this (B, Lctx); call sdmi_unet_cache_context first");
@@ -1113,8 +1136,13 @@ int UNet::run(const float* x, const int64_t* t_i64, const float* t_f32, const fl
         // every row has the hinted timestep and its emb_layers outputs are in the table: one shared row, nothing to launch
         f.emb_all = emb_tab_ + (size_t)hint_row * emb_total_;
         f.emb_ld = 0;
+        f.emb_caller = true;
       } else if (!d) {
-        int r = launch_timestep_embedding(t_i64, t_f32, temb, B, mc, stream);
+        int r;
+        {
+          TapeCaller tc(Tape::R_T, t_i64 ? (const void*)t_i64 : t_f32);
+          r = launch_timestep_embedding(t_i64, t_f32, temb, B, mc, stream);
+        }
         if (!r) r = launch_small_linear(temb, mc, te_w0_, te_b0_, e1, te_, B, te_, mc, 0, stream);
         if (!r) r = launch_small_linear(e1, te_, te_w2_, te_b2_, emb, te_, B, te_, te_, 1, stream);
         if (!r) r = launch_small_linear(emb, te_, emb_w_, emb_b_, f.emb_all, emb_total_, B, emb_total_, te_, 1, stream);
@@ -1129,9 +1157,10 @@ int UNet::run(const float* x, const int64_t* t_i64, const float* t_f32, const fl
         // the skip concat, the last output block -- ran the statistics kernel; rounds 1-5: "conv_in is not an igemm: no fused statistics")
         const char* e_cis = getenv("SDMI_CONV_IN_STATS");                 // (A/B knob, read per call; 0 = the statistics kernel as in rounds 1-5)
         h = f.make_act(f.P<float>((size_t)B * H * W * mc), mc, H, W, (H * W) % 16 == 0 && !(e_cis && atoi(e_cis) == 0));
-        IGemmParams st;                                   // (carrier of the statistics targets only)
+        IGemmParams st = IGemmParams();                                   // (carrier of the statistics targets only)
         f.attach_gn_targets(st, h);
         if (!d) {
+          TapeCaller tc(Tape::R_X, x);
           int r = launch_conv_in(x, L.w32[0], L.f32[0], h.p, B, cfg_.in_channels, H, W, mc, stream, st.gn_n, st.gn_acc, st.gn_cpg, st.gn_cbase);
           if (r) return r;
         }
@@ -1151,7 +1180,11 @@ int UNet::run(const float* x, const int64_t* t_i64, const float* t_f32, const fl
       // ---- output head: GN -> SiLU -> conv3x3 (fp32) ----
       float* hn = f.S<float>((size_t)B * H * W * mc);
       f.groupnorm(h, nullptr, out_gamma_, out_beta_, 1e-5f, 1, nullptr, hn, nullptr);
-      if (!d && !f.rc) { int r = launch_conv_out(hn, out_w_, out_b_, eps_out, B, H, W, mc, cfg_.out_channels, stream); if (r) return r; }
+      if (!d && !f.rc) {
+        TapeCaller tc(Tape::R_OUT, eps_out);
+        int r = launch_conv_out(hn, out_w_, out_b_, eps_out, B, H, W, mc, cfg_.out_channels, stream);
+        if (r) return r;
+      }
     }
     if (f.rc) return f.rc;
     if (d) { persist_bytes = (int64_t)f.persist.peak + 256; scratch_bytes = (int64_t)f.scratch.peak + 256; }
@@ -1162,28 +1195,26 @@ int UNet::run(const float* x, const int64_t* t_i64, const float* t_f32, const fl
   }
   if (bytes_needed) *bytes_needed = persist_bytes + scratch_bytes;
   if (fresh) {
-    // the caller ranges the recorded parameter bytes may point into
-    const int64_t cd = cfg_.context_dim;
-    fresh->base[Tape::R_X] = caller[Tape::R_X]; fresh->span[Tape::R_X] = (size_t)B * cfg_.in_channels * H * W * sizeof(float);
-    fresh->base[Tape::R_OUT] = caller[Tape::R_OUT]; fresh->span[Tape::R_OUT] = (size_t)B * cfg_.out_channels * H * W * sizeof(float);
-    fresh->base[Tape::R_T] = caller[Tape::R_T]; fresh->span[Tape::R_T] = caller[Tape::R_T] ? (size_t)B * (t_i64 ? 8 : 4) : 0;
-    fresh->base[Tape::R_CTX] = caller[Tape::R_CTX]; fresh->span[Tape::R_CTX] = ctx ? (size_t)B * Lctx * cd * sizeof(float) : 0;
-    fresh->base[Tape::R_EMB] = caller[Tape::R_EMB]; fresh->span[Tape::R_EMB] = caller[Tape::R_EMB] ? (size_t)emb_total_ * sizeof(float) : 0;
+    // (a declaration that matched no argument word: internal error, the executor's result of this call stands but it is not taped)
+    if (fresh->broken && !verify_against) {
+      static bool noted = false;
+      if (!noted) fprintf(stderr, "sdmi: internal: a declared caller pointer (TapeCaller) is in no launch argument; such calls run untaped\n");
+      noted = true;
+      return 0;
+    }
     fresh->bytes_needed = persist_bytes + scratch_bytes;
     fresh->sets_ctx_valid = ctx != nullptr;
-    fresh->find_relocs();
     if (verify_against) {
       const Tape& a = *verify_against; const Tape& b = *fresh;
-      // (the parameter structs carry padding bytes of unspecified content: compared are the launch list, the argument layout, the set of
-      // relocated words and their values -- i.e. every caller pointer after the retarget)
-      bool same = a.ops.size() == b.ops.size() && a.blob.size() == b.blob.size() && a.arg_off == b.arg_off && a.relocs.size() == b.relocs.size();
+      auto eq3 = [](const dim3& u, const dim3& v) { return u.x == v.x && u.y == v.y && u.z == v.z; };
+      bool same = !b.broken && a.ops.size() == b.ops.size() && a.blob == b.blob && a.arg_off == b.arg_off && a.arg_size == b.arg_size &&
+                  a.relocs.size() == b.relocs.size();
       for (size_t i = 0; same && i < a.relocs.size(); ++i)
-        same = a.relocs[i].off == b.relocs[i].off && a.relocs[i].which == b.relocs[i].which &&
-               memcmp(a.blob.data() + a.relocs[i].off, b.blob.data() + b.relocs[i].off, 8) == 0;
+        same = a.relocs[i].off == b.relocs[i].off && a.relocs[i].which == b.relocs[i].which && a.relocs[i].delta == b.relocs[i].delta;
       for (size_t i = 0; same && i < a.ops.size(); ++i) {
         const Tape::Op &p = a.ops[i], &q = b.ops[i];
-        same = p.kind == q.kind && p.fn == q.fn && p.grid.x == q.grid.x && p.grid.y == q.grid.y && p.grid.z == q.grid.z && p.block.x == q.block.x &&
-               p.shmem == q.shmem && p.ptr == q.ptr && p.value == q.value && p.bytes == q.bytes;
+        same = p.kind == q.kind && p.fn == q.fn && eq3(p.grid, q.grid) && eq3(p.block, q.block) && p.shmem == q.shmem &&
+               p.first_arg == q.first_arg && p.nargs == q.nargs && p.ptr == q.ptr && p.value == q.value && p.bytes == q.bytes;
       }
       SDMI_CHECK(same, "SDMI_REPLAY_VERIFY: the retargeted launch tape differs from what the executor launches for this call");
       ++tape_hits_;

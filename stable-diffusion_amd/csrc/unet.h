@@ -161,14 +161,14 @@ struct FwdBase {
   }
   // dense [M][K] x W[N][K]^T
   IGemmParams dense(const f16* a, int M, int K, const f16* w, int N, int rows_per_batch) {
-    IGemmParams p;
+    IGemmParams p = IGemmParams();
     p.a0 = a; p.c0 = K; p.lda0 = K;
     p.B = M / rows_per_batch; p.Hin = p.Hout = rows_per_batch; p.Win = p.Wout = 1;
     p.ksize = 1; p.w = w; p.M = M; p.N = N; p.K = K; p.splitk = 0;
     return p;
   }
   IGemmParams conv3(const f16* a, int C, int Hin, int Win, int Hout, int Wout, int stride, int up, const f16* w, int N) {
-    IGemmParams p;
+    IGemmParams p = IGemmParams();
     p.a0 = a; p.c0 = C; p.lda0 = C;
     p.B = B; p.Hin = Hin; p.Win = Win; p.Hout = Hout; p.Wout = Wout;
     p.ksize = 3; p.stride = stride; p.up = up; p.w = w; p.M = B * Hout * Wout; p.N = N; p.K = 9 * C; p.splitk = 0;
@@ -197,7 +197,7 @@ struct FwdBase {
   long long* groupnorm(const Act& x0, const Act* x1, const float* gamma, const float* beta, float eps, int silu, f16* o16,
                        float* o32, f16* raw, f16* o16_lo = nullptr, f16* raw_lo = nullptr, bool stats_only = false,
                        bool already_applied = false) {
-    GroupNormParams g;
+    GroupNormParams g = GroupNormParams();
     g.x0 = x0.p; g.c0 = x0.C;
     if (x1) { g.x1 = x1->p; g.c1 = x1->C; }
     g.B = B; g.HW = x0.H * x0.W; g.gamma = gamma; g.beta = beta; g.eps = eps; g.silu = silu;
@@ -343,14 +343,19 @@ class UNet {
     int B = 0, H = 0, W = 0, Lctx = 0, mode = 0;         // mode: 0 timestep-table row (hinted), 1 int64 timesteps, 2 fp32 timesteps
     const void* ws = nullptr; int64_t ws_bytes = 0; bool have_ctx = false;
     uint64_t env = 0, weights_gen = 0, ctx_gen = 0;
+    unsigned align = 0;        // low 4 bits of x | eps_out << 4 | ctx << 8 | t << 12: the launchers choose vector kernels by alignment
     bool operator==(const TapeKey& o) const {
       return B == o.B && H == o.H && W == o.W && Lctx == o.Lctx && mode == o.mode && ws == o.ws && ws_bytes == o.ws_bytes &&
-             have_ctx == o.have_ctx && env == o.env && weights_gen == o.weights_gen && ctx_gen == o.ctx_gen;
+             have_ctx == o.have_ctx && env == o.env && weights_gen == o.weights_gen && ctx_gen == o.ctx_gen && align == o.align;
     }
   };
   std::vector<std::pair<TapeKey, std::unique_ptr<Tape>>> tapes_;     // (most recently used last; at most kMaxTapes)
   static constexpr size_t kMaxTapes = 12;
   uint64_t weights_gen_ = 0, ctx_gen_ = 0;
+  // ResBlock conv1's IGemmParams::pgn_applied flag (Fwd::resblock): here rather than on the stack because its address rides in the
+  // recorded parameter bytes and must be the same on every call.  Per-handle mutable state like tapes_ and the arenas: a handle is not
+  // reentrant (one forward at a time).
+  int gn2_applied_ = 0;
  public:
   uint64_t tape_hits_ = 0, tape_records_ = 0;            // (sdmi_unet_tape_stats: tests / bench)
  private:

@@ -54,6 +54,65 @@ int main(){ printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu\n", sizeof(sdmi_unet_cfg
     assert got == want
 
 
+def test_launch_tape_patches_only_declared_caller_words(tmp_path):
+    """csrc/tape.h on the host: synthetic launches recorded under TapeCaller scopes, then retargeted (never replayed).  Only the
+    declared words move, each by its own range -- also when two ranges share one address (eps_out == x), for a pointer inside a
+    struct argument, and not for an undeclared launch whose int pair happens to equal a declared value."""
+    src = r'''
+#include "tape.h"
+#include <cstdio>
+namespace sdmi { thread_local Tape* g_tape_rec = nullptr; }
+using namespace sdmi;
+struct Epi { int M; float eps; const float* rowvec; int ld; };    // (padding after `ld`)
+struct Pair { int lo, hi; };
+static const void* fn = (const void*)&fn;
+#define P(a) ((float*)(uintptr_t)(a))
+int main() {
+  const uint64_t X = 0x7f0000010000ull, EMB = 0x7f0000200000ull, ARENA = 0x7f0000900000ull;
+  Tape t;
+  t.caller[Tape::R_X] = X; t.caller[Tape::R_OUT] = X; t.caller[Tape::R_EMB] = EMB;
+  g_tape_rec = &t;
+  { TapeCaller c(Tape::R_X, P(X)); SDMI_TAPE_PUSH(P(X), P(ARENA), 4); }                     // conv_in (in place: eps_out == x)
+  Epi e = Epi(); e.M = 64; e.eps = 1e-5f; e.rowvec = P(EMB + 640); e.ld = 0;
+  { TapeCaller c(Tape::R_EMB, e.rowvec); SDMI_TAPE_PUSH(e, 3); SDMI_TAPE_PUSH(e, 1); }      // a GEMM and its split-K reduce
+  { int lo = (int)(uint32_t)X, hi = (int)(X >> 32); SDMI_TAPE_PUSH(Pair{lo, hi}, lo, hi); }           // undeclared: an int pair == x
+  { TapeCaller c(Tape::R_OUT, P(X)); SDMI_TAPE_PUSH(P(ARENA), P(X), 8); }                   // conv_out
+  g_tape_rec = nullptr;
+  printf("%d %zu %zu\n", (int)t.broken, t.relocs.size(), t.ops.size());
+  std::vector<unsigned char> before = t.blob;
+  const uintptr_t nb[Tape::R_COUNT] = {0x7f0000a00000ull, 0x7f0000b00000ull, 0, 0, 0x7f0000c00000ull};
+  t.retarget(nb);
+  for (size_t o = 0; o + 8 <= t.blob.size(); o += 8) {
+    uint64_t a, b; memcpy(&a, before.data() + o, 8); memcpy(&b, t.blob.data() + o, 8);
+    if (a != b) printf("%zu %llx %llx\n", o, (unsigned long long)a, (unsigned long long)b);
+  }
+  Tape u;                                                   // a declaration no argument carries: not a usable tape
+  u.caller[Tape::R_CTX] = X;
+  g_tape_rec = &u;
+  { TapeCaller c(Tape::R_CTX, P(X)); SDMI_TAPE_PUSH(P(X + 4), 2); }
+  g_tape_rec = nullptr;
+  printf("%d %zu\n", (int)u.broken, u.relocs.size());
+}
+'''
+    src = src.replace('SDMI_TAPE_PUSH(', 'tape_push_launch(g_tape_rec, fn, dim3(1), dim3(64), 0, ')
+    c = tmp_path / 'tape_probe.cpp'
+    c.write_text(src)
+    exe = str(tmp_path / 'tape_probe')
+    rocm = os.environ.get('ROCM_PATH', '/opt/rocm')
+    subprocess.run(['g++', '-std=c++17', '-Wall', '-Werror', '-D__HIP_PLATFORM_AMD__', '-I', os.path.join(rocm, 'include'),
+                    '-I', os.path.join(ROOT, 'stable-diffusion_amd', 'csrc'), str(c), '-o', exe, '-L', os.path.join(rocm, 'lib'),
+                    '-Wl,-rpath,' + os.path.join(rocm, 'lib'), '-lamdhip64'], check=True)
+    lines = subprocess.run([exe], capture_output=True, text=True, check=True).stdout.split('\n')
+    broken, nrel, nops = map(int, lines[0].split())
+    assert (broken, nrel, nops) == (0, 4, 5)
+    moved = [tuple(int(v, 16) if i else int(v) for i, v in enumerate(ln.split())) for ln in lines[1:5]]
+    X, EMB = 0x7f0000010000, 0x7f0000200000
+    # argument words: conv_in x @0, the two Epi structs (rowvec at +8) @24 and @56, the undeclared pair @88 (unmoved), conv_out's eps_out @120
+    assert moved == [(0, X, 0x7f0000a00000), (32, EMB + 640, 0x7f0000c00000 + 640), (64, EMB + 640, 0x7f0000c00000 + 640),
+                     (120, X, 0x7f0000b00000)], moved
+    assert lines[5].split() == ['1', '0']
+
+
 def test_unet_shim_has_reference_parameter_names():
     """UNetModelHIP.state_dict() keys/shapes == the reference UNetModel's (oracle.weights is pinned to the reference by
     make_golden's strict load), so load_state_dict(sd, strict=False) at scripts/txt2img.py:56 fills every tensor."""

@@ -93,3 +93,79 @@ def test_replayed_forwards_equal_executed_forwards(cfg_name, monkeypatch):
     assert not torch.equal(e_new, want[3])
     monkeypatch.setenv('SDMI_REPLAY', '0')
     assert torch.equal(m(x, t, context=c), e_new)
+
+
+def _forward(m, x, t, ctx, out):
+    """sdmi_unet_forward straight through ctypes (the module would allocate its own eps_out): int64 timesteps, context passed"""
+    from stable_diffusion_amd import _lib
+    B, _, H, W = x.shape
+    L = ctx.shape[1]
+    ws = m._workspace(B, H, W, L, x.device)
+    m._reserve_context(B, L)
+    _lib.check(m._handle.lib.sdmi_unet_forward(m._handle.h, x.data_ptr(), t.data_ptr(), None, ctx.data_ptr(), out.data_ptr(),
+                                               B, H, W, L, ws.data_ptr(), ws.numel(), _lib.stream_ptr()))
+    torch.cuda.synchronize()
+
+
+def test_in_place_recorded_tape_replays_into_separate_buffers(monkeypatch):
+    """A tape recorded with eps_out == x, replayed with separate x' / eps_out': eps_out' gets the executor's bits, x' stays as it was
+    (the relocation of each caller pointer comes from its declaration, not from the range its address falls into)."""
+    m = _model(TINY)
+    (x, t, c, _), (x2, _, _, _) = _calls(TINY)[:2]
+    m(x, t, context=c)                                    # (packs the weights)
+    monkeypatch.setenv('SDMI_REPLAY', '0')
+    want_in_place = x.clone()
+    _forward(m, want_in_place, t, c, want_in_place)
+    want2 = torch.empty_like(x2)
+    _forward(m, x2, t, c, want2)
+    monkeypatch.setenv('SDMI_REPLAY', '1')
+    h0, r0 = _stats(m)
+    buf = x.clone()
+    _forward(m, buf, t, c, buf)                           # records, in place
+    h1, r1 = _stats(m)
+    assert (h1, r1) == (h0, r0 + 1)
+    assert torch.equal(buf, want_in_place)
+    x2c, out2 = x2.clone(), torch.full_like(x2, float('nan'))
+    _forward(m, x2c, t, c, out2)                          # replays, separate buffers
+    assert _stats(m) == (h1 + 1, r1)
+    assert torch.equal(x2c, x2)
+    assert torch.equal(out2, want2)
+
+
+def test_caller_alignment_is_part_of_the_tape_key(monkeypatch):
+    """conv_out takes its 16-byte-store kernel only for a 16-byte aligned eps_out: a tape recorded with an aligned one must not serve a
+    call whose eps_out is 4 bytes off -- that call is executed (and recorded) and gives the executor's bits."""
+    m = _model(TINY)
+    x, t, c, _ = _calls(TINY)[0]
+    m(x, t, context=c)
+
+    def misaligned(src=None, k=1):
+        big = torch.empty(x.numel() + k, dtype=torch.float32, device=x.device)
+        out = big[k:].view(x.shape)
+        assert out.data_ptr() % 16 == 4 * k
+        if src is not None:
+            out.copy_(src)
+        return out
+
+    monkeypatch.setenv('SDMI_REPLAY', '0')
+    want = misaligned()
+    _forward(m, x, t, c, want)
+    monkeypatch.setenv('SDMI_REPLAY', '1')
+    _forward(m, x, t, c, torch.empty_like(x))             # a tape of the aligned eps_out
+    h, r = _stats(m)
+    got = misaligned()
+    _forward(m, x, t, c, got)
+    assert _stats(m) == (h, r + 1)
+    assert torch.equal(got, want)
+    # each pointer's alignment is keyed on its own: a tape recorded with x 8 bytes off and eps_out aligned (conv_out's 16-byte stores)
+    # must not serve a call with x aligned and eps_out 8 bytes off (an offset no tape above was recorded with)
+    monkeypatch.setenv('SDMI_REPLAY', '0')
+    want8 = misaligned(k=2)
+    _forward(m, x, t, c, want8)
+    monkeypatch.setenv('SDMI_REPLAY', '1')
+    _forward(m, misaligned(x, k=2), t, c, torch.empty_like(x))
+    h, r = _stats(m)
+    got = misaligned(k=2)
+    _forward(m, x, t, c, got)
+    assert _stats(m) == (h, r + 1)
+    assert torch.equal(got, want8)
