@@ -52,6 +52,17 @@ int sdmi_has_experiments(void);
 /* ---- UNet handle: replaces instantiate_from_config(unet_config) + load_state_dict ----------------------- */
 /* UNetModel.__init__, openaimodel.py:443-692 */
 int sdmi_unet_create(const sdmi_unet_cfg* cfg, sdmi_unet** out);
+/* Arithmetic of a UNet handle, fixed when it is created.
+ *   MIXED  fp16 MFMA operands, with 3-pass split-fp16 on the op classes the precision allocation names
+ *   FULL   every MFMA operand split-fp16 (hi = fp16(x), lo = fp16(x - hi); a_hi b_hi + a_lo b_hi + a_hi b_lo, fp32 accumulation):
+ *          3x3 / 1x1 convolutions, resamplers, every linear and both attention products.  The row-strip chains and the
+ *          LayerNorm / GroupNorm folds are not used in this mode.  Its packed weights differ: a blob is imported only by a handle of
+ *          the mode that wrote it.
+ * sdmi_unet_create(cfg, out) = sdmi_unet_create_with_precision(cfg, SDMI_PRECISION_MIXED, out). */
+#define SDMI_PRECISION_MIXED 0
+#define SDMI_PRECISION_FULL 1
+int sdmi_unet_create_with_precision(const sdmi_unet_cfg* cfg, int precision, sdmi_unet** out);
+int sdmi_unet_precision(const sdmi_unet* h);      /* SDMI_PRECISION_*, or -1 for a null handle */
 int sdmi_unet_destroy(sdmi_unet* h);
 /* enumerate the state_dict keys the handle expects (= UNetModel.state_dict().keys()) */
 int sdmi_unet_num_weights(const sdmi_unet* h);
@@ -318,6 +329,10 @@ int sdmi_k_attention(const void* q, const void* k, const void* vt, void* out, in
 int sdmi_k_attention_ctx(const void* x, const void* wq, const void* k, const void* vt, void* out, int BH, int heads, int nq,
                          int nkv, int nkv_pad, int d, float scale, const float* lnf_part, float lnf_eps, const float* lnf_cs,
                          const float* lnf_d, void* stream);
+/* split-fp16 attention (the full-precision mode): q / k / vt and their low halves q_lo / k_lo / vt_lo in the layouts above,
+ * out / out_lo fp16 [BH/heads, nq, heads*d] = hi / lo of the fp32 result; d in {32, 40, 64, 80, 128, 160} */
+int sdmi_k_attention_split16(const void* q, const void* q_lo, const void* k, const void* k_lo, const void* vt, const void* vt_lo, void* out,
+                             void* out_lo, int BH, int heads, int nq, int nkv, int nkv_pad, int d, float scale, void* stream);
 /* same with a causal mask (query i attends to keys <= i; nq == nkv): CLIPTextModel's self-attention */
 int sdmi_k_attention_causal(const void* q, const void* k, const void* vt, void* out, int BH, int heads, int n, int n_pad,
                             int d, float scale, void* stream);
@@ -340,6 +355,13 @@ int sdmi_k_conv3gn(const float* x0, const float* x1, int c0, int c1, int B, int 
 int sdmi_k_layernorm(const float* x, const float* gamma, const float* beta, void* out_f16, int M, int C, float eps,
                      void* stream);
 int sdmi_k_cast_f16(const float* x, void* out_f16, void* out_lo, int64_t n, void* stream);
+/* Producers of split-fp16 operands in the full-precision mode: fp32 in, hi / lo fp16 out.
+ * split_heads: columns [col0, col0 + heads*dh) of src [B*ntok][ld] per head -- kind 0: [B*heads][ntok][dh] (q, k), kind 1: [B*heads][dh][ntok_pad]
+ * (v^T, pad tokens zero).  geglu_split: src [M][2F] = proj(x) + bias -> value * gelu(gate) [M][F].  layernorm_split: as sdmi_k_layernorm. */
+int sdmi_k_split_heads(const float* src, int ld, int col0, void* dst, void* dst_lo, int kind, int B, int ntok, int ntok_pad, int heads, int dh,
+                       void* stream);
+int sdmi_k_geglu_split(const float* src, int M, int F, void* out, void* out_lo, void* stream);
+int sdmi_k_layernorm_split(const float* x, const float* gamma, const float* beta, void* out, void* out_lo, int M, int C, float eps, void* stream);
 int sdmi_k_timestep_embedding(const int64_t* t_i64, const float* t_f32, float* out, int B, int dim, void* stream);
 int sdmi_k_small_linear(const float* in, int ld_in, const float* w, const float* bias, float* out, int ld_out, int B,
                         int N, int K, int silu_in, void* stream);

@@ -54,6 +54,8 @@ _SIGS = {
     'sdmi_last_error': (C.c_char_p, []),
     'sdmi_abi_version': (C.c_int, []),
     'sdmi_unet_create': (C.c_int, [C.POINTER(UNetCfg), C.POINTER(c_ptr)]),
+    'sdmi_unet_create_with_precision': (C.c_int, [C.POINTER(UNetCfg), C.c_int, C.POINTER(c_ptr)]),
+    'sdmi_unet_precision': (C.c_int, [c_ptr]),
     'sdmi_unet_destroy': (C.c_int, [c_ptr]),
     'sdmi_unet_num_weights': (C.c_int, [c_ptr]),
     'sdmi_unet_weight_info': (C.c_int, [c_ptr, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int)]),
@@ -103,6 +105,8 @@ _SIGS = {
                                 C.c_int, c_ptr]),
     'sdmi_k_st_head': (C.c_int, [c_ptr, c_ptr, C.c_int64, c_ptr, c_ptr, C.c_float, c_ptr, c_ptr, c_ptr, c_ptr, C.c_float, c_ptr, c_ptr, c_ptr,
                                  c_ptr, c_ptr, c_ptr, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_ptr]),
+    'sdmi_k_attention_split16': (C.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, C.c_int, C.c_int, C.c_int, C.c_int,
+                                           C.c_int, C.c_int, C.c_float, c_ptr]),
     'sdmi_k_attention_causal': (C.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
                                           c_ptr]),
     'sdmi_k_pointwise_nchw': (C.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, c_ptr]),
@@ -117,6 +121,10 @@ _SIGS = {
                                  c_ptr, C.c_int64, C.c_int, c_ptr, c_ptr, c_ptr]),
     'sdmi_k_layernorm': (C.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, C.c_int, C.c_int, C.c_float, c_ptr]),
     'sdmi_k_cast_f16': (C.c_int, [c_ptr, c_ptr, c_ptr, C.c_int64, c_ptr]),
+    'sdmi_k_split_heads': (C.c_int, [c_ptr, C.c_int, C.c_int, c_ptr, c_ptr, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                     c_ptr]),
+    'sdmi_k_geglu_split': (C.c_int, [c_ptr, C.c_int, C.c_int, c_ptr, c_ptr, c_ptr]),
+    'sdmi_k_layernorm_split': (C.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, C.c_int, C.c_int, C.c_float, c_ptr]),
     'sdmi_k_timestep_embedding': (C.c_int, [c_ptr, c_ptr, c_ptr, C.c_int, C.c_int, c_ptr]),
     'sdmi_k_small_linear': (C.c_int, [c_ptr, C.c_int, c_ptr, c_ptr, c_ptr, C.c_int, C.c_int, C.c_int, C.c_int,
                                       C.c_int, c_ptr]),

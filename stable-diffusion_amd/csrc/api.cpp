@@ -4,6 +4,7 @@
 #include <new>
 
 #include "prof.h"
+#include "split16.h"
 #include "unet.h"
 #include "vae.h"
 #include "clip.h"
@@ -45,13 +46,20 @@ int sdmi_has_experiments(void) {
 #endif
 }
 
-int sdmi_unet_create(const sdmi_unet_cfg* cfg, sdmi_unet** out) {
+int sdmi_unet_create(const sdmi_unet_cfg* cfg, sdmi_unet** out) { return sdmi_unet_create_with_precision(cfg, SDMI_PRECISION_MIXED, out); }
+int sdmi_unet_create_with_precision(const sdmi_unet_cfg* cfg, int precision, sdmi_unet** out) {
   SDMI_CHECK(cfg && out, "null argument");
+  SDMI_CHECK(precision == SDMI_PRECISION_MIXED || precision == SDMI_PRECISION_FULL,
+             "precision must be SDMI_PRECISION_MIXED (0) or SDMI_PRECISION_FULL (1), got " + std::to_string(precision));
   sdmi_unet* h = new (std::nothrow) sdmi_unet();
   SDMI_CHECK(h != nullptr, "out of host memory");
-  if (h->impl.build(*cfg)) { delete h; return -1; }
+  if (h->impl.build(*cfg, precision)) { delete h; return -1; }
   *out = h;
   return 0;
+}
+int sdmi_unet_precision(const sdmi_unet* h) {
+  if (!h) { fail("null handle"); return -1; }
+  return h->impl.precision_;
 }
 int sdmi_unet_destroy(sdmi_unet* h) { delete h; return 0; }
 int sdmi_unet_num_weights(const sdmi_unet* h) { return h ? (int)h->impl.slots().size() : fail("null handle"); }
@@ -365,6 +373,14 @@ int sdmi_k_attention(const void* q, const void* k, const void* vt, void* out, in
   if (const char* e = getenv("SDMI_ATTN_NW")) a.nw = atoi(e);     // test / tuning knob
   return launch_attention(a, (hipStream_t)stream);
 }
+int sdmi_k_attention_split16(const void* q, const void* q_lo, const void* k, const void* k_lo, const void* vt, const void* vt_lo, void* out,
+                             void* out_lo, int BH, int heads, int nq, int nkv, int nkv_pad, int d, float scale, void* stream) {
+  AttnSplitParams a = AttnSplitParams();
+  a.q = (const f16*)q; a.q_lo = (const f16*)q_lo; a.k = (const f16*)k; a.k_lo = (const f16*)k_lo; a.vt = (const f16*)vt;
+  a.vt_lo = (const f16*)vt_lo; a.out = (f16*)out; a.out_lo = (f16*)out_lo;
+  a.BH = BH; a.heads = heads; a.nq = nq; a.nkv = nkv; a.nkv_pad = nkv_pad; a.d = d; a.scale = scale;
+  return launch_attention_split16(a, (hipStream_t)stream);
+}
 int sdmi_k_attention_ctx(const void* x, const void* wq, const void* k, const void* vt, void* out, int BH, int heads, int nq,
                          int nkv, int nkv_pad, int d, float scale, const float* lnf_part, float lnf_eps, const float* lnf_cs,
                          const float* lnf_d, void* stream) {
@@ -416,6 +432,16 @@ int sdmi_k_layernorm(const float* x, const float* gamma, const float* beta, void
 }
 int sdmi_k_cast_f16(const float* x, void* out_f16, void* out_lo, int64_t n, void* stream) {
   return launch_cast_f16(x, (f16*)out_f16, (f16*)out_lo, n, (hipStream_t)stream);
+}
+int sdmi_k_split_heads(const float* src, int ld, int col0, void* dst, void* dst_lo, int kind, int B, int ntok, int ntok_pad, int heads, int dh,
+                       void* stream) {
+  return launch_split_heads(src, ld, col0, (f16*)dst, (f16*)dst_lo, kind, B, ntok, ntok_pad, heads, dh, (hipStream_t)stream);
+}
+int sdmi_k_geglu_split(const float* src, int M, int F, void* out, void* out_lo, void* stream) {
+  return launch_geglu_split(src, M, F, (f16*)out, (f16*)out_lo, (hipStream_t)stream);
+}
+int sdmi_k_layernorm_split(const float* x, const float* gamma, const float* beta, void* out, void* out_lo, int M, int C, float eps, void* stream) {
+  return launch_layernorm_split(x, gamma, beta, (f16*)out, (f16*)out_lo, M, C, eps, (hipStream_t)stream);
 }
 int sdmi_k_timestep_embedding(const int64_t* t_i64, const float* t_f32, float* out, int B, int dim, void* stream) {
   return launch_timestep_embedding(t_i64, t_f32, out, B, dim, (hipStream_t)stream);

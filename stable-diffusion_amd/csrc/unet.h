@@ -245,6 +245,7 @@ struct TBlock {   // BasicTransformerBlock (ldm/modules/attention.py:196-215)
   f16* wff2 = nullptr; float* bff2 = nullptr;
   float* ln[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   f16* ck = nullptr; f16* cvt = nullptr;        // cached cross-attention K [B*h][L][d] and V^T [B*h][d][Lpad]
+  f16* ck_lo = nullptr; f16* cvt_lo = nullptr;  // ... their split-fp16 low halves (full-precision mode only)
   // LayerNorm folded into the consuming GEMM (IGemmParams::lnf_cs / lnf_d; computed by finalize() from the packed weights):
   // {cs, d} of attn1 q|k|v with norm1, attn2 to_q with norm2, the GEGLU projection with norm3 (packed column order, bias inside d)
   float* lnf[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -284,7 +285,7 @@ class UNet {
   UNet(const UNet&) = delete;
   UNet& operator=(const UNet&) = delete;
 
-  int build(const sdmi_unet_cfg& cfg);
+  int build(const sdmi_unet_cfg& cfg, int precision = SDMI_PRECISION_MIXED);
   int set_weight(const char* key, const float* ptr, const int64_t* shape, int ndim, hipStream_t stream);
   int finalize();
   // packed-weight blob: every packed device buffer behind a header that pins cfg / ABI
@@ -305,6 +306,10 @@ class UNet {
   const std::vector<WeightSlot>& slots() const { return slots_; }
 
   sdmi_unet_cfg cfg_{};
+  // SDMI_PRECISION_FULL: every MFMA operand split-fp16 (every Layer::p1x1 / precise3, split-fp16 linears, resamplers and attention;
+  // the row-strip chains and the LayerNorm / GroupNorm folds off).  Fixed by build(); the packed weights depend on it.
+  int precision_ = SDMI_PRECISION_MIXED;
+  bool full() const { return precision_ == SDMI_PRECISION_FULL; }
   int te_ = 0, emb_total_ = 0, n_attn_ = 0;
   f16* zero_ = nullptr;
   // 1x1 convs on the residual stream (skip_connection, proj_in, proj_out) run as 3-pass split-fp16 GEMMs

@@ -40,13 +40,16 @@ def make_cfg(in_channels, out_channels, model_channels, num_res_blocks, channel_
     return cfg
 
 
+PRECISIONS = {'mixed': 0, 'full': 1}      # SDMI_PRECISION_MIXED / SDMI_PRECISION_FULL (include/sdmi.h)
+
+
 class _Handle:
     """Owns one sdmi_unet*."""
 
-    def __init__(self, cfg):
+    def __init__(self, cfg, precision='mixed'):
         self.lib = _lib.load()
         h = C.c_void_p()
-        _lib.check(self.lib.sdmi_unet_create(C.byref(cfg), C.byref(h)))
+        _lib.check(self.lib.sdmi_unet_create_with_precision(C.byref(cfg), PRECISIONS[precision], C.byref(h)))
         self.h = h
 
     def weight_specs(self):
@@ -78,8 +81,15 @@ class UNetModelHIP(nn.Module):
                  dropout=0, channel_mult=(1, 2, 4, 8), conv_resample=True, dims=2, num_classes=None,
                  use_checkpoint=False, use_fp16=False, num_heads=-1, num_head_channels=-1, num_heads_upsample=-1,
                  use_scale_shift_norm=False, resblock_updown=False, use_new_attention_order=False,
-                 use_spatial_transformer=False, transformer_depth=1, context_dim=None, n_embed=None, legacy=True):
+                 use_spatial_transformer=False, transformer_depth=1, context_dim=None, n_embed=None, legacy=True,
+                 hip_precision='mixed'):
+        """`hip_precision` (not a keyword of the reference UNetModel): 'mixed' (default) = fp16 MFMA operands with split-fp16 where the
+        precision allocation puts it; 'full' = every MFMA operand split-fp16 (~22-bit operands, fp32 accumulation),
+        slower.  Fixed for the module's lifetime; packed-weight blobs are tied to it."""
         super().__init__()
+        if hip_precision not in PRECISIONS:
+            raise ValueError(f"hip_precision must be one of {sorted(PRECISIONS)}, got {hip_precision!r}")
+        self.hip_precision = hip_precision
         # the SD-v1 family only (configs/stable-diffusion/v1-inference.yaml:29-44); anything else is refused loudly
         unsupported = []
         if not use_spatial_transformer or context_dim is None: unsupported.append('use_spatial_transformer=True with context_dim')
@@ -103,7 +113,7 @@ class UNetModelHIP(nn.Module):
         self.dtype = torch.float32
         self._cfg = make_cfg(in_channels, out_channels, model_channels, num_res_blocks, self.channel_mult,
                              self.attention_resolutions, num_heads, transformer_depth, self.context_dim)
-        self._handle = _Handle(self._cfg)
+        self._handle = _Handle(self._cfg, hip_precision)
         self._specs = self._handle.weight_specs()
         for key, shape in self._specs:
             *path, leaf = key.split('.')

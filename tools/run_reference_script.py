@@ -19,6 +19,9 @@ What this launcher does (nothing in the reference tree is edited or copied):
     `stable_diffusion_amd.clip.FrozenCLIPEmbedderHIP`) to a temp file, passes it as `--config`, and swaps
     `ldm.models.diffusion.plms.PLMSSampler` / `ddim.DDIMSampler` / `dpm_solver.DPMSolverSampler` for the HIP samplers
     before the script imports them;
+  * `--hip --hip-precision full`: also writes `hip_precision: full` into that copy's `unet_config.params` (UNetModelHIP's
+    full-precision mode: every MFMA operand split-fp16).  The script's own `--precision full` is NOT mapped onto it -- pass both
+    to get the reference's fp32 semantics on the HIP UNet;
   * on a GPU-less host (BASELINE.json configs[0], the CPU plumbing check) it neutralises the hard-coded
     `.cuda()` / `torch.device("cuda")` uses (`txt2img.py:64`, `plms.py:18-22`); use `--precision full` there.
 Then it `runpy`-executes the script with the remaining arguments.
@@ -251,12 +254,15 @@ def _report_hip_calls():
     import atexit
     from stable_diffusion_amd import unet as _u, vae as _v, clip as _c
     counts = {'UNetModelHIP.forward': 0, 'AutoencoderKLHIP.decode': 0, 'FrozenCLIPEmbedderHIP.forward': 0}
+    unet_precisions = set()
 
     def wrap(cls, name, key):
         real = getattr(cls, name)
 
         def counted(self, *a, **k):
             counts[key] += 1
+            if hasattr(self, 'hip_precision'):
+                unet_precisions.add(self.hip_precision)
             return real(self, *a, **k)
         setattr(cls, name, counted)
     wrap(_u.UNetModelHIP, 'forward', 'UNetModelHIP.forward')
@@ -266,7 +272,7 @@ def _report_hip_calls():
     def report():
         from stable_diffusion_amd import _lib
         print('run_reference_script: libsdmi calls -- ' + ', '.join(f'{k} x{v}' for k, v in counts.items()) +
-              f' (library: {_lib.LIB_PATH})', flush=True)
+              f' (UNet hip_precision: {", ".join(sorted(unet_precisions)) or "-"}; library: {_lib.LIB_PATH})', flush=True)
     atexit.register(report)
 
 
@@ -288,16 +294,37 @@ def patch_torch_load():
     torch.load = load
 
 
+def add_hip_precision(text, precision):
+    """`hip_precision: <precision>` as the first entry of the (patched) unet_config's params block; other lines unchanged"""
+    lines = text.splitlines(keepends=True)
+    ind = [len(l) - len(l.lstrip()) for l in lines]
+    at = next(i for i, l in enumerate(lines) if l.strip() == 'target: stable_diffusion_amd.unet.UNetModelHIP')
+    parent = next(i for i in range(at - 1, -1, -1) if lines[i].strip() and ind[i] < ind[at])       # unet_config:
+    i = parent + 1
+    while i < len(lines) and (not lines[i].strip() or ind[i] > ind[parent]):
+        if ind[i] == ind[at] and lines[i].strip() == 'params:':
+            inner = next((j for j in range(i + 1, len(lines)) if lines[j].strip()), None)
+            pad = ind[inner] if inner is not None and ind[inner] > ind[i] else ind[i] + 2
+            return ''.join(lines[:i + 1] + [' ' * pad + f'hip_precision: {precision}\n'] + lines[i + 1:])
+        i += 1
+    raise ValueError('no params block under the UNetModelHIP target')
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument('--reference', default=os.environ.get('SD_REFERENCE', '/root/reference'))
     ap.add_argument('--hip', action='store_true', help='UNetModelHIP + HIP samplers (needs the MI355X)')
+    ap.add_argument('--hip-precision', choices=['mixed', 'full'], default=None,
+                    help="with --hip: UNetModelHIP's hip_precision ('full' = split-fp16 on every MFMA operand); the default leaves the yaml "
+                         "without the key (= 'mixed')")
     ap.add_argument('--offline-stubs', action='store_true',
                     help='allow seeded stand-ins for the CLIP tokenizer / text model / safety checker when the HF hub is '
                          'unreachable (synthetic checkpoints only; each substitution prints a warning)')
     ap.add_argument('script', choices=['txt2img', 'img2img'])
     ap.add_argument('rest', nargs=argparse.REMAINDER)
     args = ap.parse_args()
+    if args.hip_precision and not args.hip:
+        ap.error('--hip-precision needs --hip')
     rest = args.rest[1:] if args.rest[:1] == ['--'] else args.rest
     ref = os.path.abspath(args.reference)
     if not os.path.isdir(os.path.join(ref, 'ldm')) and os.path.isdir(os.path.join(BUNDLE, 'ldm')):
@@ -341,7 +368,11 @@ def main():
         old_vae = 'target: ldm.models.autoencoder.AutoencoderKL'
         assert old_vae in text
         text = text.replace(old_vae, 'target: stable_diffusion_amd.vae.AutoencoderKLHIP')
-        tmp.write(text.replace(old, 'target: stable_diffusion_amd.unet.UNetModelHIP'))
+        text = text.replace(old, 'target: stable_diffusion_amd.unet.UNetModelHIP')
+        if args.hip_precision:
+            text = add_hip_precision(text, args.hip_precision)
+            print(f'run_reference_script: unet_config.params.hip_precision = {args.hip_precision}', flush=True)
+        tmp.write(text)
         tmp.close()
         rest = ['--config', tmp.name] + rest
     elif not have_gpu:
