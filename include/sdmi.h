@@ -373,6 +373,9 @@ int sdmi_k_pack_conv_weight(const float* w_oihw, void* dst_f16, int O, int I, in
 int sdmi_k_pack_conv_out(const float* w_oihw, float* dst_ohwi, int O, int I, void* stream);
 /* [N][K] fp32 -> fp16 [N][3K] = [hi | hi | lo] for the 3-pass split-fp16 1x1 convs */
 int sdmi_k_pack_split3(const float* w, void* dst_f16, int N, int K, void* stream);
+/* [O][I][KH][KW] fp32 -> fp16 [O][3 KH KW I]: the 3-pass split-fp16 3x3 conv weights [w_hi | w_hi | w_lo], i.e. sdmi_k_pack_conv_weight
+ * of the virtual [O][3 I][KH][KW] tensor, met by the K-concatenated operand a0 = hi, a1 = lo, a2 = hi (c0 = c1 = c2 = I); I % 64 == 0 */
+int sdmi_k_pack_conv_split3(const float* w_oihw, void* dst_f16, int O, int I, int KH, int KW, void* stream);
 /* first-stage helpers: 1x1 conv NCHW->NCHW on <= 16 channels (input pre-scaled); row softmax fp32 -> fp16 */
 int sdmi_k_pointwise_nchw(const float* x, const float* w, const float* bias, float* out, int B, int Cin, int Cout, int HW,
                           float in_scale, void* stream);

@@ -467,6 +467,9 @@ int sdmi_k_pack_conv_out(const float* w, float* dst, int O, int I, void* stream)
 int sdmi_k_pack_split3(const float* w, void* dst, int N, int K, void* stream) {
   return launch_pack_split3(w, (f16*)dst, N, K, (hipStream_t)stream);
 }
+int sdmi_k_pack_conv_split3(const float* w, void* dst, int O, int I, int KH, int KW, void* stream) {
+  return launch_pack_conv_split3(w, (f16*)dst, O, I, KH, KW, (hipStream_t)stream);
+}
 int sdmi_k_pack_geglu(const float* w, const float* bias, void* wdst, float* bdst, int N, int K, void* stream) {
   return launch_pack_geglu(w, bias, (f16*)wdst, bdst, N, K, (hipStream_t)stream);
 }

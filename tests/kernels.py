@@ -34,6 +34,15 @@ def pack_split3(w):
     return dst
 
 
+def pack_conv_split3(w):
+    """[O,I,KH,KW] fp32 cuda -> fp16 [O, 3*KH*KW*I]: pack_conv_weight of cat([w_hi, w_hi, w_lo], dim=1), the weights of the
+    K-concatenated 3-pass split-fp16 conv (a0 = hi, a1 = lo, a2 = hi)"""
+    O, I, KH, KW = w.shape
+    dst = torch.empty((O, 3 * KH * KW * I), dtype=torch.float16, device=w.device)
+    _lib.check(_lib.load().sdmi_k_pack_conv_split3(w.contiguous().data_ptr(), dst.data_ptr(), O, I, KH, KW, _s()))
+    return dst
+
+
 def cast_f16(x, want_lo=False):
     hi = torch.empty(x.shape, dtype=torch.float16, device=x.device)
     lo = torch.empty_like(hi) if want_lo else None

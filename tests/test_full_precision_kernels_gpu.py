@@ -59,12 +59,29 @@ def _attention_ref(q, k, vt, heads, nkv):
 
 
 ATTN_CASES = [(d, n, n) for d in (40, 80, 160) for n in (64, 1024, 4096, 9216)] + [(d, 1024, 77) for d in (40, 80, 160)]
+# the d = 32 / 64 / 128 instantiations; ragged query tails (one wave = 32 queries, one workgroup = 128); short and ragged key
+# tiles (64 keys per tile, nkv_pad = round8(nkv))
+ATTN_CASES += [(d, n, n) for d in (32, 64, 128) for n in (64, 1024)] + [(d, 1024, 77) for d in (32, 64, 128)] + [(64, 4096, 4096)]
+ATTN_CASES += [(40, 1, 77), (64, 31, 1024), (80, 33, 77), (128, 129, 130), (32, 4095, 4095)]
+ATTN_CASES += [(32, 64, 1), (40, 129, 3), (64, 33, 31), (80, 256, 33), (128, 64, 63), (160, 128, 65), (64, 1024, 130)]
+
+
+def _half_step(hi):
+    """half the fp16 spacing at each hi (the subnormal spacing at 0)"""
+    h = hi.float().abs()
+    return torch.where(h == 0, torch.full_like(h, 2.0 ** -25), 2.0 ** (torch.floor(torch.log2(h.clamp_min(2.0 ** -14))) - 11))
+
+
+def _lo_is_a_low_half(hi, lo):
+    return bool(torch.isfinite(lo.float()).all()) and bool((lo.float().abs() <= _half_step(hi) * (1 + 2.0 ** -10)).all())
 
 
 @pytest.mark.parametrize('d,nq,nkv', ATTN_CASES)
 def test_attention_split16(d, nq, nkv):
     """softmax(q k^T d^-1/2) v with every operand split-fp16: max-abs error relative to max|O| <= 1e-5 (fp16-operand attention: ~1e-3).
-    B * heads = 16; cross-attention over 77 context tokens padded to 80 (pad keys of v^T zero, as the executor writes them)."""
+    B * heads = 16; cross-attention over 77 context tokens padded to 80 (pad keys of v^T zero, as the executor writes them).
+    The low halves are finite and at most half an fp16 step of hi.  (Measured on an MI355X over these cases and the head-layout /
+    large-logit ones below: <= 3.3e-6.)"""
     g = _g(1000 + d + nq + nkv)
     BH, heads = 16, 8
     nkv_pad = (nkv + 7) // 8 * 8
@@ -78,6 +95,56 @@ def test_attention_split16(d, nq, nkv):
     rel_hi = float((out.double() - ref).abs().max() / ref.abs().max())
     print(f'[attention split16 d{d} nq{nq} nkv{nkv}] max-abs / max|O| {rel:.2e} (hi alone {rel_hi:.2e})', flush=True)
     assert bool(torch.isfinite(out.float()).all()) and rel <= 1e-5
+    assert _lo_is_a_low_half(out, out_lo)
+
+
+def _attention_inputs(g, BH, d, nq, nkv):
+    nkv_pad = (nkv + 7) // 8 * 8
+    q = torch.randn((BH, nq, d), generator=g).to(DEV)
+    k = torch.randn((BH, nkv, d), generator=g).to(DEV)
+    vt = torch.zeros((BH, d, nkv_pad), device=DEV)
+    vt[:, :, :nkv] = torch.randn((BH, d, nkv), generator=g).to(DEV)
+    return q, k, vt
+
+
+@pytest.mark.parametrize('BH,heads,d,nq,nkv', [(2, 1, 64, 129, 65), (2, 1, 160, 33, 77), (10, 5, 40, 31, 77), (10, 5, 128, 256, 33),
+                                               (10, 5, 80, 1024, 1024)])
+def test_attention_split16_head_layouts(BH, heads, d, nq, nkv):
+    """one head, and an odd head count: the output's [b][q][head * d] addressing of (batch, head) pair bh"""
+    q, k, vt = _attention_inputs(_g(2000 + BH + d + nq + nkv), BH, d, nq, nkv)
+    out, out_lo = attention_split16(q, k, vt, heads, nkv)
+    ref = _attention_ref(q, k, vt, heads, nkv)
+    rel = float((_join(out, out_lo) - ref).abs().max() / ref.abs().max())
+    print(f'[attention split16 BH{BH} heads{heads} d{d} nq{nq} nkv{nkv}] max-abs / max|O| {rel:.2e}', flush=True)
+    assert bool(torch.isfinite(out.float()).all()) and rel <= 1e-5
+    assert _lo_is_a_low_half(out, out_lo)
+
+
+@pytest.mark.parametrize('d,nq,nkv', [(64, 256, 1024), (40, 129, 77), (160, 64, 130)])
+def test_attention_split16_large_logits(d, nq, nkv):
+    """|score * scale| up to ~60 with every query's maximum in the LAST key tile: the running max jumps there and the earlier
+    tiles' sums and outputs are rescaled by alpha = exp(m_old - m_new).  Every query leans on a unit direction u (60 u) that only the
+    last key has (sqrt(d) u): its score is 60 + N(0, 10); the other keys are orthogonal to u and score ~N(0, 10^2), so in some
+    rows the earlier tiles come within ~10 of the maximum and their rescaled share is well above the bar."""
+    g = _g(3000 + d + nq + nkv)
+    BH, heads = 4, 2
+    q, k, vt = _attention_inputs(g, BH, d, nq, nkv)
+    u = torch.randn((BH, 1, d), generator=g).to(DEV)
+    u = u / u.norm(dim=-1, keepdim=True)
+    q = q * 10 ** 0.5 + 60.0 * u
+    k = k * 10 ** 0.5
+    k = k - (k @ u.transpose(1, 2)) * u              # no other key sees u
+    k[:, nkv - 1] = d ** 0.5 * u[:, 0]
+    s = (q.double() @ k.double().transpose(1, 2)) * d ** -0.5
+    last_tile = (nkv - 1) // 64 * 64
+    assert float(s.abs().max()) >= 55.0 and bool((s.argmax(dim=-1) >= last_tile).all())
+    out, out_lo = attention_split16(q, k, vt, heads, nkv)
+    ref = _attention_ref(q, k, vt, heads, nkv)
+    rel = float((_join(out, out_lo) - ref).abs().max() / ref.abs().max())
+    print(f'[attention split16 large logits d{d} nq{nq} nkv{nkv}] max |s scale| {float(s.abs().max()):.1f}, '
+          f'max-abs / max|O| {rel:.2e}', flush=True)
+    assert bool(torch.isfinite(out.float()).all()) and rel <= 1e-5
+    assert _lo_is_a_low_half(out, out_lo)
 
 
 @pytest.mark.parametrize('kind,ntok', [(0, 77), (0, 256), (1, 77), (1, 256)])
@@ -97,6 +164,36 @@ def test_split_heads(kind, ntok):
         x = torch.cat([x.transpose(1, 2), torch.zeros((B * heads, dh, ntok_pad - ntok), device=DEV)], dim=2)
     ok, worst = _reconstructs(hi, lo, x)
     print(f'[split heads kind {kind} ntok {ntok}] worst relative reconstruction error {worst:.2e}', flush=True)
+    assert ok
+
+
+@pytest.mark.parametrize('kind', [0, 1])
+@pytest.mark.parametrize('dh', [32, 64, 80, 160])
+@pytest.mark.parametrize('seg', [0, 1, 2])
+@pytest.mark.parametrize('ntok', [1, 3, 4096])
+def test_split_heads_edges(kind, dh, seg, ntok):
+    """head widths 32 .. 160, every column segment of a [q | k | v] source (col0 = 0, C, 2C), 1, 3 and 4096 tokens; kind 1
+    writes its pad tokens as exactly +0 in hi and lo (NaN before), which attn_split16 multiplies by zero probabilities"""
+    g = _g(17 + kind + dh + seg + ntok)
+    B, heads = 2, 8
+    C = heads * dh
+    ld, col0 = 3 * C, seg * C
+    ntok_pad = (ntok + 7) // 8 * 8
+    src = (torch.randn((B * ntok, ld), generator=g) * 3).to(DEV)
+    shape = (B * heads, ntok, dh) if kind == 0 else (B * heads, dh, ntok_pad)
+    hi = torch.full(shape, float('nan'), dtype=torch.float16, device=DEV)
+    lo = torch.full(shape, float('nan'), dtype=torch.float16, device=DEV)
+    _lib.check(_lib.load().sdmi_k_split_heads(src.data_ptr(), ld, col0, hi.data_ptr(), lo.data_ptr(), kind, B, ntok, ntok_pad, heads, dh, _s()))
+    torch.cuda.synchronize()
+    x = src[:, col0:col0 + C].reshape(B, ntok, heads, dh).permute(0, 2, 1, 3).reshape(B * heads, ntok, dh)
+    if kind == 1:
+        x = x.transpose(1, 2)
+        for t in (hi, lo):
+            pad = t[:, :, ntok:].contiguous().view(torch.int16)
+            assert torch.equal(pad, torch.zeros_like(pad))
+        hi, lo = hi[:, :, :ntok], lo[:, :, :ntok]
+    ok, worst = _reconstructs(hi, lo, x)
+    print(f'[split heads kind {kind} dh {dh} col0 {col0} ntok {ntok}] worst relative reconstruction error {worst:.2e}', flush=True)
     assert ok
 
 
