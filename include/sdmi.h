@@ -207,6 +207,37 @@ int64_t sdmi_clip_workspace_bytes(sdmi_clip* h, int B, int L);
 int sdmi_clip_forward(sdmi_clip* h, const int64_t* ids, float* out, int B, int L, void* workspace, int64_t workspace_bytes,
                       void* stream);
 
+/* ---- text encoder of the LAION-400M model (BERTEmbedder) -------------------------------------------------------
+ * Replaces `self.transformer(tokens, return_embeddings=True)` of BERTEmbedder.forward (ldm/modules/encoders/modules.py:
+ * 80-103): x_transformer.TransformerWrapper(attn_layers=Encoder(dim, depth)) -- token + absolute position embedding,
+ * `depth` pre-norm (attention, feed-forward) pairs (bias-free q/k/v of width heads*dim_head, non-causal, no mask; exact-erf
+ * GELU), final LayerNorm.  The tokenizer stays on the host. */
+typedef struct sdmi_bert sdmi_bert;
+/* LAION-400M (txt2img-1p4B-eval.yaml): 30522, 1280, 32, 8, 64, 5120, 77.  dim and ff_inner multiples of 64, dim_head one
+ * the attention kernel has (32, 40, 64, 80, 128, 160) */
+typedef struct sdmi_bert_cfg {
+  int32_t vocab_size;
+  int32_t dim;
+  int32_t depth;
+  int32_t heads;
+  int32_t dim_head;
+  int32_t ff_inner;
+  int32_t max_seq_len;
+} sdmi_bert_cfg;
+int sdmi_bert_create(const sdmi_bert_cfg* cfg, sdmi_bert** out);
+int sdmi_bert_destroy(sdmi_bert* h);
+/* state_dict keys of TransformerWrapper (`token_emb.weight`, `pos_emb.emb.weight`, `attn_layers.layers.N...`, `norm...`,
+ * `to_logits...`), i.e. the checkpoint's `cond_stage_model.transformer.` sub-tree.  `to_logits.*` is shape-checked and
+ * dropped (return_embeddings=True never applies it); finalize does not require it. */
+int sdmi_bert_num_weights(const sdmi_bert* h);
+int sdmi_bert_weight_info(const sdmi_bert* h, int idx, char* key_buf, int key_buf_len, int64_t* shape4, int* ndim);
+int sdmi_bert_set_weight(sdmi_bert* h, const char* key, const float* ptr, const int64_t* shape, int ndim, void* stream);
+int sdmi_bert_finalize(sdmi_bert* h);
+int64_t sdmi_bert_workspace_bytes(sdmi_bert* h, int B, int L);
+/* ids: int64 [B, L] token ids (device), B <= 64, L <= max_seq_len; out: fp32 [B, L, dim] */
+int sdmi_bert_forward(sdmi_bert* h, const int64_t* ids, float* out, int B, int L, void* workspace, int64_t workspace_bytes,
+                      void* stream);
+
 /* ---- kernel-level entry points (parity tests and micro-benchmarks; same kernels the UNet uses) ---------- */
 typedef struct sdmi_igemm_desc {
   const void* a0; const void* a1; const void* a2;   /* fp16 NHWC sources, channel concat [a0|a1|a2] (a1, a2 optional) */
@@ -380,6 +411,8 @@ int sdmi_k_pack_conv_split3(const float* w_oihw, void* dst_f16, int O, int I, in
 int sdmi_k_pointwise_nchw(const float* x, const float* w, const float* bias, float* out, int B, int Cin, int Cout, int HW,
                           float in_scale, void* stream);
 int sdmi_k_softmax_rows(const float* S, void* P_f16, int rows, int cols, float scale, void* stream);
+/* exact-erf GELU (the BERT encoder's feed-forward activation): fp32 [n] -> fp16 [n], n % 4 == 0 */
+int sdmi_k_gelu_erf(const float* x, void* out_f16, int64_t n, void* stream);
 int sdmi_k_pack_geglu(const float* w, const float* bias, void* wdst_f16, float* bdst, int N, int K, void* stream);
 /* Host post-processing of scripts/txt2img.py:313-324, on the device: img fp32 [B, C, H, W] (the
  * decode_first_stage output) -> uint8 [B, H, W, C] = astype(uint8)(255 * clamp((img + 1) / 2, 0, 1)), bit-identical to

@@ -27,6 +27,11 @@ class ClipCfg(C.Structure):
                 ('num_layers', C.c_int32), ('num_heads', C.c_int32), ('max_positions', C.c_int32)]
 
 
+class BertCfg(C.Structure):
+    _fields_ = [('vocab_size', C.c_int32), ('dim', C.c_int32), ('depth', C.c_int32), ('heads', C.c_int32),
+                ('dim_head', C.c_int32), ('ff_inner', C.c_int32), ('max_seq_len', C.c_int32)]
+
+
 class IGemmDesc(C.Structure):
     _fields_ = [('a0', c_ptr), ('a1', c_ptr), ('a2', c_ptr),
                 ('c0', C.c_int32), ('c1', C.c_int32), ('c2', C.c_int32),
@@ -94,6 +99,14 @@ _SIGS = {
     'sdmi_clip_finalize': (C.c_int, [c_ptr]),
     'sdmi_clip_workspace_bytes': (C.c_int64, [c_ptr, C.c_int, C.c_int]),
     'sdmi_clip_forward': (C.c_int, [c_ptr, c_ptr, c_ptr, C.c_int, C.c_int, c_ptr, C.c_int64, c_ptr]),
+    'sdmi_bert_create': (C.c_int, [C.POINTER(BertCfg), C.POINTER(c_ptr)]),
+    'sdmi_bert_destroy': (C.c_int, [c_ptr]),
+    'sdmi_bert_num_weights': (C.c_int, [c_ptr]),
+    'sdmi_bert_weight_info': (C.c_int, [c_ptr, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int)]),
+    'sdmi_bert_set_weight': (C.c_int, [c_ptr, C.c_char_p, c_ptr, C.POINTER(C.c_int64), C.c_int, c_ptr]),
+    'sdmi_bert_finalize': (C.c_int, [c_ptr]),
+    'sdmi_bert_workspace_bytes': (C.c_int64, [c_ptr, C.c_int, C.c_int]),
+    'sdmi_bert_forward': (C.c_int, [c_ptr, c_ptr, c_ptr, C.c_int, C.c_int, c_ptr, C.c_int64, c_ptr]),
     'sdmi_has_experiments': (C.c_int, []),
     'sdmi_k_igemm': (C.c_int, [C.POINTER(IGemmDesc), c_ptr]),
     'sdmi_k_ff_tail': (C.c_int, [C.POINTER(IGemmDesc), c_ptr, c_ptr, C.c_float, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
@@ -111,6 +124,7 @@ _SIGS = {
                                           c_ptr]),
     'sdmi_k_pointwise_nchw': (C.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, c_ptr]),
     'sdmi_k_softmax_rows': (C.c_int, [c_ptr, c_ptr, C.c_int, C.c_int, C.c_float, c_ptr]),
+    'sdmi_k_gelu_erf': (C.c_int, [c_ptr, c_ptr, C.c_int64, c_ptr]),
     'sdmi_k_attention': (C.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                    C.c_float, c_ptr]),
     'sdmi_k_groupnorm': (C.c_int, [c_ptr, c_ptr, C.c_int, C.c_int, C.c_int, C.c_int, c_ptr, c_ptr, C.c_float, C.c_int,

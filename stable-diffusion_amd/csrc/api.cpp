@@ -18,6 +18,7 @@ int fail(const std::string& msg) { g_err = msg; return -1; }
 struct sdmi_unet { sdmi::UNet impl; };
 struct sdmi_vae { sdmi::Vae impl; };
 struct sdmi_clip { sdmi::ClipText impl; };
+struct sdmi_bert { sdmi::BertText impl; };
 
 using namespace sdmi;
 
@@ -223,15 +224,19 @@ int sdmi_clip_create(const sdmi_clip_cfg* cfg, sdmi_clip** out) {
 }
 int sdmi_clip_destroy(sdmi_clip* h) { delete h; return 0; }
 int sdmi_clip_num_weights(const sdmi_clip* h) { return h ? (int)h->impl.slots().size() : fail("null handle"); }
-int sdmi_clip_weight_info(const sdmi_clip* h, int idx, char* key_buf, int key_buf_len, int64_t* shape4, int* ndim) {
-  SDMI_CHECK(h && key_buf && shape4 && ndim, "null argument");
-  SDMI_CHECK(idx >= 0 && idx < (int)h->impl.slots().size(), "weight index out of range");
-  const CWeightSlot& s = h->impl.slots()[idx];
+static int text_weight_info(const TextEncBase& t, int idx, char* key_buf, int key_buf_len, int64_t* shape4, int* ndim) {
+  SDMI_CHECK(key_buf && shape4 && ndim, "null argument");
+  SDMI_CHECK(idx >= 0 && idx < (int)t.slots().size(), "weight index out of range");
+  const CWeightSlot& s = t.slots()[idx];
   SDMI_CHECK((int)s.key.size() + 1 <= key_buf_len, "key buffer too small");
   memcpy(key_buf, s.key.c_str(), s.key.size() + 1);
   *ndim = (int)s.shape.size();
   for (int i = 0; i < 4; ++i) shape4[i] = i < *ndim ? s.shape[i] : 1;
   return 0;
+}
+int sdmi_clip_weight_info(const sdmi_clip* h, int idx, char* key_buf, int key_buf_len, int64_t* shape4, int* ndim) {
+  SDMI_CHECK(h && key_buf && shape4 && ndim, "null argument");
+  return text_weight_info(h->impl, idx, key_buf, key_buf_len, shape4, ndim);
 }
 int sdmi_clip_set_weight(sdmi_clip* h, const char* key, const float* ptr, const int64_t* shape, int ndim, void* stream) {
   SDMI_CHECK(h && key && ptr && shape, "null argument");
@@ -248,6 +253,41 @@ int sdmi_clip_forward(sdmi_clip* h, const int64_t* ids, float* out, int B, int L
                       void* stream) {
   SDMI_CHECK(h && ids && out, "null argument");
   return h->impl.forward(ids, out, B, L, workspace, workspace_bytes, (hipStream_t)stream, false, nullptr);
+}
+
+// ---- text encoder of the LAION-400M model ----------------------------------------------------------------------------
+int sdmi_bert_create(const sdmi_bert_cfg* cfg, sdmi_bert** out) {
+  SDMI_CHECK(cfg && out, "null argument");
+  sdmi_bert* h = new (std::nothrow) sdmi_bert();
+  SDMI_CHECK(h != nullptr, "out of host memory");
+  if (h->impl.build(*cfg)) { delete h; return -1; }
+  *out = h;
+  return 0;
+}
+int sdmi_bert_destroy(sdmi_bert* h) { delete h; return 0; }
+int sdmi_bert_num_weights(const sdmi_bert* h) { return h ? (int)h->impl.slots().size() : fail("null handle"); }
+int sdmi_bert_weight_info(const sdmi_bert* h, int idx, char* key_buf, int key_buf_len, int64_t* shape4, int* ndim) {
+  SDMI_CHECK(h && key_buf && shape4 && ndim, "null argument");
+  return text_weight_info(h->impl, idx, key_buf, key_buf_len, shape4, ndim);
+}
+int sdmi_bert_set_weight(sdmi_bert* h, const char* key, const float* ptr, const int64_t* shape, int ndim, void* stream) {
+  SDMI_CHECK(h && key && ptr && shape, "null argument");
+  return h->impl.set_weight(key, ptr, shape, ndim, (hipStream_t)stream);
+}
+int sdmi_bert_finalize(sdmi_bert* h) { SDMI_CHECK(h, "null handle"); return h->impl.finalize(); }
+int64_t sdmi_bert_workspace_bytes(sdmi_bert* h, int B, int L) {
+  if (!h) { fail("null handle"); return 0; }
+  int64_t need = 0;
+  if (h->impl.forward(nullptr, nullptr, B, L, nullptr, 0, nullptr, true, &need)) return 0;
+  return need;
+}
+int sdmi_bert_forward(sdmi_bert* h, const int64_t* ids, float* out, int B, int L, void* workspace, int64_t workspace_bytes,
+                      void* stream) {
+  SDMI_CHECK(h && ids && out, "null argument");
+  return h->impl.forward(ids, out, B, L, workspace, workspace_bytes, (hipStream_t)stream, false, nullptr);
+}
+int sdmi_k_gelu_erf(const float* x, void* out_f16, int64_t n, void* stream) {
+  return launch_gelu_erf(x, (f16*)out_f16, n, (hipStream_t)stream);
 }
 int sdmi_k_attention_causal(const void* q, const void* k, const void* vt, void* out, int BH, int heads, int n, int n_pad,
                             int d, float scale, void* stream) {

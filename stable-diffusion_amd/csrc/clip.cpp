@@ -13,7 +13,7 @@
 
 namespace sdmi {
 
-void ClipText::expect(const std::string& key, std::vector<int64_t> shape, CWKind kind, void** dst, int row0, int total_rows) {
+void TextEncBase::expect(const std::string& key, std::vector<int64_t> shape, CWKind kind, void** dst, int row0, int total_rows) {
   CWeightSlot s;
   s.key = key; s.shape = std::move(shape); s.kind = kind; s.dst = dst; s.row0 = row0; s.total_rows = total_rows;
   slot_index_[key] = (int)slots_.size();
@@ -56,18 +56,18 @@ int ClipText::build(const sdmi_clip_cfg& c) {
   return 0;
 }
 
-ClipText::~ClipText() {
+TextEncBase::~TextEncBase() {
   for (void* p : owned_) (void)hipFree(p);
 }
 
-int ClipText::dev_alloc(void** dst, size_t bytes) {
+int TextEncBase::dev_alloc(void** dst, size_t bytes) {
   if (*dst) return 0;
   SDMI_HIP_OK(hipMalloc(dst, bytes));
   owned_.push_back(*dst);
   return 0;
 }
 
-int ClipText::set_weight(const char* key, const float* ptr, const int64_t* shape, int ndim, hipStream_t stream) {
+int TextEncBase::set_weight(const char* key, const float* ptr, const int64_t* shape, int ndim, hipStream_t stream) {
   auto it = slot_index_.find(key);
   if (it == slot_index_.end()) return fail(std::string("unexpected weight key: ") + key);
   CWeightSlot& s = slots_[it->second];
@@ -76,6 +76,10 @@ int ClipText::set_weight(const char* key, const float* ptr, const int64_t* shape
   for (int i = 0; i < ndim; ++i) {
     SDMI_CHECK(shape[i] == s.shape[i], std::string("shape mismatch for ") + key);
     numel *= shape[i];
+  }
+  if (s.kind == CW_DROP) {
+    s.set = true;
+    return 0;
   }
   DevStage st;
   if (st.acquire(ptr, numel, stream)) return -1;
@@ -94,6 +98,8 @@ int ClipText::set_weight(const char* key, const float* ptr, const int64_t* shape
       if (!rc)
         SDMI_HIP_OK(hipMemcpyAsync((float*)*s.dst + s.row0, st.dptr, numel * sizeof(float), hipMemcpyDeviceToDevice, stream));
       break;
+    case CW_DROP:
+      break;
   }
   if (st.release(stream)) return -1;
   if (rc) return rc;
@@ -102,9 +108,9 @@ int ClipText::set_weight(const char* key, const float* ptr, const int64_t* shape
   return 0;
 }
 
-int ClipText::finalize() {
+int TextEncBase::finalize() {
   for (auto& s : slots_)
-    if (!s.set) return fail("weight not set: " + s.key);
+    if (!s.set && s.kind != CW_DROP) return fail("weight not set: " + s.key);
   if (!zero_) {
     SDMI_HIP_OK(hipMalloc((void**)&zero_, 4096));
     owned_.push_back(zero_);

@@ -1,4 +1,5 @@
-// Text-encoder executor state (see clip.cpp): HF CLIPTextModel as wrapped by FrozenCLIPEmbedder.
+// Text-encoder executor state: HF CLIPTextModel as wrapped by FrozenCLIPEmbedder (clip.cpp) and the LAION-400M model's
+// BERTEmbedder transformer (bert.cpp).
 #pragma once
 #include <map>
 #include <string>
@@ -10,7 +11,8 @@
 
 namespace sdmi {
 
-enum CWKind { CW_F32, CW_ROWS16, CW_BIAS_ROWS };
+// CW_DROP: accepted (shape-checked) and never uploaded -- a checkpoint tensor the forward does not use
+enum CWKind { CW_F32, CW_ROWS16, CW_BIAS_ROWS, CW_DROP };
 
 struct CLayer {   // CLIPEncoderLayer
   f16* wqkv = nullptr; float* bqkv = nullptr;     // [3C][C], [3C]   q_proj | k_proj | v_proj
@@ -28,32 +30,62 @@ struct CWeightSlot {
   bool set = false;
 };
 
-class ClipText {
+// Host plumbing shared by the text encoders: the weight-slot table (key -> shape, packing kind, device destination), staging of
+// caller tensors, device allocation and the all-set check.  No device code of its own.
+class TextEncBase {
  public:
-  ClipText() = default;
-  ~ClipText();
-  ClipText(const ClipText&) = delete;
-  ClipText& operator=(const ClipText&) = delete;
+  TextEncBase() = default;
+  ~TextEncBase();
+  TextEncBase(const TextEncBase&) = delete;
+  TextEncBase& operator=(const TextEncBase&) = delete;
 
-  int build(const sdmi_clip_cfg& cfg);
   int set_weight(const char* key, const float* ptr, const int64_t* shape, int ndim, hipStream_t stream);
   int finalize();
-  // ids int64 [B][L] (device) -> last_hidden_state fp32 [B][L][hidden] (after final_layer_norm)
-  int forward(const int64_t* ids, float* out, int B, int L, void* workspace, int64_t ws_bytes, hipStream_t stream, bool dry,
-              int64_t* bytes_needed);
   const std::vector<CWeightSlot>& slots() const { return slots_; }
-  sdmi_clip_cfg cfg_{};
 
- private:
+ protected:
   void expect(const std::string& key, std::vector<int64_t> shape, CWKind kind, void** dst, int row0 = 0, int total_rows = 0);
   int dev_alloc(void** dst, size_t bytes);
-  std::vector<CLayer> layers_;
   std::vector<CWeightSlot> slots_;
   std::map<std::string, int> slot_index_;
   std::vector<void*> owned_;
-  float *tok_ = nullptr, *pos_ = nullptr, *fln_g_ = nullptr, *fln_b_ = nullptr;
   f16* zero_ = nullptr;
   bool finalized_ = false;
+};
+
+class ClipText : public TextEncBase {
+ public:
+  int build(const sdmi_clip_cfg& cfg);
+  // ids int64 [B][L] (device) -> last_hidden_state fp32 [B][L][hidden] (after final_layer_norm)
+  int forward(const int64_t* ids, float* out, int B, int L, void* workspace, int64_t ws_bytes, hipStream_t stream, bool dry,
+              int64_t* bytes_needed);
+  sdmi_clip_cfg cfg_{};
+
+ private:
+  std::vector<CLayer> layers_;
+  float *tok_ = nullptr, *pos_ = nullptr, *fln_g_ = nullptr, *fln_b_ = nullptr;
+};
+
+struct BLayer {   // one ('a', 'f') pair of x_transformer.Encoder
+  f16* wqkv = nullptr;                            // [3 inner][dim]   to_q | to_k | to_v (no bias)
+  f16* wo = nullptr; float* bo = nullptr;         // to_out [dim][inner]
+  f16* w1 = nullptr; float* b1 = nullptr;         // net.0.0 [ff_inner][dim]
+  f16* w2 = nullptr; float* b2 = nullptr;         // net.2 [dim][ff_inner]
+  float* ln[4] = {nullptr, nullptr, nullptr, nullptr};   // layers.{2i}.0.{weight,bias}, layers.{2i+1}.0.{weight,bias}
+};
+
+// BERTEmbedder's TransformerWrapper(return_embeddings=True) (see bert.cpp)
+class BertText : public TextEncBase {
+ public:
+  int build(const sdmi_bert_cfg& cfg);
+  // ids int64 [B][L] (device) -> embeddings fp32 [B][L][dim] (after the final LayerNorm)
+  int forward(const int64_t* ids, float* out, int B, int L, void* workspace, int64_t ws_bytes, hipStream_t stream, bool dry,
+              int64_t* bytes_needed);
+  sdmi_bert_cfg cfg_{};
+
+ private:
+  std::vector<BLayer> layers_;
+  float *tok_ = nullptr, *pos_ = nullptr, *fln_g_ = nullptr, *fln_b_ = nullptr;
 };
 
 }  // namespace sdmi

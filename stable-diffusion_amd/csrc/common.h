@@ -453,6 +453,7 @@ int launch_dpm_step(const DpmStepParams& p, hipStream_t s);
 int launch_embed_tokens(const int64_t* ids, const float* tok_emb, const float* pos_emb, float* out, int M, int L, int C,
                         int vocab, hipStream_t s);
 int launch_quick_gelu(const float* x, f16* out, int64_t n, hipStream_t s);
+int launch_gelu_erf(const float* x, f16* out, int64_t n, hipStream_t s);
 
 // first-stage (VAE) helpers
 int launch_pointwise_nchw(const float* x_nchw, const float* w, const float* bias, float* out_nchw, int B, int Cin, int Cout,

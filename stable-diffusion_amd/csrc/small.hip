@@ -6,6 +6,7 @@
 //     they also fold the NCHW<->NHWC layout change at the library boundary.
 //   * weight packing kernels (reference layouts -> fp16 [N][K] with K = (ky,kx,cin)).
 #include "common.h"
+#include "igemm_dev.h"   // gelu_erf (shared with the GEGLU epilogue)
 #include "prof.h"
 #include <math.h>
 #include <vector>
@@ -437,6 +438,18 @@ __global__ void __launch_bounds__(256) quick_gelu_kernel(const float* x, f16* ou
   *(f16x4*)(out + i * 4) = y;
 }
 
+// exact-erf GELU (nn.GELU() of the LAION-400M BERT encoder's feed-forward, x_transformer.py:201), fp32 in -> fp16 out; the
+// same erf as the UNet's GEGLU epilogue
+__global__ void __launch_bounds__(256) gelu_erf_kernel(const float* x, f16* out, int64_t n4) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n4) return;
+  const f32x4 v = *(const f32x4*)(x + i * 4);
+  f16x4 y;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) y[j] = (f16)gelu_erf(v[j]);
+  *(f16x4*)(out + i * 4) = y;
+}
+
 // ---- first-stage (VAE) helpers ---------------------------------------------------------------------------------------
 // 1x1 conv on a few channels, NCHW fp32 -> NCHW fp32, input optionally pre-scaled:
 // post_quant_conv / quant_conv (ldm/models/autoencoder.py:302-303) and the 1/scale_factor of decode_first_stage
@@ -573,6 +586,13 @@ int launch_embed_tokens(const int64_t* ids, const float* tok_emb, const float* p
 int launch_quick_gelu(const float* x, f16* out, int64_t n, hipStream_t s) {
   SDMI_CHECK(n % 4 == 0, "quick_gelu: n % 4");
   SDMI_LAUNCH(quick_gelu_kernel, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, s, x, out, n / 4);
+  SDMI_HIP_OK(hipGetLastError());
+  return 0;
+}
+
+int launch_gelu_erf(const float* x, f16* out, int64_t n, hipStream_t s) {
+  SDMI_CHECK(n % 4 == 0, "gelu_erf: n % 4");
+  SDMI_LAUNCH(gelu_erf_kernel, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, s, x, out, n / 4);
   SDMI_HIP_OK(hipGetLastError());
   return 0;
 }

@@ -82,6 +82,27 @@ def synthetic_clip_state_dict(text_config=None, seed=0):
     return {k: v.detach().clone() for k, v in m.state_dict().items()}
 
 
+
+@torch.no_grad()
+def synthetic_bert_state_dict(n_embed=1280, n_layer=32, vocab_size=30522, max_seq_len=77, seed=0):
+    """CPU state_dict (keys `transformer.*`, as under `cond_stage_model.` in the LAION-400M checkpoint) of a seeded random
+    BERTEmbedder transformer, to_logits included."""
+    from .bert import make_bert_cfg, _BertHandle
+    specs = _BertHandle(make_bert_cfg(n_embed, n_layer, vocab_size, max_seq_len)).weight_specs()
+    g = torch.Generator().manual_seed(seed)
+    sd = {}
+    for name, shape in specs:
+        if name.startswith(('token_emb', 'pos_emb')):
+            t = torch.randn(shape, generator=g) * 0.5
+        elif name.endswith('.weight') and len(shape) == 2:
+            t = torch.randn(shape, generator=g) / math.sqrt(shape[1])
+        elif name.endswith('.weight'):
+            t = 1.0 + 0.1 * torch.randn(shape, generator=g)
+        else:
+            t = 0.02 * torch.randn(shape, generator=g)
+        sd['transformer.' + name] = t
+    return sd
+
 SD_V1_UNET_KWARGS = dict(image_size=32, in_channels=4, out_channels=4, model_channels=320,
                          attention_resolutions=[4, 2, 1], num_res_blocks=2, channel_mult=[1, 2, 4, 4], num_heads=8,
                          use_spatial_transformer=True, transformer_depth=1, context_dim=768, use_checkpoint=True,
@@ -89,3 +110,6 @@ SD_V1_UNET_KWARGS = dict(image_size=32, in_channels=4, out_channels=4, model_cha
 
 SD_V1_VAE_DDCONFIG = dict(double_z=True, z_channels=4, resolution=256, in_channels=3, out_ch=3, ch=128,
                           ch_mult=[1, 2, 4, 4], num_res_blocks=2, attn_resolutions=[], dropout=0.0)   # yaml:51-65
+
+LAION_UNET_KWARGS = dict(SD_V1_UNET_KWARGS, context_dim=1280)     # configs/latent-diffusion/txt2img-1p4B-eval.yaml:21-42
+LAION_BERT_KWARGS = dict(n_embed=1280, n_layer=32)                 # yaml:67-71

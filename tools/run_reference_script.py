@@ -19,6 +19,12 @@ What this launcher does (nothing in the reference tree is edited or copied):
     `stable_diffusion_amd.clip.FrozenCLIPEmbedderHIP`) to a temp file, passes it as `--config`, and swaps
     `ldm.models.diffusion.plms.PLMSSampler` / `ddim.DDIMSampler` / `dpm_solver.DPMSolverSampler` for the HIP samplers
     before the script imports them;
+  * `--hip txt2img -- --laion400m`: the script itself replaces `--config` / `--ckpt` after parsing (txt2img.py:237-241), so
+    the launcher redirects the load of `configs/latent-diffusion/txt2img-1p4B-eval.yaml` to a patched copy (only the UNet,
+    first-stage and cond-stage targets changed, the last to `stable_diffusion_amd.bert.BERTEmbedderHIP`); with
+    `--ckpt synthetic[:seed]` the load of `models/ldm/text2img-large/model.ckpt` gets a seeded random LAION-400M state_dict
+    (UNet at context_dim 1280, first stage, `cond_stage_model.transformer.*`).  Without a reference checkout the 1p4B
+    settings come from tests/golden/txt2img_1p4B_eval.json (the parsed yaml);
   * `--hip --hip-precision full`: also writes `hip_precision: full` into that copy's `unet_config.params` (UNetModelHIP's
     full-precision mode: every MFMA operand split-fp16).  The script's own `--precision full` is NOT mapped onto it -- pass both
     to get the reference's fp32 semantics on the HIP UNet;
@@ -230,11 +236,31 @@ def install_stubs(have_gpu, offline_stubs=False, real_ckpt=False):
     _try_real('CLIPTokenizer', 'the CLIP tokenizer', _Tokenizer)
     _try_real('CLIPTextModel', 'the CLIP text model weights', _clip_text)
 
+    class _BertTokenizer:
+        """deterministic stand-in: bytes of the prompt -> ids, [CLS] / [SEP] / [PAD] like bert-base-uncased's (101 / 102 / 0)."""
+        def __call__(self, text, truncation=True, max_length=77, padding='max_length', return_tensors='pt', **kw):
+            if isinstance(text, str):
+                text = [text]
+            ids = torch.zeros((len(text), max_length), dtype=torch.long)
+            for i, s in enumerate(text):
+                toks = [101] + [1000 + (b * 37) % 29000 for b in s.encode()][:max_length - 2] + [102]
+                ids[i, :len(toks)] = torch.tensor(toks)
+            return {'input_ids': ids}
+    if hasattr(transformers, 'BertTokenizerFast'):
+        _try_real('BertTokenizerFast', 'the BERT tokenizer', _BertTokenizer)
+
     if not have_gpu:   # configs[0]: CPU plumbing run
         nn.Module.cuda = lambda self, device=None: self
 
 
 HIP_COND_STAGE = False
+HIP_LAION = False
+LAION_YAML = 'configs/latent-diffusion/txt2img-1p4B-eval.yaml'           # txt2img.py:239
+LAION_CKPT = 'models/ldm/text2img-large/model.ckpt'                      # txt2img.py:240
+LAION_FIXTURE = os.path.join(REPO, 'tests', 'golden', 'txt2img_1p4B_eval.json')
+HIP_TARGETS = {'ldm.modules.diffusionmodules.openaimodel.UNetModel': 'stable_diffusion_amd.unet.UNetModelHIP',
+               'ldm.models.autoencoder.AutoencoderKL': 'stable_diffusion_amd.vae.AutoencoderKLHIP',
+               'ldm.modules.encoders.modules.BERTEmbedder': 'stable_diffusion_amd.bert.BERTEmbedderHIP'}
 BUNDLE = os.path.join(REPO, 'oracle', '_ref', 'refbundle')     # oracle/build_ref_bundle.py (git-ignored build output)
 
 
@@ -249,11 +275,55 @@ def _inference_yaml_text(ref):
         return yaml.safe_dump(json.load(f), default_flow_style=False, sort_keys=False)
 
 
+def laion_yaml_text(ref):
+    """configs/latent-diffusion/txt2img-1p4B-eval.yaml of a checkout, or its parsed settings (committed fixture) re-serialised."""
+    src = os.path.join(ref, LAION_YAML)
+    if os.path.exists(src):
+        return open(src).read()
+    import json
+    import yaml
+    with open(LAION_FIXTURE) as f:
+        return yaml.safe_dump(json.load(f), default_flow_style=False, sort_keys=False)
+
+
+def laion_hip_yaml_text(ref):
+    """the 1p4B config with the UNet, first-stage and cond-stage targets pointed at the HIP modules; nothing else changed"""
+    text = laion_yaml_text(ref)
+    for old, new in HIP_TARGETS.items():
+        assert text.count(f'target: {old}\n') == 1, old
+        text = text.replace(f'target: {old}\n', f'target: {new}\n')
+    return text
+
+
+def synthetic_laion_state_dict(seed=0):
+    """seeded random LAION-400M LDM-KL-8 checkpoint content under its key names"""
+    from stable_diffusion_amd.synthetic import (LAION_BERT_KWARGS, LAION_UNET_KWARGS, SD_V1_VAE_DDCONFIG,
+                                                synthetic_bert_state_dict, synthetic_state_dict, synthetic_vae_state_dict)
+    sd = {'model.diffusion_model.' + key: v for key, v in synthetic_state_dict(LAION_UNET_KWARGS, seed).items()}
+    sd.update({'first_stage_model.' + key: v for key, v in synthetic_vae_state_dict(SD_V1_VAE_DDCONFIG, 4, seed).items()})
+    sd.update({'cond_stage_model.' + key: v for key, v in synthetic_bert_state_dict(**LAION_BERT_KWARGS, seed=seed).items()})
+    return sd
+
+
+def redirect_laion_config(patched_path):
+    """OmegaConf.load of the 1p4B config (txt2img.py:239, :244) reads `patched_path` instead"""
+    from omegaconf import OmegaConf
+    real = OmegaConf.load
+
+    def load(path, *a, **k):
+        if str(path).replace(os.sep, '/').endswith(LAION_YAML):
+            print(f'run_reference_script: {LAION_YAML} -> {patched_path} (HIP targets)', flush=True)
+            path = patched_path
+        return real(path, *a, **k)
+    OmegaConf.load = load
+
+
 def _report_hip_calls():
     """--hip: count the forwards that reach libsdmi and say so at exit (the evidence that the script drove the HIP path)."""
     import atexit
-    from stable_diffusion_amd import unet as _u, vae as _v, clip as _c
-    counts = {'UNetModelHIP.forward': 0, 'AutoencoderKLHIP.decode': 0, 'FrozenCLIPEmbedderHIP.forward': 0}
+    from stable_diffusion_amd import unet as _u, vae as _v, clip as _c, bert as _b
+    counts = {'UNetModelHIP.forward': 0, 'AutoencoderKLHIP.decode': 0, 'FrozenCLIPEmbedderHIP.forward': 0,
+              'BERTEmbedderHIP.forward': 0}
     unet_precisions = set()
 
     def wrap(cls, name, key):
@@ -268,6 +338,7 @@ def _report_hip_calls():
     wrap(_u.UNetModelHIP, 'forward', 'UNetModelHIP.forward')
     wrap(_v.AutoencoderKLHIP, 'decode', 'AutoencoderKLHIP.decode')
     wrap(_c.FrozenCLIPEmbedderHIP, 'forward', 'FrozenCLIPEmbedderHIP.forward')
+    wrap(_b.BERTEmbedderHIP, 'forward', 'BERTEmbedderHIP.forward')
 
     def report():
         from stable_diffusion_amd import _lib
@@ -276,10 +347,16 @@ def _report_hip_calls():
     atexit.register(report)
 
 
+SYNTHETIC_SEED = None      # --ckpt synthetic[:seed]: the seed (the --laion400m checkpoint path is then synthetic too)
+
+
 def patch_torch_load():
     real = torch.load
 
     def load(f, *a, **k):
+        if isinstance(f, str) and HIP_LAION and SYNTHETIC_SEED is not None and f.replace(os.sep, '/').endswith(LAION_CKPT):
+            print(f'run_reference_script: {LAION_CKPT} -> synthetic LAION-400M weights (seed {SYNTHETIC_SEED})', flush=True)
+            return {'state_dict': synthetic_laion_state_dict(SYNTHETIC_SEED)}
         if isinstance(f, str) and f.startswith('synthetic'):
             seed = int(f.split(':')[1]) if ':' in f else 0
             from stable_diffusion_amd.synthetic import (SD_V1_UNET_KWARGS, SD_V1_VAE_DDCONFIG, synthetic_clip_state_dict,
@@ -347,6 +424,9 @@ def main():
         raise SystemExit('--hip needs the MI355X (the HIP path has no CPU fallback)')
     ckpt = rest[rest.index('--ckpt') + 1] if '--ckpt' in rest and rest.index('--ckpt') + 1 < len(rest) else None
     real_ckpt = not (ckpt or '').startswith('synthetic')     # the script's default --ckpt is a real file as well
+    global SYNTHETIC_SEED
+    if not real_ckpt:
+        SYNTHETIC_SEED = int(ckpt.split(':')[1]) if ':' in ckpt else 0
     install_stubs(have_gpu, offline_stubs=args.offline_stubs, real_ckpt=real_ckpt)
     patch_torch_load()
 
@@ -375,6 +455,16 @@ def main():
         tmp.write(text)
         tmp.close()
         rest = ['--config', tmp.name] + rest
+        if '--laion400m' in rest:
+            global HIP_LAION
+            HIP_LAION = True
+            text = laion_hip_yaml_text(ref)
+            if args.hip_precision:
+                text = add_hip_precision(text, args.hip_precision)
+            tmp = tempfile.NamedTemporaryFile('w', suffix='-1p4B-mi355x.yaml', delete=False)
+            tmp.write(text)
+            tmp.close()
+            redirect_laion_config(tmp.name)
     elif not have_gpu:
         import ldm.models.diffusion.dpm_solver.sampler as dpm_s
         for cls in (plms.PLMSSampler, ddim.DDIMSampler, dpm_s.DPMSolverSampler):   # plms.py:18-22 hard-codes torch.device("cuda")
