@@ -63,6 +63,21 @@ int sdmi_unet_create(const sdmi_unet_cfg* cfg, sdmi_unet** out);
 #define SDMI_PRECISION_FULL 1
 int sdmi_unet_create_with_precision(const sdmi_unet_cfg* cfg, int precision, sdmi_unet** out);
 int sdmi_unet_precision(const sdmi_unet* h);      /* SDMI_PRECISION_*, or -1 for a null handle */
+/* UNet families beyond SD v1 (additive; sdmi_unet_cfg is unchanged).  The latent-inpainting model
+ * (models/ldm/inpainting_big/config.yaml): attention_block = 1, resblock_updown = 1, context_dim = 0.
+ *   attention_block  0: SpatialTransformer with cross-attention (use_spatial_transformer=True, legacy=False: SD v1);
+ *                    1: the legacy AttentionBlock (openaimodel.py:278-323; use_spatial_transformer=False, legacy=True,
+ *                       num_head_channels=-1): GroupNorm -> conv1d qkv -> QKVAttentionLegacy over all pixels -> proj_out, + x.
+ *                       No context: sdmi_unet_forward takes ctx = NULL and Lctx = 0; transformer_depth is not read.
+ *   resblock_updown  0: Downsample / Upsample convolutions between the levels; 1: ResBlocks with down / up resampling
+ *                    (openaimodel.py:208-216,253-259: 2x2 average pool / nearest x2 of GroupNorm+SiLU(x) and of the skip x);
+ *                    the latent H and W must then be multiples of 2^(n_levels-1) (avg_pool2d rounds down).
+ * sdmi_unet_create_with_precision(cfg, p, out) = sdmi_unet_create_ext(cfg, NULL, p, out) (NULL = all zero). */
+typedef struct sdmi_unet_ext {
+  int32_t attention_block;
+  int32_t resblock_updown;
+} sdmi_unet_ext;
+int sdmi_unet_create_ext(const sdmi_unet_cfg* cfg, const sdmi_unet_ext* ext, int precision, sdmi_unet** out);
 int sdmi_unet_destroy(sdmi_unet* h);
 /* enumerate the state_dict keys the handle expects (= UNetModel.state_dict().keys()) */
 int sdmi_unet_num_weights(const sdmi_unet* h);
@@ -162,6 +177,24 @@ typedef struct sdmi_vae_cfg {
 } sdmi_vae_cfg;
 /* parts: 1 = decoder (+post_quant_conv), 2 = encoder (+quant_conv), 3 = both */
 int sdmi_vae_create(const sdmi_vae_cfg* cfg, int parts, sdmi_vae** out);
+/* First stages beyond AutoencoderKL (additive; sdmi_vae_cfg is unchanged).  VQModelInterface of the latent-inpainting model
+ * (autoencoder.py:14-283 with taming's VectorQuantizer2, legacy form): double_z = 0, mid_attn = 0 (attn_type 'none'), n_embed = 8192.
+ *   double_z   1: the encoder emits 2 z_channels and quant_conv 2 embed_dim (AutoencoderKL); 0: z_channels / embed_dim (VQModel:
+ *              sdmi_vae_encode then writes h = quant_conv(encoder(x)) [B, embed_dim, H/f, W/f], autoencoder.py:269-272)
+ *   mid_attn   1: mid.attn_1 in encoder and decoder (attn_type 'vanilla'); 0: none (attn_type 'none')
+ *   n_embed    > 0: the codebook `quantize.embedding.weight` [n_embed, embed_dim] is a weight of the decoder part; 0: none
+ * sdmi_vae_create(cfg, parts, out) = sdmi_vae_create_ext(cfg, NULL, parts, out) (NULL = {1, 1, 0}). */
+typedef struct sdmi_vae_ext {
+  int32_t double_z;
+  int32_t mid_attn;
+  int32_t n_embed;
+} sdmi_vae_ext;
+int sdmi_vae_create_ext(const sdmi_vae_cfg* cfg, const sdmi_vae_ext* ext, int parts, sdmi_vae** out);
+/* VQModelInterface.decode(h, force_not_quantize) (autoencoder.py:274-283): quantize = 1 replaces z_scale * z by its nearest
+ * codebook entry first (sdmi_k_vq_quantize's arithmetic), then post_quant_conv -> decoder; quantize = 0 is sdmi_vae_decode.
+ * The workspace is sdmi_vae_decode_workspace_bytes. */
+int sdmi_vae_decode_vq(sdmi_vae* h, const float* z, float z_scale, int quantize, float* img, int B, int H, int W, void* workspace,
+                       int64_t workspace_bytes, void* stream);
 int sdmi_vae_destroy(sdmi_vae* h);
 /* the state_dict keys the handle expects (= AutoencoderKL.state_dict() of the chosen parts, without `loss.*`) */
 int sdmi_vae_num_weights(const sdmi_vae* h);
@@ -412,6 +445,14 @@ int sdmi_k_pointwise_nchw(const float* x, const float* w, const float* bias, flo
                           float in_scale, void* stream);
 int sdmi_k_softmax_rows(const float* S, void* P_f16, int rows, int cols, float scale, void* stream);
 /* exact-erf GELU (the BERT encoder's feed-forward activation): fp32 [n] -> fp16 [n], n % 4 == 0 */
+/* The codebook quantizer of VectorQuantizer2 (legacy): per pixel of z' = z_scale * z (z fp32 NCHW [B, D, HW]) the first index of
+ * min_n d = (sum z'^2 + sum e_n^2) - 2 z'.e_n over the codebook e [n_embed, D] fp32; zq (optional, NCHW) = z' + (e[idx] - z') in fp32;
+ * idx (optional) int32 [B * HW].  norms_ws: n_embed floats of device scratch (receives sum e_n^2).  D in {1, 2, 3, 4, 8}. */
+int sdmi_k_vq_quantize(const float* z, float z_scale, const float* codebook, float* norms_ws, int n_embed, int D, float* zq, int32_t* idx,
+                       int B, int HW, void* stream);
+/* 2x2 average pool (dir 1) / nearest x2 (dir -1) of fp32 NHWC [B, H, W, C] (C % 4 == 0): out_f32 and / or out_f16 (+ out_lo =
+ * fp16(v - out_f16)), the resampling of the inpainting UNet's ResBlocks (openaimodel.py:253-259) */
+int sdmi_k_resample2(const float* x, float* out_f32, void* out_f16, void* out_lo, int B, int H, int W, int C, int dir, void* stream);
 int sdmi_k_gelu_erf(const float* x, void* out_f16, int64_t n, void* stream);
 int sdmi_k_pack_geglu(const float* w, const float* bias, void* wdst_f16, float* bdst, int N, int K, void* stream);
 /* Host post-processing of scripts/txt2img.py:313-324, on the device: img fp32 [B, C, H, W] (the

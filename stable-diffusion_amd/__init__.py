@@ -8,6 +8,7 @@ this package is the host-side mirror of the reference's interfaces for that path
     DDIMSamplerHIP    <- ldm.models.diffusion.ddim.DDIMSampler
     DPMSolverSamplerHIP <- ldm.models.diffusion.dpm_solver.sampler.DPMSolverSampler
     AutoencoderKLHIP  <- ldm.models.autoencoder.AutoencoderKL (decode / encode)
+    VQModelInterfaceHIP <- ldm.models.autoencoder.VQModelInterface (the latent-inpainting model's first stage)
     FrozenCLIPEmbedderHIP <- ldm.modules.encoders.modules.FrozenCLIPEmbedder
     BERTEmbedderHIP   <- ldm.modules.encoders.modules.BERTEmbedder (the LAION-400M model's text encoder)
 
@@ -16,10 +17,10 @@ Importable as `stable_diffusion_amd` (see stable_diffusion_amd.py at the repo ro
 from . import _lib  # noqa: F401
 from .unet import UNetModelHIP  # noqa: F401
 from .samplers import PLMSSamplerHIP, DDIMSamplerHIP, DPMSolverSamplerHIP  # noqa: F401
-from .vae import AutoencoderKLHIP  # noqa: F401
+from .vae import AutoencoderKLHIP, VQModelInterfaceHIP  # noqa: F401
 from .clip import FrozenCLIPEmbedderHIP  # noqa: F401
 from .bert import BERTEmbedderHIP  # noqa: F401
 from .ldm_shim import LatentDiffusionHIP, DiffusionWrapperHIP  # noqa: F401
 from . import debug, postprocess  # noqa: F401
 
-__all__ = ['UNetModelHIP', 'AutoencoderKLHIP', 'FrozenCLIPEmbedderHIP', 'BERTEmbedderHIP', 'PLMSSamplerHIP', 'DDIMSamplerHIP', 'DPMSolverSamplerHIP', 'LatentDiffusionHIP', 'DiffusionWrapperHIP']
+__all__ = ['UNetModelHIP', 'AutoencoderKLHIP', 'VQModelInterfaceHIP', 'FrozenCLIPEmbedderHIP', 'BERTEmbedderHIP', 'PLMSSamplerHIP', 'DDIMSamplerHIP', 'DPMSolverSamplerHIP', 'LatentDiffusionHIP', 'DiffusionWrapperHIP']

@@ -22,6 +22,14 @@ class VaeCfg(C.Structure):
                 ('embed_dim', C.c_int32)]
 
 
+class UNetExt(C.Structure):
+    _fields_ = [('attention_block', C.c_int32), ('resblock_updown', C.c_int32)]
+
+
+class VaeExt(C.Structure):
+    _fields_ = [('double_z', C.c_int32), ('mid_attn', C.c_int32), ('n_embed', C.c_int32)]
+
+
 class ClipCfg(C.Structure):
     _fields_ = [('vocab_size', C.c_int32), ('hidden_size', C.c_int32), ('intermediate_size', C.c_int32),
                 ('num_layers', C.c_int32), ('num_heads', C.c_int32), ('max_positions', C.c_int32)]
@@ -61,6 +69,7 @@ _SIGS = {
     'sdmi_unet_create': (C.c_int, [C.POINTER(UNetCfg), C.POINTER(c_ptr)]),
     'sdmi_unet_create_with_precision': (C.c_int, [C.POINTER(UNetCfg), C.c_int, C.POINTER(c_ptr)]),
     'sdmi_unet_precision': (C.c_int, [c_ptr]),
+    'sdmi_unet_create_ext': (C.c_int, [C.POINTER(UNetCfg), C.POINTER(UNetExt), C.c_int, C.POINTER(c_ptr)]),
     'sdmi_unet_destroy': (C.c_int, [c_ptr]),
     'sdmi_unet_num_weights': (C.c_int, [c_ptr]),
     'sdmi_unet_weight_info': (C.c_int, [c_ptr, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int)]),
@@ -83,6 +92,10 @@ _SIGS = {
                                        C.c_float, C.c_int, c_ptr, c_ptr, C.c_int64, c_ptr]),
     'sdmi_vae_create': (C.c_int, [C.POINTER(VaeCfg), C.c_int, C.POINTER(c_ptr)]),
     'sdmi_vae_destroy': (C.c_int, [c_ptr]),
+    'sdmi_vae_create_ext': (C.c_int, [C.POINTER(VaeCfg), C.POINTER(VaeExt), C.c_int, C.POINTER(c_ptr)]),
+    'sdmi_vae_decode_vq': (C.c_int, [c_ptr, c_ptr, C.c_float, C.c_int, c_ptr, C.c_int, C.c_int, C.c_int, c_ptr, C.c_int64, c_ptr]),
+    'sdmi_k_vq_quantize': (C.c_int, [c_ptr, C.c_float, c_ptr, c_ptr, C.c_int, C.c_int, c_ptr, c_ptr, C.c_int, C.c_int, c_ptr]),
+    'sdmi_k_resample2': (C.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_ptr]),
     'sdmi_vae_num_weights': (C.c_int, [c_ptr]),
     'sdmi_vae_weight_info': (C.c_int, [c_ptr, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int)]),
     'sdmi_vae_set_weight': (C.c_int, [c_ptr, C.c_char_p, c_ptr, C.POINTER(C.c_int64), C.c_int, c_ptr]),

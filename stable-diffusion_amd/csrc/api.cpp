@@ -58,6 +58,16 @@ int sdmi_unet_create_with_precision(const sdmi_unet_cfg* cfg, int precision, sdm
   *out = h;
   return 0;
 }
+int sdmi_unet_create_ext(const sdmi_unet_cfg* cfg, const sdmi_unet_ext* ext, int precision, sdmi_unet** out) {
+  SDMI_CHECK(cfg && out, "null argument");
+  SDMI_CHECK(precision == SDMI_PRECISION_MIXED || precision == SDMI_PRECISION_FULL,
+             "precision must be SDMI_PRECISION_MIXED (0) or SDMI_PRECISION_FULL (1), got " + std::to_string(precision));
+  sdmi_unet* h = new (std::nothrow) sdmi_unet();
+  SDMI_CHECK(h != nullptr, "out of host memory");
+  if (h->impl.build(*cfg, precision, ext)) { delete h; return -1; }
+  *out = h;
+  return 0;
+}
 int sdmi_unet_precision(const sdmi_unet* h) {
   if (!h) { fail("null handle"); return -1; }
   return h->impl.precision_;
@@ -165,6 +175,14 @@ int sdmi_vae_create(const sdmi_vae_cfg* cfg, int parts, sdmi_vae** out) {
   *out = h;
   return 0;
 }
+int sdmi_vae_create_ext(const sdmi_vae_cfg* cfg, const sdmi_vae_ext* ext, int parts, sdmi_vae** out) {
+  SDMI_CHECK(cfg && out, "null argument");
+  sdmi_vae* h = new (std::nothrow) sdmi_vae();
+  SDMI_CHECK(h != nullptr, "out of host memory");
+  if (h->impl.build(*cfg, parts, ext)) { delete h; return -1; }
+  *out = h;
+  return 0;
+}
 int sdmi_vae_destroy(sdmi_vae* h) { delete h; return 0; }
 int sdmi_vae_num_weights(const sdmi_vae* h) { return h ? (int)h->impl.slots().size() : fail("null handle"); }
 int sdmi_vae_weight_info(const sdmi_vae* h, int idx, char* key_buf, int key_buf_len, int64_t* shape4, int* ndim) {
@@ -192,6 +210,11 @@ int sdmi_vae_decode(sdmi_vae* h, const float* z, float z_scale, float* img, int 
                     int64_t workspace_bytes, void* stream) {
   SDMI_CHECK(h && z && img, "null argument");
   return h->impl.decode(z, z_scale, img, B, H, W, workspace, workspace_bytes, (hipStream_t)stream, false, nullptr);
+}
+int sdmi_vae_decode_vq(sdmi_vae* h, const float* z, float z_scale, int quantize, float* img, int B, int H, int W, void* workspace,
+                       int64_t workspace_bytes, void* stream) {
+  SDMI_CHECK(h && z && img, "null argument");
+  return h->impl.decode(z, z_scale, img, B, H, W, workspace, workspace_bytes, (hipStream_t)stream, false, nullptr, quantize != 0);
 }
 int64_t sdmi_vae_encode_workspace_bytes(sdmi_vae* h, int B, int H, int W) {
   if (!h) { fail("null handle"); return 0; }
@@ -285,6 +308,14 @@ int sdmi_bert_forward(sdmi_bert* h, const int64_t* ids, float* out, int B, int L
                       void* stream) {
   SDMI_CHECK(h && ids && out, "null argument");
   return h->impl.forward(ids, out, B, L, workspace, workspace_bytes, (hipStream_t)stream, false, nullptr);
+}
+int sdmi_k_vq_quantize(const float* z, float z_scale, const float* codebook, float* norms_ws, int n_embed, int D, float* zq, int32_t* idx,
+                       int B, int HW, void* stream) {
+  if (launch_vq_norms(codebook, norms_ws, n_embed, D, (hipStream_t)stream)) return -1;
+  return launch_vq_quantize(z, z_scale, codebook, norms_ws, n_embed, D, zq, (int*)idx, B, HW, (hipStream_t)stream);
+}
+int sdmi_k_resample2(const float* x, float* out_f32, void* out_f16, void* out_lo, int B, int H, int W, int C, int dir, void* stream) {
+  return launch_resample2(x, out_f32, (f16*)out_f16, (f16*)out_lo, B, H, W, C, dir, (hipStream_t)stream);
 }
 int sdmi_k_gelu_erf(const float* x, void* out_f16, int64_t n, void* stream) {
   return launch_gelu_erf(x, (f16*)out_f16, n, (hipStream_t)stream);

@@ -958,9 +958,10 @@ static int launch_attention_impl(const AttnParams& p_in, hipStream_t stream) {
     case 40: return launch_d<40>(p, stream);
     case 64: return launch_d<64>(p, stream);
     case 80: return launch_d<80>(p, stream);
+    case 96: return launch_d<96>(p, stream);       // (the inpainting UNet's AttentionBlocks at 768 channels, 8 heads)
     case 128: return launch_d<128>(p, stream);
     case 160: return launch_d<160>(p, stream);
-    default: return fail("attention head dim " + std::to_string(p.d) + " not instantiated (32/40/64/80/128/160)");
+    default: return fail("attention head dim " + std::to_string(p.d) + " not instantiated (32/40/64/80/96/128/160)");
   }
 }
 

@@ -220,9 +220,10 @@ int launch_attention_split16(const AttnSplitParams& p, hipStream_t stream) {
     case 40: return launch_d<40>(p, stream);
     case 64: return launch_d<64>(p, stream);
     case 80: return launch_d<80>(p, stream);
+    case 96: return launch_d<96>(p, stream);
     case 128: return launch_d<128>(p, stream);
     case 160: return launch_d<160>(p, stream);
-    default: return fail("split-fp16 attention: head dim " + std::to_string(p.d) + " has no instantiation (32, 40, 64, 80, 128, 160)");
+    default: return fail("split-fp16 attention: head dim " + std::to_string(p.d) + " has no instantiation (32, 40, 64, 80, 96, 128, 160)");
   }
 }
 

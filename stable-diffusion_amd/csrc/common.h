@@ -460,6 +460,15 @@ int launch_pointwise_nchw(const float* x_nchw, const float* w, const float* bias
                           int HW, float in_scale, hipStream_t s);
 int launch_softmax_rows(const float* S, f16* P, int rows, int cols, int lds, int ldp, float scale, hipStream_t s);
 
+// latent-inpainting model (inpaint.hip)
+// fp32 NHWC [B][H][W][C] -> dir 1: 2x2 average pool, dir -1: nearest x2; writes fp32 (o32) and / or fp16 hi (+ lo = fp16(v - hi))
+int launch_resample2(const float* x, float* o32, f16* hi, f16* lo, int B, int H, int W, int C, int dir, hipStream_t s);
+// codebook [n_embed][D] fp32 -> se[n] = sum_c e[n][c]^2
+int launch_vq_norms(const float* e, float* se, int n_embed, int D, hipStream_t s);
+// z fp32 NCHW [B][D][HW] (times z_scale) -> nearest code (first index on ties) idx [B * HW] and / or zq = z + (e[idx] - z), NCHW
+int launch_vq_quantize(const float* z, float z_scale, const float* e, const float* se, int n_embed, int D, float* zq, int* idx, int B,
+                       int HW, hipStream_t s);
+
 // cache hint (small.hip): touch every 128-byte line of a device range
 int launch_prefetch_lines(const void* ptr, int64_t bytes, hipStream_t s);
 

@@ -59,13 +59,17 @@ struct TapeRecGuard {         // recording ends with the scope, whatever path le
 };
 }  // namespace
 
-int UNet::build(const sdmi_unet_cfg& c, int precision) {
+int UNet::build(const sdmi_unet_cfg& c, int precision, const sdmi_unet_ext* ext) {
   cfg_ = c;
   precision_ = precision;
+  if (ext) ext_ = *ext;
+  SDMI_CHECK(ext_.attention_block == 0 || ext_.attention_block == 1, "attention_block must be 0 (SpatialTransformer) or 1 (AttentionBlock)");
+  SDMI_CHECK(ext_.resblock_updown == 0 || ext_.resblock_updown == 1, "resblock_updown must be 0 or 1");
   SDMI_CHECK(c.n_levels >= 1 && c.n_levels <= 8 && c.n_attention_resolutions >= 0 && c.n_attention_resolutions <= 8,
              "bad level / attention_resolutions count");
   SDMI_CHECK(c.model_channels % 64 == 0, "model_channels must be a multiple of 64 on this path");
-  SDMI_CHECK(c.context_dim % 64 == 0, "context_dim must be a multiple of 64 on this path");
+  if (has_ctx()) SDMI_CHECK(c.context_dim % 64 == 0, "context_dim must be a multiple of 64 on this path");
+  else SDMI_CHECK(c.context_dim == 0, "a UNet of AttentionBlocks has no cross-attention: context_dim must be 0");
   SDMI_CHECK(c.num_heads >= 1 && c.transformer_depth >= 1, "num_heads / transformer_depth");
   const int mc = c.model_channels;
   te_ = 4 * mc;
@@ -90,9 +94,14 @@ int UNet::build(const sdmi_unet_cfg& c, int precision) {
     return L;
   };
   auto add_attn = [&](const std::string& p, int ch) {
-    Layer L; L.kind = L_ATTN; L.prefix = p; L.cin = ch; L.cout = ch; L.heads = c.num_heads; L.dh = ch / c.num_heads;
+    Layer L; L.kind = has_ctx() ? L_ATTN : L_ATTN_LEGACY; L.prefix = p; L.cin = ch; L.cout = ch; L.heads = c.num_heads; L.dh = ch / c.num_heads;
     L.attn_index = n_attn_++;
     L.p1x1 = full() || (precise_1x1_ && cur_ds < precise_1x1_max_ds_);
+    return L;
+  };
+  auto add_updown = [&](const std::string& p, int ch, int dir) {     // resblock_updown: ResBlock(ch, down=True / up=True)
+    Layer L = add_res(p, ch, ch);
+    L.updown = dir;
     return L;
   };
 
@@ -118,6 +127,7 @@ int UNet::build(const sdmi_unet_cfg& c, int precision) {
     if (level != c.n_levels - 1) {
       const int n = (int)input_blocks_.size();
       Layer L; L.kind = L_DOWN; L.prefix = "input_blocks." + std::to_string(n) + ".0"; L.cin = ch; L.cout = ch;
+      if (ext_.resblock_updown) { cur_ds = ds; L = add_updown(L.prefix, ch, 1); }
       input_blocks_.push_back({L});
       chans.push_back(ch);
       ds *= 2;
@@ -141,11 +151,25 @@ int UNet::build(const sdmi_unet_cfg& c, int precision) {
       if (level && i == c.num_res_blocks) {
         Layer L; L.kind = L_UP; L.prefix = "output_blocks." + std::to_string(n) + "." + std::to_string(blk.size());
         L.cin = ch; L.cout = ch;
+        if (ext_.resblock_updown) L = add_updown(L.prefix, ch, -1);
         blk.push_back(L);
         ds /= 2;
       }
       output_blocks_.push_back(blk);
     }
+  }
+
+  if (!has_ctx()) {          // (the attention kernels are instantiated per head dim)
+    auto check = [&](const Layer& L) -> int {
+      if (L.kind != L_ATTN_LEGACY) return 0;
+      SDMI_CHECK(L.cin % c.num_heads == 0, L.prefix + ": channels not divisible by num_heads");
+      SDMI_CHECK(L.dh == 32 || L.dh == 40 || L.dh == 64 || L.dh == 80 || L.dh == 96 || L.dh == 128 || L.dh == 160,
+                 L.prefix + ": attention head dim " + std::to_string(L.dh) + " not instantiated (32/40/64/80/96/128/160)");
+      return 0;
+    };
+    for (auto& blk : input_blocks_) for (auto& L : blk) if (check(L)) return -1;
+    for (auto& L : middle_) if (check(L)) return -1;
+    for (auto& blk : output_blocks_) for (auto& L : blk) if (check(L)) return -1;
   }
 
   // the last ResBlock (output_blocks.<last>.0: its two 3x3 convs are the largest single contributors to the eps error)
@@ -222,6 +246,18 @@ int UNet::build(const sdmi_unet_cfg& c, int precision) {
           expect(t + ".norm3.weight", {C}, W_F32, (void**)&T.ln[4]);
           expect(t + ".norm3.bias", {C}, W_F32, (void**)&T.ln[5]);
         }
+        break;
+      }
+      case L_ATTN_LEGACY: {      // AttentionBlock (openaimodel.py:302-312): conv1d weights [out][in][1]
+        const int64_t C = ci;
+        const bool pq = L.p1x1;              // qkv as split-fp16 (the GroupNorm writes hi | lo) where the 1x1 allocation says so
+        expect(p + ".norm.weight", {C}, W_F32, (void**)&L.f32[0]);
+        expect(p + ".norm.bias", {C}, W_F32, (void**)&L.f32[1]);
+        expect(p + ".qkv.weight", {3 * C, C, 1}, W_QKV_LEGACY, (void**)&L.w16[0], L.heads, pq ? 1 : 0);
+        expect(p + ".qkv.bias", {3 * C}, W_QKV_LEGACY_B, (void**)&L.f32[2], L.heads, 0);
+        // proj_out reads the attention output: fp16 in the mixed mode, hi | lo in the full mode
+        expect(p + ".proj_out.weight", {C, C, 1}, full() ? W_SPLIT3 : W_ROWS16, (void**)&L.w16[1], 0, (int)C);
+        expect(p + ".proj_out.bias", {C}, W_F32, (void**)&L.f32[3]);
         break;
       }
       case L_DOWN:
@@ -301,7 +337,8 @@ size_t UNet::slot_bytes(const WeightSlot& s) const {
   size_t numel = 1;
   for (int64_t d : s.shape) numel *= (size_t)d;
   switch (s.kind) {
-    case W_F32: case W_CONV_OUT: case W_GEGLU_B: return numel * sizeof(float);
+    case W_F32: case W_CONV_OUT: case W_GEGLU_B: case W_QKV_LEGACY_B: return numel * sizeof(float);
+    case W_QKV_LEGACY: return numel * sizeof(f16) * (s.ld ? 3 : 1);
     case W_F32_ROWS: return (size_t)emb_total_ * s.ld * sizeof(float);
     case W_CONV: case W_GEGLU_W: return numel * sizeof(f16);
     case W_SPLIT3: case W_CONV_SPLIT3: return 3 * numel * sizeof(f16);
@@ -365,6 +402,27 @@ int UNet::set_weight(const char* key, const float* ptr, const int64_t* shape, in
       const int rows = (int)shape[0];
       rc = dev_alloc(s.dst, slot_bytes(s));
       if (!rc) rc = launch_pack_rows(dptr, (f16*)*s.dst, rows, (int)shape[1], s.row0, s.ld, stream);
+      break;
+    }
+    case W_QKV_LEGACY:
+    case W_QKV_LEGACY_B: {
+      // QKVAttentionLegacy (openaimodel.py:361-366) reads the qkv rows as [head][q | k | v][channel]: reference row h * 3d + j * d + i
+      // becomes packed row j * C + h * d + i, the [q | k | v] head-major order of the SpatialTransformer's fused projection
+      const int R = (int)shape[0], K = s.kind == W_QKV_LEGACY ? (int)shape[1] : 1, heads = s.row0, C = R / 3, d = C / heads;
+      float* perm = nullptr;
+      rc = dev_alloc(s.dst, slot_bytes(s));
+      if (!rc && s.kind == W_QKV_LEGACY) SDMI_HIP_OK(hipMalloc((void**)&perm, (size_t)R * K * sizeof(float)));
+      float* dst = s.kind == W_QKV_LEGACY ? perm : (float*)*s.dst;
+      for (int h = 0; !rc && h < heads; ++h)
+        for (int j = 0; j < 3; ++j)
+          SDMI_HIP_OK(hipMemcpyAsync(dst + ((size_t)j * C + (size_t)h * d) * K, dptr + ((size_t)h * 3 * d + (size_t)j * d) * K,
+                                     (size_t)d * K * sizeof(float), hipMemcpyDeviceToDevice, stream));
+      if (!rc && s.kind == W_QKV_LEGACY)
+        rc = s.ld ? launch_pack_split3(perm, (f16*)*s.dst, R, K, stream) : launch_pack_rows(perm, (f16*)*s.dst, R, K, 0, K, stream);
+      if (perm) {
+        SDMI_HIP_OK(hipStreamSynchronize(stream));
+        (void)hipFree(perm);
+      }
       break;
     }
     case W_GEGLU_W: {
@@ -479,6 +537,7 @@ int UNet::export_packed(void* host_buf, int64_t bytes, hipStream_t stream) {
   memcpy(h.magic, "SDMIPK01", 8);
   h.abi = SDMI_ABI_VERSION; h.precise_1x1 = precise_1x1_ ? 1 : 0; h.n_buffers = (int32_t)bufs.size(); h.cfg = cfg_;
   h.reserved = (precise_kv_ ? 1 : 0) | (precise_last_res_ ? 2 : 0) | (precise_1x1_max_ds_ << 8);      // (ABI 17: the precision allocation)
+  h.reserved |= (ext_.attention_block << 4) | (ext_.resblock_updown << 5);                          // (sdmi_unet_ext: 0 for SD v1)
   if (full()) h.reserved |= PK_FULL;
   h.total_bytes = total;
   memcpy(host_buf, &h, sizeof(h));
@@ -502,7 +561,9 @@ int UNet::import_packed(const void* host_buf, int64_t bytes, hipStream_t stream)
              ((h.reserved & PK_FULL) ? "full" : "mixed") + "-precision UNet handle and cannot be imported into a " + (full() ? "full" : "mixed") +
              "-precision one: repack it with a handle of this precision");
   SDMI_CHECK((h.precise_1x1 != 0) == precise_1x1_, "packed blob was written with a different SDMI_PRECISE_1X1 setting");
-  SDMI_CHECK((h.reserved & ~PK_FULL) == ((precise_kv_ ? 1 : 0) | (precise_last_res_ ? 2 : 0) | (precise_1x1_max_ds_ << 8)),
+  SDMI_CHECK((h.reserved & (3 << 4)) == ((ext_.attention_block << 4) | (ext_.resblock_updown << 5)),
+             "packed blob was written for a different UNet family (attention_block / resblock_updown)");
+  SDMI_CHECK((h.reserved & ~PK_FULL & ~(3 << 4)) == ((precise_kv_ ? 1 : 0) | (precise_last_res_ ? 2 : 0) | (precise_1x1_max_ds_ << 8)),
              "packed blob was written with a different precision allocation (SDMI_PRECISE_KV / _LAST_RES / _1X1_MAX_DS)");
   std::vector<std::pair<void**, size_t>> bufs;
   int64_t total = 0;
@@ -985,10 +1046,102 @@ struct Fwd : FwdBase {
     return out;
   }
 
+  // ResBlock with resblock_updown (openaimodel.py:253-259): h = conv3(resample(SiLU(GN(x)))), skip = resample(x) (Identity: the
+  // channel count does not change), resample = F.avg_pool2d(2) (dir 1) or nearest x2 (dir -1); the rest as in res_block
+  Act res_block_updown(Layer& L, const Act& x) {
+    const int dir = L.updown, H = x.H, W = x.W, C = L.cin;
+    if (x.C != C || L.cout != C) ok(fail("resampling res block channel mismatch at " + L.prefix));
+    if (dir > 0 && ((H | W) & 1)) ok(fail("resampling res block at " + L.prefix + ": the 2x2 average pool needs even H and W"));
+    const int Ho = dir > 0 ? H / 2 : 2 * H, Wo = dir > 0 ? W / 2 : 2 * W, M = B * Ho * Wo;
+    const bool p3 = L.precise3;
+    const size_t mark = scratch.off;
+    float* g = S<float>((size_t)B * H * W * C);                        // SiLU(GN(x)) at the input resolution (fp32)
+    groupnorm(x, nullptr, L.f32[0], L.f32[1], 1e-5f, 1, nullptr, g, nullptr);
+    f16* a = S<f16>((size_t)M * C);
+    f16* a_lo = p3 ? S<f16>((size_t)M * C) : nullptr;
+    float* xs = S<float>((size_t)M * C);                               // x_upd(x): the residual
+    if (!dry && !rc) ok(launch_resample2(g, nullptr, a, a_lo, B, H, W, C, dir, s));
+    if (!dry && !rc) ok(launch_resample2(x.p, xs, nullptr, nullptr, B, H, W, C, dir, s));
+    auto split3 = [&](IGemmParams& q, const f16* hi, const f16* lo) {
+      q.a1 = lo; q.c1 = C; q.lda1 = C; q.a2 = hi; q.c2 = C; q.lda2 = C; q.K = 27 * C; q.k_alg = 9 * C;
+    };
+    float* h = S<float>((size_t)M * C);
+    Act out = make_act(P<float>((size_t)M * C), C, Ho, Wo, true);
+    Act hact = make_act(h, C, Ho, Wo, true);
+    {
+      IGemmParams p = conv3(a, C, Ho, Wo, Ho, Wo, 1, 0, L.w16[0], C);
+      if (p3) split3(p, a, a_lo);
+      p.bias = L.f32[2]; p.rowvec = emb_all + L.emb_off; p.ld_rowvec = emb_ld;
+      p.out_f32 = h; p.ldo = C;
+      attach_gn_targets(p, hact);
+      TapeCaller tc(Tape::R_EMB, emb_caller ? p.rowvec : nullptr);
+      gemm(p);
+    }
+    {
+      f16* a2 = S<f16>((size_t)M * C);
+      f16* a2_lo = p3 ? S<f16>((size_t)M * C) : nullptr;
+      groupnorm(hact, nullptr, L.f32[3], L.f32[4], 1e-5f, 1, a2, nullptr, nullptr, a2_lo, nullptr);
+      IGemmParams p = conv3(a2, C, Ho, Wo, Ho, Wo, 1, 0, L.w16[1], C);
+      if (p3) split3(p, a2, a2_lo);
+      p.bias = L.f32[5]; p.residual = xs; p.ldr = C; p.out_f32 = out.p; p.ldo = C;
+      attach_gn_targets(p, out);
+      gemm(p);
+    }
+    scratch.off = mark;
+    return out;
+  }
+
+  // AttentionBlock._forward (openaimodel.py:318-323): x + proj_out(QKVAttentionLegacy(qkv(GroupNorm32(x)))) over all H * W pixels.
+  // The qkv rows were permuted at pack time (W_QKV_LEGACY), so the fp32 GEMM output is [q | k | v] with heads contiguous; the
+  // legacy scale 1/sqrt(sqrt(d)) on q and on k is the one scale 1/sqrt(d) on q k^T here.  Full mode: split-fp16 everywhere.
+  Act attn_block_legacy(Layer& L, const Act& x) {
+    const int H = x.H, W = x.W, N = H * W, M = B * N, C = L.cin;
+    const int Np = (int)round_up(N, 8);
+    const bool fm = u->full();
+    const bool pq = L.p1x1;                 // qkv GEMM on split-fp16 operands (packed accordingly, see UNet::build)
+    const size_t mark = scratch.off;
+    f16* xn = S<f16>((size_t)M * C);
+    f16* xn_lo = pq ? S<f16>((size_t)M * C) : nullptr;
+    groupnorm(x, nullptr, L.f32[0], L.f32[1], 1e-5f, 0, xn, nullptr, nullptr, xn_lo, nullptr);
+    float* qkv = S<float>((size_t)M * 3 * C);
+    {
+      IGemmParams p = dense1x1(xn, xn_lo, M, C, L.w16[0], 3 * C, N, pq);
+      p.bias = L.f32[2]; p.out_f32 = qkv; p.ldo = 3 * C;
+      gemm(p);
+    }
+    f16* q = S<f16>((size_t)M * C); f16* q_lo = S<f16>((size_t)M * C);
+    f16* k = S<f16>((size_t)M * C); f16* k_lo = S<f16>((size_t)M * C);
+    f16* vt = S<f16>((size_t)B * C * Np); f16* vt_lo = S<f16>((size_t)B * C * Np);
+    if (!dry && !rc) ok(launch_split_heads(qkv, 3 * C, 0, q, q_lo, 0, B, N, Np, L.heads, L.dh, s));
+    if (!dry && !rc) ok(launch_split_heads(qkv, 3 * C, C, k, k_lo, 0, B, N, Np, L.heads, L.dh, s));
+    if (!dry && !rc) ok(launch_split_heads(qkv, 3 * C, 2 * C, vt, vt_lo, 1, B, N, Np, L.heads, L.dh, s));
+    f16* ao = S<f16>((size_t)M * C);
+    f16* ao_lo = fm ? S<f16>((size_t)M * C) : nullptr;
+    const float scale = 1.0f / sqrtf((float)L.dh);
+    if (fm) {
+      AttnSplitParams a = AttnSplitParams();
+      a.q = q; a.q_lo = q_lo; a.k = k; a.k_lo = k_lo; a.vt = vt; a.vt_lo = vt_lo; a.out = ao; a.out_lo = ao_lo;
+      a.BH = B * L.heads; a.heads = L.heads; a.nq = N; a.nkv = N; a.nkv_pad = Np; a.d = L.dh; a.scale = scale;
+      if (!dry && !rc) ok(launch_attention_split16(a, s));
+    } else {
+      attention(q, k, vt, ao, L, N, N, Np, scale);
+    }
+    Act out = make_act(P<float>((size_t)M * C), C, H, W, true);
+    {
+      IGemmParams p = dense1x1(ao, ao_lo, M, C, L.w16[1], C, N, fm);
+      p.bias = L.f32[3]; p.residual = x.p; p.ldr = C; p.out_f32 = out.p; p.ldo = C;
+      attach_gn_targets(p, out);
+      gemm(p);
+    }
+    scratch.off = mark;
+    return out;
+  }
+
   Act run_layer(Layer& L, const Act& x, const Act* skip) {
     switch (L.kind) {
-      case L_RES: return res_block(L, x, skip);
+      case L_RES: return L.updown ? res_block_updown(L, x) : res_block(L, x, skip);
       case L_ATTN: return attn_block(L, x);
+      case L_ATTN_LEGACY: return attn_block_legacy(L, x);
       case L_DOWN: return resample(L, x, false);
       case L_UP: return resample(L, x, true);
       default: ok(fail("unexpected layer kind")); return x;
@@ -1090,8 +1243,13 @@ int UNet::run(const float* x, const int64_t* t_i64, const float* t_f32, const fl
               int64_t* bytes_needed) {
   SDMI_CHECK(dry || finalized_, "sdmi_unet_finalize() has not succeeded yet");
   SDMI_CHECK(B >= 1 && B <= 8, "batch (CFG rows) must be 1..8 per call");
-  SDMI_CHECK(H >= 1 && W >= 1 && Lctx >= 1, "bad shape");
+  if (has_ctx()) SDMI_CHECK(H >= 1 && W >= 1 && Lctx >= 1, "bad shape");
+  else SDMI_CHECK(H >= 1 && W >= 1 && Lctx == 0 && ctx == nullptr && !ctx_only,
+                  "bad shape: this UNet has no cross-attention (AttentionBlocks): pass ctx = NULL and Lctx = 0");
   const int down = 1 << (cfg_.n_levels - 1);
+  if (ext_.resblock_updown)
+    SDMI_CHECK(H % down == 0 && W % down == 0, "latent H and W must be multiples of " + std::to_string(down) +
+               " for resblock_updown (the down ResBlocks' avg_pool2d rounds down, the skip concat needs the sizes back)");
   SDMI_CHECK(H % down == 0 && W % down == 0, "H and W must be divisible by 2^(levels-1) (the UNet's skip concat requires it)");
 
   // The timestep hint is an announcement about THIS call only: consume it up front, so that a call that fails on any of the
@@ -1136,7 +1294,7 @@ int UNet::run(const float* x, const int64_t* t_i64, const float* t_f32, const fl
       tapes_.erase(tapes_.begin() + (long)i);
       SDMI_CHECK(finalized_, "sdmi_unet_finalize() has not succeeded yet");
       if (ensure_ctx_cache(B, Lctx, false)) return -1;
-      if (!ctx) SDMI_CHECK(ctx_valid_, "ctx == NULL but no cached context for this (B, Lctx); call sdmi_unet_cache_context first");
+      if (!ctx && has_ctx()) SDMI_CHECK(ctx_valid_, "ctx == NULL but no cached context for this (B, Lctx); call sdmi_unet_cache_context first");
       hit->retarget(caller);
       if (replay_verify) { verify_against = std::move(hit); break; }      // run the executor and compare what it launches
       const int e = hit->replay(stream);
@@ -1220,8 +1378,10 @@ int UNet::run(const float* x, const int64_t* t_i64, const float* t_f32, const fl
     if (f.begin_pass((int64_t)12 << 20)) return -1;    // 48 MB of fp32 split-K slabs (largest user: 8 x 512 x 1280)
     f16* ctx16 = f.P<f16>((size_t)B * Lctx * cfg_.context_dim);
     f16* ctx16_lo = precise_kv_ ? f.P<f16>((size_t)B * Lctx * cfg_.context_dim) : nullptr;
-    const bool have_ctx = (ctx != nullptr) || d;
-    if (have_ctx) {
+    const bool have_ctx = has_ctx() && ((ctx != nullptr) || d);
+    if (!has_ctx()) {
+      f.ctx16 = nullptr; f.ctx16_lo = nullptr;          // (no cross-attention: nothing reads a context)
+    } else if (have_ctx) {
       if (!d) {
         TapeCaller tc(Tape::R_CTX, ctx);
         int r = launch_cast_f16(ctx, ctx16, ctx16_lo, (int64_t)B * Lctx * cfg_.context_dim, stream);

@@ -232,8 +232,12 @@ struct DevStage {
   int release(hipStream_t stream);
 };
 
-enum LayerKind { L_CONV_IN, L_RES, L_ATTN, L_DOWN, L_UP };
-enum WKind { W_F32, W_F32_ROWS, W_CONV, W_CONV_OUT, W_ROWS16, W_GEGLU_W, W_GEGLU_B, W_SPLIT3, W_SPLIT3_ROWS, W_CONV_SPLIT3 };
+// L_ATTN_LEGACY: the AttentionBlock of a UNet without spatial transformer (openaimodel.py:278-323, QKVAttentionLegacy :347-376)
+enum LayerKind { L_CONV_IN, L_RES, L_ATTN, L_DOWN, L_UP, L_ATTN_LEGACY };
+// W_QKV_LEGACY / W_QKV_LEGACY_B: the AttentionBlock's conv1d qkv weight / bias, its head-interleaved rows (head, q | k | v, channel)
+// permuted to the [q | k | v] head-major rows launch_split_heads reads (WeightSlot::row0 = heads; ld = 1: split-fp16 [hi | hi | lo])
+enum WKind { W_F32, W_F32_ROWS, W_CONV, W_CONV_OUT, W_ROWS16, W_GEGLU_W, W_GEGLU_B, W_SPLIT3, W_SPLIT3_ROWS, W_CONV_SPLIT3, W_QKV_LEGACY,
+             W_QKV_LEGACY_B };
 
 struct TBlock {   // BasicTransformerBlock (ldm/modules/attention.py:196-215)
   f16* wqkv = nullptr;   // [3C][C]   attn1 to_q | to_k | to_v
@@ -258,6 +262,7 @@ struct Layer {
   LayerKind kind = L_RES;
   std::string prefix;
   int cin = 0, cout = 0, heads = 0, dh = 0, emb_off = 0, attn_index = -1;
+  int updown = 0;           // L_RES with resblock_updown (openaimodel.py:208-216,253-259): 1 avg-pool 2x2 (down), -1 nearest x2 (up)
   // Precision allocation by measured sensitivity (round 6; DESIGN.md section 2, oracle/fp16_floor.py):
   //   p1x1     the layer's 1x1 convs on the residual stream (skip_connection / proj_in / proj_out) as 3-pass split-fp16 -- the two upper levels
   //            (downsample factors 1 and 2): single-pass fp16 there would add 87 % / 15 % to the eps error variance, at downsample factor 4
@@ -285,7 +290,7 @@ class UNet {
   UNet(const UNet&) = delete;
   UNet& operator=(const UNet&) = delete;
 
-  int build(const sdmi_unet_cfg& cfg, int precision = SDMI_PRECISION_MIXED);
+  int build(const sdmi_unet_cfg& cfg, int precision = SDMI_PRECISION_MIXED, const sdmi_unet_ext* ext = nullptr);
   int set_weight(const char* key, const float* ptr, const int64_t* shape, int ndim, hipStream_t stream);
   int finalize();
   // packed-weight blob: every packed device buffer behind a header that pins cfg / ABI
@@ -306,6 +311,8 @@ class UNet {
   const std::vector<WeightSlot>& slots() const { return slots_; }
 
   sdmi_unet_cfg cfg_{};
+  sdmi_unet_ext ext_{};        // (all zero: the SD-v1 family)
+  bool has_ctx() const { return ext_.attention_block == 0; }      // SpatialTransformers with cross-attention
   // SDMI_PRECISION_FULL: every MFMA operand split-fp16 (every Layer::p1x1 / precise3, split-fp16 linears, resamplers and attention;
   // the row-strip chains and the LayerNorm / GroupNorm folds off).  Fixed by build(); the packed weights depend on it.
   int precision_ = SDMI_PRECISION_MIXED;

@@ -25,8 +25,13 @@ void Vae::expect(const std::string& key, std::vector<int64_t> shape, VWKind kind
   slots_.push_back(std::move(s));
 }
 
-int Vae::build(const sdmi_vae_cfg& c, int parts) {
+int Vae::build(const sdmi_vae_cfg& c, int parts, const sdmi_vae_ext* ext) {
   cfg_ = c; parts_ = parts;
+  if (ext) ext_ = *ext;
+  SDMI_CHECK((ext_.double_z == 0 || ext_.double_z == 1) && (ext_.mid_attn == 0 || ext_.mid_attn == 1) && ext_.n_embed >= 0,
+             "first-stage extension: double_z and mid_attn are 0 or 1, n_embed >= 0");
+  SDMI_CHECK(ext_.n_embed == 0 || (c.embed_dim == 1 || c.embed_dim == 2 || c.embed_dim == 3 || c.embed_dim == 4 || c.embed_dim == 8),
+             "codebook quantizer: embed_dim must be 1, 2, 3, 4 or 8");
   SDMI_CHECK(parts >= 1 && parts <= 3, "parts: 1 decoder, 2 encoder, 3 both");
   SDMI_CHECK(c.n_levels >= 1 && c.n_levels <= 8 && c.num_res_blocks >= 1, "bad level / res block count");
   SDMI_CHECK(c.ch % 64 == 0, "ch must be a multiple of 64 on this path");
@@ -43,7 +48,7 @@ int Vae::build(const sdmi_vae_cfg& c, int parts) {
   if (parts & 1) {
     int bi = c.ch * c.ch_mult[n - 1];
     dec_.push_back(res("decoder.mid.block_1", bi, bi));
-    dec_.push_back(one(V_ATTN, "decoder.mid.attn_1", bi));
+    if (ext_.mid_attn) dec_.push_back(one(V_ATTN, "decoder.mid.attn_1", bi));
     dec_.push_back(res("decoder.mid.block_2", bi, bi));
     for (int lvl = n - 1; lvl >= 0; --lvl) {
       const int bo = c.ch * c.ch_mult[lvl];
@@ -66,7 +71,7 @@ int Vae::build(const sdmi_vae_cfg& c, int parts) {
       if (lvl != n - 1) enc_.push_back(one(V_DOWN, "encoder.down." + std::to_string(lvl) + ".downsample", bi));
     }
     enc_.push_back(res("encoder.mid.block_1", bi, bi));
-    enc_.push_back(one(V_ATTN, "encoder.mid.attn_1", bi));
+    if (ext_.mid_attn) enc_.push_back(one(V_ATTN, "encoder.mid.attn_1", bi));
     enc_.push_back(res("encoder.mid.block_2", bi, bi));
     enc_c_end_ = bi;
   }
@@ -114,12 +119,13 @@ int Vae::build(const sdmi_vae_cfg& c, int parts) {
     for (auto& L : enc_) visit(L);
     expect("encoder.norm_out.weight", {enc_c_end_}, VW_F32, (void**)&eno_g_);
     expect("encoder.norm_out.bias", {enc_c_end_}, VW_F32, (void**)&eno_b_);
-    expect("encoder.conv_out.weight", {2 * c.z_channels, enc_c_end_, 3, 3}, VW_CONV_OUT, (void**)&eco_w_);
-    expect("encoder.conv_out.bias", {2 * c.z_channels}, VW_F32, (void**)&eco_b_);
-    expect("quant_conv.weight", {2 * c.embed_dim, 2 * c.z_channels, 1, 1}, VW_F32, (void**)&q_w_);
-    expect("quant_conv.bias", {2 * c.embed_dim}, VW_F32, (void**)&q_b_);
+    expect("encoder.conv_out.weight", {enc_zc(), enc_c_end_, 3, 3}, VW_CONV_OUT, (void**)&eco_w_);
+    expect("encoder.conv_out.bias", {enc_zc()}, VW_F32, (void**)&eco_b_);
+    expect("quant_conv.weight", {enc_ed(), enc_zc(), 1, 1}, VW_F32, (void**)&q_w_);
+    expect("quant_conv.bias", {enc_ed()}, VW_F32, (void**)&q_b_);
   }
   if (parts & 1) {
+    if (ext_.n_embed > 0) expect("quantize.embedding.weight", {ext_.n_embed, c.embed_dim}, VW_F32, (void**)&cb_);
     expect("post_quant_conv.weight", {c.z_channels, c.embed_dim, 1, 1}, VW_F32, (void**)&pq_w_);
     expect("post_quant_conv.bias", {c.z_channels}, VW_F32, (void**)&pq_b_);
     expect("decoder.conv_in.weight", {c.ch * c.ch_mult[n - 1], c.z_channels, 3, 3}, VW_F32, (void**)&dci_w_);
@@ -194,6 +200,12 @@ int Vae::finalize() {
     SDMI_HIP_OK(hipMalloc((void**)&zero_, 4096));
     owned_.push_back(zero_);
     SDMI_HIP_OK(hipMemset(zero_, 0, 4096));
+  }
+  if (cb_) {          // sum e^2 of every code, once per set of weights (the quantizer's distance expression)
+    if (dev_alloc((void**)&cb_norm_, (size_t)ext_.n_embed * sizeof(float))) return -1;
+    SDMI_HIP_OK(hipDeviceSynchronize());         // (set_weight copied the codebook on the caller's stream)
+    if (launch_vq_norms(cb_, cb_norm_, ext_.n_embed, cfg_.embed_dim, nullptr)) return -1;
+    SDMI_HIP_OK(hipDeviceSynchronize());
   }
   finalized_ = true;
   return 0;
@@ -349,8 +361,9 @@ static int run_two_pass(VFwd& f, bool dry, void* workspace, int64_t ws_bytes, in
 }
 
 int Vae::decode(const float* z, float z_scale, float* img, int B, int H, int W, void* workspace, int64_t ws_bytes,
-                hipStream_t stream, bool dry, int64_t* bytes_needed) {
+                hipStream_t stream, bool dry, int64_t* bytes_needed, bool quantize) {
   SDMI_CHECK(parts_ & 1, "this handle was created without the decoder");
+  SDMI_CHECK(!quantize || ext_.n_embed > 0, "this first stage has no codebook (n_embed = 0): nothing to quantize");
   SDMI_CHECK(dry || finalized_, "sdmi_vae_finalize() has not succeeded yet");
   SDMI_CHECK(B >= 1 && B <= 8, "batch must be 1..8 per call");
   SDMI_CHECK(H >= 1 && W >= 1, "bad shape");
@@ -361,7 +374,12 @@ int Vae::decode(const float* z, float z_scale, float* img, int B, int H, int W, 
   return run_two_pass(f, dry, workspace, ws_bytes, bytes_needed, [&](VFwd& f) -> int {
     const bool d = f.dry;
     float* zq = f.P<float>((size_t)B * cfg_.z_channels * H * W);
-    if (!d && launch_pointwise_nchw(z, pq_w_, pq_b_, zq, B, cfg_.embed_dim, cfg_.z_channels, H * W, z_scale, stream)) return -1;
+    // (VQ: quantize(z_scale * z) first -- the workspace always has room for it, so its size does not depend on the flag)
+    float* zc = ext_.n_embed > 0 ? f.P<float>((size_t)B * cfg_.embed_dim * H * W) : nullptr;
+    if (!d && quantize) {
+      if (launch_vq_quantize(z, z_scale, cb_, cb_norm_, ext_.n_embed, cfg_.embed_dim, zc, nullptr, B, H * W, stream)) return -1;
+      if (launch_pointwise_nchw(zc, pq_w_, pq_b_, zq, B, cfg_.embed_dim, cfg_.z_channels, H * W, 1.0f, stream)) return -1;
+    } else if (!d && launch_pointwise_nchw(z, pq_w_, pq_b_, zq, B, cfg_.embed_dim, cfg_.z_channels, H * W, z_scale, stream)) return -1;
     Act x; x.p = f.P<float>((size_t)B * H * W * c_in); x.C = c_in; x.H = H; x.W = W;
     if (!d && launch_conv_in(zq, dci_w_, dci_b_, x.p, B, cfg_.z_channels, H, W, c_in, stream)) return -1;
     for (auto& L : dec_) x = f.run_layer(L, x);
@@ -391,10 +409,10 @@ int Vae::encode(const float* img, float* moments, int B, int H, int W, void* wor
     if (f.rc) return f.rc;
     float* hn = f.S<float>((size_t)B * x.H * x.W * x.C);
     f.groupnorm(x, nullptr, eno_g_, eno_b_, VFwd::EPS, 1, nullptr, hn, nullptr);
-    const int zc2 = 2 * cfg_.z_channels;
+    const int zc2 = enc_zc();
     float* mo = f.S<float>((size_t)B * zc2 * x.H * x.W);
     if (!d && !f.rc && launch_conv_out(hn, eco_w_, eco_b_, mo, B, x.H, x.W, x.C, zc2, stream)) return -1;
-    if (!d && !f.rc && launch_pointwise_nchw(mo, q_w_, q_b_, moments, B, zc2, 2 * cfg_.embed_dim, x.H * x.W, 1.0f, stream))
+    if (!d && !f.rc && launch_pointwise_nchw(mo, q_w_, q_b_, moments, B, zc2, enc_ed(), x.H * x.W, 1.0f, stream))
       return -1;
     return f.rc;
   });

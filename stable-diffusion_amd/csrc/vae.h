@@ -39,13 +39,14 @@ class Vae {
   Vae(const Vae&) = delete;
   Vae& operator=(const Vae&) = delete;
 
-  int build(const sdmi_vae_cfg& cfg, int parts);
+  int build(const sdmi_vae_cfg& cfg, int parts, const sdmi_vae_ext* ext = nullptr);
   int set_weight(const char* key, const float* ptr, const int64_t* shape, int ndim, hipStream_t stream);
   int finalize();
   // z [B, embed_dim, H, W] fp32 NCHW -> img [B, out_ch, H*f, W*f] fp32 NCHW; z is multiplied by z_scale first
+  // quantize: VQModelInterface.decode without force_not_quantize -- z_scale * z is replaced by its nearest codebook entry first
   int decode(const float* z, float z_scale, float* img, int B, int H, int W, void* workspace, int64_t ws_bytes,
-             hipStream_t stream, bool dry, int64_t* bytes_needed);
-  // img [B, in_channels, H, W] fp32 NCHW -> moments [B, 2*embed_dim, H/f, W/f] fp32 NCHW
+             hipStream_t stream, bool dry, int64_t* bytes_needed, bool quantize = false);
+  // img [B, in_channels, H, W] fp32 NCHW -> moments [B, 2*embed_dim, H/f, W/f] fp32 NCHW (double_z; else h [B, embed_dim, H/f, W/f])
   int encode(const float* img, float* moments, int B, int H, int W, void* workspace, int64_t ws_bytes, hipStream_t stream,
              bool dry, int64_t* bytes_needed);
 
@@ -53,7 +54,10 @@ class Vae {
   int factor() const { return 1 << (cfg_.n_levels - 1); }
 
   sdmi_vae_cfg cfg_{};
+  sdmi_vae_ext ext_{1, 1, 0};       // AutoencoderKL unless created with an extension (include/sdmi.h)
   int parts_ = 0;
+  int enc_zc() const { return ext_.double_z ? 2 * cfg_.z_channels : cfg_.z_channels; }    // encoder.conv_out channels
+  int enc_ed() const { return ext_.double_z ? 2 * cfg_.embed_dim : cfg_.embed_dim; }      // quant_conv output channels
   f16* zero_ = nullptr;
   bool precise_1x1_ = true;
 
@@ -74,6 +78,7 @@ class Vae {
   float *eci_w_ = nullptr, *eci_b_ = nullptr;
   float *eno_g_ = nullptr, *eno_b_ = nullptr, *eco_w_ = nullptr, *eco_b_ = nullptr;
   float *q_w_ = nullptr, *q_b_ = nullptr;                   // quant_conv
+  float *cb_ = nullptr, *cb_norm_ = nullptr;                // codebook [n_embed][embed_dim] (quantize.embedding.weight), sum e^2 per row
   int dec_c_end_ = 0, enc_c_end_ = 0;                       // channels entering norm_out
   bool finalized_ = false;
 };

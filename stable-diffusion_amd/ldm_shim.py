@@ -1,6 +1,7 @@
 """The two thin wrappers between the samplers and the UNet, restated so the hot path can be driven without
 pytorch_lightning: `LatentDiffusion.apply_model` (ldm/models/diffusion/ddpm.py:891-900,986-992) and
-`DiffusionWrapper.forward` (ddpm.py:1402-1410, conditioning_key 'crossattn'), plus the schedule buffers
+`DiffusionWrapper.forward` (ddpm.py:1402-1421, conditioning_key 'crossattn', or 'concat' for the latent-inpainting
+model: the UNet reads cat([x, c_concat], 1) and no context), plus the schedule buffers
 `DDPM.register_schedule` registers (ddpm.py:117-169) that the samplers read.
 
 With the real `ldm` package installed the reference's own LatentDiffusion does this job;
@@ -17,12 +18,17 @@ def make_beta_schedule_linear(n_timestep=1000, linear_start=0.00085, linear_end=
 
 
 class DiffusionWrapperHIP(nn.Module):
-    def __init__(self, diffusion_model):
+    def __init__(self, diffusion_model, conditioning_key='crossattn'):
         super().__init__()
+        if conditioning_key not in ('crossattn', 'concat'):
+            raise NotImplementedError(f"conditioning_key {conditioning_key!r}: 'crossattn' and 'concat' only")
         self.diffusion_model = diffusion_model
-        self.conditioning_key = 'crossattn'
+        self.conditioning_key = conditioning_key
 
     def forward(self, x, t, c_concat=None, c_crossattn=None):
+        if self.conditioning_key == 'concat':          # ddpm.py:1411-1413
+            xc = torch.cat([x] + list(c_concat), dim=1)
+            return self.diffusion_model(xc, t)
         cc = c_crossattn[0] if len(c_crossattn) == 1 else torch.cat(c_crossattn, 1)
         return self.diffusion_model(x, t, context=cc)
 
@@ -30,9 +36,11 @@ class DiffusionWrapperHIP(nn.Module):
 class LatentDiffusionHIP(nn.Module):
     """What the samplers touch on `model`: num_timesteps, betas, alphas_cumprod(_prev), device, apply_model."""
 
-    def __init__(self, unet, timesteps=1000, linear_start=0.00085, linear_end=0.0120):
+    def __init__(self, unet, timesteps=1000, linear_start=0.00085, linear_end=0.0120, conditioning_key='crossattn'):
+        """The latent-inpainting model: linear_start=0.0015, linear_end=0.0205, conditioning_key='concat'
+        (models/ldm/inpainting_big/config.yaml:5-14)."""
         super().__init__()
-        self.model = DiffusionWrapperHIP(unet)
+        self.model = DiffusionWrapperHIP(unet, conditioning_key)
         betas = make_beta_schedule_linear(timesteps, linear_start, linear_end)
         alphas_cumprod = np.cumprod(1. - betas, axis=0)
         self.num_timesteps = int(timesteps)
@@ -49,8 +57,9 @@ class LatentDiffusionHIP(nn.Module):
         return self.betas.device
 
     def apply_model(self, x_noisy, t, cond, return_ids=False):
-        if not isinstance(cond, dict):
-            cond = {'c_crossattn': [cond] if not isinstance(cond, list) else cond}
+        if not isinstance(cond, dict):          # ddpm.py:986-992
+            key = 'c_concat' if self.model.conditioning_key == 'concat' else 'c_crossattn'
+            cond = {key: [cond] if not isinstance(cond, list) else cond}
         return self.model(x_noisy, t, **cond)
 
     def q_sample(self, x_start, t, noise=None):

@@ -113,3 +113,58 @@ SD_V1_VAE_DDCONFIG = dict(double_z=True, z_channels=4, resolution=256, in_channe
 
 LAION_UNET_KWARGS = dict(SD_V1_UNET_KWARGS, context_dim=1280)     # configs/latent-diffusion/txt2img-1p4B-eval.yaml:21-42
 LAION_BERT_KWARGS = dict(n_embed=1280, n_layer=32)                 # yaml:67-71
+
+# ---- the latent-inpainting model (models/ldm/inpainting_big/config.yaml) ----------------------------------------------------
+INPAINT_UNET_KWARGS = dict(image_size=64, in_channels=7, out_channels=3, model_channels=256, attention_resolutions=[8, 4, 2],
+                           num_res_blocks=2, channel_mult=[1, 2, 3, 4], num_heads=8, resblock_updown=True)   # yaml:24-41
+INPAINT_VQ_DDCONFIG = dict(attn_type='none', double_z=False, z_channels=3, resolution=256, in_channels=3, out_ch=3, ch=128,
+                           ch_mult=[1, 2, 4], num_res_blocks=2, attn_resolutions=[], dropout=0.0)          # yaml:45-61
+INPAINT_VQ_KWARGS = dict(embed_dim=3, n_embed=8192, ddconfig=INPAINT_VQ_DDCONFIG)
+INPAINT_SCHEDULE = dict(timesteps=1000, linear_start=0.0015, linear_end=0.0205, conditioning_key='concat')   # yaml:5-14
+
+
+def _key_generator(name, seed):
+    """One CPU generator per tensor, seeded by (seed, key name): the values do not depend on the order the keys are listed in
+    (the reference modules and the HIP modules enumerate their parameters in different orders)."""
+    import zlib
+    return torch.Generator().manual_seed((int(seed) * 1000003 + zlib.crc32(name.encode())) & 0x7fffffffffffffff)
+
+
+@torch.no_grad()
+def synthetic_named_state_dict(specs, seed=0, codebook_std=1.0):
+    """CPU fp32 state_dict for a list of (key, shape): deterministic per (seed, key).  Every `zero_module` tensor of the reference
+    (out_layers.3, proj_out, out.2) is drawn too -- at 0.5 / sqrt(fan_in) -- so that the attention and ResBlock branches contribute;
+    other weights 0.577 / sqrt(fan_in) (unit gain through the 1x1 / 3x3 convs), norm gammas 1 + 0.1 N, biases / betas 0.02 N,
+    a codebook (quantize.embedding.weight) codebook_std * N."""
+    sd = {}
+    for name, shape in specs:
+        shape = tuple(int(s) for s in shape)
+        g = _key_generator(name, seed)
+        if name == 'quantize.embedding.weight':
+            t = codebook_std * torch.randn(shape, generator=g)
+        elif name.endswith('.weight') and len(shape) >= 2:
+            fan_in = 1
+            for s in shape[1:]:
+                fan_in *= s
+            zero_init = name.endswith('out_layers.3.weight') or name.endswith('proj_out.weight') or name == 'out.2.weight'
+            t = torch.randn(shape, generator=g) * ((0.5 if zero_init else 0.577) / math.sqrt(fan_in))
+        elif name.endswith('.weight'):
+            t = 1.0 + 0.1 * torch.randn(shape, generator=g)
+        else:
+            t = 0.02 * torch.randn(shape, generator=g)
+        sd[name] = t
+    return sd
+
+
+def synthetic_inpaint_unet_state_dict(seed=0, unet_kwargs=None):
+    """CPU state_dict (reference UNetModel key names) of a seeded random latent-inpainting UNet."""
+    from .unet import UNetModelHIP
+    m = UNetModelHIP(**(unet_kwargs or INPAINT_UNET_KWARGS))
+    return synthetic_named_state_dict([(k, tuple(v.shape)) for k, v in m.state_dict().items()], seed)
+
+
+def synthetic_inpaint_vq_state_dict(seed=0, vq_kwargs=None):
+    """CPU state_dict (reference VQModelInterface key names, without loss.*) of a seeded random VQ first stage."""
+    from .vae import VQModelInterfaceHIP
+    m = VQModelInterfaceHIP(**(vq_kwargs or INPAINT_VQ_KWARGS))
+    return synthetic_named_state_dict([(k, tuple(v.shape)) for k, v in m.state_dict().items()], seed)

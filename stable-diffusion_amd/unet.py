@@ -8,7 +8,9 @@ a copy of configs/stable-diffusion/v1-inference.yaml with
 
 Same constructor keywords (openaimodel.py:443-470), same parameter names (so
 `model.load_state_dict(sd, strict=False)` at scripts/txt2img.py:56 fills it), same call
-`diffusion_model(x, t, context=cc)` (ldm/models/diffusion/ddpm.py:1410).  The arithmetic runs in
+`diffusion_model(x, t, context=cc)` (ldm/models/diffusion/ddpm.py:1410).  The latent-inpainting UNet
+(models/ldm/inpainting_big/config.yaml: legacy AttentionBlocks, resblock_updown, no context) is the second family:
+`diffusion_model(cat([x, c_concat], 1), t)` (ddpm.py:1411-1413).  The arithmetic runs in
 libsdmi.so (hand-written gfx950 kernels); this class only owns the parameters, packs them into the
 library on first use and hands raw device pointers across the C ABI.
 """
@@ -46,10 +48,13 @@ PRECISIONS = {'mixed': 0, 'full': 1}      # SDMI_PRECISION_MIXED / SDMI_PRECISIO
 class _Handle:
     """Owns one sdmi_unet*."""
 
-    def __init__(self, cfg, precision='mixed'):
+    def __init__(self, cfg, precision='mixed', ext=None):
         self.lib = _lib.load()
         h = C.c_void_p()
-        _lib.check(self.lib.sdmi_unet_create_with_precision(C.byref(cfg), PRECISIONS[precision], C.byref(h)))
+        if ext is None:
+            _lib.check(self.lib.sdmi_unet_create_with_precision(C.byref(cfg), PRECISIONS[precision], C.byref(h)))
+        else:
+            _lib.check(self.lib.sdmi_unet_create_ext(C.byref(cfg), C.byref(ext), PRECISIONS[precision], C.byref(h)))
         self.h = h
 
     def weight_specs(self):
@@ -90,19 +95,32 @@ class UNetModelHIP(nn.Module):
         if hip_precision not in PRECISIONS:
             raise ValueError(f"hip_precision must be one of {sorted(PRECISIONS)}, got {hip_precision!r}")
         self.hip_precision = hip_precision
-        # the SD-v1 family only (configs/stable-diffusion/v1-inference.yaml:29-44); anything else is refused loudly
+        # two families, anything else is refused loudly:
+        #   SD v1 (configs/stable-diffusion/v1-inference.yaml:29-44): SpatialTransformers with cross-attention, legacy=False
+        #   latent inpainting (models/ldm/inpainting_big/config.yaml:24-41): legacy AttentionBlocks (num_heads, no context),
+        #   ResBlocks with resampling (resblock_updown)
+        self.use_spatial_transformer = bool(use_spatial_transformer)
         unsupported = []
-        if not use_spatial_transformer or context_dim is None: unsupported.append('use_spatial_transformer=True with context_dim')
-        if legacy: unsupported.append('legacy=False')
+        if use_spatial_transformer:
+            if context_dim is None: unsupported.append('use_spatial_transformer=True with context_dim')
+            if legacy: unsupported.append('legacy=False')
+            if resblock_updown: unsupported.append('resblock_updown=False with a spatial transformer')
+        else:
+            if context_dim is not None: unsupported.append('context_dim=None without a spatial transformer')
+            if not legacy: unsupported.append('legacy=True without a spatial transformer')
+            if use_new_attention_order: unsupported.append('use_new_attention_order=False (QKVAttentionLegacy)')
         if num_heads == -1 or num_head_channels != -1: unsupported.append('num_heads (not num_head_channels)')
         if num_heads_upsample not in (-1, num_heads): unsupported.append('num_heads_upsample == num_heads')
-        if dims != 2 or not conv_resample or resblock_updown or use_scale_shift_norm: unsupported.append('dims=2, conv_resample, plain ResBlocks')
+        if dims != 2 or not conv_resample or use_scale_shift_norm: unsupported.append('dims=2, conv_resample, no scale-shift norm')
         if num_classes is not None or n_embed is not None: unsupported.append('no class conditioning / codebook head')
         if dropout != 0: unsupported.append('dropout=0')
         if unsupported:
-            raise NotImplementedError('UNetModelHIP supports the SD-v1 UNet family only; needs: ' + '; '.join(unsupported))
+            raise NotImplementedError('UNetModelHIP supports the SD-v1 and latent-inpainting UNet families only; needs: ' +
+                                      '; '.join(unsupported))
         if isinstance(context_dim, (list, tuple)) or type(context_dim).__name__ == 'ListConfig':
             context_dim = list(context_dim)[0]
+        context_dim = 0 if context_dim is None else context_dim
+        self.resblock_updown = bool(resblock_updown)
         self.image_size = image_size
         self.in_channels, self.model_channels, self.out_channels = in_channels, model_channels, out_channels
         self.num_res_blocks = num_res_blocks
@@ -113,7 +131,11 @@ class UNetModelHIP(nn.Module):
         self.dtype = torch.float32
         self._cfg = make_cfg(in_channels, out_channels, model_channels, num_res_blocks, self.channel_mult,
                              self.attention_resolutions, num_heads, transformer_depth, self.context_dim)
-        self._handle = _Handle(self._cfg, hip_precision)
+        ext = None
+        if not use_spatial_transformer or resblock_updown:
+            ext = _lib.UNetExt()
+            ext.attention_block, ext.resblock_updown = int(not use_spatial_transformer), int(bool(resblock_updown))
+        self._handle = _Handle(self._cfg, hip_precision, ext)
         self._specs = self._handle.weight_specs()
         for key, shape in self._specs:
             *path, leaf = key.split('.')
@@ -247,7 +269,10 @@ class UNetModelHIP(nn.Module):
         """Compute the cross-attention K/V of every SpatialTransformer for `context` once (attention.py:174-176
         depend on the context only) and reuse them for every forward() until unpin_context().  A forward() that gets a
         different tensor object is compared with the pinned contents (one small device compare) and, if it differs,
-        recomputes its K/V -- an img_callback or a second sampler sharing the UNet never sees stale K/V."""
+        recomputes its K/V -- an img_callback or a second sampler sharing the UNet never sees stale K/V.
+        A UNet without cross-attention (AttentionBlocks) has nothing to cache: a no-op."""
+        if not getattr(self, 'use_spatial_transformer', True):
+            return
         if not context.is_cuda:
             raise RuntimeError('UNetModelHIP runs on an MI355X device tensor only (no CPU fallback)')
         if self._needs_pack():
@@ -310,8 +335,15 @@ class UNetModelHIP(nn.Module):
         # leave it behind for a later, unrelated forward
         t_hint, self._t_hint = getattr(self, '_t_hint', None), None
         assert y is None, 'must specify y if and only if the model is class-conditional'
+        no_ctx = not getattr(self, 'use_spatial_transformer', True)
+        if no_ctx and context is not None:
+            raise ValueError('this UNet has no cross-attention (AttentionBlocks): context must be None')
         if not x.is_cuda:
             raise RuntimeError('UNetModelHIP runs on an MI355X device tensor only (no CPU fallback)')
+        if no_ctx:
+            if timesteps is None:
+                raise ValueError('timesteps are required')
+            return self._forward_no_context(x, timesteps, t_hint)
         if context is None or timesteps is None:
             raise ValueError('timesteps and context are required')
         if self._needs_pack():
@@ -332,6 +364,36 @@ class UNetModelHIP(nn.Module):
                     for i in range(0, B, self.MAX_ROWS)]
             return torch.cat(outs, dim=0)
         return self._forward_rows(x, timesteps, context, allow_reuse=True, t_hint=t_hint)
+
+    def _forward_no_context(self, x, timesteps, t_hint):
+        """UNetModel.forward(x, timesteps) of the AttentionBlock family: sdmi_unet_forward with ctx = NULL, Lctx = 0."""
+        if self._needs_pack():
+            self.pack()
+        B, Cin, H, W = x.shape
+        assert Cin == self.in_channels
+        assert timesteps.shape == (B,)
+        down = 2 ** (len(self.channel_mult) - 1)
+        if H % down or W % down:
+            raise ValueError(f'latent H and W must be multiples of {down} for this UNet (got {H} x {W}): the down ResBlocks '
+                             'average-pool 2 x 2 and round down')
+        outs = []
+        for i in range(0, B, self.MAX_ROWS):
+            xi = x[i:i + self.MAX_ROWS].detach().float().contiguous()
+            ti = timesteps[i:i + self.MAX_ROWS]
+            if ti.dtype in (torch.int64, torch.int32, torch.int16, torch.uint8):
+                t_i64, t_f32 = ti.detach().to(torch.int64).contiguous(), None
+            else:
+                t_i64, t_f32 = None, ti.detach().float().contiguous()
+            b = xi.shape[0]
+            ws = self._workspace(b, H, W, 0, x.device)
+            out = torch.empty((b, self.out_channels, H, W), dtype=torch.float32, device=x.device)
+            if t_hint is not None and t_i64 is not None:
+                _lib.check(self._handle.lib.sdmi_unet_hint_timestep(self._handle.h, int(t_hint)))
+            _lib.check(self._handle.lib.sdmi_unet_forward(
+                self._handle.h, xi.data_ptr(), _lib.ptr(t_i64), _lib.ptr(t_f32), None, out.data_ptr(),
+                b, H, W, 0, ws.data_ptr(), ws.numel(), _lib.stream_ptr()))
+            outs.append(out)
+        return outs[0] if len(outs) == 1 else torch.cat(outs, dim=0)
 
     def _forward_rows(self, x, timesteps, context, allow_reuse, t_hint=None):
         B, Cin, H, W = x.shape

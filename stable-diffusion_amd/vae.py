@@ -51,17 +51,24 @@ def _posterior(moments):
         return DiagonalGaussianDistributionHIP(moments)
 
 
-def make_vae_cfg(ddconfig, embed_dim):
+def make_vae_cfg(ddconfig, embed_dim, vq=False):
+    """vq: the VQModelInterface family (double_z False, attn_type 'vanilla' or 'none'); else the SD-v1 AutoencoderKL one."""
     dd = dict(ddconfig)
     unsupported = []
     if list(dd.get('attn_resolutions', [])): unsupported.append('attn_resolutions=[] (mid-block attention only)')
     if dd.get('dropout', 0.0) != 0: unsupported.append('dropout=0')
-    if not dd.get('double_z', True): unsupported.append('double_z=True')
+    if vq:
+        if dd.get('double_z', True): unsupported.append('double_z=False')
+        if dd.get('use_linear_attn', False) or dd.get('attn_type', 'vanilla') not in ('vanilla', 'none'):
+            unsupported.append("attn_type='vanilla' or 'none'")
+    else:
+        if not dd.get('double_z', True): unsupported.append('double_z=True')
+        if dd.get('use_linear_attn', False) or dd.get('attn_type', 'vanilla') != 'vanilla': unsupported.append("attn_type='vanilla'")
     if not dd.get('resamp_with_conv', True): unsupported.append('resamp_with_conv=True')
-    if dd.get('use_linear_attn', False) or dd.get('attn_type', 'vanilla') != 'vanilla': unsupported.append("attn_type='vanilla'")
     if dd.get('tanh_out', False) or dd.get('give_pre_end', False): unsupported.append('tanh_out=False, give_pre_end=False')
     if unsupported:
-        raise NotImplementedError('AutoencoderKLHIP supports the SD-v1 first stage family only; needs: ' + '; '.join(unsupported))
+        raise NotImplementedError(('VQModelInterfaceHIP supports the latent-inpainting first stage family only; needs: ' if vq else
+                                   'AutoencoderKLHIP supports the SD-v1 first stage family only; needs: ') + '; '.join(unsupported))
     cfg = _lib.VaeCfg()
     ch_mult = list(dd.get('ch_mult', (1, 2, 4, 8)))
     if len(ch_mult) > 8:
@@ -77,10 +84,13 @@ def make_vae_cfg(ddconfig, embed_dim):
 class _VaeHandle:
     """Owns one sdmi_vae*."""
 
-    def __init__(self, cfg, parts):
+    def __init__(self, cfg, parts, ext=None):
         self.lib = _lib.load()
         h = C.c_void_p()
-        _lib.check(self.lib.sdmi_vae_create(C.byref(cfg), parts, C.byref(h)))
+        if ext is None:
+            _lib.check(self.lib.sdmi_vae_create(C.byref(cfg), parts, C.byref(h)))
+        else:
+            _lib.check(self.lib.sdmi_vae_create_ext(C.byref(cfg), C.byref(ext), parts, C.byref(h)))
         self.h = h
 
     def weight_specs(self):
@@ -253,3 +263,134 @@ class AutoencoderKLHIP(nn.Module):
     def encode_first_stage(self, x, scale_factor=0.18215, sample=True):
         p = self.encode(x)
         return scale_factor * (p.sample() if sample else p.mode())
+
+
+class _QuantizerHIP(nn.Module):
+    """`quantize` of VQModelInterface (taming's VectorQuantizer2): holds `embedding.weight`; calling it returns the reference's
+    (z_q, emb_loss, (perplexity, min_encodings, indices)) with the loss terms None (inference)."""
+
+    def __init__(self, run):
+        super().__init__()
+        self._run = run          # (a plain function, not a module: no parameter cycle)
+
+    def forward(self, h):
+        zq, idx = self._run(h, True)
+        return zq, None, (None, None, idx.reshape(-1))
+
+
+class VQModelInterfaceHIP(AutoencoderKLHIP):
+    """`VQModelInterfaceHIP` -- drop-in for `ldm.models.autoencoder.VQModelInterface` (inference only), the first stage and
+    the `__is_first_stage__` cond stage of the latent-inpainting model (models/ldm/inpainting_big/config.yaml:42-64):
+
+        first_stage_config:
+          target: stable_diffusion_amd.vae.VQModelInterfaceHIP
+
+    encode(x) = quant_conv(encoder(x)) with no quantization (autoencoder.py:269-272); decode(h, force_not_quantize=False) =
+    decoder(post_quant_conv(quantize(h))) (:274-283), the quantizer being taming's VectorQuantizer2 in its legacy form: the
+    nearest codebook row by sum(z^2) + sum(e^2) - 2 z.e, first index on ties, z_q = z + (e[idx] - z) in fp32 (HIP kernel).
+    Parameter names: encoder.*, decoder.*, quant_conv.*, post_quant_conv.*, quantize.embedding.weight."""
+
+    def __init__(self, embed_dim, ddconfig=None, n_embed=None, lossconfig=None, ckpt_path=None, ignore_keys=[],
+                 image_key='image', colorize_nlabels=None, monitor=None, batch_resize_range=None, scheduler_config=None,
+                 lr_g_factor=1.0, remap=None, sane_index_shape=False, use_ema=False):
+        if ddconfig is None or n_embed is None:
+            raise TypeError('VQModelInterfaceHIP needs ddconfig and n_embed')
+        unsupported = []
+        if remap is not None: unsupported.append('remap=None')
+        if use_ema: unsupported.append('use_ema=False')
+        if unsupported:
+            raise NotImplementedError('VQModelInterfaceHIP supports the latent-inpainting first stage family only; needs: ' +
+                                      '; '.join(unsupported))
+        self.n_embed = int(n_embed)
+        nn.Module.__init__(self)
+        self.image_key = image_key
+        self.embed_dim = int(embed_dim)
+        self.ddconfig = dict(ddconfig)
+        self._cfg = make_vae_cfg(ddconfig, embed_dim, vq=True)
+        ext = _lib.VaeExt()
+        ext.double_z, ext.mid_attn, ext.n_embed = 0, int(self.ddconfig.get('attn_type', 'vanilla') != 'none'), self.n_embed
+        self._parts = 3
+        self._handle = _VaeHandle(self._cfg, 3, ext)
+        self._specs = self._handle.weight_specs()
+        self.add_module('quantize', _QuantizerHIP(self._quantize))
+        for key, shape in self._specs:
+            *path, leaf = key.split('.')
+            node = self
+            for name in path:
+                if name not in node._modules:
+                    node.add_module(name, _Node())
+                node = node._modules[name]
+            node.register_parameter(leaf, nn.Parameter(torch.zeros(shape), requires_grad=False))
+        if monitor is not None:
+            self.monitor = monitor
+        self._packed_sig = None
+        self._sentinels = None
+        self._ws = {}
+        if ckpt_path is not None:
+            self.init_from_ckpt(ckpt_path, ignore_keys=ignore_keys)
+
+    @torch.no_grad()
+    def encode(self, x):
+        """autoencoder.py:269-272: h = quant_conv(encoder(x)) [B, embed_dim, H/f, W/f] (the library's encode writes h, not moments)."""
+        return self.encode_moments(x)
+
+    @torch.no_grad()
+    def encode_moments(self, x):
+        self._ready(x)
+        B, Cin, H, W = x.shape
+        assert Cin == self._cfg.in_channels
+        f = self.factor
+        if H % f or W % f:
+            raise ValueError(f'image sides must be multiples of {f}')
+        x32 = x.detach().float().contiguous()
+        out = torch.empty((B, self.embed_dim, H // f, W // f), dtype=torch.float32, device=x.device)
+        for b0 in range(0, B, self.MAX_BATCH):
+            nb = min(self.MAX_BATCH, B - b0)
+            ws = self._workspace('enc', nb, H, W, x.device)
+            _lib.check(self._handle.lib.sdmi_vae_encode(self._handle.h, x32[b0:b0 + nb].data_ptr(),
+                                                        out[b0:b0 + nb].data_ptr(), nb, H, W, ws.data_ptr(), ws.numel(),
+                                                        _lib.stream_ptr()))
+        return out
+
+    @torch.no_grad()
+    def decode(self, h, force_not_quantize=False, z_scale=1.0):
+        """autoencoder.py:274-283.  `z_scale` multiplies h first (the 1/scale_factor of decode_first_stage, ddpm.py:713)."""
+        self._ready(h)
+        B, Cz, H, W = h.shape
+        assert Cz == self.embed_dim
+        z32 = h.detach().float().contiguous()
+        f = self.factor
+        out = torch.empty((B, self._cfg.out_ch, H * f, W * f), dtype=torch.float32, device=h.device)
+        for b0 in range(0, B, self.MAX_BATCH):
+            nb = min(self.MAX_BATCH, B - b0)
+            ws = self._workspace('dec', nb, H, W, h.device)
+            _lib.check(self._handle.lib.sdmi_vae_decode_vq(self._handle.h, z32[b0:b0 + nb].data_ptr(), float(z_scale),
+                                                           0 if force_not_quantize else 1, out[b0:b0 + nb].data_ptr(), nb, H,
+                                                           W, ws.data_ptr(), ws.numel(), _lib.stream_ptr()))
+        return out
+
+    @torch.no_grad()
+    def _quantize(self, h, return_indices=False):
+        """The quantizer alone (self.quantize(h) calls it): z_q [B, embed_dim, H, W] (and the int64 indices [B, H, W])."""
+        self._ready(h)
+        B, Cz, H, W = h.shape
+        assert Cz == self.embed_dim
+        z32 = h.detach().float().contiguous()
+        zq = torch.empty_like(z32)
+        idx = torch.empty((B, H, W), dtype=torch.int32, device=h.device)
+        norms = torch.empty(self.n_embed, dtype=torch.float32, device=h.device)
+        cb = dict(self.named_parameters())['quantize.embedding.weight'].detach().float().contiguous()
+        _lib.check(self._handle.lib.sdmi_k_vq_quantize(z32.data_ptr(), 1.0, cb.data_ptr(), norms.data_ptr(), self.n_embed,
+                                                       self.embed_dim, zq.data_ptr(), idx.data_ptr(), B, H * W,
+                                                       _lib.stream_ptr()))
+        return (zq, idx.long()) if return_indices else zq
+
+    def forward(self, input, return_pred_indices=False):
+        """autoencoder.py:94-100 (eval): decode(encode(x)) through the quantizer."""
+        return self.decode(self.encode(input))
+
+    def decode_first_stage(self, z, scale_factor=1.0, force_not_quantize=False):
+        return self.decode(z, force_not_quantize=force_not_quantize, z_scale=1.0 / scale_factor)
+
+    def encode_first_stage(self, x, scale_factor=1.0):
+        return scale_factor * self.encode(x)
