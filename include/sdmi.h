@@ -44,9 +44,7 @@ typedef struct sdmi_unet_cfg {
 
 const char* sdmi_last_error(void);
 int sdmi_abi_version(void);
-/* 1 if the library was built with -DSDMI_EXPERIMENTS: the kernels that lost their same-box A/Bs (the GroupNorm-folding halo conv / split-fp16
- * GEMM / split-K reduction, the five-wave tile 22, attention with the to_q projection inside, the ping-pong attention schedule) and their
- * environment knobs are compiled in.  The product library (0) has neither; their entry points fail with a message that says so. */
+/* Always 0: no experiments build exists any more (the kernels that lost their same-box A/Bs were removed).  Kept for callers that ask. */
 int sdmi_has_experiments(void);
 
 /* ---- UNet handle: replaces instantiate_from_config(unet_config) + load_state_dict ----------------------- */
@@ -293,9 +291,7 @@ typedef struct sdmi_igemm_desc {
                                            8 64x128/4/3, 9 128x128/8/3, 10 64x64/4/4, 11 128x256/8/2, 12 64x256/4/3, 13 256x64/4/3;
                                            halo-staged 3x3 conv (stride 1, pad 1, width 16/32/64, whole-row tiles):
                                            14 256x64/8/5, 15 256x128/8/3, 16 128x64/4/8, 17 128x128/4/5;
-                                           deep rings (generic): 18 64x64/4/8, 19 64x128/4/6, 20 128x64/4/6, 21 128x128/8/4;
-                                           22 64x160/5/5: five waves side by side (csrc/igemm5.hip; 1x1 / 3x3 stride 1-2, N % 160 == 0
-                                           for the auto choice): M = 8192, N = 320 -> 256 workgroups = one per CU */
+                                           deep rings (generic): 18 64x64/4/8, 19 64x128/4/6, 20 128x64/4/6, 21 128x128/8/4 */
   int32_t dma;                          /* -1 default, 0 register staging, 1 LDS-DMA */
   int32_t asym_pad;                     /* 3x3 only: 0 = zero pad 1 on every side; 1 = pad right/bottom only, i.e.
                                            F.pad(x,(0,1,0,1)) + conv(padding=0) of the VAE Downsample (model.py:72-76) */
@@ -305,10 +301,8 @@ typedef struct sdmi_igemm_desc {
    * sumsq frac * 2^40}; zero them first);
    * the output is channels [gn_cbase, gn_cbase + N) of that GroupNorm's input, gn_cpg channels per group */
   int32_t gn_n; void* gn_acc[2]; int32_t gn_cpg[2]; int32_t gn_cbase[2];
-  /* optional: one int per output tile, zero before the first launch (the kernel leaves them zero).  With it the split-K
-   * reduction happens inside the GEMM (the last block of a tile to arrive sums the splits in index order and runs the
-   * epilogue; no reduce launch) and splitk_ws holds splitk * round_up(M, BM) * round_up(N, BN) floats in register order;
-   * without it: slabs [splitk][M][N] and a separate reduce kernel */
+  /* optional: ints zeroed before the first launch (the kernels leave them zero); the GroupNorm-applying split-K reduction
+   * below keeps its grid-barrier words in the last 576 of them */
   int32_t* splitk_cnt; int32_t splitk_cnt_ints;
   /* split-fp16 dense GEMM (csrc/gemm_split16.hip; ksize 1, mode 0): a0 = high halves and a1 = low halves of the fp32
    * activation ([M][c0] each, sdmi_k_cast_f16), w = sdmi_k_pack_split3 ([N][3 c0] = [hi | hi | lo]);
@@ -321,11 +315,11 @@ typedef struct sdmi_igemm_desc {
    * rstd_m * (acc - mean_m * lnf_cs[n]) + lnf_d[n] (vectors from sdmi_k_ln_fold_prep) before the mode's epilogue. */
   const float* f16_scale; float* lnp_out;
   const float* lnf_part; int32_t lnf_npart; float lnf_eps; const float* lnf_cs; const float* lnf_d;
-  /* GroupNorm(32, pgn_eps) (+ SiLU) of the finished OUTPUT inside the split-K reduction (ABI 11; mode 0, N % 128 == 0, Hout*Wout *
-   * N / 128 <= 5120: ResBlock conv1 -> out_layers.0-1, openaimodel.py:225-227): when the GEMM is split, one workgroup per (sample,
-   * group) sums the slabs, takes the group's statistics and stores pgn_out [M][N] fp16 = SiLU(GN(v)); out_f32 is then written
-   * only with pgn_keep_f32.  *pgn_applied (host int, optional) is set to 1 when that happened; when it is left 0 the launch was an
-   * ordinary one and pgn_out is untouched. */
+  /* GroupNorm(32, pgn_eps) (+ SiLU) of the finished OUTPUT inside the split-K reduction (ABI 11; mode 0, N % 128 == 0: ResBlock
+   * conv1 -> out_layers.0-1, openaimodel.py:225-227): with SDMI_REDUCE_GN_XCD=1, when the GEMM is split, the output is its one
+   * GroupNorm statistics target and splitk_cnt is given, the reduction takes the statistics behind a grid barrier and stores
+   * pgn_out [M][N] fp16 = SiLU(GN(v)); out_f32 is then written only with pgn_keep_f32.  *pgn_applied (host int, optional) is set
+   * to 1 when that happened; when it is left 0 the launch was an ordinary one and pgn_out is untouched. */
   const float* pgn_gamma; const float* pgn_beta; float pgn_eps; int32_t pgn_silu;
   void* pgn_out; int32_t pgn_keep_f32; int32_t* pgn_applied;
   /* optional (ABI 12; mode 0, ldo % 4 == 0): fp16(v - float(fp16(v))) beside out_f16 -- the low half of the split-fp16 operand a
@@ -387,12 +381,6 @@ int sdmi_k_ln_fold_prep(const void* w_f16, int N, int K, int ldw, const float* g
 /* q [BH,nq,d], k [BH,nkv,d], vt [BH,d,nkv_pad] fp16 -> out fp16 [BH/heads, nq, heads*d]; attention.py:178-192 */
 int sdmi_k_attention(const void* q, const void* k, const void* vt, void* out, int BH, int heads, int nq, int nkv,
                      int nkv_pad, int d, float scale, void* stream);
-/* cross-attention with the to_q projection inside the kernel (csrc/attn_ctx.hip; attention.py:161,170-193): x fp16 [B*nq][C] token
- * rows, wq fp16 [C][C] (rows = head * d + dd), k / vt as above with nkv <= 128 -> out fp16 [B, nq, C]; d in {40, 80, 160}.
- * Optional LayerNorm fold (lnf_part != NULL): x = fp16(gamma * t), partials [C / 32][B * nq][2], cs / d from sdmi_k_ln_fold_prep. */
-int sdmi_k_attention_ctx(const void* x, const void* wq, const void* k, const void* vt, void* out, int BH, int heads, int nq,
-                         int nkv, int nkv_pad, int d, float scale, const float* lnf_part, float lnf_eps, const float* lnf_cs,
-                         const float* lnf_d, void* stream);
 /* split-fp16 attention (the full-precision mode): q / k / vt and their low halves q_lo / k_lo / vt_lo in the layouts above,
  * out / out_lo fp16 [BH/heads, nq, heads*d] = hi / lo of the fp32 result; d in {32, 40, 64, 80, 128, 160} */
 int sdmi_k_attention_split16(const void* q, const void* q_lo, const void* k, const void* k_lo, const void* vt, const void* vt_lo, void* out,
@@ -406,16 +394,6 @@ int sdmi_k_groupnorm(const float* x0, const float* x1, int c0, int c1, int B, in
                      const float* beta, float eps, int silu, void* out_f16, float* out_f32, void* raw_f16, void* out_lo,
                      void* raw_lo, float* partial_ws, int64_t partial_floats, void* stream);
 int64_t sdmi_k_groupnorm_ws_floats(int B, int HW);
-/* GroupNorm(32, eps) + SiLU folded into the staging of a 3x3 convolution (stride 1, pad 1) over cat(x0, x1) fp32 NHWC ->
- * out fp32 [B*H*W][N] (+bias[n] +rowvec[b][n] +residual): ResBlock in_layers / out_layers, openaimodel.py:201-204,225-231.
- * Runs the statistics kernel, then the halo-staged convolution that normalises its own input (csrc/conv3halo.hip);
- * w_packed from sdmi_k_pack_conv_weight; power-of-two W in 8..64, (c0 + c1) / 32 >= 8; tile = -1 (auto) or a halo tile id
- * 14..17; raw_hi / raw_lo (optional): split-fp16 copy of the raw input [B*H*W][c0 + c1]. */
-int sdmi_k_conv3gn(const float* x0, const float* x1, int c0, int c1, int B, int H, int W, const float* gamma,
-                   const float* beta, float eps, const void* w_packed, int N, const float* bias, const float* rowvec,
-                   int ld_rowvec, const float* residual, int ldr, float* out, int ldo, int splitk, float* splitk_ws,
-                   int64_t splitk_ws_floats, float* gn_ws, int64_t gn_ws_floats, int tile, void* raw_hi, void* raw_lo,
-                   void* stream);
 int sdmi_k_layernorm(const float* x, const float* gamma, const float* beta, void* out_f16, int M, int C, float eps,
                      void* stream);
 int sdmi_k_cast_f16(const float* x, void* out_f16, void* out_lo, int64_t n, void* stream);

@@ -143,9 +143,6 @@ _SIGS = {
     'sdmi_k_groupnorm': (C.c_int, [c_ptr, c_ptr, C.c_int, C.c_int, C.c_int, C.c_int, c_ptr, c_ptr, C.c_float, C.c_int,
                                    c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, C.c_int64, c_ptr]),
     'sdmi_k_groupnorm_ws_floats': (C.c_int64, [C.c_int, C.c_int]),
-    'sdmi_k_conv3gn': (C.c_int, [c_ptr, c_ptr, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_ptr, c_ptr, C.c_float, c_ptr,
-                                 C.c_int, c_ptr, c_ptr, C.c_int, c_ptr, C.c_int, c_ptr, C.c_int, C.c_int, c_ptr, C.c_int64,
-                                 c_ptr, C.c_int64, C.c_int, c_ptr, c_ptr, c_ptr]),
     'sdmi_k_layernorm': (C.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, C.c_int, C.c_int, C.c_float, c_ptr]),
     'sdmi_k_cast_f16': (C.c_int, [c_ptr, c_ptr, c_ptr, C.c_int64, c_ptr]),
     'sdmi_k_split_heads': (C.c_int, [c_ptr, C.c_int, C.c_int, c_ptr, c_ptr, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
@@ -162,8 +159,6 @@ _SIGS = {
     'sdmi_k_pack_split3': (C.c_int, [c_ptr, c_ptr, C.c_int, C.c_int, c_ptr]),
     'sdmi_k_pack_conv_split3': (C.c_int, [c_ptr, c_ptr, C.c_int, C.c_int, C.c_int, C.c_int, c_ptr]),
     'sdmi_k_pack_geglu': (C.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, C.c_int, C.c_int, c_ptr]),
-    'sdmi_k_attention_ctx': (C.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
-                                       c_ptr, C.c_float, c_ptr, c_ptr, c_ptr]),
     'sdmi_k_ln_fold_prep': (C.c_int, [c_ptr, C.c_int, C.c_int, C.c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
     'sdmi_image_to_uint8': (C.c_int, [c_ptr, c_ptr, C.c_int, C.c_int, C.c_int, C.c_int, c_ptr]),
     'sdmi_range_check': (C.c_int, [C.c_int]),

@@ -39,13 +39,7 @@ extern "C" {
 
 const char* sdmi_last_error(void) { return g_err.c_str(); }
 int sdmi_abi_version(void) { return SDMI_ABI_VERSION; }
-int sdmi_has_experiments(void) {
-#ifdef SDMI_EXPERIMENTS
-  return 1;
-#else
-  return 0;
-#endif
-}
+int sdmi_has_experiments(void) { return 0; }      // (see include/sdmi.h)
 
 int sdmi_unet_create(const sdmi_unet_cfg* cfg, sdmi_unet** out) { return sdmi_unet_create_with_precision(cfg, SDMI_PRECISION_MIXED, out); }
 int sdmi_unet_create_with_precision(const sdmi_unet_cfg* cfg, int precision, sdmi_unet** out) {
@@ -452,15 +446,6 @@ int sdmi_k_attention_split16(const void* q, const void* q_lo, const void* k, con
   a.BH = BH; a.heads = heads; a.nq = nq; a.nkv = nkv; a.nkv_pad = nkv_pad; a.d = d; a.scale = scale;
   return launch_attention_split16(a, (hipStream_t)stream);
 }
-int sdmi_k_attention_ctx(const void* x, const void* wq, const void* k, const void* vt, void* out, int BH, int heads, int nq,
-                         int nkv, int nkv_pad, int d, float scale, const float* lnf_part, float lnf_eps, const float* lnf_cs,
-                         const float* lnf_d, void* stream) {
-  AttnCtxParams a = AttnCtxParams();
-  a.x = (const f16*)x; a.wq = (const f16*)wq; a.k = (const f16*)k; a.vt = (const f16*)vt; a.out = (f16*)out;
-  a.BH = BH; a.heads = heads; a.nq = nq; a.nkv = nkv; a.nkv_pad = nkv_pad; a.d = d; a.C = heads * d; a.scale = scale;
-  if (lnf_part) { a.lnf_part = lnf_part; a.lnf_npart = a.C / 32; a.lnf_eps = lnf_eps; a.M = (BH / heads) * nq; a.lnf_cs = lnf_cs; a.lnf_d = lnf_d; }
-  return launch_attention_ctx(a, (hipStream_t)stream);
-}
 int64_t sdmi_k_groupnorm_ws_floats(int B, int HW) { (void)HW; return gn_acc_words(B) * 2; }   // int64 words, counted in floats
 int sdmi_k_groupnorm(const float* x0, const float* x1, int c0, int c1, int B, int HW, const float* gamma,
                      const float* beta, float eps, int silu, void* out_f16, float* out_f32, void* raw_f16, void* out_lo,
@@ -473,29 +458,6 @@ int sdmi_k_groupnorm(const float* x0, const float* x1, int c0, int c1, int B, in
   g.silu = silu; g.out_f16 = (f16*)out_f16; g.out_f32 = out_f32; g.raw_f16 = (f16*)raw_f16; g.out_lo = (f16*)out_lo; g.raw_lo = (f16*)raw_lo;
   g.acc = (long long*)partial_ws;
   return launch_groupnorm(g, (hipStream_t)stream);
-}
-int sdmi_k_conv3gn(const float* x0, const float* x1, int c0, int c1, int B, int H, int W, const float* gamma,
-                   const float* beta, float eps, const void* w_packed, int N, const float* bias, const float* rowvec,
-                   int ld_rowvec, const float* residual, int ldr, float* out, int ldo, int splitk, float* splitk_ws,
-                   int64_t splitk_ws_floats, float* gn_ws, int64_t gn_ws_floats, int tile, void* raw_hi, void* raw_lo,
-                   void* stream) {
-  SDMI_CHECK(gn_ws_floats >= gn_acc_words(B) * 2, "groupnorm workspace too small");
-  SDMI_HIP_OK(hipMemsetAsync(gn_ws, 0, gn_acc_words(B) * sizeof(long long), (hipStream_t)stream));
-  GroupNormParams g = GroupNormParams();
-  g.x0 = x0; g.x1 = x1; g.c0 = c0; g.c1 = c1; g.B = B; g.HW = H * W; g.gamma = gamma; g.beta = beta; g.eps = eps;
-  g.stats_only = 1; g.acc = (long long*)gn_ws;
-  if (launch_groupnorm(g, (hipStream_t)stream)) return -1;
-  IGemmParams p = IGemmParams();                       // the 3x3 convolution that normalises its own input (conv3halo.hip)
-  p.xf0 = x0; p.xf1 = x1; p.c0 = c0; p.c1 = c1; p.lda0 = c0 + c1;
-  p.gn_in_acc = (const long long*)gn_ws; p.gn_in_gamma = gamma; p.gn_in_beta = beta; p.gn_in_eps = eps; p.gn_in_silu = 1;
-  p.raw_hi = (f16*)raw_hi; p.raw_lo = (f16*)raw_lo;
-  p.B = B; p.Hin = p.Hout = H; p.Win = p.Wout = W; p.ksize = 3; p.stride = 1; p.up = 0; p.pad = 1;
-  p.w = (const f16*)w_packed; p.M = B * H * W; p.N = N; p.K = 9 * (c0 + c1);
-  p.bias = bias; p.rowvec = rowvec; p.ld_rowvec = ld_rowvec; p.residual = residual; p.ldr = ldr; p.out_f32 = out; p.ldo = ldo;
-  p.splitk = splitk; p.splitk_ws = splitk_ws; p.splitk_ws_floats = splitk_ws_floats;
-  if (zero_page(&p.zero_page)) return -1;
-  IGemmTune t; t.tile = tile;
-  return launch_igemm(p, t, (hipStream_t)stream);
 }
 int sdmi_k_layernorm(const float* x, const float* gamma, const float* beta, void* out_f16, int M, int C, float eps,
                      void* stream) {

@@ -192,12 +192,11 @@ struct IGemmParams {
   // ([split][M][N]); a second kernel sums the slabs in a fixed order and applies the epilogue (deterministic).
   int splitk = 1;                                      // 1 none, 0 auto, >1 forced
   float* splitk_ws = nullptr; int64_t splitk_ws_floats = 0;
-  // fused reduction (default when splitk_cnt is given): every split stores its accumulators in register order, takes a
-  // ticket from the tile's counter, and the LAST block to arrive sums the splits in index order and runs the normal
-  // epilogue -- no reduce kernel.  Counters: one int per output tile, zero before the first launch (the last block resets
-  // its counter).  Slabs then need splitk * round_up(M, BM) * round_up(N, BN) floats.
+  // counters, zero before the first launch: the grid barrier of the GroupNorm-applying reduction (igemm.hip, COOP_BAR_INTS)
+  // uses the tail.  (The fused reduction of the kernels' splitk_fused arm -- the last block of a tile to arrive sums the
+  // splits -- lost its A/B, profiles/splitk_fused_r02.txt: no launcher enables it.)
   int* splitk_cnt = nullptr; int splitk_cnt_ints = 0;
-  int gn_safe = 0;                                     // debugging (SDMI_GN_SAFE=1): the GroupNorm-folding conv drains the queue at every counted wait
+  int gn_safe = 0;                                     // unused (its GroupNorm-folding conv was removed); kept for the by-value layout
 #ifdef SDMI_IGEMM_TIMING
   long long* dbg_times = nullptr;                      // timing build only: 6 s_memtime slots per workgroup (5 used)
   int dbg_abl = 0;                                     // timing build only (SDMI_EPI_ABL): 1 no residual loads, 2 no GroupNorm statistics, 4 no output stores
@@ -221,11 +220,11 @@ struct IGemmParams {
   int gn_cpg[2] = {0, 0}, gn_cbase[2] = {0, 0};
   unsigned long long gn_magic[2] = {0, 0};             // ceil(2^40 / gn_cpg), filled by the launcher
   // optional (plain mode, round 4): GroupNorm(32) (+ SiLU) of the finished OUTPUT applied by the split-K reduction itself --
-  // ResBlock conv1 -> out_layers' GroupNorm + SiLU -> conv2 (openaimodel.py:225-231).  When this GEMM ends up split and the
-  // geometry fits (splitk_reduce_gn_kernel: one workgroup per (sample, group) sums the slabs, has the whole group in registers,
-  // takes its statistics there and stores pgn_out = fp16(SiLU(GN(v))) -- the conv2 operand; no statistics atomics, no
-  // GroupNorm-apply launch, and the fp32 value v is not stored unless pgn_keep_f32), *pgn_applied is set to 1; otherwise it is
-  // left alone and the caller runs its GroupNorm-apply launch as before.
+  // ResBlock conv1 -> out_layers' GroupNorm + SiLU -> conv2 (openaimodel.py:225-231).  When this GEMM ends up split, the
+  // geometry fits and SDMI_REDUCE_GN_XCD is on (splitk_reduce_tiled_kernel<true>: the reduction takes the statistics behind a
+  // grid barrier and stores pgn_out = fp16(SiLU(GN(v))) -- the conv2 operand; no GroupNorm-apply launch, and the fp32 value v
+  // is not stored unless pgn_keep_f32), *pgn_applied is set to 1; otherwise it is left alone and the caller runs its
+  // GroupNorm-apply launch as before.
   const float* pgn_gamma = nullptr; const float* pgn_beta = nullptr; float pgn_eps = 1e-5f; int pgn_silu = 1;
   f16* pgn_out = nullptr;                              // [M][N] fp16
   int pgn_keep_f32 = 0;                                // also store out_f32 (someone besides that GroupNorm reads it)
@@ -233,17 +232,12 @@ struct IGemmParams {
   // filled by the launcher: ceil(2^40 / (Hout*Wout)) and ceil(2^40 / Wout) for the kernel's division-free row split
   unsigned long long magic_hw = 0, magic_w = 0, magic_w2 = 0;   // (magic_w2: Wout + 2, halo-staged conv)
   int log2w = 0;
-  // ---- GroupNorm(32) (+ SiLU) of the INPUT folded into the halo staging (conv3halo.hip, conv3halo_gn_kernel): the A operand is
-  // then the fp32 residual stream itself (channel concat [xf0 | xf1], row pitches c0 / c1) and a0 / a1 / a2 are unused.  The
-  // statistics accumulators must be complete when the kernel starts (GroupNormParams::acc of that GroupNorm).  Optional raw_hi /
-  // raw_lo: the split-fp16 copy of the raw input ([M][c0 + c1], the operand of a ResBlock's 1x1 skip convolution), written once
-  // per pixel by the tile_n == 0 workgroups.
+  // ---- unused: the GroupNorm-folding convolutions that read these fields were removed (they lost their A/B); the fields stay
+  // so that the layout of this by-value kernel argument does not change.
   const float* xf0 = nullptr; const float* xf1 = nullptr;
   const long long* gn_in_acc = nullptr;
   const float* gn_in_gamma = nullptr; const float* gn_in_beta = nullptr; float gn_in_eps = 1e-5f; int gn_in_silu = 1;
   f16* raw_hi = nullptr; f16* raw_lo = nullptr;
-  // optional fp16 [M][c0 + c1] scratch: with it the launcher may run this convolution as TWO launches instead (GroupNorm-apply
-  // kernel into the scratch, then the LDS-DMA convolution) where the tuning table measured that faster (tile id SDMI_TILE_TWO_LAUNCH)
   f16* gn_scratch = nullptr;
   unsigned long long magic_cpg_in = 0;                 // launcher: ceil(2^40 / ((c0 + c1) / 32))
   // halo-staged conv geometry (launcher): output rows per image in a tile, images per tile, log2(pixels per image part)
@@ -251,21 +245,13 @@ struct IGemmParams {
   unsigned long long magic_hpi = 0;
 };
 
-constexpr int SDMI_TILE_TWO_LAUNCH = 99;   // (tuning table, GroupNorm-folding conv keys only) GroupNorm-apply launch + LDS-DMA conv
-constexpr int SDMI_NUM_TILES = 23;   // tile ids 0 .. 22 (14..17: halo-staged 3x3 conv, 22: five-wave 64 x 160), see kTiles in igemm.hip and include/sdmi.h
+constexpr int SDMI_NUM_TILES = 22;   // tile ids 0 .. 21 (14..17: halo-staged 3x3 conv), see kTiles in igemm.hip and include/sdmi.h
 struct IGemmTune {        // runtime knobs (tests sweep them; the executor takes the tuning table's choice)
   int tile = -1;          // -1 auto (tuning table, then heuristic); else a tile id
   int dma = -1;           // -1 default, 0 register-staged loads, 1 global_load_lds
 };
 
 int launch_igemm(const IGemmParams& p, const IGemmTune& tune, hipStream_t stream);
-// split-fp16 1x1 conv with GroupNorm(32) of its fp32 input rows applied while the A operand is staged (gemm_split16.hip,
-// gemm_split16_gn_kernel): x = xf0 [M][K], statistics gn_in_acc (complete), gn_in_gamma / beta / eps, weights packed [N][3K]
-bool split16_gn_supported(const IGemmParams& p);
-int launch_split16_gn(const IGemmParams& p, hipStream_t stream);
-// may a stride-1 3x3 convolution over cat(c0, c1) fp32 channels at B x H x W fold the GroupNorm(32) of its input into its
-// staging (IGemmParams::xf0 / gn_in_*; conv3halo.hip)?
-bool gn_fold_conv_supported(int B, int H, int W, int c0, int c1, int N);
 // fp16 range guard (range.hip, debug): scan an fp16 activation buffer a launch just wrote; see SDMI_CHECK_RANGE
 bool range_check_enabled();
 uint64_t tune_generation();
@@ -368,26 +354,10 @@ struct AttnParams {
   float scale = 1.f;
   int nw = 0;                // waves per workgroup (0 = auto): each wave owns 32 queries
   int causal = 0;            // 1: key j attends only to queries i >= j (CLIP text model); needs nq == nkv
-  int prio = 0;              // launcher (SDMI_ATTN_PRIO=1): s_setprio 1 for the second-dispatched half of an 8-wave workgroup
-  int pingpong = 0;          // launcher (SDMI_ATTN_PP): 8-wave launches on attn_pp_kernel (the halves of a workgroup alternate matrix / VALU blocks)
+  int prio = 0;              // 1: s_setprio 1 for the second-dispatched half of an 8-wave workgroup (measured no faster; no caller sets it)
+  int pingpong = 0;          // unused (its ping-pong kernel lost its A/B and was removed); kept for the by-value layout
 };
 int launch_attention(const AttnParams& p, hipStream_t stream);
-
-// Cross-attention with the query projection inside the kernel (attn_ctx.hip): out = softmax((x Wq^T) K^T scale) V over <= 128 cached keys
-struct AttnCtxParams {
-  const f16* x = nullptr;    // [B * nq][C] token rows: LayerNorm output, or fp16(gamma * t) with the LayerNorm fold below
-  const f16* wq = nullptr;   // [C][C] to_q weight, rows = output channels (head * d + dd)
-  const f16* k = nullptr;    // [BH][nkv][d]
-  const f16* vt = nullptr;   // [BH][d][nkv_pad]
-  f16* out = nullptr;        // [B][nq][heads * d]
-  int BH = 0, heads = 0, nq = 0, nkv = 0, nkv_pad = 0, d = 0, C = 0;
-  float scale = 1.f;
-  // optional LayerNorm fold (as IGemmParams::lnf_*): partials [lnf_npart = C / 32][M][2], M = B * nq rows
-  const float* lnf_part = nullptr; int lnf_npart = 0; float lnf_eps = 1e-5f; int M = 0;
-  const float* lnf_cs = nullptr; const float* lnf_d = nullptr;
-};
-bool attention_ctx_supported(int d, int C, int nkv);
-int launch_attention_ctx(const AttnCtxParams& p, hipStream_t stream);
 
 // GroupNorm(32) (+SiLU) over fp32 NHWC, channel-concat of two sources, fp16 or fp32 output
 struct GroupNormParams {
@@ -395,7 +365,7 @@ struct GroupNormParams {
   int B = 0, HW = 0;
   const float* gamma = nullptr; const float* beta = nullptr; float eps = 1e-5f;
   int silu = 0;
-  int stats_only = 0;          // 1: only fill the statistics accumulators (consumed by a GroupNorm-folding convolution, IGemmParams::gn_in_acc)
+  int stats_only = 0;          // 1: only fill the statistics accumulators (consumed by a launch that normalises its own input: gnconv.hip, rowchain.hip)
   int skip_stats = 0;          // 1: the accumulators were already filled by the producing GEMM epilogues (IGemmParams::gn_*)
   f16* out_f16 = nullptr;      // [B*HW][C] normalised (+SiLU)
   float* out_f32 = nullptr;    // same in fp32 (used by the output head)

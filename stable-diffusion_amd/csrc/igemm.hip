@@ -166,128 +166,6 @@ __device__ __forceinline__ f32x4 quad_transpose(const f32x4 v, int sub) {
   const f32x4 r = {r0, r1, r2, r3};                               // r[k] = element (row sub, column (sub - k) & 3)
   return f32x4{pick4(r, sub & 3), pick4(r, (sub - 1) & 3), pick4(r, (sub - 2) & 3), pick4(r, (sub - 3) & 3)};
 }
-#ifdef SDMI_EXPERIMENTS      // (bit-identical, 15 launches fewer, measured slower in round 4: profiles/splitk_slabs_r04.txt)
-// Split-K reduction + GroupNorm(32) (+ SiLU) of the result in ONE launch (IGemmParams::pgn_*; ResBlock conv1 -> out_layers'
-// GroupNorm -> SiLU, openaimodel.py:225-231, at the levels where conv1 is split: 8x8, 16x16, the concat blocks of 32x32).
-// Workgroup (g, b) owns group g of sample b: HW rows x cpg = N / 32 channels.  Thread t handles the 16-byte quads t, t + 1024, ...
-// of that block (quad = 4 channels of a row): it sums their nsplit partials in slab order, + bias + rowvec + residual -- the
-// operations of splitk_reduce_kernel in the same order, i.e. the same fp32 value v -- and keeps v in registers.
-// Statistics, BIT-IDENTICAL to the path it replaces (splitk_reduce_kernel's statistics + norm.hip's fold): there, with 32 rows per
-// block (every shape this kernel accepts: the launcher checks), a thread's partial is ONE quad's {((v0 + v1) + v2) + v3, the same
-// over the rounded squares}, added as fixed-point int64 words -- exact, order-free -- and folded by gn_mean_rstd.  Here the same
-// per-quad fp32 partials are split into the same words (gn_fixed_split), summed as integers in registers / LDS, and folded by
-// the same function; every thread then normalises its quads with gn_apply_elem (the apply kernel's arithmetic) into pgn_out, the
-// fp16 operand of conv2.  No statistics atomics, no GroupNorm-apply launch, and v is not written at all unless pgn_keep_f32.
-__device__ __forceinline__ void quad_partials(const f32x4 a, float* q1, float* q2) {
-#pragma clang fp contract(off)
-  // (no fused multiply-add: splitk_reduce_kernel adds the rounded squares -- its product feeds two exec-masked branches)
-  *q1 = ((a[0] + a[1]) + a[2]) + a[3];
-  const float s0 = a[0] * a[0], s1 = a[1] * a[1], s2 = a[2] * a[2], s3 = a[3] * a[3];
-  *q2 = ((s0 + s1) + s2) + s3;
-}
-// TILED: the slabs hold whole tiles in the MFMA register order (IGemmParams::slab_tiled).  Thread idx then loads the slab quad
-// (4 rows x 1 column) of row group idx / cpg, column idx % cpg -- four consecutive threads = four consecutive columns of the same
-// four rows (cpg % 4 == 0), a run of <= 32 columns is <= 512 contiguous bytes -- and the 4 x 4 lane transpose hands every lane the
-// row-major quad (row 4 * (idx / cpg) + (idx & 3), columns 4 * ((idx % cpg) / 4) ..).  Which thread holds which quad does not matter
-// to anything below (integer statistics, stores).
-template <int MAXQ, bool TILED>
-__global__ void __launch_bounds__(1024) splitk_reduce_gn_kernel(IGemmParams p, int nsplit, unsigned long long magic_qpr) {
-  __shared__ long long s_red[16][4];
-  const int g = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
-  const int HW = p.Hout * p.Wout;
-  const int cpg = p.N >> 5, qpr = cpg >> 2;
-  const int total = HW * qpr;
-  const size_t slab_sz = TILED ? (size_t)(((p.M + p.slab_bm - 1) / p.slab_bm) * ((p.N + p.slab_bn - 1) / p.slab_bn)) * (size_t)(p.slab_bm * p.slab_bn)
-                               : (size_t)p.M * p.N;
-  f32x4 v[MAXQ];
-  int rown[MAXQ][2];                                    // the quad this thread holds: row inside the sample, first column
-  long long w[4] = {0, 0, 0, 0};                       // {sum int, sum frac, sumsq int, sumsq frac} of this thread's quads
-#pragma unroll
-  for (int i = 0; i < MAXQ; ++i) {
-    const int idx = tid + i * 1024;
-    v[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-    rown[i][0] = 0; rown[i][1] = g * cpg;
-    if (idx < total) {                                   // (total % 4 == 0 and idx % 4 == lane % 4: a lane quad is inside or outside as a whole)
-      int row, n;
-      const float* src;
-      if (TILED) {
-        const int row4 = fast_div(idx, p.gn_magic[0]);   // idx / cpg (the launcher checked gn_cpg[0] == cpg)
-        const int c = idx - row4 * cpg;
-        const int m4 = b * HW + 4 * row4, nc = g * cpg + c;
-        const int BM = p.slab_bm, BN = p.slab_bn, WTM = BM / p.slab_wm, WTN = BN >> p.slab_sh_wn;
-        const int tiles_n = (p.N + BN - 1) / BN;
-        const int tile_m = m4 / BM, mm = m4 - tile_m * BM, wm = mm / WTM, mw = mm - wm * WTM, ii = mw >> 5, r32 = mw & 31;
-        const int tile_n = nc / BN, nn = nc - tile_n * BN, wn = nn / WTN, nw = nn - wn * WTN, jj = nw >> 5, l31 = nw & 31;
-        const int blk = (((ii << p.slab_sh_tn) + jj) << 2) + (r32 >> 3);
-        const int t_in = (((wm << p.slab_sh_wn) + wn) << 6) + (((r32 >> 2) & 1) << 5) + l31;
-        src = p.splitk_ws + (size_t)(tile_m * tiles_n + tile_n) * (size_t)(BM * BN) + (((size_t)blk << p.slab_sh_nt) + t_in) * 4;
-        row = 4 * row4 + (tid & 3);
-        n = g * cpg + (c & ~3);
-      } else {
-        row = fast_div(idx, magic_qpr);
-        n = g * cpg + (idx - row * qpr) * 4;
-        src = p.splitk_ws + ((size_t)b * HW + row) * p.N + n;
-      }
-      rown[i][0] = row; rown[i][1] = n;
-      const size_t m = (size_t)b * HW + row;
-      f32x4 biasv = {0.f, 0.f, 0.f, 0.f}, rvv = {0.f, 0.f, 0.f, 0.f}, resv = {0.f, 0.f, 0.f, 0.f};
-      if (p.bias) biasv = *(const f32x4*)(p.bias + n);
-      if (p.rowvec) rvv = *(const f32x4*)(p.rowvec + (size_t)b * p.ld_rowvec + n);
-      if (p.residual) resv = *(const f32x4*)(p.residual + m * p.ldr + n);
-      f32x4 part[16];
-#pragma unroll
-      for (int s = 0; s < 16; ++s) part[s] = (s < nsplit) ? *(const f32x4*)(src + s * slab_sz) : f32x4{0.f, 0.f, 0.f, 0.f};
-      f32x4 a = part[0];
-#pragma unroll
-      for (int s = 1; s < 16; ++s) a += part[s];       // fixed order; absent splits add +0
-      if (TILED) a = quad_transpose(a, tid & 3);       // (all four lanes of a quad are in this branch together)
-      a += biasv;
-      if (p.rowvec) a += rvv;
-      if (p.residual) a += resv;
-      v[i] = a;
-      if (p.out_f32 && p.pgn_keep_f32) SDMI_ST_F32X4(p.out_f32, m * p.ldo + n, a);
-      // the quad's partials as splitk_reduce_kernel forms them: plain adds over the values, plain adds over the ROUNDED squares
-      float q1, q2;
-      quad_partials(a, &q1, &q2);
-      long long hi, lo;
-      gn_fixed_split(q1, &hi, &lo); w[0] += hi; w[1] += lo;
-      gn_fixed_split(q2, &hi, &lo); w[2] += hi; w[3] += lo;
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) w[k] += __shfl_xor(w[k], o);      // integer adds: exact in any order
-  }
-  if ((tid & 63) == 0) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) s_red[tid >> 6][k] = w[k];
-  }
-  __syncthreads();
-  long long t[4] = {0, 0, 0, 0};
-#pragma unroll
-  for (int wv = 0; wv < 16; ++wv)
-#pragma unroll
-    for (int k = 0; k < 4; ++k) t[k] += s_red[wv][k];
-  float mean, rstd;
-  gn_mean_rstd(t[0], t[1], t[2], t[3], (double)cpg * (double)HW, p.pgn_eps, &mean, &rstd);
-#pragma unroll
-  for (int i = 0; i < MAXQ; ++i) {
-    const int idx = tid + i * 1024;
-    if (idx < total) {
-      const int n = rown[i][1];
-      const size_t m = (size_t)b * HW + rown[i][0];
-      const f32x4 ga = *(const f32x4*)(p.pgn_gamma + n), be = *(const f32x4*)(p.pgn_beta + n);
-      f16x4 y;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) y[j] = (f16)gn_apply_elem(v[i][j], mean, rstd, ga[j], be[j], p.pgn_silu);
-      SDMI_ST_F16X4(p.pgn_out, m * p.N + n, y);
-    }
-  }
-}
-
-#endif  // SDMI_EXPERIMENTS
-
 // ---- reduction over register-order slabs (IGemmParams::slab_tiled) -------------------------------------------------------
 // a quad's statistics partials as splitk_reduce_kernel forms them with one row per thread: channels j < gsplit belong to the first
 // group, the rest to the next; plain adds over the values and over the ROUNDED squares (no fused multiply-add)
@@ -510,28 +388,6 @@ __global__ void __launch_bounds__(256) splitk_reduce_tiled_heads_kernel(IGemmPar
 
 int launch_splitk_reduce(const IGemmParams& p, int nsplit, hipStream_t stream) {
   SDMI_CHECK(nsplit >= 1 && nsplit <= 16 && p.N % 4 == 0 && p.splitk_ws, "splitk_reduce: bad arguments");
-#ifdef SDMI_EXPERIMENTS
-  if (const int maxq = reduce_gn_maxq(p, nsplit)) {       // the consuming GroupNorm (+ SiLU) inside the reduction: see the kernel
-    const unsigned long long magic_qpr = div_magic(p.N / 128);
-    const double mn = (double)p.M * p.N;
-    ProfScope psg("splitk_reduce_gn", 0.0, mn * 4.0 * nsplit + mn * 2.0 + (p.residual ? mn * 4.0 : 0.0) + (p.pgn_keep_f32 ? mn * 4.0 : 0.0), stream);
-    const dim3 grid(32, (unsigned)p.B), block(1024);
-    if (p.slab_tiled) {
-      if (maxq == 1) SDMI_LAUNCH((splitk_reduce_gn_kernel<1, true>), grid, block, 0, stream, p, nsplit, magic_qpr);
-      else if (maxq == 3) SDMI_LAUNCH((splitk_reduce_gn_kernel<3, true>), grid, block, 0, stream, p, nsplit, magic_qpr);
-      else SDMI_LAUNCH((splitk_reduce_gn_kernel<5, true>), grid, block, 0, stream, p, nsplit, magic_qpr);
-    } else {
-      if (maxq == 1) SDMI_LAUNCH((splitk_reduce_gn_kernel<1, false>), grid, block, 0, stream, p, nsplit, magic_qpr);
-      else if (maxq == 3) SDMI_LAUNCH((splitk_reduce_gn_kernel<3, false>), grid, block, 0, stream, p, nsplit, magic_qpr);
-      else SDMI_LAUNCH((splitk_reduce_gn_kernel<5, false>), grid, block, 0, stream, p, nsplit, magic_qpr);
-    }
-    SDMI_HIP_OK(hipGetLastError());
-    psg.end();
-    if (p.pgn_applied) *p.pgn_applied = 1;
-    if (range_check_enabled() && range_scan("GroupNorm fp16 output (split-K reduction)", p.pgn_out, (int64_t)p.M * p.N, stream)) return -1;
-    return 0;
-  }
-#endif
   if (p.slab_tiled) {                  // register-order slabs: one thread per slab quad, whole tiles (padding rows / columns masked)
     const int64_t quads = (int64_t)cdiv(p.M, p.slab_bm) * cdiv(p.N, p.slab_bn) * (p.slab_bm * p.slab_bn / 4);
     SDMI_CHECK(quads % 256 == 0 && quads / 256 < (1ll << 31) && p.slab_wm > 0 && p.slab_wn > 0, "tiled split-K slabs: bad geometry");
@@ -620,15 +476,7 @@ static const TileCfg kTiles[SDMI_NUM_TILES] = {
     {64, 128, 2, 2, 6},    // 19  1x2, 144 KB
     {128, 64, 2, 2, 6},    // 20  2x1, 144 KB
     {128, 128, 4, 2, 4},   // 21  8 waves, 1x2, 128 KB
-    // five waves side by side (igemm5.hip): N = 160 k, M = 8192 -> exactly one workgroup per CU
-    {64, 160, 1, 5, 5},    // 22  5 waves, 2x1 per wave, 140 KB
 };
-static inline bool tile_is5(int t) { return t == 22; }
-#ifdef SDMI_EXPERIMENTS
-constexpr bool kExperiments = true;
-#else
-constexpr bool kExperiments = false;      // product build: tile 22, the GroupNorm-folding kernels and the GroupNorm-applying split-K reduction are not compiled in
-#endif
 static inline bool tile_is_halo(int t) { return t >= 14 && t <= 17; }
 static inline bool tile_tn_even(int t) { return (kTiles[t].bn / kTiles[t].wn / 32) % 2 == 0; }
 
@@ -638,9 +486,7 @@ static int launch_tile(int tile, const IGemmParams& p, bool dma, int splitk, hip
     case 0: case 1: case 2: case 3: case 4: case 5: return launch_generic_tile_g0(tile, p, dma, splitk, stream);
     case 6: case 7: case 8: case 9: case 10: return launch_generic_tile_g1(tile, p, dma, splitk, stream);
     case 11: case 12: case 13: case 18: case 19: case 20: case 21: return launch_generic_tile_g2(tile, p, dma, splitk, stream);
-    case 14: case 15: case 16: case 17:
-      return p.xf0 ? launch_halo_gn_tile(tile, p, splitk, stream) : launch_halo_tile(tile, p, splitk, stream);
-    case 22: return launch_igemm5_tile(tile, p, splitk, stream);
+    case 14: case 15: case 16: case 17: return launch_halo_tile(tile, p, splitk, stream);
     default: return fail("unknown igemm tile id");
   }
 }
@@ -690,8 +536,7 @@ class Tuner {
       if (line[0] == '#') continue;
       TuneKey k; TuneChoice c; c.us = 0;
       if (sscanf(line, "%d %d %d %d %d %d %d %d %d %d %lf", &k.M, &k.N, &k.K, &k.ksize, &k.stride, &k.up, &k.mode,
-                 &k.splitk_req, &c.tile, &c.splitk, &c.us) >= 10 && c.tile >= 0 &&
-              (c.tile < SDMI_NUM_TILES || (c.tile == SDMI_TILE_TWO_LAUNCH && k.ksize == 13)) && c.splitk >= 1 &&
+                 &k.splitk_req, &c.tile, &c.splitk, &c.us) >= 10 && c.tile >= 0 && c.tile < SDMI_NUM_TILES && c.splitk >= 1 &&
           c.splitk <= 16)
         table[k] = c;
     }
@@ -720,9 +565,7 @@ static std::vector<TuneChoice> tune_candidates(const IGemmParams& p, bool can_sp
   for (int t = 0; t < SDMI_NUM_TILES; ++t) {
     const TileCfg& c = kTiles[t];
     if (tile_is_halo(t) && !halo_supported(p, c.bm)) continue;
-    if (p.xf0 && (!tile_is_halo(t) || !halo_gn_supported(p, c.bm))) continue;     // GroupNorm-folding conv: halo tiles only
     if (p.split16 && !split16_tile_supported(t)) continue;                         // split-fp16 GEMM: its own instantiations
-    if (tile_is5(t) && (!kExperiments || p.up || p.split16 || p.xf0 || p.N % c.bn != 0)) continue;   // five-wave tile: whole 160-column tiles, plain gathers
     // never chosen by any of the round-2 collection runs (profiles/tune_candidates_r02.txt): the 2-stage twins of the
     // 3-stage tiles, 128x128 / 256x128 with 2 stages, and the 64x256 / 256x64 4-wave tiles -- fewer candidates = more
     // samples per candidate
@@ -746,7 +589,6 @@ static std::vector<TuneChoice> tune_candidates(const IGemmParams& p, bool can_sp
       if (p.splitk != 0) break;
     }
   }
-  if (p.xf0 && p.gn_scratch) out.push_back({SDMI_TILE_TWO_LAUNCH, 1, 0.0});      // GroupNorm-apply launch + LDS-DMA conv (its own table entry)
   if (out.empty()) out.push_back({5, p.splitk > 0 ? p.splitk : 1, 0.0});
   return out;
 }
@@ -837,17 +679,12 @@ int launch_igemm(const IGemmParams& p, const IGemmTune& tune, hipStream_t stream
   const int Cin = p.c0 + p.c1 + p.c2;
   SDMI_CHECK(p.K == p.ksize * p.ksize * Cin, "K != ksize^2 * (c0 + c1 + c2)");
   SDMI_CHECK(Cin % BK == 0 && p.c0 % BK == 0 && p.c1 % BK == 0, "channel counts must be multiples of 64");
-  const bool gn_fold = p.xf0 != nullptr;       // GroupNorm + SiLU folded into the conv's staging: the A operand is the fp32 stream
-  if (gn_fold)
-    SDMI_CHECK(p.ksize == 3 && p.stride == 1 && p.pad == 1 && !p.up && p.mode == EPI_PLAIN && p.c2 == 0 && p.gn_in_acc &&
-                   p.gn_in_gamma && p.gn_in_beta && (p.c1 == 0 || p.xf1),
-               "GroupNorm-folding conv: 3x3 stride 1 pad 1, plain epilogue, statistics + gamma + beta");
-  SDMI_CHECK(gn_fold || (p.lda0 % 8 == 0 && (p.a1 == nullptr || p.lda1 % 8 == 0)), "A row pitch must be a multiple of 8 halves");
+  SDMI_CHECK(p.lda0 % 8 == 0 && (p.a1 == nullptr || p.lda1 % 8 == 0), "A row pitch must be a multiple of 8 halves");
   SDMI_CHECK(p.zero_page != nullptr, "zero page missing");
   SDMI_CHECK(p.M == p.B * p.Hout * p.Wout, "M != B * Hout * Wout");
-  SDMI_CHECK(gn_fold || p.c1 == 0 || p.a1 != nullptr, "second A source missing");
+  SDMI_CHECK(p.c1 == 0 || p.a1 != nullptr, "second A source missing");
   SDMI_CHECK(p.c2 == 0 || (p.a2 != nullptr && p.lda2 % 8 == 0), "third A source missing");
-  SDMI_CHECK(gn_fold || ((p.c1 == 0 || p.lda1 == p.lda0) && (p.c2 == 0 || p.lda2 == p.lda0)), "all A sources must share one row pitch");
+  SDMI_CHECK((p.c1 == 0 || p.lda1 == p.lda0) && (p.c2 == 0 || p.lda2 == p.lda0), "all A sources must share one row pitch");
   SDMI_CHECK(!p.up || (p.ksize == 3 && p.stride == 1), "upsample folding needs a 3x3 stride-1 conv");
   if (p.mode == EPI_GEGLU) SDMI_CHECK(p.N % 64 == 0 && p.out_f16 != nullptr, "GEGLU needs N % 64 == 0 and an fp16 output");
   if (p.ln_out)
@@ -870,7 +707,7 @@ int launch_igemm(const IGemmParams& p, const IGemmTune& tune, hipStream_t stream
   }
   if (p.mode == EPI_HEADS) SDMI_CHECK(p.segC > 0 && p.dh > 0 && p.N % p.segC == 0 && p.N / p.segC <= 3, "bad head scatter");
 
-  SDMI_CHECK((gn_fold || (int64_t)p.B * p.Hin * p.Win * p.lda0 * 2 + (int64_t)(p.Win + 1) * p.lda0 * 2 < ((int64_t)1 << 31) - 65536) &&
+  SDMI_CHECK((int64_t)p.B * p.Hin * p.Win * p.lda0 * 2 + (int64_t)(p.Win + 1) * p.lda0 * 2 < ((int64_t)1 << 31) - 65536 &&
                  (int64_t)p.N * p.K * 2 < ((int64_t)1 << 31) - 65536,
              "tensor too large for 31-bit byte offsets (buffer addressing)");
   static const int env_dma = env_int("SDMI_IGEMM_DMA", 1);
@@ -889,15 +726,14 @@ int launch_igemm(const IGemmParams& p, const IGemmTune& tune, hipStream_t stream
 
   // ---- (tile, split-K): explicit request > tuning table / collection run > heuristic ------------------------------
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  // (the GroupNorm-folding conv is its own family of kernels: keyed apart with ksize 13)
-  // (... and so is the split-fp16 dense GEMM: ksize 11)
-  TuneKey tkey{p.M, p.N, p.K, gn_fold ? 13 : (p.split16 ? 11 : p.ksize), p.stride, p.up, p.mode, splitk};
+  // (the split-fp16 dense GEMM is its own family of kernels: keyed apart with ksize 11)
+  TuneKey tkey{p.M, p.N, p.K, p.split16 ? 11 : p.ksize, p.stride, p.up, p.mode, splitk};
   int tcand = -1;
   if (tile < 0) {
     std::lock_guard<std::mutex> lk(g_tuner.mu);
     g_tuner.ensure_loaded();
-    // SDMI_TUNE_ONLY_KSIZE=<k> restricts a collection run to one kernel family (the key's ksize: 1, 3, or 13 = the GroupNorm-
-    // folding conv); every other launch keeps its table entry, so the run measures the new family inside an unchanged call
+    // SDMI_TUNE_ONLY_KSIZE=<k> restricts a collection run to one kernel family (the key's ksize: 1, 3, or 11 = the split-fp16
+    // dense GEMM); every other launch keeps its table entry, so the run measures the new family inside an unchanged call
     static const int only_ksize = env_int("SDMI_TUNE_ONLY_KSIZE", -1);
     if (g_tuner.collecting && (only_ksize < 0 || tkey.ksize == only_ksize)) {
       IGemmParams q = p; q.splitk = splitk;
@@ -911,9 +747,7 @@ int launch_igemm(const IGemmParams& p, const IGemmTune& tune, hipStream_t stream
       // a table entry is taken only if it passes the predicates tune_candidates() generated it under (the key does not carry
       // the whole geometry, and the file may be stale or hand-edited): otherwise the heuristic below decides
       auto it = g_tuner.table.find(tkey);
-      if (it != g_tuner.table.end() && it->second.tile == SDMI_TILE_TWO_LAUNCH) {
-        if (gn_fold && p.gn_scratch) tile = SDMI_TILE_TWO_LAUNCH;
-      } else if (it != g_tuner.table.end()) {
+      if (it != g_tuner.table.end()) {
         const int tt = it->second.tile, sk = it->second.splitk;
         const bool halo = tile_is_halo(tt);
         const bool ws_ok = sk == 1 || (can_split && splitk_ws_need(p, kTiles[tt].bm, kTiles[tt].bn, sk) <= p.splitk_ws_floats);
@@ -921,62 +755,13 @@ int launch_igemm(const IGemmParams& p, const IGemmTune& tune, hipStream_t stream
                                           : (sk == 1 || (ws_ok && nkt / sk >= 4 && (halo || (sk != 5 && sk != 10)) &&
                                                          (!halo || (nkt / 9) % sk == 0)));
         if (split_ok && (p.mode != EPI_GEGLU || tile_tn_even(tt)) && (!halo || halo_supported(p, kTiles[tt].bm)) &&
-            (!tile_is5(tt) || (kExperiments && !p.up && !p.split16 && p.N % kTiles[tt].bn == 0)) &&
-            (!gn_fold || (halo && halo_gn_supported(p, kTiles[tt].bm))) && (!p.split16 || split16_tile_supported(tt))) {
+            (!p.split16 || split16_tile_supported(tt))) {
           tile = tt; splitk = sk;
         }
       }
     }
   }
   if (p.mode == EPI_GEGLU && tile >= 0 && !tile_tn_even(tile)) tile = 0;   // GEGLU pairs 32-col tiles inside a wave
-  static const int force_two = env_int("SDMI_GN_FORCE_TWO", 0);         // A/B: 1 = every folded conv as two launches, -1 = none
-  if (gn_fold && p.gn_scratch && force_two > 0 && tcand < 0) tile = SDMI_TILE_TWO_LAUNCH;
-  if (gn_fold && force_two < 0 && tile == SDMI_TILE_TWO_LAUNCH && tcand < 0) tile = -1;
-  if (gn_fold && tile < 0 && p.gn_scratch && force_two >= 0 && (p.M < 512 || p.c1 > 0)) {
-    // no table entry: the round-3 measurements have the two launches ahead at the 8x8 level (the normalisation repeats in every
-    // one of 20 N-tiles) and on the skip-concat inputs of the output blocks, the folding kernel elsewhere
-    tile = SDMI_TILE_TWO_LAUNCH;
-  }
-  if (gn_fold && tile == SDMI_TILE_TWO_LAUNCH) {
-    SDMI_CHECK(p.gn_scratch != nullptr, "two-launch GroupNorm + conv needs the fp16 scratch");
-    if (ev0) SDMI_HIP_OK(hipEventRecord(ev0, stream));
-    GroupNormParams g = GroupNormParams();
-    g.x0 = p.xf0; g.x1 = p.xf1; g.c0 = p.c0; g.c1 = p.c1; g.B = p.B; g.HW = p.Hout * p.Wout;
-    g.gamma = p.gn_in_gamma; g.beta = p.gn_in_beta; g.eps = p.gn_in_eps; g.silu = p.gn_in_silu;
-    g.skip_stats = 1; g.acc = (long long*)p.gn_in_acc;                   // (complete: see IGemmParams::gn_in_acc)
-    g.out_f16 = p.gn_scratch; g.raw_f16 = p.raw_hi; g.raw_lo = p.raw_lo;
-    if (launch_groupnorm(g, stream)) return -1;
-    IGemmParams q = p;
-    q.xf0 = q.xf1 = nullptr; q.gn_in_acc = nullptr; q.raw_hi = q.raw_lo = nullptr; q.gn_scratch = nullptr;
-    q.a0 = p.gn_scratch; q.c0 = Cin; q.c1 = 0; q.lda0 = Cin;
-    const int rc2 = launch_igemm(q, IGemmTune(), stream);
-    if (ev0) {
-      SDMI_HIP_OK(hipEventRecord(ev1, stream));
-      std::lock_guard<std::mutex> lk(g_tuner.mu);
-      g_tuner.recs.push_back({tkey, tcand, ev0, ev1});
-    }
-    return rc2;
-  }
-  if (gn_fold) {
-    // halo tiles only.  Without a table entry: the 256 x 64 tile (whole images of the 16x16 / 8x8 levels fit it too), the
-    // 128 x 64 one for 128 rows; split at 64-channel-chunk granularity until ~200 workgroups exist.
-    static const int pref[4] = {14, 16, 15, 17};
-    if (tile >= 0) SDMI_CHECK(tile_is_halo(tile) && halo_gn_supported(p, kTiles[tile].bm), "GroupNorm-folding conv: unsupported tile for this shape");
-    for (int i = 0; i < 4 && tile < 0; ++i)
-      if (halo_gn_supported(p, kTiles[pref[i]].bm) && kTiles[pref[i]].bm <= std::max(p.M, 128)) tile = pref[i];
-    SDMI_CHECK(tile >= 0, "GroupNorm-folding conv: no halo tile fits this shape (the executor checks halo_gn_supported first)");
-    if (splitk <= 0) {
-      splitk = 1;
-      if (can_split) {
-        const long blocks = (long)cdiv(p.M, kTiles[tile].bm) * cdiv(p.N, kTiles[tile].bn);
-        const int nch = Cin / BK;
-        static const int cand[] = {2, 3, 4, 5, 6, 8, 10};
-        for (int sk : cand)
-          if (nch % sk == 0 && nch / sk >= 2 && blocks * sk <= 320 && splitk_ws_need(p, kTiles[tile].bm, kTiles[tile].bn, sk) <= p.splitk_ws_floats)
-            splitk = sk;
-      }
-    }
-  }
   if (p.split16) {
     if (tile >= 0) SDMI_CHECK(split16_tile_supported(tile), "split-fp16 GEMM: tile id without an instantiation");
     else tile = 5;                       // 64 x 64, 3 stages: the many-workgroup tile (table entries refine it)

@@ -344,7 +344,7 @@ int launch_cfg(const IGemmParams& p, bool dma, int splitk, hipStream_t stream) {
   IGemmParams q = p;
   q.splitk = nsplit;
   q.tile_n_fastest = tile_order_n_fastest(p);
-  q.splitk_fused = nsplit > 1 && splitk_fusable(p, BM, BN);
+  q.splitk_fused = 0;
   slab_layout(q, BM, BN, WARPS_M, WARPS_N, nsplit);
   q.epi_vec = epi_vec_ok(p);
   SDMI_CHECK(splitk_ws_need(p, BM, BN, nsplit) <= p.splitk_ws_floats, "split-K workspace too small");
@@ -384,7 +384,7 @@ int launch_cfg(const IGemmParams& p, bool dma, int splitk, hipStream_t stream) {
 #undef SDMI_LAUNCH_KIND
   SDMI_HIP_OK(hipGetLastError());
   ps.end();
-  if (nsplit > 1 && !q.splitk_fused) return launch_splitk_reduce(q, nsplit, stream);     // (+ the LayerNorm launch when q.ln_out)
+  if (nsplit > 1) return launch_splitk_reduce(q, nsplit, stream);     // (+ the LayerNorm launch when q.ln_out)
   if (q.ln_out) return launch_layernorm(q.out_f32, q.ln_gamma, q.ln_beta, q.ln_out, q.M, q.N, q.ln_eps, stream);
   return 0;
 }

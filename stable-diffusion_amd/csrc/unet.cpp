@@ -73,17 +73,9 @@ int UNet::build(const sdmi_unet_cfg& c, int precision, const sdmi_unet_ext* ext)
   SDMI_CHECK(c.num_heads >= 1 && c.transformer_depth >= 1, "num_heads / transformer_depth");
   const int mc = c.model_channels;
   te_ = 4 * mc;
-#ifdef SDMI_EXPERIMENTS      // knobs that LOWER the arithmetic or lost their A/B: not read by the product library
-  if (const char* e = getenv("SDMI_PRECISE_1X1")) precise_1x1_ = atoi(e) != 0;
-  if (const char* e = getenv("SDMI_PRECISE_KV")) precise_kv_ = atoi(e) != 0;
-  if (const char* e = getenv("SDMI_PRECISE_LAST_RES")) precise_last_res_ = atoi(e) != 0;
-  if (const char* e = getenv("SDMI_PRECISE_1X1_MAX_DS")) precise_1x1_max_ds_ = atoi(e);
-  if (const char* e = getenv("SDMI_SIDE_STREAM")) side_stream_ = atoi(e) != 0;
-#endif
   if (const char* e = getenv("SDMI_FUSE_GN_STATS")) fuse_gn_stats_ = atoi(e) != 0;
   if (const char* e = getenv("SDMI_LN_FOLD")) ln_fold_ = atoi(e) != 0;
   if (const char* e = getenv("SDMI_LN_FOLD_MIN_ROWS")) ln_fold_min_rows_ = atoi(e);
-  if (full()) precise_kv_ = true;      // (full mode: every operand split-fp16, whatever the experiments build's knobs say)
 
   int cur_ds = 1;               // downsample factor of the layer being added (ds below; the middle block sits at the deepest one)
   auto add_res = [&](const std::string& p, int cin, int cout) {
@@ -304,11 +296,6 @@ int DevStage::release(hipStream_t stream) {
 }
 
 UNet::~UNet() {
-  if (side_) {
-    (void)hipStreamSynchronize(side_);
-    for (auto& e : side_ev_) if (e) (void)hipEventDestroy(e);
-    (void)hipStreamDestroy(side_);
-  }
   for (void* p : owned_) (void)hipFree(p);
   if (emb_tab_) (void)hipFree(emb_tab_);
   if (emb_tab_tdev_) (void)hipFree(emb_tab_tdev_);
@@ -560,11 +547,11 @@ int UNet::import_packed(const void* host_buf, int64_t bytes, hipStream_t stream)
   SDMI_CHECK(((h.reserved & PK_FULL) != 0) == full(), std::string("packed blob was written by a ") +
              ((h.reserved & PK_FULL) ? "full" : "mixed") + "-precision UNet handle and cannot be imported into a " + (full() ? "full" : "mixed") +
              "-precision one: repack it with a handle of this precision");
-  SDMI_CHECK((h.precise_1x1 != 0) == precise_1x1_, "packed blob was written with a different SDMI_PRECISE_1X1 setting");
+  SDMI_CHECK((h.precise_1x1 != 0) == precise_1x1_, "packed blob was written with a different precision allocation (split-fp16 1x1 convs)");
   SDMI_CHECK((h.reserved & (3 << 4)) == ((ext_.attention_block << 4) | (ext_.resblock_updown << 5)),
              "packed blob was written for a different UNet family (attention_block / resblock_updown)");
   SDMI_CHECK((h.reserved & ~PK_FULL & ~(3 << 4)) == ((precise_kv_ ? 1 : 0) | (precise_last_res_ ? 2 : 0) | (precise_1x1_max_ds_ << 8)),
-             "packed blob was written with a different precision allocation (SDMI_PRECISE_KV / _LAST_RES / _1X1_MAX_DS)");
+             "packed blob was written with a different precision allocation (context K / V, last ResBlock, 1x1 conv levels)");
   std::vector<std::pair<void**, size_t>> bufs;
   int64_t total = 0;
   packed_layout(&bufs, &total);
@@ -594,35 +581,11 @@ struct Fwd : FwdBase {
   bool st_tail_on = false;      // ... and the out-projection of attn2 in front of the tail's chain launch (SDMI_ST_TAIL)
   bool st_mid_ctx_on = false;   // ... and the cross-attention inside the st_mid launch (SDMI_ST_MID_CTX)
   bool gn_conv_on = false;      // ResBlock GroupNorm + SiLU + conv3x3 as one launch where a workgroup can own all output columns (gnconv.hip; SDMI_GN_CONV)
-  // cross-attention with the to_q projection inside the kernel (attn_ctx.hip), SDMI_ATTN_CTX_FUSED=1.  Default off: same-box A/B,
-  // round 3 (profiles/experiments_r03.txt): 5.98 vs 5.88 ms per UNet call -- -3.8 us per launch at d = 40, +1.4 at d = 80, +13 at d = 160
-  bool fuse_ctx_q = false;
-  int fuse_ctx_maxd = 160;      // ... for head dims up to this (SDMI_ATTN_CTX_MAXD)
-  // SpatialTransformer norm applied inside the proj_in GEMM (gemm_split16_gn_kernel), SDMI_GN_PROJ_FOLD=1.  Default off: bit-identical,
-  // 15 launches fewer, but 7.05 vs 6.86 ms per UNet call same box (profiles/experiments_r03.txt): -4.7 us per site at 2048 rows, a tie at
-  // 8192, +7 us at 512 rows / 1280 channels (20 k-tiles, each one drained register-load round trip)
-  bool gn_proj_fold = false;
   float* emb_all = nullptr;     // [B][emb_total] (emb_ld = emb_total), or one row of the timestep table shared by every sample (emb_ld = 0)
   int emb_ld = 0;
   bool emb_caller = false;      // emb_all is that table row: a caller pointer of a launch tape (Tape::R_EMB)
   const f16* ctx16 = nullptr;   // [B*L][context_dim], null when the cached K/V are used
   const f16* ctx16_lo = nullptr; // ... its split-fp16 low half fp16(ctx - fp16(ctx)) (precise K / V projections)
-
-  // conv3x3(SiLU(GroupNorm32(cat(x0, x1)))) with the normalisation folded into the convolution's halo staging
-  // (openaimodel.py:201-204,225-231): statistics first (from the producers' epilogues when the plan has them), then ONE launch
-  IGemmParams conv3_gn(const Act& x0, const Act* x1, const float* gamma, const float* beta, const f16* w, int N, f16* raw_hi,
-                       f16* raw_lo) {
-    long long* acc = groupnorm(x0, x1, gamma, beta, 1e-5f, 1, nullptr, nullptr, nullptr, nullptr, nullptr, /*stats_only=*/true);
-    const int Cin = x0.C + (x1 ? x1->C : 0);
-    IGemmParams p = conv3(nullptr, Cin, x0.H, x0.W, x0.H, x0.W, 1, 0, w, N);
-    p.xf0 = x0.p; p.c0 = x0.C; p.xf1 = x1 ? x1->p : nullptr; p.c1 = x1 ? x1->C : 0; p.lda0 = Cin;
-    p.gn_in_acc = acc; p.gn_in_gamma = gamma; p.gn_in_beta = beta; p.gn_in_eps = 1e-5f; p.gn_in_silu = 1;
-    p.raw_hi = raw_hi; p.raw_lo = raw_lo;
-    // (scratch for the launcher's two-launch alternative: per shape, the tuning table decides between the folding kernel and
-    // GroupNorm-apply + LDS-DMA conv -- same operand bits either way)
-    p.gn_scratch = S<f16>((size_t)B * x0.H * x0.W * Cin);
-    return p;
-  }
 
   Act res_block(Layer& L, const Act& x0, const Act* x1) {
     const int H = x0.H, W = x0.W, M = B * H * W;
@@ -630,17 +593,6 @@ struct Fwd : FwdBase {
     if (Cin != L.cin) { ok(fail("res block channel mismatch at " + L.prefix)); }
     if (Cin == Cout && x1) ok(fail("identity skip with a concatenated input at " + L.prefix));
     const size_t mark = scratch.off;
-    // GroupNorm + SiLU folded into the halo staging of the 3x3 convs where the geometry allows (every level of SD v1)
-    // (SDMI_FUSE_GN_WHICH: bit 0 in_layers, bit 1 out_layers; SDMI_FUSE_GN_W: only at this width -- bisecting knobs)
-#ifdef SDMI_EXPERIMENTS
-    static const int fold_which = getenv("SDMI_FUSE_GN_WHICH") ? atoi(getenv("SDMI_FUSE_GN_WHICH")) : 3;
-    static const int fold_w = getenv("SDMI_FUSE_GN_W") ? atoi(getenv("SDMI_FUSE_GN_W")) : 0;
-#else
-    constexpr int fold_which = 3, fold_w = 0;     // (gn_fold_conv_supported() is false in the product build: no fold site)
-#endif
-    const bool fold_here = fold_w == 0 || fold_w == W;
-    const bool fold1 = !L.precise3 && (fold_which & 1) && fold_here && gn_fold_conv_supported(B, H, W, x0.C, x1 ? x1->C : 0, Cout);
-    const bool fold2 = !L.precise3 && (fold_which & 2) && fold_here && gn_fold_conv_supported(B, H, W, Cout, 0, Cout);
     f16* raw = (Cin != Cout) ? S<f16>((size_t)M * Cin) : nullptr;
     const bool p1 = L.p1x1;              // this layer's skip convolution as 3-pass split-fp16
     const bool p3 = L.precise3;          // ... and its two 3x3 convs (the last ResBlock): operands [hi | lo | hi] against packed [w_hi | w_hi | w_lo]
@@ -656,8 +608,8 @@ struct Fwd : FwdBase {
     gn2_applied = 0;
     // in_layers / out_layers as ONE launch each (gnconv.hip: 32 pixels x all 320 output channels per workgroup, the halo normalised once):
     // the 64 x 64 level of SD v1.  (in_layers only without a skip convolution: that one reads raw fp16 copies the GroupNorm launch writes.)
-    const bool gc1 = gn_conv_on && !L.precise3 && !fold1 && Cin == Cout && gn_conv3_supported(B, H, W, x0.C, x1 ? x1->C : 0, Cout);
-    const bool gc2 = gn_conv_on && !L.precise3 && !fold2 && gn_conv3_supported(B, H, W, Cout, 0, Cout);
+    const bool gc1 = gn_conv_on && !p3 && Cin == Cout && gn_conv3_supported(B, H, W, x0.C, x1 ? x1->C : 0, Cout);
+    const bool gc2 = gn_conv_on && !p3 && gn_conv3_supported(B, H, W, Cout, 0, Cout);
     auto gn_conv = [&](const Act& a0, const Act* a1, const float* gamma, const float* beta, const f16* w, IGemmParams& e) {
       GnConvParams g = GnConvParams();
       g.gn_acc = groupnorm(a0, a1, gamma, beta, 1e-5f, 1, nullptr, nullptr, nullptr, nullptr, nullptr, /*stats_only=*/true);
@@ -673,21 +625,15 @@ struct Fwd : FwdBase {
       TapeCaller tc(Tape::R_EMB, emb_caller ? p.rowvec : nullptr);
       gn_conv(x0, x1, L.f32[0], L.f32[1], L.w16[0], p);
     } else {
-      IGemmParams p = IGemmParams();
-      if (fold1) {
-        p = conv3_gn(x0, x1, L.f32[0], L.f32[1], L.w16[0], Cout, raw, raw_lo);    // (+ the skip conv's raw hi | lo operand)
-      } else {
-        f16* a = S<f16>((size_t)M * Cin);
-        f16* a_lo = p3 ? S<f16>((size_t)M * Cin) : nullptr;
-        groupnorm(x0, x1, L.f32[0], L.f32[1], 1e-5f, 1, a, nullptr, raw, a_lo, raw_lo);
-        p = conv3(a, Cin, H, W, H, W, 1, 0, L.w16[0], Cout);
-        if (p3) split3(p, a, a_lo, Cin);
-      }
-      if (Cin != Cout && !fold1) fork_side();
+      f16* a = S<f16>((size_t)M * Cin);
+      f16* a_lo = p3 ? S<f16>((size_t)M * Cin) : nullptr;
+      groupnorm(x0, x1, L.f32[0], L.f32[1], 1e-5f, 1, a, nullptr, raw, a_lo, raw_lo);
+      IGemmParams p = conv3(a, Cin, H, W, H, W, 1, 0, L.w16[0], Cout);
+      if (p3) split3(p, a, a_lo, Cin);
       p.bias = L.f32[2]; p.rowvec = emb_all + L.emb_off; p.ld_rowvec = emb_ld;
       p.out_f32 = h; p.ldo = Cout;
       attach_gn_targets(p, hact);          // statistics of out_layers' GroupNorm come out of this epilogue
-      if (!fold2 && !gc2 && !p3) {
+      if (!gc2 && !p3) {
         // ... or, where this conv ends up split along K (8x8, 16x16, the concat blocks of 32x32), GroupNorm + SiLU are applied by
         // its split-K reduction: a2 = the conv2 operand comes straight out of it (IGemmParams::pgn_*; gn2_applied says so)
         a2 = S<f16>((size_t)M * Cout);
@@ -697,31 +643,24 @@ struct Fwd : FwdBase {
       gemm(p);
     }
     const float* residual = x0.p;
-    if (Cin != Cout) {       // skip_connection: needs only the raw fp16 copies (written by GroupNorm 1 / by conv1's staging)
+    if (Cin != Cout) {       // skip_connection: needs only the raw fp16 copies (written by GroupNorm 1)
       IGemmParams p = dense1x1(raw, raw_lo, M, Cin, L.w16[2], Cout, H * W, p1);
       p.bias = L.f32[6]; p.out_f32 = out.p; p.ldo = Cout;
-      if (fold1) gemm(p); else gemm_side(p);
+      gemm(p);
       residual = out.p;
     }
     if (gc2) {
       IGemmParams p = conv3(nullptr, Cout, H, W, H, W, 1, 0, L.w16[1], Cout);
-      if (Cin != Cout && !fold1) join_side();
       p.bias = L.f32[5]; p.residual = residual; p.ldr = Cout; p.out_f32 = out.p; p.ldo = Cout;
       attach_gn_targets(p, out);
       attach_f16_copy(p, out);
       gn_conv(hact, nullptr, L.f32[3], L.f32[4], L.w16[1], p);
     } else {
-      IGemmParams p = IGemmParams();
-      if (fold2) {
-        p = conv3_gn(hact, nullptr, L.f32[3], L.f32[4], L.w16[1], Cout, nullptr, nullptr);
-      } else {
-        f16* a2_lo = nullptr;
-        if (p3) { a2 = S<f16>((size_t)M * Cout); a2_lo = S<f16>((size_t)M * Cout); }
-        groupnorm(hact, nullptr, L.f32[3], L.f32[4], 1e-5f, 1, a2, nullptr, nullptr, a2_lo, nullptr, false, gn2_applied != 0);
-        p = conv3(a2, Cout, H, W, H, W, 1, 0, L.w16[1], Cout);
-        if (p3) split3(p, a2, a2_lo, Cout);
-      }
-      if (Cin != Cout && !fold1) join_side();
+      f16* a2_lo = nullptr;
+      if (p3) { a2 = S<f16>((size_t)M * Cout); a2_lo = S<f16>((size_t)M * Cout); }
+      groupnorm(hact, nullptr, L.f32[3], L.f32[4], 1e-5f, 1, a2, nullptr, nullptr, a2_lo, nullptr, false, gn2_applied != 0);
+      IGemmParams p = conv3(a2, Cout, H, W, H, W, 1, 0, L.w16[1], Cout);
+      if (p3) split3(p, a2, a2_lo, Cout);
       p.bias = L.f32[5]; p.residual = residual; p.ldr = Cout; p.out_f32 = out.p; p.ldo = Cout;
       attach_gn_targets(p, out);           // ... and those of the GroupNorm(s) that read this block's output
       attach_f16_copy(p, out);             // ... and the fp16 copy a Downsample / Upsample behind this block wants
@@ -832,18 +771,15 @@ struct Fwd : FwdBase {
     f16* xn = S<f16>((size_t)M * C);
     const bool p1 = L.p1x1;              // proj_in / proj_out of this SpatialTransformer as 3-pass split-fp16
     f16* xn_lo = p1 ? S<f16>((size_t)M * C) : nullptr;
-    // proj_in(norm(x)), attention.py:254-255: the GroupNorm either as its own launch (fp32 stream -> split-fp16 hi | lo operands) or
-    // applied inside the GEMM while it stages its A operand (gemm_split16_gn_kernel: same operand bits, same products, one launch less)
-    IGemmParams pin = IGemmParams();
-    pin.M = M; pin.N = C; pin.K = C; pin.ksize = 1; pin.Hout = N; pin.Wout = 1; pin.B = B;
+    // proj_in(norm(x)), attention.py:254-255: the GroupNorm as its own launch (fp32 stream -> split-fp16 hi | lo operands) or inside
+    // the chain launch below
     const bool fold_ln = ln_fold_on && C % 64 == 0 && C <= 1280 && N % 64 == 0 && M % 64 == 0 && M >= u->ln_fold_min_rows_;
-    const bool gn_in_gemm = gn_proj_fold && fold_ln && p1 && M >= 512 && split16_gn_supported(pin);
     // the head of the SpatialTransformer (GroupNorm-apply -> proj_in -> q | k | v of the first transformer block) as one row-strip chain
     // launch (rowchain.hip st_head_kernel; UNet::st_head_): LayerNorm fold on, split-fp16 proj_in, C = 320
-    const bool chain_head = st_head_on && fold_ln && p1 && !gn_in_gemm && L.tb[0].lnf[0] != nullptr &&
+    const bool chain_head = st_head_on && fold_ln && p1 && L.tb[0].lnf[0] != nullptr &&
                             st_head_supported(C, M, N, Np, L.heads, L.dh) && dense1x1(nullptr, nullptr, M, C, L.w16[0], C, N, p1).split16;
     long long* gn_stats = nullptr;
-    if (gn_in_gemm || chain_head) gn_stats = groupnorm(x, nullptr, L.f32[0], L.f32[1], 1e-6f, 0, nullptr, nullptr, nullptr, nullptr, nullptr, /*stats_only=*/true);
+    if (chain_head) gn_stats = groupnorm(x, nullptr, L.f32[0], L.f32[1], 1e-6f, 0, nullptr, nullptr, nullptr, nullptr, nullptr, /*stats_only=*/true);
     else groupnorm(x, nullptr, L.f32[0], L.f32[1], 1e-6f, 0, xn, nullptr, nullptr, xn_lo, nullptr);
     float* t = S<float>((size_t)M * C);
     f16* ln = S<f16>((size_t)M * C);
@@ -877,14 +813,6 @@ struct Fwd : FwdBase {
         if (e != hipSuccess) ok(fail(std::string("hipMemsetAsync: ") + hipGetErrorString(e)));
       }
       if (!dry && !rc) ok(launch_st_head(h, s));
-    } else if (gn_in_gemm) {
-      IGemmParams p = dense(nullptr, M, C, L.w16[0], C, N);
-      p.xf0 = x.p; p.gn_in_acc = gn_stats; p.gn_in_gamma = L.f32[0]; p.gn_in_beta = L.f32[1]; p.gn_in_eps = 1e-6f; p.gn_in_silu = 0;
-      p.ldw = 3 * C; p.splitk = 1;
-      p.bias = L.f32[2]; p.out_f32 = t; p.ldo = C;
-      with_ln(p, L.tb[0].ln[0], L.tb[0].ln[1]);
-      if (p.ln_out) ok(fail("internal: GroupNorm-folding proj_in needs the LayerNorm fold"));
-      if (!dry && !rc) ok(launch_split16_gn(p, s));
     } else {
       IGemmParams p = dense1x1(xn, xn_lo, M, C, L.w16[0], C, N, p1);
       p.bias = L.f32[2]; p.out_f32 = t; p.ldo = C;
@@ -914,9 +842,8 @@ struct Fwd : FwdBase {
       }
       attention(q, k, vt, ao, L, N, N, Np, scale);
       // attn1's out-projection (+ x) and attn2's to_q over norm2 as one row-strip chain launch (rowchain.hip, st_head_kernel KIND 1)
-      const bool ctx_fused_here = fuse_ctx_q && L.dh <= fuse_ctx_maxd && attention_ctx_supported(L.dh, C, Lctx) && !(fold_ln && C > 640);
       bool chain_ctx = false;
-      const bool chain_mid = st_mid_on && fold_ln && !ctx_fused_here && T.lnf[2] != nullptr && st_head_supported(C, M, N, Np, L.heads, L.dh);
+      const bool chain_mid = st_mid_on && fold_ln && T.lnf[2] != nullptr && st_head_supported(C, M, N, Np, L.heads, L.dh);
       if (chain_mid) {
         StHeadParams h = StHeadParams();
         h.a16 = ao; h.w_in = T.wo1; h.b_in = T.bo1; h.t = t; h.ln_gamma = T.ln[2]; h.ln_eps = 1e-5f;
@@ -937,13 +864,6 @@ struct Fwd : FwdBase {
       if (ctx16 && !chain_mid) context_kv(L, d);
       if (chain_mid) {
         if (!chain_ctx) attention(q, T.ck, T.cvt, ao, L, N, Lctx, Lp, scale);       // (q = to_q(norm2(t)) came out of the chain launch)
-      } else if (fuse_ctx_q && L.dh <= fuse_ctx_maxd && attention_ctx_supported(L.dh, C, Lctx) && !(fold_ln && C > 640)) {
-        // to_q inside the attention kernel (attn_ctx.hip): one launch for q = norm2(x) Wq^T and softmax(q K^T) V
-        AttnCtxParams a = AttnCtxParams();
-        a.x = ln; a.wq = T.wq2; a.k = T.ck; a.vt = T.cvt; a.out = ao;
-        a.BH = B * L.heads; a.heads = L.heads; a.nq = N; a.nkv = Lctx; a.nkv_pad = Lp; a.d = L.dh; a.C = C; a.scale = scale;
-        if (fold_ln) { a.lnf_part = lnp; a.lnf_npart = C / 32; a.lnf_eps = 1e-5f; a.M = M; a.lnf_cs = T.lnf[2]; a.lnf_d = T.lnf[3]; }
-        if (!dry && !rc) ok(launch_attention_ctx(a, s));
       } else {
         IGemmParams p = dense(ln, M, C, T.wq2, C, N);
         p.mode = EPI_HEADS; p.seg_dst[0] = q; p.seg_kind[0] = 0;
@@ -1270,7 +1190,7 @@ int UNet::run(const float* x, const int64_t* t_i64, const float* t_f32, const fl
     return p && (uintptr_t)p < (uintptr_t)workspace + (uint64_t)ws_bytes && (uintptr_t)workspace < (uintptr_t)p + bytes;
   };
   const size_t img = (size_t)B * H * W * sizeof(float);
-  const bool tape_ok = replay_on && !dry && !ctx_only && !side_stream_ && !prof_enabled() && !tune_collecting() && !range_check_enabled() &&
+  const bool tape_ok = replay_on && !dry && !ctx_only && !prof_enabled() && !tune_collecting() && !range_check_enabled() &&
                        workspace != nullptr && (t_i64 || t_f32) && !in_ws(x, img * cfg_.in_channels) && !in_ws(eps_out, img * cfg_.out_channels) &&
                        !in_ws(t_i64 ? (const void*)t_i64 : t_f32, (size_t)B * (t_i64 ? 8 : 4)) &&
                        !in_ws(ctx, (size_t)B * Lctx * cfg_.context_dim * sizeof(float));
@@ -1333,26 +1253,10 @@ int UNet::run(const float* x, const int64_t* t_i64, const float* t_f32, const fl
     f.st_mid_ctx_on = e_mc ? atoi(e_mc) != 0 : st_head_;
     const char* e_gc = getenv("SDMI_GN_CONV");
     f.gn_conv_on = e_gc ? atoi(e_gc) != 0 : false;       // (opt-in: bit-identical, 36 us against 41 us with hot operands, +4 us per launch inside a UNet call -- profiles/gn_conv3_r05.txt)
-#ifdef SDMI_EXPERIMENTS      // (kernels of the experiments build: attn_ctx.hip, gemm_split16_gn_kernel)
-    const char* e_ctx = getenv("SDMI_ATTN_CTX_FUSED");
-    f.fuse_ctx_q = e_ctx && atoi(e_ctx) != 0;
-    if (const char* e_md = getenv("SDMI_ATTN_CTX_MAXD")) f.fuse_ctx_maxd = atoi(e_md);
-    const char* e_gp = getenv("SDMI_GN_PROJ_FOLD");
-    f.gn_proj_fold = (e_gp && atoi(e_gp) != 0) && f.ln_fold_on;       // (the kernel has no LayerNorm post-op launch: it rides on the fold)
-#endif
     if (full()) {
       // every chain and fold rounds some operand to fp16 once: the full-precision mode runs the per-op path whatever the knobs say
-      // (the GroupNorm-folding convolutions are already off there: they are never taken for a Layer::precise3 ResBlock)
       f.ln_fold_on = f.ff_tail_on = f.st_head_on = f.st_mid_on = f.st_tail_on = f.st_mid_ctx_on = f.gn_conv_on = false;
-      f.fuse_ctx_q = f.gn_proj_fold = false;
     }
-  }
-  if (side_stream_ && !dry && !prof_enabled()) {      // (the per-launch profiler times launches on one stream)
-    if (!side_) {
-      SDMI_HIP_OK(hipStreamCreateWithFlags(&side_, hipStreamNonBlocking));
-      for (auto& e : side_ev_) SDMI_HIP_OK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    }
-    f.side = side_; f.side_ev = side_ev_; f.side_nev = 32;
   }
   // first pass (always dry) sizes the two arenas; the persist arena sits in front of the scratch arena
   int64_t persist_bytes = 0, scratch_bytes = 0;

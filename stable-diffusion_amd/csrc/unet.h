@@ -55,11 +55,6 @@ struct FwdBase {
   float* splitk_ws = nullptr; int64_t splitk_ws_floats = 0;
   int* splitk_cnt = nullptr;                          // one int per output tile of a split-K GEMM (igemm.hip)
   static constexpr int SPLITK_CNT_INTS = 8192;
-  // side stream (optional): work that is independent of the main chain for a while -- the ResBlock's 1x1 skip convolution
-  // runs beside conv1 / GroupNorm 2 -- is enqueued there between two events; it has its own split-K slabs
-  hipStream_t side = nullptr;
-  hipEvent_t* side_ev = nullptr; int side_nev = 0, side_next = 0;
-  float* splitk_ws2 = nullptr; int64_t splitk_ws2_floats = 0;
   int rc = 0;
   GnPlan* plan = nullptr;         // null: GroupNorm statistics always by the statistics kernel (first stage, text encoder)
   int n_acts = 0;
@@ -129,28 +124,10 @@ struct FwdBase {
     if (!dry) SDMI_HIP_OK(memset_async(blk, 0, (acc_words + SPLITK_CNT_INTS / 2) * sizeof(long long), s));
     splitk_ws_floats = splitk_floats;
     splitk_ws = P<float>((size_t)splitk_floats);
-    splitk_ws2_floats = splitk_floats / 2;               // (always: the workspace size must not depend on the side stream)
-    splitk_ws2 = P<float>((size_t)splitk_ws2_floats);
+    // unused half-size reservation behind the slabs (it held the slabs of a side stream that lost its A/B): kept so that every
+    // buffer address and the workspace size stay as they were
+    (void)P<float>((size_t)(splitk_floats / 2));
     return 0;
-  }
-  // fork: the side stream continues from this point of the main stream; join: the main stream waits for the side stream
-  hipEvent_t next_side_event() { hipEvent_t e = side_ev[side_next]; side_next = (side_next + 1) % side_nev; return e; }
-  void fork_side() {
-    if (dry || rc || !side) return;
-    hipEvent_t e = next_side_event();
-    if (hipEventRecord(e, s) != hipSuccess || hipStreamWaitEvent(side, e, 0) != hipSuccess) ok(fail("side stream fork failed"));
-  }
-  void join_side() {
-    if (dry || rc || !side) return;
-    hipEvent_t e = next_side_event();
-    if (hipEventRecord(e, side) != hipSuccess || hipStreamWaitEvent(s, e, 0) != hipSuccess) ok(fail("side stream join failed"));
-  }
-  void gemm_side(IGemmParams& p) {        // like gemm(), on the side stream (falls back to the main stream without one)
-    if (!side) { gemm(p); return; }
-    p.zero_page = zero;
-    p.splitk_ws = splitk_ws2; p.splitk_ws_floats = splitk_ws2_floats;
-    p.splitk_cnt = nullptr; p.splitk_cnt_ints = 0;
-    if (!dry && !rc) ok(launch_igemm(p, IGemmTune(), side));
   }
 
   void gemm(IGemmParams& p) {
@@ -243,7 +220,7 @@ struct TBlock {   // BasicTransformerBlock (ldm/modules/attention.py:196-215)
   f16* wqkv = nullptr;   // [3C][C]   attn1 to_q | to_k | to_v
   f16* wo1 = nullptr; float* bo1 = nullptr;
   f16* wq2 = nullptr;    // [C][C]
-  f16* wkv2 = nullptr;   // attn2 to_k | to_v: [2C][3 context_dim] split-fp16 {hi | hi | lo} (round 6; [2C][context_dim] in the experiments build with SDMI_PRECISE_KV=0)
+  f16* wkv2 = nullptr;   // attn2 to_k | to_v: [2C][3 context_dim] split-fp16 {hi | hi | lo} (round 6)
   f16* wo2 = nullptr; float* bo2 = nullptr;
   f16* wgg = nullptr; float* bgg = nullptr;     // GEGLU proj, rows interleaved (value32 | gate32)
   f16* wff2 = nullptr; float* bff2 = nullptr;
@@ -325,8 +302,6 @@ class UNet {
   bool precise_last_res_ = true;   // the last ResBlock's 3x3 convs as 3-pass split-fp16 (round 6; Layer::precise3)
   int precise_1x1_max_ds_ = 4;     // stream 1x1 convs are split-fp16 at downsample factors below this (round 6; Layer::p1x1)
   bool precise_kv_ = true;     // context K / V projections as 3-pass split-fp16 (round 6; see UNet::build)
-  // ResBlock convs fold the GroupNorm + SiLU of their input into their halo staging (conv3halo.hip, conv3halo_gn_kernel) wherever
-  // gn_fold_conv_supported() says so; SDMI_FUSE_GN_CONV=0 restores the GroupNorm-apply launches (A/B).
 
  private:
   friend struct Fwd;
@@ -336,8 +311,6 @@ class UNet {
   size_t slot_bytes(const WeightSlot& s) const;
   int ensure_ctx_cache(int B, int Lctx, bool may_grow);
   GnPlan gn_plan_;           // GroupNorm-statistics fusion plan of the current forward (rebuilt by its dry pass)
-  bool side_stream_ = false;    // SDMI_SIDE_STREAM=1: ResBlock skip convolutions on a side stream (measured 3 % slower)
-  hipStream_t side_ = nullptr; hipEvent_t side_ev_[32] = {};
   bool fuse_gn_stats_ = true;   // SDMI_FUSE_GN_STATS=0: every GroupNorm runs its own statistics kernel (A/B, debugging)
   // The LayerNorms of a BasicTransformerBlock (attention.py:211-215) folded into the GEMMs that read them, where the producing
   // GEMM is not split (>= ln_fold_min_rows_ token rows; the fold pins its producers to split 1): no LayerNorm launch, one fp32 read of the token stream less per site.

@@ -208,20 +208,6 @@ def gn_acc_sums(acc):
     return s, ss
 
 
-def attention_ctx(x16, wq16, k, vt, heads, nkv, scale, lnf=None):
-    """x16 [B*nq, C] fp16, wq16 [C, C] fp16, k [BH, nkv, d], vt [BH, d, nkv_pad] -> [B, nq, C] fp16 (to_q inside the kernel);
-    lnf = (partials [C/32, B*nq, 2], eps, cs, d): LayerNorm fold"""
-    BH, _, d = k.shape
-    B = BH // heads
-    nq = x16.shape[0] // B
-    out = torch.empty((B, nq, heads * d), dtype=torch.float16, device=x16.device)
-    part, eps, cs, dn = lnf if lnf is not None else (None, 1e-5, None, None)
-    _lib.check(_lib.load().sdmi_k_attention_ctx(x16.data_ptr(), wq16.data_ptr(), k.data_ptr(), vt.data_ptr(), out.data_ptr(), BH, heads,
-                                                nq, nkv, vt.shape[2], d, float(scale), _lib.ptr(part), float(eps), _lib.ptr(cs),
-                                                _lib.ptr(dn), _s()))
-    return out
-
-
 def ln_fold_prep(w16, K, gamma, beta, bias=None):
     """column terms of a LayerNorm-folding GEMM from the packed fp16 weights w16 [N, ldw >= K]: (cs, d) fp32 [N]"""
     N = w16.shape[0]
@@ -350,25 +336,3 @@ def report(name, got, ref, tol):
           f'{d.pow(2).mean().sqrt().item():.3e} at flat {idx}: got {got.flatten()[idx].item():.6f} ref '
           f'{ref.flatten()[idx].item():.6f} nan={bool(torch.isnan(got).any())}', flush=True)
     return mx
-
-
-def conv3gn(x0, x1, gamma, beta, eps, w, bias=None, rowvec=None, residual=None, splitk=0, tile=-1, want_raw=False):
-    """GroupNorm + SiLU folded into the halo-staged 3x3 conv.  x0/x1: fp32 [B, H, W, C]; w: OIHW fp32 -> out fp32 [B*H*W, N]
-    (and, with want_raw, the split-fp16 copy (hi, lo) of cat(x0, x1))"""
-    B, H, W, c0 = x0.shape
-    c1 = 0 if x1 is None else x1.shape[3]
-    N = w.shape[0]
-    dev = x0.device
-    wp = pack_conv_weight(w)
-    out = torch.full((B * H * W, N), float('nan'), device=dev)
-    n = _lib.load().sdmi_k_groupnorm_ws_floats(B, H * W)
-    gws = torch.empty((n,), dtype=torch.float32, device=dev)
-    ws = torch.empty((16 * B * H * W * N,), dtype=torch.float32, device=dev)
-    rhi = torch.full((B * H * W, c0 + c1), float('nan'), dtype=torch.float16, device=dev) if want_raw else None
-    rlo = torch.full((B * H * W, c0 + c1), float('nan'), dtype=torch.float16, device=dev) if want_raw else None
-    _lib.check(_lib.load().sdmi_k_conv3gn(
-        x0.data_ptr(), _lib.ptr(x1), c0, c1, B, H, W, gamma.data_ptr(), beta.data_ptr(), float(eps), wp.data_ptr(), N,
-        _lib.ptr(bias), _lib.ptr(rowvec), 0 if rowvec is None else rowvec.stride(0), _lib.ptr(residual),
-        0 if residual is None else residual.stride(0), out.data_ptr(), N, splitk, ws.data_ptr(), ws.numel(),
-        gws.data_ptr(), n, tile, _lib.ptr(rhi), _lib.ptr(rlo), _s()))
-    return (out, rhi, rlo) if want_raw else out

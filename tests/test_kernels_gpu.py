@@ -309,82 +309,6 @@ def test_igemm_splitk_reduce_groupnorm_behind_a_grid_barrier(B, H, W, C, N, spli
     assert diff.max().item() <= 8e-3 and nflip <= 2e-3 * diff.numel() + 2, (diff.max().item(), nflip)
 
 
-@pytest.mark.parametrize('B,H,W,C,N,splitk,tile,ksize,resid', [
-    (2, 8, 8, 1280, 1280, 12, 19, 3, False),      # the 8x8 level: igemm 64x128, 12-way split (ResBlock conv1)
-    (2, 16, 16, 1280, 1280, 10, 15, 3, False),    # 16x16: halo tile, split at 64-channel chunks
-    (2, 32, 32, 1280, 640, 5, 15, 3, False),      # 32x32 concat block: 20 channels per group, 5 quads per thread
-    (2, 16, 16, 640, 1280, 5, 14, 3, True),       # with a residual
-    (3, 8, 8, 256, 128, 2, 2, 1, False),          # smallest legal width: 4 channels per group
-    (2, 16, 16, 320, 256, 0, -1, 3, False),       # auto split / auto tile: applied or not, the launcher says which
-])
-@pytest.mark.experiments
-@pytest.mark.parametrize('tiled', ['1', '0'])
-def test_igemm_splitk_reduce_applies_groupnorm(B, H, W, C, N, splitk, tile, ksize, resid, tiled, monkeypatch):
-    """GroupNorm(32) + SiLU of a split-K conv's output applied by its reduction (splitk_reduce_gn_kernel, sdmi_igemm_desc::pgn_*):
-    against torch's GroupNorm + SiLU of the fp32 conv result, four bit-identical repeats, and against this library's own
-    GroupNorm kernels on the reduction's fp32 output (statistics kernel + apply: same elementwise function, statistics from a
-    different partition of the same values -- rounding flips only; the bit-identity with the producers' fused statistics is
-    checked on whole UNet calls, tests/test_unet_gpu.py)."""
-    monkeypatch.setenv('SDMI_SLAB_TILED', tiled)      # register-order slabs (default) / row-major slabs: the kernel reads either
-    monkeypatch.setenv('SDMI_REDUCE_GN', '1')         # (opt-in: measured slower than reduce + GroupNorm-apply, DESIGN.md section 4)
-    g = _g(91)
-    a = _rand16((B * H * W, C), g)
-    w = _rand16((N, C, ksize, ksize), g, 1.0 / math.sqrt(ksize * ksize * C))
-    bias = torch.randn(N, generator=g)
-    rowvec = torch.randn(B, N, generator=g)
-    res = torch.randn(B * H * W, N, generator=g) if resid else None
-    gamma = 1.0 + 0.3 * torch.randn(N, generator=g)
-    beta = 0.2 * torch.randn(N, generator=g)
-    v_ref = _nhwc(_conv_ref(a, None, w, B, H, W, ksize, 1, 0)) + bias[None] + rowvec.repeat_interleave(H * W, dim=0)
-    if resid:
-        v_ref = v_ref + res
-    y_ref = F.silu(F.group_norm(v_ref.view(B, H * W, N).permute(0, 2, 1).double(), 32, gamma.double(), beta.double(), 1e-5))
-    y_ref = y_ref.permute(0, 2, 1).reshape(B * H * W, N).float()
-    wp = K.pack_conv_weight(w.float().to(DEV))
-    a_d, bias_d, rv_d = a.to(DEV), bias.to(DEV), rowvec.to(DEV)
-    res_d = res.to(DEV) if resid else None
-    ga_d, be_d = gamma.to(DEV), beta.to(DEV)
-    outs = []
-    for rep in range(4):
-        o16 = torch.full((B * H * W, N), float('nan'), dtype=torch.float16, device=DEV)
-        o32 = torch.full((B * H * W, N), float('nan'), device=DEV)
-        # (the executor's situation: that GroupNorm is the output's one statistics target -- the condition under which the
-        # reduction may apply it, because only then is the result the two-launch path's, bit for bit)
-        acc = torch.zeros((B, 32, 8, 16), dtype=torch.int64, device=DEV)
-        applied = K.igemm(a_d, wp, N, B, H, W, H, W, ksize, 1, 0, bias=bias_d, rowvec=rv_d, residual=res_d, out_f32=o32,
-                          splitk=splitk, tile=tile, fused_splitk=False, pgn=(ga_d, be_d, 1e-5, 1, o16, rep % 2),
-                          gn=[(acc, N // 32, 0)])
-        if applied:
-            assert int(acc.abs().sum().item()) == 0        # no statistics atomics: the group never leaves the workgroup
-        outs.append((applied, o16, o32))
-    torch.cuda.synchronize()
-    applied = outs[0][0]
-    if splitk > 1:
-        assert applied == 1
-    # the library's two launches on the same inputs: the reduce kernel's fp32 output, then GroupNorm-apply
-    v2 = torch.full((B * H * W, N), float('nan'), device=DEV)
-    K.igemm(a_d, wp, N, B, H, W, H, W, ksize, 1, 0, bias=bias_d, rowvec=rv_d, residual=res_d, out_f32=v2, splitk=splitk, tile=tile,
-            fused_splitk=False)
-    y2 = K.groupnorm(v2.view(B, H * W, N), None, ga_d, be_d, 1e-5, 1)['f16'].view(B * H * W, N)
-    torch.cuda.synchronize()
-    if not applied:        # the auto choice did not split: nothing was applied, the fp32 output is the ordinary one
-        assert torch.equal(outs[0][2], v2) and torch.isnan(outs[0][1].float()).all()
-        return
-    y = outs[0][1].float().cpu()
-    err = (y - y_ref).abs().max().item()
-    print(f'[reduce+gn M{B * H * W} N{N} split{splitk} tile{tile}] max-abs vs torch {err:.3e} (|y| max {y_ref.abs().max():.2f})', flush=True)
-    assert err <= 2e-3 * max(1.0, y_ref.abs().max().item())          # one fp16 rounding of values up to ~4
-    diff = (outs[0][1].float() - y2.float()).abs()
-    nflip = int((diff > 0).sum().item())
-    assert diff.max().item() <= 8e-3 and nflip <= 2e-3 * diff.numel() + 2, (diff.max().item(), nflip)    # rounding flips only
-    for rep, (ap, o16, o32) in enumerate(outs):
-        assert ap == 1 and torch.equal(o16, outs[0][1])
-        if rep % 2:
-            assert torch.equal(o32, v2)                 # pgn_keep_f32: the reduction's fp32 value, bit for bit
-        else:
-            assert torch.isnan(o32).all()               # ... and not written otherwise
-
-
 @pytest.mark.parametrize('B,H,W,C,N,splitk,tile,ksize', [
     (2, 8, 8, 1280, 1280, 12, 19, 3),      # 8x8 level, igemm 64x128 deep ring
     (2, 16, 16, 1280, 1280, 10, 15, 3),    # halo tile 256x128, 8 waves
@@ -753,18 +677,6 @@ def test_attention_key_split(heads, nq, nkv, monkeypatch):
     again = K.attention(qd, kd, vd, heads, nkv, scale)
     torch.cuda.synchronize()
     assert torch.equal(two, again)
-    from stable_diffusion_amd import _lib
-    if _lib.load().sdmi_has_experiments():
-        # experiments build: the rotated second key group and one barrier per two key tiles -- the same values, the same bits (both measured slower)
-        monkeypatch.setenv('SDMI_ATTN_ROT', '1')
-        rot = K.attention(qd, kd, vd, heads, nkv, scale).clone()
-        monkeypatch.setenv('SDMI_ATTN_ROT', '0')
-        monkeypatch.setenv('SDMI_ATTN_TPB', '2')
-        tp = K.attention(qd, kd, vd, heads, nkv, scale).clone()
-        monkeypatch.setenv('SDMI_ATTN_KVS', '0')
-        tp8 = K.attention(qd, kd, vd, heads, nkv, scale).clone()
-        torch.cuda.synchronize()
-        assert torch.equal(rot, two) and torch.equal(tp, two) and torch.equal(tp8, one)
     e1 = K.report(f'attention one group  d40 nq{nq} nkv{nkv}', one, ref, 3e-3)
     e2 = K.report(f'attention key split  d40 nq{nq} nkv{nkv}', two, ref, 3e-3)
     dd = (one.float() - two.float()).abs().max().item()
@@ -992,83 +904,6 @@ def test_sampler_step_bit_exact(mode, cfg):
     assert torch.equal(x_o.cpu(), xp), 'x_prev not bit-exact'
 
 
-# ---- GroupNorm + SiLU folded into the halo staging of the 3x3 convolution (csrc/conv3halo.hip, conv3halo_gn_kernel) ---------------
-GN_FOLD_CASES = [
-    # name, B, H, W, c0, c1, N, splitk, tile  (at least 8 channels per group: c0 + c1 >= 256)
-    ('l0_w64_t14', 2, 64, 64, 320, 0, 64, 1, 14),
-    ('l0_w64_t15', 1, 64, 64, 256, 0, 128, 2, 15),
-    ('l0_w64_t16_cat', 1, 64, 64, 192, 128, 64, 1, 16),       # two fp32 sources with different row pitches
-    ('l1_w32_t14_cat', 2, 32, 32, 640, 320, 128, 3, 14),
-    ('l1_w32_t17', 2, 32, 32, 320, 0, 128, 1, 17),
-    ('l2_w16_t14', 2, 16, 16, 1280, 0, 128, 5, 14),           # one whole 16x16 image per 256-row tile
-    ('l2_w16_t16', 2, 16, 16, 640, 0, 64, 2, 16),
-    ('l3_w8_t16', 2, 8, 8, 1280, 0, 128, 10, 16),             # two whole 8x8 images per 128-row tile
-    ('l3_w8_t14_b4', 4, 8, 8, 640, 640, 64, 4, 14),           # four whole images per 256-row tile
-    ('auto', 2, 32, 32, 640, 0, 640, 0, -1),                  # tile and split chosen by the launcher
-    # a workgroup's chunk range crossing from the first fp32 source into the second, small channel counts (the TINY / SMALL40
-    # configurations' output blocks), every tile at W = 64
-    ('l0_w64_t16', 1, 64, 64, 320, 0, 64, 1, 16),
-    ('l0_w64_t14_cat', 1, 64, 64, 192, 128, 64, 1, 14),
-    ('l0_w64_t17_cat', 1, 64, 64, 192, 128, 128, 1, 17),
-    ('l1_w32_t16_cat', 1, 32, 32, 192, 128, 64, 1, 16),
-    ('l1_w32_t14_cat_cross', 2, 32, 32, 640, 320, 128, 1, 14),
-    ('tiny_w16_t14_cat', 2, 16, 16, 128, 128, 128, 2, 14),
-    ('tiny_w16_t14_cat_k1', 2, 16, 16, 128, 128, 128, 1, 14),
-    ('tiny_w8_t16_cat', 2, 8, 8, 128, 128, 64, 1, 16),
-    ('tiny_w8_t16_cat_k2', 2, 8, 8, 128, 128, 64, 2, 16),
-]
-
-
-def _gn_fold_inputs(B, H, W, c0, c1, N, seed):
-    g = _g(seed)
-    C = c0 + c1
-    x0 = torch.randn(B, H, W, c0, generator=g) * 1.3 + 0.2
-    x1 = torch.randn(B, H, W, c1, generator=g) * 0.8 - 0.1 if c1 else None
-    gamma = 1 + 0.1 * torch.randn(C, generator=g)
-    beta = 0.1 * torch.randn(C, generator=g)
-    w = torch.randn(N, C, 3, 3, generator=g) / math.sqrt(9 * C)
-    bias = torch.randn(N, generator=g) * 0.1
-    rowvec = torch.randn(B, N, generator=g)
-    resid = torch.randn(B * H * W, N, generator=g)
-    return x0, x1, gamma, beta, w, bias, rowvec, resid
-
-
-@pytest.mark.experiments
-@pytest.mark.parametrize('case', GN_FOLD_CASES, ids=[c[0] for c in GN_FOLD_CASES])
-def test_conv3_gn_fold(case):
-    """ResBlock in_layers / out_layers: conv3x3(SiLU(GroupNorm32(cat(x0, x1)))) + bias + emb + residual
-    (openaimodel.py:201-204,225-231,263-275) as ONE launch that normalises its input while staging it: against the fp32 torch
-    ops, and BIT FOR BIT against the two-launch path it replaces (GroupNorm-apply kernel -> LDS-DMA halo conv, same tile)."""
-    name, B, H, W, c0, c1, N, splitk, tile = case
-    x0, x1, gamma, beta, w, bias, rowvec, resid = _gn_fold_inputs(B, H, W, c0, c1, N, B * H + c0 + N)
-    C = c0 + c1
-    x = x0 if x1 is None else torch.cat([x0, x1], dim=3)
-    xn = F.silu(F.group_norm(x.permute(0, 3, 1, 2), 32, gamma, beta, 1e-5))
-    # the kernel rounds the normalised activation and the weights to fp16 once (MFMA operands), accumulates in fp32
-    ref = F.conv2d(xn.half().float(), w.half().float(), None, padding=1)
-    ref = _nhwc(ref) + bias[None] + rowvec.repeat_interleave(H * W, dim=0) + resid
-    d = lambda t: None if t is None else t.to(DEV)
-    out, rhi, rlo = K.conv3gn(d(x0), d(x1), d(gamma), d(beta), 1e-5, d(w), bias=d(bias), rowvec=d(rowvec), residual=d(resid),
-                              splitk=splitk, tile=tile, want_raw=True)
-    torch.cuda.synchronize()
-    # vs the fp16-operand reference: fp32 GN rounding flips of fp16 operands (<= 1 fp16 ulp on a handful of A elements) and
-    # accumulation order
-    assert K.report(f'conv3 gn-fold {name}', out, ref, 3e-3) < 3e-3
-    # the raw split-fp16 copy (operand of the ResBlock's 1x1 skip conv): exactly the cast kernel's values, every pixel once
-    xc = x.reshape(B * H * W, C).to(DEV)
-    hi, lo = K.cast_f16(xc, want_lo=True)
-    assert torch.equal(rhi, hi) and torch.equal(rlo, lo)
-    if tile >= 0:
-        # the path it replaces, same tile and split: identical fp16 operand -> identical MFMA sequence -> identical bits
-        gn = K.groupnorm(d(x0).reshape(B, H * W, c0), None if x1 is None else d(x1).reshape(B, H * W, c1), d(gamma), d(beta), 1e-5, 1,
-                         want=('f16',))
-        out2 = torch.full((B * H * W, N), float('nan'), device=DEV)
-        K.igemm(gn['f16'].reshape(B * H * W, C), K.pack_conv_weight(d(w)), N, B, H, W, H, W, ksize=3, bias=d(bias), rowvec=d(rowvec),
-                residual=d(resid), out_f32=out2, splitk=splitk, tile=tile, fused_splitk=False)
-        torch.cuda.synchronize()
-        assert torch.equal(out, out2), float((out - out2).abs().max())
-
-
 @pytest.mark.parametrize('ptile,ctile', [(-1, -1), (5, 5), (4, 8), (1, 0), (10, 3)])
 @pytest.mark.parametrize('mode', ['heads', 'geglu', 'plain'])
 def test_layernorm_folded_into_consumer(mode, ptile, ctile):
@@ -1147,148 +982,3 @@ def test_layernorm_folded_into_consumer(mode, ptile, ctile):
     # the fold must not cost accuracy: the two-launch path's error level (both round one fp16 operand per element; the maxima of
     # 1-3 M outputs scatter by +-20 %)
     assert e1 < 8e-3 and e1 <= 1.5 * e2 + 5e-4, (e1, e2)
-
-
-FIVE_WAVE_CASES = [c for c in CONV_CASES if not c[9]]        # (the five-wave tile has no upsampling gather)
-
-
-@pytest.mark.experiments
-@pytest.mark.parametrize('case', FIVE_WAVE_CASES, ids=[c[0] for c in FIVE_WAVE_CASES])
-@pytest.mark.parametrize('splitk', [1, 3])
-def test_igemm_five_wave_tile(case, splitk):
-    """tile 22 (csrc/igemm5.hip): 64 x 160, five waves side by side, operands dealt in 8-row octets over the (A | W) rows -- the
-    conv / linear cases of test_igemm_conv incl. masked taps, stride 2, concatenated sources, M and N tails, with and without
-    split-K (separate reduce)."""
-    name, B, Hin, Win, c0, c1, N, ksize, stride, up = case
-    g = _g(hash(name) % 1000 + 5)
-    Cin = c0 + c1
-    big = _rand16((B * Hin * Win, Cin), g)
-    a0 = big[:, :c0]
-    a1 = big[:, c0:] if c1 else None
-    w = _rand16((N, Cin, ksize, ksize), g, 1.0 / math.sqrt(Cin * ksize * ksize))
-    ref = _conv_ref(a0, a1, w, B, Hin, Win, ksize, stride, up)
-    Hout, Wout = ref.shape[2], ref.shape[3]
-    M = B * Hout * Wout
-    bias = torch.randn(N, generator=g)
-    rowvec = torch.randn(B, N, generator=g)
-    resid = torch.randn(M, N, generator=g)
-    ref2 = _nhwc(ref) + bias[None] + rowvec.repeat_interleave(Hout * Wout, dim=0) + resid
-    wp = K.pack_conv_weight(w.float().to(DEV))
-    nkt = (ksize * ksize * Cin) // 64
-    if splitk > 1 and (N % 4 or nkt < splitk):
-        pytest.skip('split-K needs N % 4 == 0 and enough k-tiles')
-    out32 = torch.full((M, N), float('nan'), device=DEV)
-    out16 = torch.full((M, N), float('nan'), device=DEV, dtype=torch.float16)
-    big_d = big.to(DEV)
-    K.igemm(big_d[:, :c0], wp, N, B, Hin, Win, Hout, Wout, ksize, stride, up, a1=big_d[:, c0:] if c1 else None,
-            bias=bias.to(DEV), rowvec=rowvec.to(DEV), residual=resid.to(DEV), out_f32=out32, out_f16=out16,
-            tile=22, splitk=splitk, fused_splitk=False)
-    torch.cuda.synchronize()
-    assert K.report(f'igemm5 {name} split{splitk} f32', out32, ref2, 2e-4) < 2e-4
-    assert K.report(f'igemm5 {name} split{splitk} f16', out16, ref2, 6e-3) < 6e-3
-
-
-@pytest.mark.experiments
-@pytest.mark.parametrize('B,H,W,C,N,ksize', [(2, 64, 64, 320, 320, 3), (2, 64, 64, 320, 320, 1), (2, 32, 32, 640, 640, 3), (2, 64, 64, 320, 960, 1)])
-def test_igemm_five_wave_tile_sd_shapes(B, H, W, C, N, ksize):
-    """the shapes tile 22 is for (64x64 / 32x32 levels of SD v1), with the GroupNorm statistics of the output from the epilogue:
-    against tile 5 (64 x 64) on the same operands -- same products, per-k-tile accumulation order, so the outputs agree to the
-    last bits of an fp32 sum -- and the statistics against torch."""
-    g = _g(C + N + ksize)
-    a = _rand16((B * H * W, C), g)
-    w = _rand16((N, C, ksize, ksize), g, 1.0 / math.sqrt(C * ksize * ksize))
-    bias = torch.randn(N, generator=g)
-    resid = torch.randn(B * H * W, N, generator=g)
-    wp = K.pack_conv_weight(w.float().to(DEV))
-    outs, accs = [], []
-    for tile in (22, 5):
-        out = torch.full((B * H * W, N), float('nan'), device=DEV)
-        acc = torch.zeros((B, 32, 8, 16), dtype=torch.int64, device=DEV)
-        gn = [(acc, N // 32, 0)] if N // 32 >= 2 else None
-        K.igemm(a.to(DEV), wp, N, B, H, W, H, W, ksize, bias=bias.to(DEV), residual=resid.to(DEV), out_f32=out, tile=tile, gn=gn)
-        torch.cuda.synchronize()
-        outs.append(out); accs.append(acc)
-    assert K.report(f'igemm5 sd M{B * H * W} N{N} K{C * ksize * ksize} vs tile 5', outs[0], outs[1], 1e-5) < 1e-5
-    s0, q0 = K.gn_acc_sums(accs[0])
-    xs = outs[0].cpu().double().reshape(B, H * W, 32, N // 32)
-    assert torch.allclose(s0, xs.sum(dim=(1, 3)), rtol=1e-6, atol=1e-3)
-    assert torch.allclose(q0, (xs * xs).sum(dim=(1, 3)), rtol=1e-6, atol=1e-2)
-
-
-@pytest.mark.experiments
-@pytest.mark.parametrize('d,heads,nq,nkv,B', [(40, 8, 4096, 77, 2), (80, 8, 1024, 77, 2), (160, 8, 256, 77, 2), (160, 8, 64, 77, 2),
-                                              (40, 8, 100, 77, 1), (80, 8, 64, 128, 1), (160, 8, 33, 5, 3), (40, 8, 256, 96, 2)])
-@pytest.mark.parametrize('fold', [False, True])
-def test_attention_ctx_fused_q(d, heads, nq, nkv, B, fold, monkeypatch):
-    """Cross-attention with the to_q projection inside the kernel (csrc/attn_ctx.hip; attention.py:161,170-193):
-    out = softmax((LN(t) Wq^T) K^T d^-0.5) V over the cached context keys, against fp32 torch and against the two-launch path
-    (to_q GEMM with the per-head scatter -> flash attention); with and without the LayerNorm fold (x = fp16(gamma t) + row partials)."""
-    g = _g(d + nq + nkv + (7 if fold else 0))
-    C = heads * d
-    M = B * nq
-    t = torch.randn(M, C, generator=g) * 1.2 + 0.2
-    gamma = 1 + 0.2 * torch.randn(C, generator=g)
-    beta = 0.1 * torch.randn(C, generator=g)
-    wq = (torch.randn(C, C, generator=g) / math.sqrt(C)).half()
-    nkv_pad = (nkv + 7) // 8 * 8
-    k = (torch.randn(B * heads, nkv, d, generator=g) * 0.8).half()
-    v = (torch.randn(B * heads, nkv, d, generator=g)).half()
-    vt = torch.zeros(B * heads, d, nkv_pad, dtype=torch.float16)
-    vt[:, :, :nkv] = v.transpose(1, 2)
-    scale = d ** -0.5
-    xn = F.layer_norm(t, (C,), gamma, beta, 1e-5)
-    q = (xn @ wq.float().t()).reshape(B, nq, heads, d).permute(0, 2, 1, 3).reshape(B * heads, nq, d)
-    att = torch.softmax(q @ k.float().transpose(1, 2) * scale, dim=-1) @ v.float()
-    ref = att.reshape(B, heads, nq, d).permute(0, 2, 1, 3).reshape(B, nq, C)
-    dv = lambda z: z.to(DEV)
-    ln16 = K.layernorm(dv(t), dv(gamma), dv(beta))
-    if fold:
-        if C > 640:
-            pytest.skip('the fold is taken for C <= 640 (20 partials)')
-        # the producer's side, emulated: fp16(gamma * t) and {sum, sumsq} per 32-column block
-        x16 = (t * gamma).half()
-        tb = t.double().reshape(M, C // 32, 32)
-        part = torch.stack([tb.sum(-1), (tb * tb).sum(-1)], dim=-1).permute(1, 0, 2).float().contiguous()
-        cs, dn = K.ln_fold_prep(dv(wq), C, dv(gamma), dv(beta))
-        out = K.attention_ctx(dv(x16), dv(wq), dv(k), dv(vt), heads, nkv, scale, lnf=(dv(part), 1e-5, cs, dn))
-    else:
-        out = K.attention_ctx(ln16, dv(wq), dv(k), dv(vt), heads, nkv, scale)
-    # the two-launch path on the same operands
-    qd = torch.empty(B * heads, nq, d, dtype=torch.float16, device=DEV)
-    K.igemm(ln16, dv(wq), C, B, nq, 1, nq, 1, mode=2,
-            heads=dict(segs=[(qd, 0)], heads=heads, dh=d, ntok=nq, ntok_pad=(nq + 7) // 8 * 8, segC=C))
-    out2 = K.attention(qd, dv(k), dv(vt), heads, nkv, scale)
-    torch.cuda.synchronize()
-    e1 = K.report(f'attn_ctx fused d{d} nq{nq} nkv{nkv} B{B} fold{int(fold)}', out, ref, 4e-3)
-    e2 = K.report(f'attn_ctx two-launch d{d} nq{nq} nkv{nkv} B{B}', out2, ref, 4e-3)
-    assert not torch.isnan(out).any()
-    assert e1 < 4e-3 and e1 <= 1.5 * e2 + 3e-4, (e1, e2)
-
-
-@pytest.mark.experiments
-@pytest.mark.parametrize('d,heads,nq,nkv', [(40, 8, 4096, 4096), (40, 8, 4096, 4000), (80, 8, 1024, 1024), (64, 4, 512, 77), (40, 8, 2304, 2304),
-                                            (128, 2, 300, 130), (32, 4, 256, 64)])
-def test_attention_pingpong_is_bit_identical(d, heads, nq, nkv, monkeypatch):
-    """attn_pp_kernel (SDMI_ATTN_PP=1): the halves of an 8-wave workgroup alternate their matrix and VALU blocks instead of running
-    in lock-step -- per wave the same instructions on the same values as attn_dma_kernel, so the output must not change by one bit
-    (and both are within the usual tolerance of fp32 torch)."""
-    monkeypatch.setenv('SDMI_ATTN_KVS', '0')     # (the 8-wave kernel is the one it mirrors; round 6's default at 4096 keys is the key-split kernel)
-    g = _g(d + nq + nkv)
-    B = 2
-    q = (torch.randn(B * heads, nq, d, generator=g)).half()
-    k = (torch.randn(B * heads, nkv, d, generator=g)).half()
-    v = (torch.randn(B * heads, nkv, d, generator=g)).half()
-    nkv_pad = (nkv + 7) // 8 * 8
-    vt = torch.zeros(B * heads, d, nkv_pad, dtype=torch.float16)
-    vt[:, :, :nkv] = v.transpose(1, 2)
-    scale = d ** -0.5
-    ref = (torch.softmax(q.float() @ k.float().transpose(1, 2) * scale, dim=-1) @ v.float())
-    ref = ref.reshape(B, heads, nq, d).permute(0, 2, 1, 3).reshape(B, nq, heads * d)
-    monkeypatch.setenv('SDMI_ATTN_NW', '8')
-    monkeypatch.setenv('SDMI_ATTN_PP', '0')
-    o0 = K.attention(q.to(DEV), k.to(DEV), vt.to(DEV), heads, nkv, scale).clone()
-    monkeypatch.setenv('SDMI_ATTN_PP', '1')
-    o1 = K.attention(q.to(DEV), k.to(DEV), vt.to(DEV), heads, nkv, scale).clone()
-    torch.cuda.synchronize()
-    assert K.report(f'attention ping-pong d{d} nq{nq} nkv{nkv}', o1, ref, 3e-3) < 3e-3
-    assert torch.equal(o0, o1), float((o0.float() - o1.float()).abs().max())

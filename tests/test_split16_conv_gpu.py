@@ -247,18 +247,6 @@ def test_split16_conv3_dropped_lo_term_fails_the_bar(case, tile, splitk):
     assert err >= 10 * BAR
 
 
-FIVE_WAVE = [s for s in SMALL if not s[7]]      # (the five-wave tile has no upsampling gather)
-
-
-@pytest.mark.experiments
-@pytest.mark.parametrize('case', FIVE_WAVE, ids=[c[0] for c in FIVE_WAVE])
-@pytest.mark.parametrize('splitk', [1, 3])
-def test_split16_conv3_five_wave_tile(case, splitk):
-    """tile 22 (igemm5.hip) on the three-source operand"""
-    c = _conv_case(*case)
-    _check(case[0], c, 22, splitk, fused_splitk=False)
-
-
 # ---- 3. three-source 1x1 with the per-head scatter: the context K / V projection -------------------------------------
 
 KV = [(320, 8), (640, 8), (1280, 8), (768, 12)]      # (C, heads): dh = 40, 80, 160, 64

@@ -1,4 +1,4 @@
-"""Time the attention kernel on one shape under the kernel variants (SDMI_ATTN_V1, waves per workgroup) and, with
+"""Time the attention kernel on one shape under the kernel variants (waves per workgroup, SDMI_ATTN_NW) and, with
 --ablate, the timing-only ablations of attn.hip (SDMI_ATTN_ABL): one subprocess per setting, HIP events around 20 launches."""
 import os
 import subprocess
@@ -32,9 +32,8 @@ def run(env, shape):
 
 if __name__ == '__main__':
     shapes = [(40, 8, 2, 4096, 4096), (80, 8, 2, 1024, 1024), (40, 8, 2, 4096, 77)]
-    settings = [('dma ring (default)', {}), ('register staged (v1)', {'SDMI_ATTN_V1': '1'}),
-                ('dma ring, 4 waves / workgroup', {'SDMI_ATTN_NW_GT1K': '4', 'SDMI_ATTN_NW_LE1K': '4'}),
-                ('dma ring, 8 waves / workgroup', {'SDMI_ATTN_NW_GT1K': '8', 'SDMI_ATTN_NW_LE1K': '8'})]
+    settings = [('dma ring (default)', {}), ('dma ring, 4 waves / workgroup', {'SDMI_ATTN_NW': '4'}),
+                ('dma ring, 8 waves / workgroup', {'SDMI_ATTN_NW': '8'})]
     if '--ablate' in sys.argv:
         settings += [(f'dma ring, ablation {a} ({n})', {'SDMI_ATTN_ABL': str(a)})
                      for a, n in ((1, 'no wait+barrier'), (2, 'no DMA'), (3, 'no exp'), (4, 'no PV MFMA'), (5, 'no QK MFMA'), (6, 'LDS tile 0 only'))]

@@ -1,5 +1,5 @@
 #!/bin/bash
-# PMC passes over the attention kernel alone (d40, 4096 x 4096): pipelined, dma ring, register staged
+# PMC passes over the attention kernel alone (d40, 4096 x 4096): pipelined, dma ring
 cd "${GRAFT_REPO_ROOT:-/root/repo}"; export TMPDIR=/tmp PYTHONUNBUFFERED=1
 O=$PWD/gpurun_out/attn_pmc; mkdir -p $O
 rocprofv3 -L > $O/avail.txt 2>&1
@@ -8,7 +8,7 @@ run() { # name, env, counters...
   local name=$1; shift; local envs=$1; shift
   env $envs timeout 300 rocprofv3 --pmc "$@" -d $O/$name -o pmc -- python tools/attn_one.py > $O/$name.log 2>&1; echo "$name exit $?"
 }
-for v in "pipe:SDMI_X=1" "dma:SDMI_ATTN_PIPE_MIN=1000000" "v1:SDMI_ATTN_V1=1"; do
+for v in "pipe:SDMI_X=1" "dma:SDMI_ATTN_PIPE_MIN=1000000"; do
   n=${v%%:*}; e=${v#*:}
   run ${n}_a $e SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES
   run ${n}_b $e SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_MISC SQ_INST_CYCLES_VMEM SQ_WAIT_INST_LDS
