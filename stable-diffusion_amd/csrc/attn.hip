@@ -667,7 +667,7 @@ static int launch_attention_impl(const AttnParams& p, hipStream_t stream) {
     case 96: return launch_d<96>(p, stream);       // (the inpainting UNet's AttentionBlocks at 768 channels, 8 heads)
     case 128: return launch_d<128>(p, stream);
     case 160: return launch_d<160>(p, stream);
-    default: return fail("attention head dim " + std::to_string(p.d) + " not instantiated (32/40/64/80/96/128/160)");
+    default: return launch_attention_wide(p, stream);      // 192 .. 1024 in steps of 64 (attn_wide.hip), or the error
   }
 }
 

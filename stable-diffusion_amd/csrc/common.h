@@ -358,6 +358,8 @@ struct AttnParams {
   int pingpong = 0;          // unused (its ping-pong kernel lost its A/B and was removed); kept for the by-value layout
 };
 int launch_attention(const AttnParams& p, hipStream_t stream);
+// head dims 192 .. 1024 in steps of 64, non-causal (attn_wide.hip); launch_attention dispatches to it by d
+int launch_attention_wide(const AttnParams& p, hipStream_t stream);
 
 // GroupNorm(32) (+SiLU) over fp32 NHWC, channel-concat of two sources, fp16 or fp32 output
 struct GroupNormParams {
@@ -398,6 +400,8 @@ int launch_small_linear(const float* in, int ld_in, const float* w, const float*
                         int B, int N, int K, int silu_in, hipStream_t s);
 // gn_*: GroupNorm statistics of the output for up to two consuming GroupNorms (accumulator regions, channels per group, channel offset of
 // this tensor inside the GroupNorm's input: IGemmParams::gn_acc / gn_cpg / gn_cbase); needs H * W % 16 == 0
+// one-token context: ao[(b * ntok + tok) * C + c] = vt[(b * C + c) * ld_v] -- the cross-attention output of every query of sample b (small.hip)
+int launch_ctx1_broadcast(const f16* vt, int ld_v, f16* ao, int B, int ntok, int C, hipStream_t s);
 int launch_conv_in(const float* x_nchw, const float* w, const float* bias, float* out_nhwc, int B, int Cin, int H,
                    int W, int Cout, hipStream_t s, int gn_n = 0, long long* const* gn_acc = nullptr, const int* gn_cpg = nullptr,
                    const int* gn_cbase = nullptr);

@@ -537,6 +537,30 @@ int launch_small_linear(const float* in, int ld_in, const float* w, const float*
   return 0;
 }
 
+// One-token context (the class-conditional model's ClassEmbedder: context [B][1][context_dim]): softmax over one key is exactly 1, so
+// the cross-attention returns V of the sample for every query, whatever q and k are (attention.py:170-193 with nkv = 1; the attention
+// kernels do return fp16(V) bit for bit there).  This writes those rows without to_q and without the attention launch:
+//   ao[(b * ntok + tok) * C + c] = vt[(b * C + c) * ld_v]          (vt = the cached V^T [B * heads][dh][ld_v], key 0)
+// A workgroup owns 16 tokens of one sample; a thread gathers eight channels once and stores them as one 16-byte row piece per token.
+__global__ void __launch_bounds__(256) ctx1_broadcast_kernel(const f16* vt, int ld_v, f16* ao, int ntok, int C) {
+  const int b = blockIdx.y, t0 = blockIdx.x * 16, t1 = min(t0 + 16, ntok);
+  for (int c8 = threadIdx.x; c8 * 8 < C; c8 += 256) {
+    f16x8 v;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) v[e] = vt[((size_t)b * C + c8 * 8 + e) * ld_v];
+    for (int t = t0; t < t1; ++t) SDMI_ST(f16x8, ao + ((size_t)b * ntok + t) * C + c8 * 8, v);
+  }
+}
+
+int launch_ctx1_broadcast(const f16* vt, int ld_v, f16* ao, int B, int ntok, int C, hipStream_t s) {
+  SDMI_CHECK(B >= 1 && B <= 65535 && ntok >= 1 && ld_v >= 1 && C >= 8 && C % 8 == 0 && ((uintptr_t)ao & 15) == 0,
+             "ctx1_broadcast: channels a multiple of 8, 16-byte aligned output rows");
+  ProfScope ps("ctx1_broadcast", 0.0, 2.0 * B * (double)ntok * C, s);
+  SDMI_LAUNCH(ctx1_broadcast_kernel, dim3(cdiv(ntok, 16), B), dim3(256), 0, s, vt, ld_v, ao, ntok, C);
+  SDMI_HIP_OK(hipGetLastError());
+  return 0;
+}
+
 int launch_conv_in(const float* x, const float* w, const float* bias, float* out, int B, int Cin, int H, int W, int Cout,
                    hipStream_t s, int gn_n, long long* const* gn_acc, const int* gn_cpg, const int* gn_cbase) {
   SDMI_CHECK(Cin * 9 <= CI_MAXK, "conv_in: in_channels <= 16");

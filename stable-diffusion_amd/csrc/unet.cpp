@@ -151,8 +151,13 @@ int UNet::build(const sdmi_unet_cfg& c, int precision, const sdmi_unet_ext* ext)
     }
   }
 
-  if (!has_ctx()) {          // (the attention kernels are instantiated per head dim)
+  {                          // (the attention kernels are instantiated per head dim)
     auto check = [&](const Layer& L) -> int {
+      if (L.kind == L_ATTN) {      // wide heads (num_heads = 1: d_head = C) run on attn_wide.hip, which has no split-fp16 form yet
+        SDMI_CHECK(!(full() && L.dh > 160), L.prefix + ": attention head dim " + std::to_string(L.dh) +
+                   " has no full-precision kernel (split-fp16 attention is instantiated up to head dim 160)");
+        return 0;
+      }
       if (L.kind != L_ATTN_LEGACY) return 0;
       SDMI_CHECK(L.cin % c.num_heads == 0, L.prefix + ": channels not divisible by num_heads");
       SDMI_CHECK(L.dh == 32 || L.dh == 40 || L.dh == 64 || L.dh == 80 || L.dh == 96 || L.dh == 128 || L.dh == 160,
@@ -580,6 +585,7 @@ struct Fwd : FwdBase {
   bool st_mid_on = false;       // ... and the out-projection of attn1 with attn2's to_q (SDMI_ST_MID)
   bool st_tail_on = false;      // ... and the out-projection of attn2 in front of the tail's chain launch (SDMI_ST_TAIL)
   bool st_mid_ctx_on = false;   // ... and the cross-attention inside the st_mid launch (SDMI_ST_MID_CTX)
+  bool ctx1_on = false;         // a context of ONE token: the cross-attention output is V of the sample, copied from the cached V^T (SDMI_CTX1, read per call)
   bool gn_conv_on = false;      // ResBlock GroupNorm + SiLU + conv3x3 as one launch where a workgroup can own all output columns (gnconv.hip; SDMI_GN_CONV)
   float* emb_all = nullptr;     // [B][emb_total] (emb_ld = emb_total), or one row of the timestep table shared by every sample (emb_ld = 0)
   int emb_ld = 0;
@@ -864,6 +870,10 @@ struct Fwd : FwdBase {
       if (ctx16 && !chain_mid) context_kv(L, d);
       if (chain_mid) {
         if (!chain_ctx) attention(q, T.ck, T.cvt, ao, L, N, Lctx, Lp, scale);       // (q = to_q(norm2(t)) came out of the chain launch)
+      } else if (ctx1_on && Lctx == 1) {
+        // one-token context: softmax over one key is 1, the attention output is V of the sample for every query, bit for bit -- written
+        // straight from the cached V^T: no to_q GEMM, no attention launch.  Every other launch is the general path's, so eps is too.
+        if (!dry && !rc) ok(launch_ctx1_broadcast(T.cvt, Lp, ao, B, N, C, s));
       } else {
         IGemmParams p = dense(ln, M, C, T.wq2, C, N);
         p.mode = EPI_HEADS; p.seg_dst[0] = q; p.seg_kind[0] = 0;
@@ -1251,6 +1261,8 @@ int UNet::run(const float* x, const int64_t* t_i64, const float* t_f32, const fl
     f.st_tail_on = e_st ? atoi(e_st) != 0 : ff_tail_;
     const char* e_mc = getenv("SDMI_ST_MID_CTX");
     f.st_mid_ctx_on = e_mc ? atoi(e_mc) != 0 : st_head_;
+    const char* e_c1 = getenv("SDMI_CTX1");               // (A/B knob, read per call: 0 = the general cross-attention path at one key)
+    f.ctx1_on = !(e_c1 && atoi(e_c1) == 0);
     const char* e_gc = getenv("SDMI_GN_CONV");
     f.gn_conv_on = e_gc ? atoi(e_gc) != 0 : false;       // (opt-in: bit-identical, 36 us against 41 us with hot operands, +4 us per launch inside a UNet call -- profiles/gn_conv3_r05.txt)
     if (full()) {

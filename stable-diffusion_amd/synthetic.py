@@ -123,6 +123,18 @@ INPAINT_VQ_KWARGS = dict(embed_dim=3, n_embed=8192, ddconfig=INPAINT_VQ_DDCONFIG
 INPAINT_SCHEDULE = dict(timesteps=1000, linear_start=0.0015, linear_end=0.0205, conditioning_key='concat')   # yaml:5-14
 
 
+# ---- the class-conditional ImageNet model (configs/latent-diffusion/cin256-v2.yaml) -----------------------------------------
+CIN_UNET_KWARGS = dict(image_size=64, in_channels=3, out_channels=3, model_channels=192, attention_resolutions=[8, 4, 2],
+                       num_res_blocks=2, channel_mult=[1, 2, 3, 5], num_heads=1, use_spatial_transformer=True, transformer_depth=1,
+                       context_dim=512)                                                                    # yaml:19-39 (legacy stays True)
+# (no attn_type in this yaml: the first stage's mid-block attention is on, unlike the inpainting model's)
+CIN_VQ_DDCONFIG = dict(double_z=False, z_channels=3, resolution=256, in_channels=3, out_ch=3, ch=128, ch_mult=[1, 2, 4],
+                       num_res_blocks=2, attn_resolutions=[], dropout=0.0)                                 # yaml:46-59
+CIN_VQ_KWARGS = dict(embed_dim=3, n_embed=8192, ddconfig=CIN_VQ_DDCONFIG)
+CIN_SCHEDULE = dict(timesteps=1000, linear_start=0.0015, linear_end=0.0195)                                # yaml:5-9, conditioning_key crossattn
+CIN_CLASS_KWARGS = dict(n_classes=1001, embed_dim=512, key='class_label')                                  # yaml:63-68 (class 1000 = unconditional)
+
+
 def _key_generator(name, seed):
     """One CPU generator per tensor, seeded by (seed, key name): the values do not depend on the order the keys are listed in
     (the reference modules and the HIP modules enumerate their parameters in different orders)."""
@@ -135,13 +147,15 @@ def synthetic_named_state_dict(specs, seed=0, codebook_std=1.0):
     """CPU fp32 state_dict for a list of (key, shape): deterministic per (seed, key).  Every `zero_module` tensor of the reference
     (out_layers.3, proj_out, out.2) is drawn too -- at 0.5 / sqrt(fan_in) -- so that the attention and ResBlock branches contribute;
     other weights 0.577 / sqrt(fan_in) (unit gain through the 1x1 / 3x3 convs), norm gammas 1 + 0.1 N, biases / betas 0.02 N,
-    a codebook (quantize.embedding.weight) codebook_std * N."""
+    a codebook (quantize.embedding.weight) codebook_std * N, a class table (embedding.weight) N."""
     sd = {}
     for name, shape in specs:
         shape = tuple(int(s) for s in shape)
         g = _key_generator(name, seed)
         if name == 'quantize.embedding.weight':
             t = codebook_std * torch.randn(shape, generator=g)
+        elif name == 'embedding.weight':               # ClassEmbedder: nn.Embedding's own N(0, 1), so that the context is O(1)
+            t = torch.randn(shape, generator=g)
         elif name.endswith('.weight') and len(shape) >= 2:
             fan_in = 1
             for s in shape[1:]:

@@ -96,14 +96,18 @@ class UNetModelHIP(nn.Module):
             raise ValueError(f"hip_precision must be one of {sorted(PRECISIONS)}, got {hip_precision!r}")
         self.hip_precision = hip_precision
         # two families, anything else is refused loudly:
-        #   SD v1 (configs/stable-diffusion/v1-inference.yaml:29-44): SpatialTransformers with cross-attention, legacy=False
+        #   SD v1 (configs/stable-diffusion/v1-inference.yaml:29-44): SpatialTransformers with cross-attention, legacy=False; the
+        #   class-conditional ImageNet model (configs/latent-diffusion/cin256-v2.yaml:19-39) is the same family with num_heads=1
+        #   (d_head = C = 384 / 576 / 960) and legacy left at True -- with num_head_channels == -1 that flag changes nothing for a
+        #   SpatialTransformer (openaimodel.py:542-549: dim_head = ch // num_heads either way)
         #   latent inpainting (models/ldm/inpainting_big/config.yaml:24-41): legacy AttentionBlocks (num_heads, no context),
         #   ResBlocks with resampling (resblock_updown)
         self.use_spatial_transformer = bool(use_spatial_transformer)
         unsupported = []
         if use_spatial_transformer:
             if context_dim is None: unsupported.append('use_spatial_transformer=True with context_dim')
-            if legacy: unsupported.append('legacy=False')
+            if legacy and num_head_channels != -1:
+                unsupported.append('a spatial transformer with num_heads, not num_head_channels (legacy=True recomputes dim_head from it)')
             if resblock_updown: unsupported.append('resblock_updown=False with a spatial transformer')
         else:
             if context_dim is not None: unsupported.append('context_dim=None without a spatial transformer')
@@ -117,6 +121,13 @@ class UNetModelHIP(nn.Module):
         if unsupported:
             raise NotImplementedError('UNetModelHIP supports the SD-v1 and latent-inpainting UNet families only; needs: ' +
                                       '; '.join(unsupported))
+        if use_spatial_transformer and hip_precision == 'full':
+            # heads wider than 160 run on the wide-head kernel (csrc/attn_wide.hip), which has no split-fp16 form
+            levels = [model_channels * m for i, m in enumerate(channel_mult) if 2 ** i in list(attention_resolutions)]
+            d_max = max(levels + [model_channels * list(channel_mult)[-1]]) // num_heads
+            if d_max > self.FULL_MAX_HEAD_DIM:
+                raise NotImplementedError(f"hip_precision='full' supports attention head dims up to {self.FULL_MAX_HEAD_DIM}; this "
+                                          f'configuration has d_head = {d_max} (num_heads={num_heads}): use hip_precision=\'mixed\'')
         if isinstance(context_dim, (list, tuple)) or type(context_dim).__name__ == 'ListConfig':
             context_dim = list(context_dim)[0]
         context_dim = 0 if context_dim is None else context_dim
@@ -327,6 +338,7 @@ class UNetModelHIP(nn.Module):
         return bool(torch.equal(c if c.dtype == torch.float32 else c.float(), saved))
 
     # ---- UNetModel.forward (openaimodel.py:710-742) ----------------------------------------------------------
+    FULL_MAX_HEAD_DIM = 160       # widest head of the split-fp16 attention kernel (csrc/attn_split16.hip)
     MAX_ROWS = 8      # rows per library call (sdmi_unet_forward); larger batches are split, rows are independent
 
     @torch.no_grad()
