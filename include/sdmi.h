@@ -378,7 +378,12 @@ int sdmi_k_st_mid_ctx(const void* a_f16, const void* wo_f16, const float* bo, fl
  * (first K columns of a row): the column terms of a GEMM that folds LayerNorm(gamma, beta) of its input rows */
 int sdmi_k_ln_fold_prep(const void* w_f16, int N, int K, int ldw, const float* gamma, const float* beta, const float* bias,
                         float* cs, float* d, void* stream);
-/* q [BH,nq,d], k [BH,nkv,d], vt [BH,d,nkv_pad] fp16 -> out fp16 [BH/heads, nq, heads*d]; attention.py:178-192 */
+/* q [BH,nq,d], k [BH,nkv,d], vt [BH,d,nkv_pad] fp16 -> out fp16 [BH/heads, nq, heads*d]; attention.py:178-192.
+ * nkv_pad is a multiple of 8 and >= nkv.  The pad columns nkv .. nkv_pad of every V^T row must be ZERO for head dims up to 160 (csrc/attn.hip,
+ * and likewise for both halves in sdmi_k_attention_split16): the key tiles are staged past nkv, the score mask zeroes the probabilities of
+ * those keys, and 0 x (a non-finite pad value) would still be NaN in the P V product.  The wide-head kernel (d = 192 .. 1024 in steps of 64,
+ * csrc/attn_wide.hip) replaces the pad columns by zeros itself: they may hold anything there.  Producers inside the library keep the
+ * contract (sdmi_k_igemm mode 2 into a cleared buffer, sdmi_k_split_heads kind 1 writes the pad tokens as zeros). */
 int sdmi_k_attention(const void* q, const void* k, const void* vt, void* out, int BH, int heads, int nq, int nkv,
                      int nkv_pad, int d, float scale, void* stream);
 /* split-fp16 attention (the full-precision mode): q / k / vt and their low halves q_lo / k_lo / vt_lo in the layouts above,

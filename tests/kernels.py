@@ -52,7 +52,7 @@ def cast_f16(x, want_lo=False):
 
 def igemm(a0, w, N, B, Hin, Win, Hout, Wout, ksize=1, stride=1, up=0, a1=None, a2=None, bias=None, rowvec=None,
           residual=None, out_f32=None, out_f16=None, ldo=None, mode=0, splitk=1, tile=-1, dma=-1, heads=None, fused_splitk=True,
-          asym_pad=0, gn=None, split16=False, f16_scale=None, lnp_out=None, lnf=None, pgn=None, out_lo=None):
+          asym_pad=0, gn=None, split16=False, f16_scale=None, lnp_out=None, lnf=None, pgn=None, out_lo=None, ws=None, cnt=None):
     """a0/a1: fp16 [B*Hin*Win, C] ; w: fp16 [N, K].
     LayerNorm fold: producer f16_scale (gamma [N]) + lnp_out ([N/32, M, 2] fp32); consumer lnf = (partials, eps, cs, d)."""
     d = _lib.IGemmDesc()
@@ -93,8 +93,12 @@ def igemm(a0, w, N, B, Hin, Win, Hout, Wout, ksize=1, stride=1, up=0, a1=None, a
         ga, be, eps, silu, o16, keep = pgn
         d.pgn_gamma = ga.data_ptr(); d.pgn_beta = be.data_ptr(); d.pgn_eps = float(eps); d.pgn_silu = int(silu)
         d.pgn_out = o16.data_ptr(); d.pgn_keep_f32 = int(keep); d.pgn_applied = C.pointer(applied)
-    ws = None
-    if splitk != 1:
+    if ws is not None:     # the caller's split-K slabs (fp32) and zeroed tile counters (int32), e.g. in guarded buffers (tests/guard.py)
+        d.splitk_ws = ws.data_ptr(); d.splitk_ws_floats = ws.numel()
+        if fused_splitk:
+            cnt = _splitk_counters(a0.device) if cnt is None else cnt
+            d.splitk_cnt = cnt.data_ptr(); d.splitk_cnt_ints = cnt.numel()
+    elif splitk != 1:
         M = B * Hout * Wout
         ws = torch.empty((16 * (M + 255) * (N + 255),), dtype=torch.float32, device=a0.device)
         d.splitk_ws = ws.data_ptr(); d.splitk_ws_floats = ws.numel()

@@ -174,7 +174,7 @@ def test_conv3halo(case, tile):
     assert torch.equal(out32, out2)
 
 
-@pytest.mark.parametrize('tile', [2, 5, 7, 8, 9, 12, 13])
+@pytest.mark.parametrize('tile', [0, 2, 3, 5, 7, 8, 9, 11, 12, 13])
 @pytest.mark.parametrize('splitk', [1, 3])
 @pytest.mark.parametrize('B,H,W,C,N', [(2, 8, 8, 128, 320), (3, 4, 8, 64, 200), (2, 16, 16, 64, 64)])
 def test_igemm_groupnorm_statistics(tile, splitk, B, H, W, C, N):
