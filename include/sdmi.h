@@ -76,6 +76,13 @@ typedef struct sdmi_unet_ext {
   int32_t resblock_updown;
 } sdmi_unet_ext;
 int sdmi_unet_create_ext(const sdmi_unet_cfg* cfg, const sdmi_unet_ext* ext, int precision, sdmi_unet** out);
+/* ... with a word of creation flags (additive; sdmi_unet_ext is unchanged).  sdmi_unet_create_ext(cfg, ext, p, out) = flags 0.
+ *   SDMI_UNET_SCALE_SHIFT_NORM  every ResBlock is a use_scale_shift_norm one (openaimodel.py:267-271): emb_layers.1 is [2 cout][4 mc] and
+ *                               h = out_norm(h) * (1 + scale) + shift in front of SiLU and the second convolution, instead of h + emb_out behind
+ *                               the first.  The unconditional models (models/ldm/lsun_churches256/config.yaml): needs attention_block = 1 and
+ *                               resblock_updown = 1. */
+#define SDMI_UNET_SCALE_SHIFT_NORM 1u
+int sdmi_unet_create_flags(const sdmi_unet_cfg* cfg, const sdmi_unet_ext* ext, unsigned flags, int precision, sdmi_unet** out);
 int sdmi_unet_destroy(sdmi_unet* h);
 /* enumerate the state_dict keys the handle expects (= UNetModel.state_dict().keys()) */
 int sdmi_unet_num_weights(const sdmi_unet* h);
@@ -387,7 +394,7 @@ int sdmi_k_ln_fold_prep(const void* w_f16, int N, int K, int ldw, const float* g
 int sdmi_k_attention(const void* q, const void* k, const void* vt, void* out, int BH, int heads, int nq, int nkv,
                      int nkv_pad, int d, float scale, void* stream);
 /* split-fp16 attention (the full-precision mode): q / k / vt and their low halves q_lo / k_lo / vt_lo in the layouts above,
- * out / out_lo fp16 [BH/heads, nq, heads*d] = hi / lo of the fp32 result; d in {32, 40, 64, 80, 128, 160} */
+ * out / out_lo fp16 [BH/heads, nq, heads*d] = hi / lo of the fp32 result; d in {24, 32, 40, 48, 64, 80, 96, 128, 160} */
 int sdmi_k_attention_split16(const void* q, const void* q_lo, const void* k, const void* k_lo, const void* vt, const void* vt_lo, void* out,
                              void* out_lo, int BH, int heads, int nq, int nkv, int nkv_pad, int d, float scale, void* stream);
 /* same with a causal mask (query i attends to keys <= i; nq == nkv): CLIPTextModel's self-attention */
@@ -399,6 +406,13 @@ int sdmi_k_groupnorm(const float* x0, const float* x1, int c0, int c1, int B, in
                      const float* beta, float eps, int silu, void* out_f16, float* out_f32, void* raw_f16, void* out_lo,
                      void* raw_lo, float* partial_ws, int64_t partial_floats, void* stream);
 int64_t sdmi_k_groupnorm_ws_floats(int B, int HW);
+/* sdmi_k_groupnorm with the scale-shift rows of a use_scale_shift_norm ResBlock (openaimodel.py:267-271) applied in the same launch:
+ * y = SiLU((GN(x) gamma + beta) (1 + scale[b][c]) + shift[b][c]) feeds out_f16 / out_lo / out_f32; the raw copies are unchanged.
+ * film: row b at film + b * film_ld holds scale in its first c0 + c1 floats and shift in the next c0 + c1 (th.chunk(emb_out, 2, dim=1));
+ * film_ld = 0: one row shared by every sample; 16-byte aligned, film_ld % 4 == 0.  film = NULL: the same bits as sdmi_k_groupnorm. */
+int sdmi_k_groupnorm_film(const float* x0, const float* x1, int c0, int c1, int B, int HW, const float* gamma, const float* beta, float eps,
+                          int silu, const float* film, int film_ld, void* out_f16, float* out_f32, void* raw_f16, void* out_lo, void* raw_lo,
+                          float* partial_ws, int64_t partial_floats, void* stream);
 int sdmi_k_layernorm(const float* x, const float* gamma, const float* beta, void* out_f16, int M, int C, float eps,
                      void* stream);
 int sdmi_k_cast_f16(const float* x, void* out_f16, void* out_lo, int64_t n, void* stream);

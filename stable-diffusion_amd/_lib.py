@@ -70,6 +70,7 @@ _SIGS = {
     'sdmi_unet_create_with_precision': (C.c_int, [C.POINTER(UNetCfg), C.c_int, C.POINTER(c_ptr)]),
     'sdmi_unet_precision': (C.c_int, [c_ptr]),
     'sdmi_unet_create_ext': (C.c_int, [C.POINTER(UNetCfg), C.POINTER(UNetExt), C.c_int, C.POINTER(c_ptr)]),
+    'sdmi_unet_create_flags': (C.c_int, [C.POINTER(UNetCfg), C.POINTER(UNetExt), C.c_uint, C.c_int, C.POINTER(c_ptr)]),
     'sdmi_unet_destroy': (C.c_int, [c_ptr]),
     'sdmi_unet_num_weights': (C.c_int, [c_ptr]),
     'sdmi_unet_weight_info': (C.c_int, [c_ptr, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int)]),
@@ -143,6 +144,8 @@ _SIGS = {
     'sdmi_k_groupnorm': (C.c_int, [c_ptr, c_ptr, C.c_int, C.c_int, C.c_int, C.c_int, c_ptr, c_ptr, C.c_float, C.c_int,
                                    c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, C.c_int64, c_ptr]),
     'sdmi_k_groupnorm_ws_floats': (C.c_int64, [C.c_int, C.c_int]),
+    'sdmi_k_groupnorm_film': (C.c_int, [c_ptr, c_ptr, C.c_int, C.c_int, C.c_int, C.c_int, c_ptr, c_ptr, C.c_float, C.c_int, c_ptr, C.c_int,
+                                        c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, C.c_int64, c_ptr]),
     'sdmi_k_layernorm': (C.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, C.c_int, C.c_int, C.c_float, c_ptr]),
     'sdmi_k_cast_f16': (C.c_int, [c_ptr, c_ptr, c_ptr, C.c_int64, c_ptr]),
     'sdmi_k_split_heads': (C.c_int, [c_ptr, C.c_int, C.c_int, c_ptr, c_ptr, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,

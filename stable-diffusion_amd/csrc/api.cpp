@@ -53,12 +53,15 @@ int sdmi_unet_create_with_precision(const sdmi_unet_cfg* cfg, int precision, sdm
   return 0;
 }
 int sdmi_unet_create_ext(const sdmi_unet_cfg* cfg, const sdmi_unet_ext* ext, int precision, sdmi_unet** out) {
+  return sdmi_unet_create_flags(cfg, ext, 0u, precision, out);
+}
+int sdmi_unet_create_flags(const sdmi_unet_cfg* cfg, const sdmi_unet_ext* ext, unsigned flags, int precision, sdmi_unet** out) {
   SDMI_CHECK(cfg && out, "null argument");
   SDMI_CHECK(precision == SDMI_PRECISION_MIXED || precision == SDMI_PRECISION_FULL,
              "precision must be SDMI_PRECISION_MIXED (0) or SDMI_PRECISION_FULL (1), got " + std::to_string(precision));
   sdmi_unet* h = new (std::nothrow) sdmi_unet();
   SDMI_CHECK(h != nullptr, "out of host memory");
-  if (h->impl.build(*cfg, precision, ext)) { delete h; return -1; }
+  if (h->impl.build(*cfg, precision, ext, flags)) { delete h; return -1; }
   *out = h;
   return 0;
 }
@@ -456,6 +459,18 @@ int sdmi_k_groupnorm(const float* x0, const float* x1, int c0, int c1, int B, in
   GroupNormParams g = GroupNormParams();
   g.x0 = x0; g.x1 = x1; g.c0 = c0; g.c1 = c1; g.B = B; g.HW = HW; g.gamma = gamma; g.beta = beta; g.eps = eps;
   g.silu = silu; g.out_f16 = (f16*)out_f16; g.out_f32 = out_f32; g.raw_f16 = (f16*)raw_f16; g.out_lo = (f16*)out_lo; g.raw_lo = (f16*)raw_lo;
+  g.acc = (long long*)partial_ws;
+  return launch_groupnorm(g, (hipStream_t)stream);
+}
+int sdmi_k_groupnorm_film(const float* x0, const float* x1, int c0, int c1, int B, int HW, const float* gamma, const float* beta, float eps,
+                          int silu, const float* film, int film_ld, void* out_f16, float* out_f32, void* raw_f16, void* out_lo, void* raw_lo,
+                          float* partial_ws, int64_t partial_floats, void* stream) {
+  SDMI_CHECK(partial_floats >= gn_acc_words(B) * 2, "groupnorm workspace too small");
+  SDMI_HIP_OK(hipMemsetAsync(partial_ws, 0, gn_acc_words(B) * sizeof(long long), (hipStream_t)stream));
+  GroupNormParams g = GroupNormParams();
+  g.x0 = x0; g.x1 = x1; g.c0 = c0; g.c1 = c1; g.B = B; g.HW = HW; g.gamma = gamma; g.beta = beta; g.eps = eps;
+  g.silu = silu; g.out_f16 = (f16*)out_f16; g.out_f32 = out_f32; g.raw_f16 = (f16*)raw_f16; g.out_lo = (f16*)out_lo; g.raw_lo = (f16*)raw_lo;
+  g.film = film; g.film_ld = film_ld;
   g.acc = (long long*)partial_ws;
   return launch_groupnorm(g, (hipStream_t)stream);
 }

@@ -660,8 +660,12 @@ static int launch_attention_impl(const AttnParams& p, hipStream_t stream) {
   SDMI_CHECK(p.nkv_pad % 8 == 0 && p.nkv_pad >= p.nkv, "nkv_pad must be a multiple of 8 and >= nkv");
   SDMI_CHECK(!p.causal || p.nq == p.nkv, "causal attention needs nq == nkv");
   switch (p.d) {
+    // (24 / 48: the unconditional LSUN-Churches UNet's AttentionBlocks at 192 / 384 channels, 8 heads.  d = 24 fills half of its second
+    // k-step: Q is zero there, the K columns 24 .. 31 staged beside it are the next key's finite values; V^T row 24 is the ONES row)
+    case 24: return launch_d<24>(p, stream);
     case 32: return launch_d<32>(p, stream);
     case 40: return launch_d<40>(p, stream);
+    case 48: return launch_d<48>(p, stream);
     case 64: return launch_d<64>(p, stream);
     case 80: return launch_d<80>(p, stream);
     case 96: return launch_d<96>(p, stream);       // (the inpainting UNet's AttentionBlocks at 768 channels, 8 heads)

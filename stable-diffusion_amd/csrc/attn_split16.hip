@@ -216,14 +216,16 @@ int launch_attention_split16(const AttnSplitParams& p, hipStream_t stream) {
   const double bytes = 2.0 * 2.0 * p.BH * ((double)p.nq * p.d * 2 + (double)p.nkv * p.d + (double)p.d * p.nkv_pad);
   ProfScope ps("attention_split16", flops, bytes, stream, 3.0 * flops);
   switch (p.d) {
+    case 24: return launch_d<24>(p, stream);       // (the staging writes zeros into the unused half of the second k-step and the V^T rows past d)
     case 32: return launch_d<32>(p, stream);
     case 40: return launch_d<40>(p, stream);
+    case 48: return launch_d<48>(p, stream);
     case 64: return launch_d<64>(p, stream);
     case 80: return launch_d<80>(p, stream);
     case 96: return launch_d<96>(p, stream);
     case 128: return launch_d<128>(p, stream);
     case 160: return launch_d<160>(p, stream);
-    default: return fail("split-fp16 attention: head dim " + std::to_string(p.d) + " has no instantiation (32, 40, 64, 80, 96, 128, 160)");
+    default: return fail("split-fp16 attention: head dim " + std::to_string(p.d) + " has no instantiation (24, 32, 40, 48, 64, 80, 96, 128, 160)");
   }
 }
 

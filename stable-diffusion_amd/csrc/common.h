@@ -23,6 +23,15 @@ __device__ __forceinline__ float gn_apply_elem(float v, float mean, float rstd, 
   if (silu) t = t * __builtin_amdgcn_rcpf(1.0f + __expf(-t));
   return t;
 }
+// ... with the scale-shift ("FiLM") modulation of a use_scale_shift_norm ResBlock between the affine and the SiLU (openaimodel.py:267-271:
+// out_norm(h) * (1 + scale) + shift, then SiLU): the same two expressions around one more fused multiply-add
+__device__ __forceinline__ float gn_apply_film_elem(float v, float mean, float rstd, float gamma, float beta, float scale, float shift,
+                                                    int silu) {
+  float t = __builtin_fmaf((v - mean) * rstd, gamma, beta);
+  t = __builtin_fmaf(t, 1.0f + scale, shift);
+  if (silu) t = t * __builtin_amdgcn_rcpf(1.0f + __expf(-t));
+  return t;
+}
 // GroupNorm statistics words (see GroupNormParams::acc): add one fp32 partial / read a folded total
 __device__ __forceinline__ void gn_acc_add(unsigned long long* dst, float v) {
   const double d = (double)v;
@@ -374,6 +383,10 @@ struct GroupNormParams {
   f16* raw_f16 = nullptr;      // optional: un-normalised fp16 copy of cat(x0,x1) (A operand of the 1x1 skip conv)
   f16* out_lo = nullptr;       // optional: fp16(y - float(fp16(y)))   -- low half of a split-fp16 operand
   f16* raw_lo = nullptr;       // optional: same for the raw copy
+  // optional scale-shift rows of a use_scale_shift_norm ResBlock (openaimodel.py:267-271): row b = film + b * film_ld holds scale in its first
+  // C floats and shift in the next C (th.chunk(emb_out, 2, dim=1)); y = SiLU((GN(x) gamma + beta) (1 + scale) + shift) then feeds out_f16 / out_lo /
+  // out_f32 (the raw copies are unchanged).  film_ld = 0: one row shared by every sample (a timestep-table row).  16-byte aligned, film_ld % 4 == 0.
+  const float* film = nullptr; int film_ld = 0;
   // fixed-point statistics accumulators of THIS GroupNorm call: [B][32 groups][GN_SLOTS][GN_STRIDE] int64 (GN_WORDS used), zero before
   // the launch.  Each of {sum, sumsq} is kept as an integer part and a 2^-40 fraction (two words), so the range is that
   // of an int64 and nothing can wrap.  Integer atomics are associative: the statistics are bit-reproducible without a

@@ -109,7 +109,9 @@ static unsigned long long gn_div_magic(int d) { return ((1ull << 40) + (unsigned
 // xcd_affine: the dispatcher places block L (x fastest) on XCD L % 8; renumbered so that XCD x handles the x-th eighth of the
 // (sample, pixel) range -- the rows a following row-affine GEMM (igemm: "an XCD owns rows of A" when M > N) reads on that same XCD,
 // whose L2 then already holds the fp16 operand this kernel wrote (plain stores stay in the L2).  Speed only; any placement is correct.
-template <int U>
+// FILM: the scale-shift rows of GroupNormParams::film are applied between the affine and the SiLU (their quads are requested with the
+// activation's, in front of the statistics fold); a separate instantiation, so the plain kernels keep their registers and their code
+template <int U, bool FILM = false>
 __global__ void __launch_bounds__(256) gn_apply_kernel(GroupNormParams p, const unsigned long long magic_nq,
                                                        const unsigned long long magic_cpg, const int xcd_affine) {
   __shared__ float s_mean[32], s_rstd[32];
@@ -129,6 +131,8 @@ __global__ void __launch_bounds__(256) gn_apply_kernel(GroupNormParams p, const 
   const int64_t total = (int64_t)p.HW * nq;
   const int64_t base = (int64_t)bx * (256 * U) + tid;           // quad index inside this batch row
   f32x4 v[U], ga[U], be[U]; size_t pix[U]; int ch[U];
+  f32x4 fsc[FILM ? U : 1], fsh[FILM ? U : 1];
+  const float* const frow = FILM ? p.film + (size_t)b * p.film_ld : nullptr;
 #pragma unroll
   for (int u = 0; u < U; ++u) {
     const int64_t idx = base + u * 256;
@@ -141,6 +145,10 @@ __global__ void __launch_bounds__(256) gn_apply_kernel(GroupNormParams p, const 
       v[u] = load_cat4(p.x0, p.x1, p.c0, p.c1, pix[u], ch[u]);
       ga[u] = *(const f32x4*)(p.gamma + ch[u]);
       be[u] = *(const f32x4*)(p.beta + ch[u]);
+      if constexpr (FILM) {
+        fsc[u] = *(const f32x4*)(frow + ch[u]);
+        fsh[u] = *(const f32x4*)(frow + C + ch[u]);
+      }
     }
   }
   {
@@ -160,7 +168,8 @@ __global__ void __launch_bounds__(256) gn_apply_kernel(GroupNormParams p, const 
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const bool second = j >= split;
-      y[j] = gn_apply_elem(v[u][j], second ? m1 : m0, second ? r1 : r0, ga[u][j], be[u][j], p.silu);
+      if constexpr (FILM) y[j] = gn_apply_film_elem(v[u][j], second ? m1 : m0, second ? r1 : r0, ga[u][j], be[u][j], fsc[u][j], fsh[u][j], p.silu);
+      else y[j] = gn_apply_elem(v[u][j], second ? m1 : m0, second ? r1 : r0, ga[u][j], be[u][j], p.silu);
     }
     const size_t o = pix[u] * C + c;
     if (p.out_f16) SDMI_ST_F16X4(p.out_f16, o, (f16x4{(f16)y[0], (f16)y[1], (f16)y[2], (f16)y[3]}));
@@ -233,6 +242,8 @@ int launch_groupnorm(const GroupNormParams& p, hipStream_t stream) {
   SDMI_CHECK(p.acc != nullptr && p.gamma && p.beta && p.x0, "GroupNorm: missing pointer");
   SDMI_CHECK(p.c1 == 0 || p.x1 != nullptr, "GroupNorm: second source missing");
   SDMI_CHECK(C / 32 >= 2, "GroupNorm: at least 2 channels per group");
+  SDMI_CHECK(p.film == nullptr || ((((uintptr_t)p.film) & 15) == 0 && p.film_ld % 4 == 0 && (p.film_ld == 0 || p.film_ld >= 2 * C)),
+             "GroupNorm: scale-shift rows must be 16-byte aligned with a pitch of 0 (shared row) or a multiple of 4 >= 2 C");
   const int chunk_px = gn_chunk(p.HW, C);
   const int nchunk = cdiv(p.HW, chunk_px);
   const double nel = (double)p.B * p.HW * C;
@@ -249,10 +260,14 @@ int launch_groupnorm(const GroupNormParams& p, hipStream_t stream) {
     const int want_xcd = getenv("SDMI_GN_XCD") ? atoi(getenv("SDMI_GN_XCD")) : 0;
     if (quads >= u4_from) {
       const unsigned nb = (unsigned)((quads + 1023) / 1024);
-      SDMI_LAUNCH(gn_apply_kernel<4>, dim3(nb, p.B), dim3(256), 0, stream, p, magic_nq, magic_cpg, (want_xcd && (nb * p.B) % 8 == 0) ? 1 : 0);
+      const int xa = (want_xcd && (nb * p.B) % 8 == 0) ? 1 : 0;
+      if (p.film) SDMI_LAUNCH((gn_apply_kernel<4, true>), dim3(nb, p.B), dim3(256), 0, stream, p, magic_nq, magic_cpg, xa);
+      else SDMI_LAUNCH(gn_apply_kernel<4>, dim3(nb, p.B), dim3(256), 0, stream, p, magic_nq, magic_cpg, xa);
     } else {
       const unsigned nb = (unsigned)((quads + 255) / 256);
-      SDMI_LAUNCH(gn_apply_kernel<1>, dim3(nb, p.B), dim3(256), 0, stream, p, magic_nq, magic_cpg, (want_xcd && (nb * p.B) % 8 == 0) ? 1 : 0);
+      const int xa = (want_xcd && (nb * p.B) % 8 == 0) ? 1 : 0;
+      if (p.film) SDMI_LAUNCH((gn_apply_kernel<1, true>), dim3(nb, p.B), dim3(256), 0, stream, p, magic_nq, magic_cpg, xa);
+      else SDMI_LAUNCH(gn_apply_kernel<1>, dim3(nb, p.B), dim3(256), 0, stream, p, magic_nq, magic_cpg, xa);
     }
   }
   SDMI_HIP_OK(hipGetLastError());

@@ -59,10 +59,15 @@ struct TapeRecGuard {         // recording ends with the scope, whatever path le
 };
 }  // namespace
 
-int UNet::build(const sdmi_unet_cfg& c, int precision, const sdmi_unet_ext* ext) {
+int UNet::build(const sdmi_unet_cfg& c, int precision, const sdmi_unet_ext* ext, unsigned flags) {
   cfg_ = c;
   precision_ = precision;
   if (ext) ext_ = *ext;
+  SDMI_CHECK((flags & ~(unsigned)SDMI_UNET_SCALE_SHIFT_NORM) == 0, "unknown UNet creation flag");
+  scale_shift_ = (flags & SDMI_UNET_SCALE_SHIFT_NORM) != 0;
+  // (the family this executor path is validated for: the unconditional LDMs -- AttentionBlocks and resampling ResBlocks)
+  SDMI_CHECK(!scale_shift_ || (ext_.attention_block == 1 && ext_.resblock_updown == 1),
+             "SDMI_UNET_SCALE_SHIFT_NORM needs attention_block = 1 and resblock_updown = 1");
   SDMI_CHECK(ext_.attention_block == 0 || ext_.attention_block == 1, "attention_block must be 0 (SpatialTransformer) or 1 (AttentionBlock)");
   SDMI_CHECK(ext_.resblock_updown == 0 || ext_.resblock_updown == 1, "resblock_updown must be 0 or 1");
   SDMI_CHECK(c.n_levels >= 1 && c.n_levels <= 8 && c.n_attention_resolutions >= 0 && c.n_attention_resolutions <= 8,
@@ -80,7 +85,7 @@ int UNet::build(const sdmi_unet_cfg& c, int precision, const sdmi_unet_ext* ext)
   int cur_ds = 1;               // downsample factor of the layer being added (ds below; the middle block sits at the deepest one)
   auto add_res = [&](const std::string& p, int cin, int cout) {
     Layer L; L.kind = L_RES; L.prefix = p; L.cin = cin; L.cout = cout;
-    L.emb_off = emb_total_; emb_total_ += cout;
+    L.emb_off = emb_total_; emb_total_ += scale_shift_ ? 2 * cout : cout;      // (scale-shift: [scale | shift], th.chunk(emb_out, 2, dim=1))
     L.p1x1 = full() || (precise_1x1_ && cur_ds < precise_1x1_max_ds_);
     L.precise3 = full();        // (build() requires model_channels % 64 == 0: every ResBlock's channel counts are multiples of 64)
     return L;
@@ -160,8 +165,8 @@ int UNet::build(const sdmi_unet_cfg& c, int precision, const sdmi_unet_ext* ext)
       }
       if (L.kind != L_ATTN_LEGACY) return 0;
       SDMI_CHECK(L.cin % c.num_heads == 0, L.prefix + ": channels not divisible by num_heads");
-      SDMI_CHECK(L.dh == 32 || L.dh == 40 || L.dh == 64 || L.dh == 80 || L.dh == 96 || L.dh == 128 || L.dh == 160,
-                 L.prefix + ": attention head dim " + std::to_string(L.dh) + " not instantiated (32/40/64/80/96/128/160)");
+      SDMI_CHECK(L.dh == 24 || L.dh == 32 || L.dh == 40 || L.dh == 48 || L.dh == 64 || L.dh == 80 || L.dh == 96 || L.dh == 128 || L.dh == 160,
+                 L.prefix + ": attention head dim " + std::to_string(L.dh) + " not instantiated (24/32/40/48/64/80/96/128/160)");
       return 0;
     };
     for (auto& blk : input_blocks_) for (auto& L : blk) if (check(L)) return -1;
@@ -193,8 +198,8 @@ int UNet::build(const sdmi_unet_cfg& c, int precision, const sdmi_unet_ext* ext)
         expect(p + ".in_layers.0.bias", {ci}, W_F32, (void**)&L.f32[1]);
         expect(p + ".in_layers.2.weight", {co, ci, 3, 3}, L.precise3 ? W_CONV_SPLIT3 : W_CONV, (void**)&L.w16[0]);
         expect(p + ".in_layers.2.bias", {co}, W_F32, (void**)&L.f32[2]);
-        expect(p + ".emb_layers.1.weight", {co, TE}, W_F32_ROWS, (void**)&emb_w_, L.emb_off, te_);
-        expect(p + ".emb_layers.1.bias", {co}, W_F32_ROWS, (void**)&emb_b_, L.emb_off, 1);
+        expect(p + ".emb_layers.1.weight", {scale_shift_ ? 2 * co : co, TE}, W_F32_ROWS, (void**)&emb_w_, L.emb_off, te_);
+        expect(p + ".emb_layers.1.bias", {scale_shift_ ? 2 * co : co}, W_F32_ROWS, (void**)&emb_b_, L.emb_off, 1);
         expect(p + ".out_layers.0.weight", {co}, W_F32, (void**)&L.f32[3]);
         expect(p + ".out_layers.0.bias", {co}, W_F32, (void**)&L.f32[4]);
         expect(p + ".out_layers.3.weight", {co, co, 3, 3}, L.precise3 ? W_CONV_SPLIT3 : W_CONV, (void**)&L.w16[1]);
@@ -529,7 +534,7 @@ int UNet::export_packed(void* host_buf, int64_t bytes, hipStream_t stream) {
   memcpy(h.magic, "SDMIPK01", 8);
   h.abi = SDMI_ABI_VERSION; h.precise_1x1 = precise_1x1_ ? 1 : 0; h.n_buffers = (int32_t)bufs.size(); h.cfg = cfg_;
   h.reserved = (precise_kv_ ? 1 : 0) | (precise_last_res_ ? 2 : 0) | (precise_1x1_max_ds_ << 8);      // (ABI 17: the precision allocation)
-  h.reserved |= (ext_.attention_block << 4) | (ext_.resblock_updown << 5);                          // (sdmi_unet_ext: 0 for SD v1)
+  h.reserved |= (ext_.attention_block << 4) | (ext_.resblock_updown << 5) | ((scale_shift_ ? 1 : 0) << 6);   // (sdmi_unet_ext, creation flags: 0 for SD v1)
   if (full()) h.reserved |= PK_FULL;
   h.total_bytes = total;
   memcpy(host_buf, &h, sizeof(h));
@@ -553,9 +558,9 @@ int UNet::import_packed(const void* host_buf, int64_t bytes, hipStream_t stream)
              ((h.reserved & PK_FULL) ? "full" : "mixed") + "-precision UNet handle and cannot be imported into a " + (full() ? "full" : "mixed") +
              "-precision one: repack it with a handle of this precision");
   SDMI_CHECK((h.precise_1x1 != 0) == precise_1x1_, "packed blob was written with a different precision allocation (split-fp16 1x1 convs)");
-  SDMI_CHECK((h.reserved & (3 << 4)) == ((ext_.attention_block << 4) | (ext_.resblock_updown << 5)),
-             "packed blob was written for a different UNet family (attention_block / resblock_updown)");
-  SDMI_CHECK((h.reserved & ~PK_FULL & ~(3 << 4)) == ((precise_kv_ ? 1 : 0) | (precise_last_res_ ? 2 : 0) | (precise_1x1_max_ds_ << 8)),
+  SDMI_CHECK((h.reserved & (7 << 4)) == ((ext_.attention_block << 4) | (ext_.resblock_updown << 5) | ((scale_shift_ ? 1 : 0) << 6)),
+             "packed blob was written for a different UNet family (attention_block / resblock_updown / scale-shift norm)");
+  SDMI_CHECK((h.reserved & ~PK_FULL & ~(7 << 4)) == ((precise_kv_ ? 1 : 0) | (precise_last_res_ ? 2 : 0) | (precise_1x1_max_ds_ << 8)),
              "packed blob was written with a different precision allocation (context K / V, last ResBlock, 1x1 conv levels)");
   std::vector<std::pair<void**, size_t>> bufs;
   int64_t total = 0;
@@ -614,8 +619,12 @@ struct Fwd : FwdBase {
     gn2_applied = 0;
     // in_layers / out_layers as ONE launch each (gnconv.hip: 32 pixels x all 320 output channels per workgroup, the halo normalised once):
     // the 64 x 64 level of SD v1.  (in_layers only without a skip convolution: that one reads raw fp16 copies the GroupNorm launch writes.)
-    const bool gc1 = gn_conv_on && !p3 && Cin == Cout && gn_conv3_supported(B, H, W, x0.C, x1 ? x1->C : 0, Cout);
-    const bool gc2 = gn_conv_on && !p3 && gn_conv3_supported(B, H, W, Cout, 0, Cout);
+    // scale-shift ResBlock (openaimodel.py:267-271): conv1 adds no embedding row; out_layers' GroupNorm takes the layer's [scale | shift] row
+    // in its apply launch (GroupNormParams::film) -- so neither the one-launch forms nor the split-K reduction that applies a GroupNorm
+    const bool ss = u->scale_shift_;
+    const float* const film = ss ? emb_all + L.emb_off : nullptr;
+    const bool gc1 = gn_conv_on && !ss && !p3 && Cin == Cout && gn_conv3_supported(B, H, W, x0.C, x1 ? x1->C : 0, Cout);
+    const bool gc2 = gn_conv_on && !ss && !p3 && gn_conv3_supported(B, H, W, Cout, 0, Cout);
     auto gn_conv = [&](const Act& a0, const Act* a1, const float* gamma, const float* beta, const f16* w, IGemmParams& e) {
       GnConvParams g = GnConvParams();
       g.gn_acc = groupnorm(a0, a1, gamma, beta, 1e-5f, 1, nullptr, nullptr, nullptr, nullptr, nullptr, /*stats_only=*/true);
@@ -636,16 +645,17 @@ struct Fwd : FwdBase {
       groupnorm(x0, x1, L.f32[0], L.f32[1], 1e-5f, 1, a, nullptr, raw, a_lo, raw_lo);
       IGemmParams p = conv3(a, Cin, H, W, H, W, 1, 0, L.w16[0], Cout);
       if (p3) split3(p, a, a_lo, Cin);
-      p.bias = L.f32[2]; p.rowvec = emb_all + L.emb_off; p.ld_rowvec = emb_ld;
+      p.bias = L.f32[2];
+      if (!ss) { p.rowvec = emb_all + L.emb_off; p.ld_rowvec = emb_ld; }
       p.out_f32 = h; p.ldo = Cout;
       attach_gn_targets(p, hact);          // statistics of out_layers' GroupNorm come out of this epilogue
-      if (!gc2 && !p3) {
+      if (!gc2 && !p3 && !ss) {
         // ... or, where this conv ends up split along K (8x8, 16x16, the concat blocks of 32x32), GroupNorm + SiLU are applied by
         // its split-K reduction: a2 = the conv2 operand comes straight out of it (IGemmParams::pgn_*; gn2_applied says so)
         a2 = S<f16>((size_t)M * Cout);
         p.pgn_gamma = L.f32[3]; p.pgn_beta = L.f32[4]; p.pgn_eps = 1e-5f; p.pgn_silu = 1; p.pgn_out = a2; p.pgn_applied = &gn2_applied;
       }
-      TapeCaller tc(Tape::R_EMB, emb_caller ? p.rowvec : nullptr);
+      TapeCaller tc(Tape::R_EMB, emb_caller ? p.rowvec : nullptr);      // (null for a scale-shift block: declares nothing)
       gemm(p);
     }
     const float* residual = x0.p;
@@ -664,7 +674,13 @@ struct Fwd : FwdBase {
     } else {
       f16* a2_lo = nullptr;
       if (p3) { a2 = S<f16>((size_t)M * Cout); a2_lo = S<f16>((size_t)M * Cout); }
-      groupnorm(hact, nullptr, L.f32[3], L.f32[4], 1e-5f, 1, a2, nullptr, nullptr, a2_lo, nullptr, false, gn2_applied != 0);
+      if (ss && !a2) a2 = S<f16>((size_t)M * Cout);
+      {
+        // the row is a caller pointer of the launch tape whenever it comes from the timestep table: a replay at another timestep
+        // must normalise with that step's row
+        TapeCaller tc(Tape::R_EMB, emb_caller ? film : nullptr);
+        groupnorm(hact, nullptr, L.f32[3], L.f32[4], 1e-5f, 1, a2, nullptr, nullptr, a2_lo, nullptr, false, gn2_applied != 0, film, emb_ld);
+      }
       IGemmParams p = conv3(a2, Cout, H, W, H, W, 1, 0, L.w16[1], Cout);
       if (p3) split3(p, a2, a2_lo, Cout);
       p.bias = L.f32[5]; p.residual = residual; p.ldr = Cout; p.out_f32 = out.p; p.ldo = Cout;
@@ -984,6 +1000,8 @@ struct Fwd : FwdBase {
     if (dir > 0 && ((H | W) & 1)) ok(fail("resampling res block at " + L.prefix + ": the 2x2 average pool needs even H and W"));
     const int Ho = dir > 0 ? H / 2 : 2 * H, Wo = dir > 0 ? W / 2 : 2 * W, M = B * Ho * Wo;
     const bool p3 = L.precise3;
+    const bool ss = u->scale_shift_;                                   // (as in res_block: the row modulates out_layers' GroupNorm)
+    const float* const film = ss ? emb_all + L.emb_off : nullptr;
     const size_t mark = scratch.off;
     float* g = S<float>((size_t)B * H * W * C);                        // SiLU(GN(x)) at the input resolution (fp32)
     groupnorm(x, nullptr, L.f32[0], L.f32[1], 1e-5f, 1, nullptr, g, nullptr);
@@ -1001,7 +1019,8 @@ struct Fwd : FwdBase {
     {
       IGemmParams p = conv3(a, C, Ho, Wo, Ho, Wo, 1, 0, L.w16[0], C);
       if (p3) split3(p, a, a_lo);
-      p.bias = L.f32[2]; p.rowvec = emb_all + L.emb_off; p.ld_rowvec = emb_ld;
+      p.bias = L.f32[2];
+      if (!ss) { p.rowvec = emb_all + L.emb_off; p.ld_rowvec = emb_ld; }
       p.out_f32 = h; p.ldo = C;
       attach_gn_targets(p, hact);
       TapeCaller tc(Tape::R_EMB, emb_caller ? p.rowvec : nullptr);
@@ -1010,7 +1029,10 @@ struct Fwd : FwdBase {
     {
       f16* a2 = S<f16>((size_t)M * C);
       f16* a2_lo = p3 ? S<f16>((size_t)M * C) : nullptr;
-      groupnorm(hact, nullptr, L.f32[3], L.f32[4], 1e-5f, 1, a2, nullptr, nullptr, a2_lo, nullptr);
+      {
+        TapeCaller tc(Tape::R_EMB, emb_caller ? film : nullptr);
+        groupnorm(hact, nullptr, L.f32[3], L.f32[4], 1e-5f, 1, a2, nullptr, nullptr, a2_lo, nullptr, false, false, film, emb_ld);
+      }
       IGemmParams p = conv3(a2, C, Ho, Wo, Ho, Wo, 1, 0, L.w16[1], C);
       if (p3) split3(p, a2, a2_lo);
       p.bias = L.f32[5]; p.residual = xs; p.ldr = C; p.out_f32 = out.p; p.ldo = C;

@@ -173,8 +173,9 @@ struct FwdBase {
   // keeps the plan's bookkeeping (accumulator region, call index) in step and launches nothing.
   long long* groupnorm(const Act& x0, const Act* x1, const float* gamma, const float* beta, float eps, int silu, f16* o16,
                        float* o32, f16* raw, f16* o16_lo = nullptr, f16* raw_lo = nullptr, bool stats_only = false,
-                       bool already_applied = false) {
+                       bool already_applied = false, const float* film = nullptr, int film_ld = 0) {
     GroupNormParams g = GroupNormParams();
+    g.film = film; g.film_ld = film_ld;             // scale-shift rows of a use_scale_shift_norm ResBlock (GroupNormParams::film)
     g.x0 = x0.p; g.c0 = x0.C;
     if (x1) { g.x1 = x1->p; g.c1 = x1->C; }
     g.B = B; g.HW = x0.H * x0.W; g.gamma = gamma; g.beta = beta; g.eps = eps; g.silu = silu;
@@ -267,7 +268,7 @@ class UNet {
   UNet(const UNet&) = delete;
   UNet& operator=(const UNet&) = delete;
 
-  int build(const sdmi_unet_cfg& cfg, int precision = SDMI_PRECISION_MIXED, const sdmi_unet_ext* ext = nullptr);
+  int build(const sdmi_unet_cfg& cfg, int precision = SDMI_PRECISION_MIXED, const sdmi_unet_ext* ext = nullptr, unsigned flags = 0);
   int set_weight(const char* key, const float* ptr, const int64_t* shape, int ndim, hipStream_t stream);
   int finalize();
   // packed-weight blob: every packed device buffer behind a header that pins cfg / ABI
@@ -290,6 +291,9 @@ class UNet {
   sdmi_unet_cfg cfg_{};
   sdmi_unet_ext ext_{};        // (all zero: the SD-v1 family)
   bool has_ctx() const { return ext_.attention_block == 0; }      // SpatialTransformers with cross-attention
+  // SDMI_UNET_SCALE_SHIFT_NORM (sdmi_unet_create_flags): every ResBlock is a use_scale_shift_norm one (openaimodel.py:267-271) -- its
+  // emb_layers output is 2 cout wide [scale | shift] and modulates out_layers' GroupNorm instead of being added behind conv1
+  bool scale_shift_ = false;
   // SDMI_PRECISION_FULL: every MFMA operand split-fp16 (every Layer::p1x1 / precise3, split-fp16 linears, resamplers and attention;
   // the row-strip chains and the LayerNorm / GroupNorm folds off).  Fixed by build(); the packed weights depend on it.
   int precision_ = SDMI_PRECISION_MIXED;

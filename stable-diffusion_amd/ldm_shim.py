@@ -1,7 +1,8 @@
 """The two thin wrappers between the samplers and the UNet, restated so the hot path can be driven without
 pytorch_lightning: `LatentDiffusion.apply_model` (ldm/models/diffusion/ddpm.py:891-900,986-992) and
-`DiffusionWrapper.forward` (ddpm.py:1402-1421, conditioning_key 'crossattn', or 'concat' for the latent-inpainting
-model: the UNet reads cat([x, c_concat], 1) and no context), plus the schedule buffers
+`DiffusionWrapper.forward` (ddpm.py:1402-1421, conditioning_key 'crossattn', 'concat' for the latent-inpainting
+model: the UNet reads cat([x, c_concat], 1) and no context, or None for the unconditional models: the UNet reads x and t
+alone), plus the schedule buffers
 `DDPM.register_schedule` registers (ddpm.py:117-169) that the samplers read.
 
 With the real `ldm` package installed the reference's own LatentDiffusion does this job;
@@ -20,12 +21,14 @@ def make_beta_schedule_linear(n_timestep=1000, linear_start=0.00085, linear_end=
 class DiffusionWrapperHIP(nn.Module):
     def __init__(self, diffusion_model, conditioning_key='crossattn'):
         super().__init__()
-        if conditioning_key not in ('crossattn', 'concat'):
-            raise NotImplementedError(f"conditioning_key {conditioning_key!r}: 'crossattn' and 'concat' only")
+        if conditioning_key not in (None, 'crossattn', 'concat'):
+            raise NotImplementedError(f"conditioning_key {conditioning_key!r}: None, 'crossattn' and 'concat' only")
         self.diffusion_model = diffusion_model
         self.conditioning_key = conditioning_key
 
     def forward(self, x, t, c_concat=None, c_crossattn=None):
+        if self.conditioning_key is None:              # ddpm.py:1408-1409
+            return self.diffusion_model(x, t)
         if self.conditioning_key == 'concat':          # ddpm.py:1411-1413
             xc = torch.cat([x] + list(c_concat), dim=1)
             return self.diffusion_model(xc, t)
@@ -38,7 +41,9 @@ class LatentDiffusionHIP(nn.Module):
 
     def __init__(self, unet, timesteps=1000, linear_start=0.00085, linear_end=0.0120, conditioning_key='crossattn'):
         """The latent-inpainting model: linear_start=0.0015, linear_end=0.0205, conditioning_key='concat'
-        (models/ldm/inpainting_big/config.yaml:5-14)."""
+        (models/ldm/inpainting_big/config.yaml:5-14).  The unconditional LSUN-Churches model: linear_start=0.0015,
+        linear_end=0.0155, conditioning_key=None (models/ldm/lsun_churches256/config.yaml:5-6, cond_stage_config
+        '__is_unconditional__': ddpm.py:455-456 leaves the key at None); apply_model(x, t, None)."""
         super().__init__()
         self.model = DiffusionWrapperHIP(unet, conditioning_key)
         betas = make_beta_schedule_linear(timesteps, linear_start, linear_end)

@@ -135,6 +135,14 @@ CIN_SCHEDULE = dict(timesteps=1000, linear_start=0.0015, linear_end=0.0195)     
 CIN_CLASS_KWARGS = dict(n_classes=1001, embed_dim=512, key='class_label')                                  # yaml:63-68 (class 1000 = unconditional)
 
 
+# ---- the unconditional LSUN-Churches model (models/ldm/lsun_churches256/config.yaml) ------------------------------------------
+CHURCHES_UNET_KWARGS = dict(image_size=32, in_channels=4, out_channels=4, model_channels=192, attention_resolutions=[1, 2, 4, 8],
+                            num_res_blocks=2, channel_mult=[1, 2, 2, 4, 4], num_heads=8, use_scale_shift_norm=True,
+                            resblock_updown=True)                                                          # yaml:33-52
+CHURCHES_VAE_DDCONFIG = SD_V1_VAE_DDCONFIG                     # yaml:57-71: the KL-f8 autoencoder with SD v1's ddconfig, embed_dim 4
+CHURCHES_SCHEDULE = dict(timesteps=1000, linear_start=0.0015, linear_end=0.0155, conditioning_key=None)   # yaml:5-6,9; unconditional
+
+
 def _key_generator(name, seed):
     """One CPU generator per tensor, seeded by (seed, key name): the values do not depend on the order the keys are listed in
     (the reference modules and the HIP modules enumerate their parameters in different orders)."""
@@ -181,4 +189,11 @@ def synthetic_inpaint_vq_state_dict(seed=0, vq_kwargs=None):
     """CPU state_dict (reference VQModelInterface key names, without loss.*) of a seeded random VQ first stage."""
     from .vae import VQModelInterfaceHIP
     m = VQModelInterfaceHIP(**(vq_kwargs or INPAINT_VQ_KWARGS))
+    return synthetic_named_state_dict([(k, tuple(v.shape)) for k, v in m.state_dict().items()], seed)
+
+
+def synthetic_churches_unet_state_dict(seed=0, unet_kwargs=None):
+    """CPU state_dict (reference UNetModel key names) of a seeded random unconditional LSUN-Churches UNet."""
+    from .unet import UNetModelHIP
+    m = UNetModelHIP(**(unet_kwargs or CHURCHES_UNET_KWARGS))
     return synthetic_named_state_dict([(k, tuple(v.shape)) for k, v in m.state_dict().items()], seed)

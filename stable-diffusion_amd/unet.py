@@ -10,7 +10,9 @@ Same constructor keywords (openaimodel.py:443-470), same parameter names (so
 `model.load_state_dict(sd, strict=False)` at scripts/txt2img.py:56 fills it), same call
 `diffusion_model(x, t, context=cc)` (ldm/models/diffusion/ddpm.py:1410).  The latent-inpainting UNet
 (models/ldm/inpainting_big/config.yaml: legacy AttentionBlocks, resblock_updown, no context) is the second family:
-`diffusion_model(cat([x, c_concat], 1), t)` (ddpm.py:1411-1413).  The arithmetic runs in
+`diffusion_model(cat([x, c_concat], 1), t)` (ddpm.py:1411-1413).  The unconditional LSUN-Churches UNet
+(models/ldm/lsun_churches256/config.yaml: the same blocks with use_scale_shift_norm, five levels, attention at the full
+latent resolution) is the third: `diffusion_model(x, t)` (ddpm.py DiffusionWrapper, conditioning_key None).  The arithmetic runs in
 libsdmi.so (hand-written gfx950 kernels); this class only owns the parameters, packs them into the
 library on first use and hands raw device pointers across the C ABI.
 """
@@ -43,15 +45,18 @@ def make_cfg(in_channels, out_channels, model_channels, num_res_blocks, channel_
 
 
 PRECISIONS = {'mixed': 0, 'full': 1}      # SDMI_PRECISION_MIXED / SDMI_PRECISION_FULL (include/sdmi.h)
+UNET_SCALE_SHIFT_NORM = 1                 # SDMI_UNET_SCALE_SHIFT_NORM (sdmi_unet_create_flags)
 
 
 class _Handle:
     """Owns one sdmi_unet*."""
 
-    def __init__(self, cfg, precision='mixed', ext=None):
+    def __init__(self, cfg, precision='mixed', ext=None, flags=0):
         self.lib = _lib.load()
         h = C.c_void_p()
-        if ext is None:
+        if flags:
+            _lib.check(self.lib.sdmi_unet_create_flags(C.byref(cfg), C.byref(ext), flags, PRECISIONS[precision], C.byref(h)))
+        elif ext is None:
             _lib.check(self.lib.sdmi_unet_create_with_precision(C.byref(cfg), PRECISIONS[precision], C.byref(h)))
         else:
             _lib.check(self.lib.sdmi_unet_create_ext(C.byref(cfg), C.byref(ext), PRECISIONS[precision], C.byref(h)))
@@ -95,13 +100,16 @@ class UNetModelHIP(nn.Module):
         if hip_precision not in PRECISIONS:
             raise ValueError(f"hip_precision must be one of {sorted(PRECISIONS)}, got {hip_precision!r}")
         self.hip_precision = hip_precision
-        # two families, anything else is refused loudly:
+        # three families, anything else is refused loudly:
         #   SD v1 (configs/stable-diffusion/v1-inference.yaml:29-44): SpatialTransformers with cross-attention, legacy=False; the
         #   class-conditional ImageNet model (configs/latent-diffusion/cin256-v2.yaml:19-39) is the same family with num_heads=1
         #   (d_head = C = 384 / 576 / 960) and legacy left at True -- with num_head_channels == -1 that flag changes nothing for a
         #   SpatialTransformer (openaimodel.py:542-549: dim_head = ch // num_heads either way)
         #   latent inpainting (models/ldm/inpainting_big/config.yaml:24-41): legacy AttentionBlocks (num_heads, no context),
         #   ResBlocks with resampling (resblock_updown)
+        #   unconditional LSUN-Churches (models/ldm/lsun_churches256/config.yaml:33-52): the inpainting family's blocks with
+        #   use_scale_shift_norm (openaimodel.py:267-271), nothing concatenated (in_channels == out_channels), five levels, attention
+        #   at every resolution down to the full latent one (head dims 24 / 48 / 96)
         self.use_spatial_transformer = bool(use_spatial_transformer)
         unsupported = []
         if use_spatial_transformer:
@@ -115,11 +123,22 @@ class UNetModelHIP(nn.Module):
             if use_new_attention_order: unsupported.append('use_new_attention_order=False (QKVAttentionLegacy)')
         if num_heads == -1 or num_head_channels != -1: unsupported.append('num_heads (not num_head_channels)')
         if num_heads_upsample not in (-1, num_heads): unsupported.append('num_heads_upsample == num_heads')
-        if dims != 2 or not conv_resample or use_scale_shift_norm: unsupported.append('dims=2, conv_resample, no scale-shift norm')
+        if dims != 2 or not conv_resample: unsupported.append('dims=2, conv_resample')
+        if use_scale_shift_norm:
+            # admitted for the family it is validated on and no wider: the unconditional models
+            rule = []
+            if use_spatial_transformer: rule.append('no spatial transformer')
+            if not resblock_updown: rule.append('resblock_updown=True')
+            if num_heads == -1 or num_head_channels != -1: rule.append('num_heads (not num_head_channels)')
+            if in_channels != out_channels: rule.append('in_channels == out_channels (nothing concatenated)')
+            if rule:
+                unsupported.append('scale-shift norm (use_scale_shift_norm=True) only for the unconditional family -- no spatial '
+                                   'transformer, resblock_updown=True, num_heads given, in_channels == out_channels; this configuration '
+                                   'lacks: ' + ', '.join(rule))
         if num_classes is not None or n_embed is not None: unsupported.append('no class conditioning / codebook head')
         if dropout != 0: unsupported.append('dropout=0')
         if unsupported:
-            raise NotImplementedError('UNetModelHIP supports the SD-v1 and latent-inpainting UNet families only; needs: ' +
+            raise NotImplementedError('UNetModelHIP supports the SD-v1, latent-inpainting and unconditional UNet families only; needs: ' +
                                       '; '.join(unsupported))
         if use_spatial_transformer and hip_precision == 'full':
             # heads wider than 160 run on the wide-head kernel (csrc/attn_wide.hip), which has no split-fp16 form
@@ -132,6 +151,7 @@ class UNetModelHIP(nn.Module):
             context_dim = list(context_dim)[0]
         context_dim = 0 if context_dim is None else context_dim
         self.resblock_updown = bool(resblock_updown)
+        self.use_scale_shift_norm = bool(use_scale_shift_norm)
         self.image_size = image_size
         self.in_channels, self.model_channels, self.out_channels = in_channels, model_channels, out_channels
         self.num_res_blocks = num_res_blocks
@@ -146,7 +166,7 @@ class UNetModelHIP(nn.Module):
         if not use_spatial_transformer or resblock_updown:
             ext = _lib.UNetExt()
             ext.attention_block, ext.resblock_updown = int(not use_spatial_transformer), int(bool(resblock_updown))
-        self._handle = _Handle(self._cfg, hip_precision, ext)
+        self._handle = _Handle(self._cfg, hip_precision, ext, UNET_SCALE_SHIFT_NORM if use_scale_shift_norm else 0)
         self._specs = self._handle.weight_specs()
         for key, shape in self._specs:
             *path, leaf = key.split('.')

@@ -1,6 +1,6 @@
 """In-situ tuning of the implicit-GEMM tile / split-K choice on the MI355X (writes stable-diffusion_amd/tune_gfx950.txt).
 
-    python tools/tune.py [--out PATH] [--rounds 64] [--reps 2] [--workloads unet64,unet96,...]
+    python tools/tune.py [--out PATH] [--rounds 64] [--reps 2] [--workloads unet64,unet96,...] [--append-new]
 
 Every auto-configured GEMM launch of the real executors (UNet, first stage, text encoder) runs candidate
 (round mod #candidates) of its shape while the library times it with HIP events on the launch stream
@@ -8,6 +8,9 @@ Every auto-configured GEMM launch of the real executors (UNet, first stage, text
 in HBM (1.7 GB of them stream through per UNet call), activations warm from the producing kernel -- the conditions a
 stand-alone sweep of one shape does not reproduce.  The resulting table is committed, so the choice (and with it the
 split-K summation order, i.e. the exact output bits) is fixed.
+
+--append-new: the table at --out keeps every row it has; only shapes whose key is not in it yet are appended (a model added
+later brings its own shapes and changes no other model's tiles): `--workloads churches32b8,churches32b2 --append-new`.
 """
 import argparse
 import ctypes as C
@@ -27,6 +30,7 @@ def main():
     ap.add_argument('--rounds', type=int, default=72)
     ap.add_argument('--reps', type=int, default=3)
     ap.add_argument('--workloads', default='unet64,unet96,unet32,unet64b4,unet64b6,unet64b8,vaedec64,vaedec96,vaeenc512,clip')
+    ap.add_argument('--append-new', action='store_true', help='keep every row of the table at --out; append the shapes it does not have')
     args = ap.parse_args()
     from stable_diffusion_amd import AutoencoderKLHIP, FrozenCLIPEmbedderHIP, UNetModelHIP, _lib
     from stable_diffusion_amd.synthetic import (SD_V1_UNET_KWARGS, SD_V1_VAE_DDCONFIG, randomize_, randomize_vae_,
@@ -66,7 +70,19 @@ def main():
         ids = torch.randint(0, 49408, (2, 77), generator=g).to(dev)
         return lambda: clip.encode_ids(ids)
 
+    churches = None
+
+    def churches_fn(B):              # the unconditional LSUN-Churches UNet at its native 32 x 32 latent (8 + 2 rows of a batch of 10)
+        nonlocal churches
+        from stable_diffusion_amd.synthetic import CHURCHES_UNET_KWARGS
+        if churches is None:
+            churches = randomize_(UNetModelHIP(**CHURCHES_UNET_KWARGS).to(dev).eval(), 0)
+        x = torch.randn(B, 4, 32, 32, generator=g).to(dev)
+        t = torch.full((B,), 481, device=dev)
+        return lambda: churches(x, t)
+
     makers = {
+        'churches32b8': lambda: churches_fn(8), 'churches32b2': lambda: churches_fn(2),
         'unet64': lambda: unet_fn(2, 64), 'unet96': lambda: unet_fn(2, 96), 'unet32': lambda: unet_fn(2, 32),
         'unet64b4': lambda: unet_fn(4, 64), 'unet64b6': lambda: unet_fn(6, 64), 'unet64b8': lambda: unet_fn(8, 64),
         'vaedec64': lambda: vaedec_fn(64), 'vaedec96': lambda: vaedec_fn(96), 'vaeenc512': lambda: vaeenc_fn(512),
@@ -91,7 +107,17 @@ def main():
         torch.cuda.synchronize()
     n = C.c_int(0)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    _lib.check(lib.sdmi_tune_end(args.out.encode(), C.byref(n)))
+    out = args.out + '.new' if args.append_new else args.out
+    _lib.check(lib.sdmi_tune_end(out.encode(), C.byref(n)))
+    if args.append_new:
+        key = lambda ln: tuple(ln.split()[:8])
+        rows = lambda path: [ln for ln in open(path).read().splitlines() if ln and not ln.startswith('#')]
+        have = {key(ln) for ln in rows(args.out)} if os.path.exists(args.out) else set()
+        fresh = [ln for ln in rows(out) if key(ln) not in have]
+        with open(args.out, 'a') as f:
+            f.write(''.join(ln + '\n' for ln in fresh))
+        os.remove(out)
+        print(f'[tune] --append-new: {len(fresh)} new rows appended, {len(have)} kept as they were', flush=True)
     print(f'[tune] {n.value} shapes tuned over {args.reps} x {args.rounds} rounds of {[w for w, _ in fns]} in '
           f'{time.time() - t0:.1f} s -> {args.out}', flush=True)
     if args.dump:
