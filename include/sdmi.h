@@ -82,6 +82,16 @@ int sdmi_unet_create_ext(const sdmi_unet_cfg* cfg, const sdmi_unet_ext* ext, int
  *                               the first.  The unconditional models (models/ldm/lsun_churches256/config.yaml): needs attention_block = 1 and
  *                               resblock_updown = 1. */
 #define SDMI_UNET_SCALE_SHIFT_NORM 1u
+/*   SDMI_UNET_NUM_HEAD_CHANNELS(n)  num_head_channels = n (openaimodel.py:532-535,561-563; cfg.num_heads is then not read, pass -1 as the
+ *                               reference does): every AttentionBlock runs ch / n heads of n channels, QKVAttentionLegacy row order.  n must divide
+ *                               every attention level's channel count and be an instantiated head dim.  attention_block = 1 only.  The face /
+ *                               bedroom LDMs (models/ldm/celeba256, ffhq256, lsun_beds256: model_channels 224, n = 32 -> 14 / 21 / 28 heads) and
+ *                               bsr_sr (160, n = 32 -> 20 heads).  A handle with attention_block = 1 takes model_channels % 32 == 0 (GEMM sources
+ *                               of 32 (mod 64) channels end in a half k-tile); SpatialTransformer handles keep model_channels % 64 == 0.
+ *                               A packed blob records n and is imported only by a handle created with the same n. */
+#define SDMI_UNET_NUM_HEAD_CHANNELS_SHIFT 16
+#define SDMI_UNET_NUM_HEAD_CHANNELS_MASK 0x0fff0000u
+#define SDMI_UNET_NUM_HEAD_CHANNELS(n) (((unsigned)(n) << SDMI_UNET_NUM_HEAD_CHANNELS_SHIFT) & SDMI_UNET_NUM_HEAD_CHANNELS_MASK)
 int sdmi_unet_create_flags(const sdmi_unet_cfg* cfg, const sdmi_unet_ext* ext, unsigned flags, int precision, sdmi_unet** out);
 int sdmi_unet_destroy(sdmi_unet* h);
 /* enumerate the state_dict keys the handle expects (= UNetModel.state_dict().keys()) */
@@ -281,7 +291,7 @@ typedef struct sdmi_igemm_desc {
   const void* a0; const void* a1; const void* a2;   /* fp16 NHWC sources, channel concat [a0|a1|a2] (a1, a2 optional) */
   int32_t c0, c1, c2, lda0, lda1, lda2;
   int32_t B, Hin, Win, Hout, Wout, ksize, stride, up;
-  const void* w;                        /* fp16 [N][K] from sdmi_k_pack_conv_weight: K = ksize*ksize*(c0+c1+c2), ordered (64-ch chunk, ky, kx, ch) */
+  const void* w;                        /* fp16 [N][K] from sdmi_k_pack_conv_weight(_src): K = ksize*ksize*(c0+c1+c2), ordered (64-ch chunk, ky, kx, ch); c0, c1, c2 % 32 == 0 */
   int32_t N;
   int32_t mode;                         /* 0 plain, 1 GEGLU (w/bias packed by sdmi_k_pack_geglu), 2 per-head scatter */
   const float* bias; const float* rowvec; int32_t ld_rowvec;
@@ -431,11 +441,15 @@ int sdmi_k_conv_in(const float* x_nchw, const float* w_oihw, const float* bias, 
 int sdmi_k_conv_out(const float* h_nhwc, const float* w_ohwi, const float* bias, float* out_nchw, int B, int H, int W,
                     int Cin, int Cout, void* stream);
 int sdmi_k_pack_conv_weight(const float* w_oihw, void* dst_f16, int O, int I, int KH, int KW, void* stream);
+/* ... for A sources that are multiples of 32 channels (c0 + c1 + c2 == I, each % 32 == 0): the 64-channel chunks are numbered per source,
+ * and the last chunk of a source of 32 (mod 64) channels is 32 wide (the kernels' half k-tile).  K = KH*KW*I stays dense.  With every source
+ * a multiple of 64 the output equals sdmi_k_pack_conv_weight's, byte for byte.  sdmi_k_pack_conv_weight itself takes one source of I % 32 == 0. */
+int sdmi_k_pack_conv_weight_src(const float* w_oihw, void* dst_f16, int O, int I, int KH, int KW, int c0, int c1, int c2, void* stream);
 int sdmi_k_pack_conv_out(const float* w_oihw, float* dst_ohwi, int O, int I, void* stream);
 /* [N][K] fp32 -> fp16 [N][3K] = [hi | hi | lo] for the 3-pass split-fp16 1x1 convs */
 int sdmi_k_pack_split3(const float* w, void* dst_f16, int N, int K, void* stream);
 /* [O][I][KH][KW] fp32 -> fp16 [O][3 KH KW I]: the 3-pass split-fp16 3x3 conv weights [w_hi | w_hi | w_lo], i.e. sdmi_k_pack_conv_weight
- * of the virtual [O][3 I][KH][KW] tensor, met by the K-concatenated operand a0 = hi, a1 = lo, a2 = hi (c0 = c1 = c2 = I); I % 64 == 0 */
+ * of the virtual [O][3 I][KH][KW] tensor, met by the K-concatenated operand a0 = hi, a1 = lo, a2 = hi (c0 = c1 = c2 = I); I % 32 == 0 */
 int sdmi_k_pack_conv_split3(const float* w_oihw, void* dst_f16, int O, int I, int KH, int KW, void* stream);
 /* first-stage helpers: 1x1 conv NCHW->NCHW on <= 16 channels (input pre-scaled); row softmax fp32 -> fp16 */
 int sdmi_k_pointwise_nchw(const float* x, const float* w, const float* bias, float* out, int B, int Cin, int Cout, int HW,

@@ -509,6 +509,9 @@ int sdmi_k_conv_out(const float* h, const float* w, const float* bias, float* ou
 int sdmi_k_pack_conv_weight(const float* w, void* dst, int O, int I, int KH, int KW, void* stream) {
   return launch_pack_conv_weight(w, (f16*)dst, O, I, KH, KW, (hipStream_t)stream);
 }
+int sdmi_k_pack_conv_weight_src(const float* w, void* dst, int O, int I, int KH, int KW, int c0, int c1, int c2, void* stream) {
+  return launch_pack_conv_weight_src(w, (f16*)dst, O, I, KH, KW, c0, c1, c2, (hipStream_t)stream);
+}
 int sdmi_k_pack_conv_out(const float* w, float* dst, int O, int I, void* stream) {
   return launch_pack_conv_out(w, dst, O, I, (hipStream_t)stream);
 }

@@ -88,7 +88,8 @@ static inline int64_t round_up(int64_t a, int64_t b) { return (a + b - 1) / b * 
 //   A is fp16 NHWC activations (one or two channel-concatenated sources), gathered as a
 //   1x1 or 3x3 (stride 1/2, optional nearest-x2 upsampled input) convolution; a Linear is ksize=1.
 //   W is fp16 [N][K], K ordered (64-channel chunk, ky, kx, channel within chunk); for 1x1 / Linear simply [N][Cin]
-//   -- packed once by small.hip.
+//   -- packed once by small.hip.  Every source is a multiple of 32 channels; the chunks are per source, and the last chunk of a
+//   source of 32 (mod 64) channels is 32 wide (launch_pack_conv_weight_src takes the source split).
 // ----------------------------------------------------------------------------------------------
 enum EpiMode { EPI_PLAIN = 0, EPI_GEGLU = 1, EPI_HEADS = 2 };
 
@@ -205,7 +206,7 @@ struct IGemmParams {
   // uses the tail.  (The fused reduction of the kernels' splitk_fused arm -- the last block of a tile to arrive sums the
   // splits -- lost its A/B, profiles/splitk_fused_r02.txt: no launcher enables it.)
   int* splitk_cnt = nullptr; int splitk_cnt_ints = 0;
-  int gn_safe = 0;                                     // unused (its GroupNorm-folding conv was removed); kept for the by-value layout
+  int nkt = 0;                                         // set by the launcher: k-tiles of the whole K (igemm_nkt: a source of 32 (mod 64) channels ends in a half tile)
 #ifdef SDMI_IGEMM_TIMING
   long long* dbg_times = nullptr;                      // timing build only: 6 s_memtime slots per workgroup (5 used)
   int dbg_abl = 0;                                     // timing build only (SDMI_EPI_ABL): 1 no residual loads, 2 no GroupNorm statistics, 4 no output stores
@@ -468,6 +469,9 @@ int launch_ln_fold_prep(const f16* w, int N, int K, int ldw, const float* gamma,
                         float* d, hipStream_t s);
 // split-fp16 weights for the 3-pass 1x1 convs: dst [N][3K] = [hi | hi | lo], lo = fp16(w - float(hi))
 int launch_pack_split3(const float* w, f16* dst, int N, int K, hipStream_t s);
+// ... for A sources that are multiples of 32 channels: K chunk-major PER SOURCE (c0 + c1 + c2 == I), the last chunk of a source of
+// 32 (mod 64) channels 32 wide.  The same bytes as launch_pack_conv_weight when every source is a multiple of 64.
+int launch_pack_conv_weight_src(const float* w_oihw, f16* dst, int O, int I, int KH, int KW, int c0, int c1, int c2, hipStream_t s);
 int launch_pack_conv_split3(const float* w, f16* dst, int O, int I, int KH, int KW, hipStream_t s);
 int launch_pack_geglu(const float* w, const float* bias, f16* wdst, float* bdst, int N, int K, hipStream_t s);
 int launch_pack_conv_out(const float* w_oihw, float* dst, int O, int I, hipStream_t s);   // -> [O][3][3][I] fp32

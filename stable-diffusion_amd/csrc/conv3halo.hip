@@ -271,6 +271,8 @@ __global__ void __launch_bounds__(WARPS_M* WARPS_N * 64) conv3halo_kernel(const 
 // image rows that do not straddle samples
 bool halo_supported(const IGemmParams& p, int bm) {
   const int W = p.Wout, HW = p.Hout * p.Wout;
+  // (whole 64-channel chunks only: a source that ends in a half k-tile stays on the generic kernel)
+  if (p.c0 % BK || p.c1 % BK || p.c2 % BK) return false;
   if (!(p.ksize == 3 && p.stride == 1 && p.pad == 1 && !p.up && p.Hin == p.Hout && p.Win == p.Wout && W >= 8 && W <= 64 &&
         (W & (W - 1)) == 0 && bm % W == 0))
     return false;

@@ -19,7 +19,8 @@
 namespace sdmi {
 namespace {
 
-template <int BM, int BN, int WARPS_M, int WARPS_N, int NS>
+// HALF: K = 32 (mod 64), the last k-tile is a half one -- its own instantiation, the whole-chunk launches keep their k-loop
+template <int BM, int BN, int WARPS_M, int WARPS_N, int NS, bool HALF>
 __global__ void __launch_bounds__(WARPS_M* WARPS_N * 64) gemm_split16_kernel(const IGemmParams p, const int tiles_m, const int tiles_n,
                                                                                const int kt_per_split) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -49,7 +50,7 @@ __global__ void __launch_bounds__(WARPS_M* WARPS_N * 64) gemm_split16_kernel(con
   if (p.tile_n_fastest) { tile_m = tmn / tiles_n; tile_n = tmn - tile_m * tiles_n; }
   else { tile_n = tmn / tiles_m; tile_m = tmn - tile_n * tiles_m; }
   const int m0 = tile_m * BM, n0 = tile_n * BN;
-  const int nkt = p.K / BK;
+  const int nkt = HALF ? p.nkt : p.K / BK;       // (HALF: ceil(K / 64))
   const int kt_begin = split * kt_per_split;
   const int kt_end = min(nkt, kt_begin + kt_per_split);
   if (kt_begin >= kt_end) return;
@@ -59,6 +60,10 @@ __global__ void __launch_bounds__(WARPS_M* WARPS_N * 64) gemm_split16_kernel(con
   const int lane = tid & 63, wave = tid >> 6;
   const int cpos = tid & 7, lrow = tid >> 3;
   const int gch = cpos ^ ((lrow >> 1) & 7);      // global chunk that lands at (row, cpos)
+  // half k-tile (the last 32 of K = 32 (mod 64) columns): chunk lanes 4..7 -- by gch -- load nothing (voffset >= num_records: zeros,
+  // also into LDS), for all four operand tiles; the MFMAs of the upper two k-steps multiply zeros
+  const int hi_oob = (HALF && gch >= 4) ? (int)0x80000000 : 0;
+  const int kt_half = HALF ? nkt - 1 : -1;
   const int wave_u = __builtin_amdgcn_readfirstlane(wave);
 
   // rows past M / N are clamped to the last valid row (copies the epilogue never stores): every load unconditional, in bounds
@@ -76,14 +81,15 @@ __global__ void __launch_bounds__(WARPS_M* WARPS_N * 64) gemm_split16_kernel(con
   // DMA piece q of k-tile kt into ring stage `stage`: q in [0, A_PASSES) a_hi, then a_lo, then w_hi, then w_lo
   auto issue_piece = [&](int kt, int stage, int q) {
     const int soff = kt * (BK * 2);
+    const int half = HALF ? (hi_oob & (kt == kt_half ? (int)0x80000000 : 0)) : 0;
     const bool isA = q < 2 * A_PASSES;
     const int qa = isA ? q : q - 2 * A_PASSES;
     const int npass = isA ? A_PASSES : B_PASSES;
-    const int half = qa >= npass ? 1 : 0, pass = qa - half * npass;
-    const unsigned row0 = (isA ? half * BM : 2 * BM + half * BN) + pass * RPP + wave_u * 8;
+    const int hl = qa >= npass ? 1 : 0, pass = qa - hl * npass;
+    const unsigned row0 = (isA ? hl * BM : 2 * BM + hl * BN) + pass * RPP + wave_u * 8;
     auto dst = (__attribute__((address_space(3))) void*)(smem + stage * STAGE_BYTES + row0 * 128);
-    if (isA) __builtin_amdgcn_raw_ptr_buffer_load_lds(half ? rsrc_lo : rsrc_hi, dst, 16, a_off[pass], soff, 0, 0);
-    else __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_w, dst, 16, b_off[pass], soff + (half ? w_lo_off : 0), 0, SDMI_W_AUX);
+    if (isA) __builtin_amdgcn_raw_ptr_buffer_load_lds(hl ? rsrc_lo : rsrc_hi, dst, 16, a_off[pass] | half, soff, 0, 0);
+    else __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_w, dst, 16, b_off[pass] | half, soff + (hl ? w_lo_off : 0), 0, SDMI_W_AUX);
   };
 
   const int wm = wave / WARPS_N, wn = wave - wm * WARPS_N;
@@ -182,10 +188,11 @@ __global__ void __launch_bounds__(WARPS_M* WARPS_N * 64) gemm_split16_kernel(con
 template <int BM, int BN, int WARPS_M, int WARPS_N, int NS>
 int launch_split16_cfg(const IGemmParams& p, int splitk, hipStream_t stream) {
   const int tiles_m = cdiv(p.M, BM), tiles_n = cdiv(p.N, BN);
-  const int nkt = p.K / BK;
+  const int nkt = igemm_nkt(p);
   const int kt_per_split = cdiv(nkt, splitk);
   const int nsplit = cdiv(nkt, kt_per_split);
   IGemmParams q = p;
+  q.nkt = nkt;
   q.splitk = nsplit;
   q.tile_n_fastest = tile_order_n_fastest(p);
   q.splitk_fused = 0;
@@ -207,7 +214,8 @@ int launch_split16_cfg(const IGemmParams& p, int splitk, hipStream_t stream) {
                (double)p.M * p.K * 2.0 + (double)p.N * p.K * 2.0 + (double)p.M * p.N * ((p.out_f32 ? 4.0 : 0.0) + (p.out_f16 ? 2.0 : 0.0)) +
                    (p.residual ? (double)p.M * p.N * 4.0 : 0.0),
                stream, 6.0 * p.M * (double)p.N * p.K);
-  SDMI_LAUNCH((gemm_split16_kernel<BM, BN, WARPS_M, WARPS_N, NS>), grid, block, 0, stream, q, tiles_m, tiles_n, kt_per_split);
+  if (igemm_has_half(p)) SDMI_LAUNCH((gemm_split16_kernel<BM, BN, WARPS_M, WARPS_N, NS, true>), grid, block, 0, stream, q, tiles_m, tiles_n, kt_per_split);
+  else SDMI_LAUNCH((gemm_split16_kernel<BM, BN, WARPS_M, WARPS_N, NS, false>), grid, block, 0, stream, q, tiles_m, tiles_n, kt_per_split);
   SDMI_HIP_OK(hipGetLastError());
   ps.end();
   if (nsplit > 1) return launch_splitk_reduce(q, nsplit, stream);
@@ -222,9 +230,9 @@ int launch_split16_cfg(const IGemmParams& p, int splitk, hipStream_t stream) {
 bool split16_tile_supported(int tile) { return tile == 0 || tile == 1 || tile == 2 || tile == 4 || tile == 5 || tile == 8 || tile == 10; }
 
 int launch_split16_tile(int tile, const IGemmParams& p, int splitk, hipStream_t stream) {
-  SDMI_CHECK(p.a0 && p.a1 && p.ksize == 1 && p.mode == EPI_PLAIN && p.c1 == 0 && p.c2 == 0 && p.K == p.c0 && p.K % BK == 0 &&
+  SDMI_CHECK(p.a0 && p.a1 && p.ksize == 1 && p.mode == EPI_PLAIN && p.c1 == 0 && p.c2 == 0 && p.K == p.c0 && p.K % BKH == 0 &&
                  p.lda0 % 8 == 0 && p.ldw % 8 == 0 && p.ldw >= 3 * p.K,
-             "split-fp16 GEMM: hi + lo operands, plain epilogue, K % 64 == 0, packed [N][3K] weights");
+             "split-fp16 GEMM: hi + lo operands, plain epilogue, K % 32 == 0, packed [N][3K] weights");
   switch (tile) {
     case 0: return launch_split16_cfg<128, 128, 2, 2, 2>(p, splitk, stream);      // 128 KB
     case 1: return launch_split16_cfg<128, 64, 2, 2, 2>(p, splitk, stream);       //  96 KB

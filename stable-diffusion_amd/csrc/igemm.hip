@@ -482,6 +482,14 @@ static inline bool tile_tn_even(int t) { return (kTiles[t].bn / kTiles[t].wn / 3
 
 static int launch_tile(int tile, const IGemmParams& p, bool dma, int splitk, hipStream_t stream) {
   if (p.split16) return launch_split16_tile(tile, p, splitk, stream);
+  if (igemm_has_half(p)) {   // a source of 32 (mod 64) channels: the kernels with the half k-tile (igemm_h0 / h1 / h2.hip); the halo tiles refuse
+    switch (tile) {
+      case 0: case 1: case 2: case 3: case 4: case 5: return launch_generic_tile_h0(tile, p, dma, splitk, stream);
+      case 6: case 7: case 8: case 9: case 10: return launch_generic_tile_h1(tile, p, dma, splitk, stream);
+      case 11: case 12: case 13: case 18: case 19: case 20: case 21: return launch_generic_tile_h2(tile, p, dma, splitk, stream);
+      default: break;
+    }
+  }
   switch (tile) {            // tile ids: see include/sdmi.h (sdmi_igemm_desc.tile); the generic tiles are instantiated in igemm_t0 / t1 / t2.hip
     case 0: case 1: case 2: case 3: case 4: case 5: return launch_generic_tile_g0(tile, p, dma, splitk, stream);
     case 6: case 7: case 8: case 9: case 10: return launch_generic_tile_g1(tile, p, dma, splitk, stream);
@@ -560,7 +568,7 @@ static Tuner g_tuner;
 // candidate (tile, split-K) pairs of a shape, in a fixed order (the collection run indexes them by round)
 static std::vector<TuneChoice> tune_candidates(const IGemmParams& p, bool can_split) {
   std::vector<TuneChoice> out;
-  const int nkt = p.K / BK;
+  const int nkt = igemm_nkt(p);
   static const int splits[] = {1, 2, 3, 4, 5, 6, 8, 10, 12, 16};     // 5 / 10: halo tiles only (20 / 40 channel chunks)
   for (int t = 0; t < SDMI_NUM_TILES; ++t) {
     const TileCfg& c = kTiles[t];
@@ -678,7 +686,9 @@ int launch_igemm(const IGemmParams& p, const IGemmTune& tune, hipStream_t stream
   SDMI_CHECK(p.ksize == 1 || p.ksize == 3, "ksize must be 1 or 3");
   const int Cin = p.c0 + p.c1 + p.c2;
   SDMI_CHECK(p.K == p.ksize * p.ksize * Cin, "K != ksize^2 * (c0 + c1 + c2)");
-  SDMI_CHECK(Cin % BK == 0 && p.c0 % BK == 0 && p.c1 % BK == 0, "channel counts must be multiples of 64");
+  // (a source of 32 (mod 64) channels ends in a half k-tile; the split-fp16 dense family checks its own K)
+  SDMI_CHECK(p.c0 % BKH == 0 && p.c1 % BKH == 0 && p.c2 % BKH == 0 && p.c0 > 0, "channel counts of every A source must be multiples of 32");
+  SDMI_CHECK((p.c2 == 0 || p.c1 > 0), "third A source without a second");
   SDMI_CHECK(p.lda0 % 8 == 0 && (p.a1 == nullptr || p.lda1 % 8 == 0), "A row pitch must be a multiple of 8 halves");
   SDMI_CHECK(p.zero_page != nullptr, "zero page missing");
   SDMI_CHECK(p.M == p.B * p.Hout * p.Wout, "M != B * Hout * Wout");
@@ -716,7 +726,7 @@ int launch_igemm(const IGemmParams& p, const IGemmTune& tune, hipStream_t stream
   int tile = tune.tile >= 0 ? tune.tile : env_tile;
   SDMI_CHECK(tile < SDMI_NUM_TILES, "unknown igemm tile id");
   int splitk = p.splitk;
-  const int nkt = p.K / BK;
+  const int nkt = igemm_nkt(p);
   static const int env_split = env_int("SDMI_SPLITK", -1);     // 1 disables split-K everywhere
   const bool can_split_plain = p.mode == EPI_PLAIN && p.splitk_ws && p.N % 4 == 0 && p.ldo % 4 == 0 &&
                                (p.residual == nullptr || p.ldr % 4 == 0);
@@ -727,7 +737,9 @@ int launch_igemm(const IGemmParams& p, const IGemmTune& tune, hipStream_t stream
   // ---- (tile, split-K): explicit request > tuning table / collection run > heuristic ------------------------------
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   // (the split-fp16 dense GEMM is its own family of kernels: keyed apart with ksize 11)
-  TuneKey tkey{p.M, p.N, p.K, p.split16 ? 11 : p.ksize, p.stride, p.up, p.mode, splitk};
+  // (the key's K counts whole k-tiles, nkt * 64: = K for sources of whole 64-channel chunks; a source that ends in a half tile is keyed as if
+  // padded, so every K of the table stays a multiple of 64)
+  TuneKey tkey{p.M, p.N, nkt * BK, p.split16 ? 11 : p.ksize, p.stride, p.up, p.mode, splitk};
   int tcand = -1;
   if (tile < 0) {
     std::lock_guard<std::mutex> lk(g_tuner.mu);

@@ -14,6 +14,10 @@ int launch_splitk_reduce(const IGemmParams& p, int nsplit, hipStream_t stream);
 int launch_generic_tile_g0(int tile, const IGemmParams& p, bool dma, int splitk, hipStream_t stream);
 int launch_generic_tile_g1(int tile, const IGemmParams& p, bool dma, int splitk, hipStream_t stream);
 int launch_generic_tile_g2(int tile, const IGemmParams& p, bool dma, int splitk, hipStream_t stream);
+// ... and the same tile shapes for launches with a half k-tile (igemm_h0 / h1 / h2.hip)
+int launch_generic_tile_h0(int tile, const IGemmParams& p, bool dma, int splitk, hipStream_t stream);
+int launch_generic_tile_h1(int tile, const IGemmParams& p, bool dma, int splitk, hipStream_t stream);
+int launch_generic_tile_h2(int tile, const IGemmParams& p, bool dma, int splitk, hipStream_t stream);
 
 static int env_int(const char* name, int dflt) {
   const char* v = getenv(name);
@@ -23,6 +27,16 @@ static int env_int(const char* name, int dflt) {
 namespace {
 
 constexpr int BK = 64;
+// An A source whose channel count is 32 (mod 64) ends in a HALF k-tile: 32 halves = 64 bytes per row, chunk lanes 0..3 of the 128-byte LDS
+// row.  K stays dense (K = ksize^2 * Cin; the packed weights are chunk-major per source with chunk widths 64, ..., 64, 32), so the k-loop
+// counts TILES, not K / 64: per source ceil(c / 64) chunks, each with ksize^2 taps.
+constexpr int BKH = 32;
+static inline int src_chunks(int c) { return (c + BK - 1) / BK; }
+static inline bool igemm_has_half(const IGemmParams& p) { return p.split16 ? (p.K % BK != 0) : (p.c0 % BK || p.c1 % BK || p.c2 % BK); }
+static inline int igemm_nkt(const IGemmParams& p) {
+  if (p.split16) return src_chunks(p.K);
+  return p.ksize * p.ksize * (src_chunks(p.c0) + src_chunks(p.c1) + src_chunks(p.c2));
+}
 
 // Per-workgroup phase stamps (s_memtime at kernel entry, k-loop entry, k-loop exit, kernel exit) exist only in a build with
 // -DSDMI_IGEMM_TIMING (SDMI_CXXFLAGS=-DSDMI_IGEMM_TIMING SDMI_LIB_OUT=... python stable-diffusion_amd/build.py; tools/igemm_timing.py):

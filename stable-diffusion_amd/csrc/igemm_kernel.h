@@ -1,6 +1,6 @@
 // The generic implicit-GEMM kernel (igemm_kernel) and its launcher template (launch_cfg): included by the translation units that
-// instantiate its tile shapes (igemm_t0.hip / igemm_t1.hip / igemm_t2.hip -- three files so that the 60-odd instantiations compile in
-// parallel; igemm.hip keeps the split-K reductions, the tile table, the tuner and launch_igemm).  Design notes: igemm.hip.
+// instantiate its tile shapes (igemm_t0.hip / igemm_t1.hip / igemm_t2.hip, and igemm_h0 / h1 / h2.hip for the launches with a half k-tile --
+// six files so that the instantiations compile in parallel; igemm.hip keeps the split-K reductions, the tile table, the tuner and launch_igemm).  Design notes: igemm.hip.
 #pragma once
 #include <string>
 
@@ -13,7 +13,9 @@ namespace {
 // NS = LDS pipeline depth.  DMA path: NS-1 k-tiles are in flight across the (raw) barrier, retired by a counted
 // s_waitcnt vmcnt(N); the global->LDS latency (~1 us under load) is several k-tiles of MFMA work, so NS = 2 leaves
 // every block waiting on its single outstanding tile.
-template <int BM, int BN, int WARPS_M, int WARPS_N, bool DMA, int NS, int KIND>
+// HALF: some A source has 32 (mod 64) channels and ends in a half k-tile.  Its own instantiation (igemm_h0 / h1 / h2.hip): the launches whose
+// sources are whole 64-channel chunks keep the code they had -- no mask, no extra cursor arithmetic in their k-loop.
+template <int BM, int BN, int WARPS_M, int WARPS_N, bool DMA, int NS, int KIND, bool HALF = false>
 __global__ void __launch_bounds__(WARPS_M* WARPS_N * 64) igemm_kernel(const IGemmParams p, const int tiles_m,
                                                                        const int tiles_n, const int kt_per_split) {
   static_assert(DMA || NS == 2, "the register-staged path is double buffered");
@@ -49,7 +51,7 @@ __global__ void __launch_bounds__(WARPS_M* WARPS_N * 64) igemm_kernel(const IGem
   if (p.tile_n_fastest) { tile_m = tmn / tiles_n; tile_n = tmn - tile_m * tiles_n; }
   else { tile_n = tmn / tiles_m; tile_m = tmn - tile_n * tiles_m; }
   const int m0 = tile_m * BM, n0 = tile_n * BN;
-  const int nkt = p.K / BK;
+  const int nkt = HALF ? p.nkt : p.K / BK;       // (HALF: tiles, not K / 64 -- a source of 32 (mod 64) channels ends in a half tile)
   const int kt_begin = split * kt_per_split;
   const int kt_end = min(nkt, kt_begin + kt_per_split);
   if (kt_begin >= kt_end) return;
@@ -66,6 +68,9 @@ __global__ void __launch_bounds__(WARPS_M* WARPS_N * 64) igemm_kernel(const IGem
   const int cpos = tid & 7;                      // chunk position inside the LDS row
   const int lrow = tid >> 3;                     // row inside a load pass
   const int gch = cpos ^ ((lrow >> 1) & 7);      // global chunk that lands at (row, cpos)
+  // half k-tile (the last 32 channels of a source): the lanes that would carry channels 32..63 -- by gch, not by cpos -- load nothing:
+  // their voffset gets the sign bit (>= num_records: the load returns zeros, also into LDS), for A and for the weights alike
+  const int hi_oob = (HALF && gch >= 4) ? (int)0x80000000 : 0;
 
   // ---- per-row gather metadata (computed once; the k-loop only adds wave-uniform offsets) -----------------
   // Row m of the implicit A matrix is output pixel (b, oy, ox).  Tap (ky, kx) of a 3x3 conv reads input pixel
@@ -102,7 +107,7 @@ __global__ void __launch_bounds__(WARPS_M* WARPS_N * 64) igemm_kernel(const IGem
         const int iy = oy + t / 3 - 1, ix = ox + t % 3 - 1;
         if (iy >= 0 && iy < Hv && ix >= 0 && ix < Wv) mk |= 1u << t;
       }
-      a_mask[i] = mk;
+      a_mask[i] = mk | ((HALF && gch < 4) ? mk << 9 : 0u);         // bits 9..17: the taps of a half k-tile (none for chunk lanes 4..7)
       a_off[i] = 0;
     } else {
       const int cy = oy * p.stride, cx = ox * p.stride;          // tap (pad, pad)
@@ -114,7 +119,7 @@ __global__ void __launch_bounds__(WARPS_M* WARPS_N * 64) igemm_kernel(const IGem
           const int iy = cy + t / 3 - pad, ix = cx + t % 3 - pad;
           if (iy >= 0 && iy < p.Hin && ix >= 0 && ix < p.Win) mk |= 1u << t;
         }
-        a_mask[i] = mk;
+        a_mask[i] = mk | ((HALF && gch < 4) ? mk << 9 : 0u);       // bits 9..17: the taps of a half k-tile (none for chunk lanes 4..7)
       }
     }
   }
@@ -131,10 +136,20 @@ __global__ void __launch_bounds__(WARPS_M* WARPS_N * 64) igemm_kernel(const IGem
   // load cursor (wave-uniform): next k-tile to issue, its tap and first channel.  It stops on the last k-tile of this
   // split: the NS - 1 surplus issues at the end of the pipeline reload that tile (in bounds, never consumed).
   int ld_kt = kt_begin;
-  // K order is chunk-major: k-tile kt = (64-channel chunk, tap), tap fastest (see pack_conv_kernel)
+  // K order is chunk-major: k-tile kt = (chunk, tap), tap fastest (see pack_conv_kernel); the chunks are numbered per source, 64 channels
+  // each but for the last one of a source of 32 (mod 64) channels.  ld_cin0 walks PADDED channel coordinates (64 per chunk, pp0 / pp01 =
+  // where the second / third source begins in them), ld_boff the dense weight columns (bytes): b_soff accumulates the real widths.
   int ld_tap = K3 ? kt_begin % ntap : 0;
   int ld_cin0 = (kt_begin / ntap) * BK;
   int ld_ky = K3 ? ld_tap / 3 : 0, ld_kx = K3 ? ld_tap - 3 * (ld_tap / 3) : 0;
+  const int pc0 = p.c0, pc1 = p.c1, pc2 = p.c2;
+  const int pp0 = (pc0 + BK - 1) & ~(BK - 1), pp01 = pp0 + ((pc1 + BK - 1) & ~(BK - 1));      // (= c0, c0 + c1 without HALF)
+  int ld_boff = 0;
+  if constexpr (HALF) {
+    const int dense0 = ld_cin0 - (ld_cin0 >= pp0 ? pp0 - pc0 : 0) - (ld_cin0 >= pp01 ? pp01 - pp0 - pc1 : 0);
+    const int left = ld_cin0 < pp0 ? pc0 - ld_cin0 : (ld_cin0 < pp01 ? pc1 - (ld_cin0 - pp0) : pc2 - (ld_cin0 - pp01));
+    ld_boff = (ntap * dense0 + ld_tap * min(left, BK)) * 2;
+  }
 
   // Operands are addressed through buffer descriptors (MUBUF): address = base + per-lane voffset + scalar soffset, so a
   // pass costs no 64-bit VALU address arithmetic, and an out-of-image tap is a lane whose voffset is beyond num_records:
@@ -147,23 +162,26 @@ __global__ void __launch_bounds__(WARPS_M* WARPS_N * 64) igemm_kernel(const IGem
   const char* const srcA0 = (const char*)p.a0 - a_shift; const char* const srcA1 = (const char*)p.a1 - a_shift;
   const char* const srcA2 = (const char*)p.a2 - a_shift;
   const __amdgpu_buffer_rsrc_t rsrc_w = __builtin_amdgcn_make_buffer_rsrc((void*)p.w, 0, OOB, 0x00020000);
-  const int pc0 = p.c0, pc01 = p.c0 + p.c1, pWin = p.Win;
+  const int pWin = p.Win;
 
   // the scalar part of one k-tile's addresses, captured when the tile is scheduled; the per-pass issues may come later
-  struct TileCursor { __amdgpu_buffer_rsrc_t rsrc_a; int a_soff, b_soff; unsigned tapbit; int ky, kx; unsigned lds; };
+  struct TileCursor { __amdgpu_buffer_rsrc_t rsrc_a; int a_soff, b_soff; unsigned tapbit; int ky, kx; unsigned lds; int half; };
   auto next_tile = [&](int stage) {
     TileCursor c;
-    const char* src; int coff;
-    if (ld_cin0 < pc0) { src = srcA0; coff = ld_cin0; }
-    else if (ld_cin0 < pc01) { src = srcA1; coff = ld_cin0 - pc0; }
-    else { src = srcA2; coff = ld_cin0 - pc01; }
+    const char* src; int coff, left;
+    if (ld_cin0 < pp0) { src = srcA0; coff = ld_cin0; left = pc0 - coff; }
+    else if (ld_cin0 < pp01) { src = srcA1; coff = ld_cin0 - pp0; left = pc1 - coff; }
+    else { src = srcA2; coff = ld_cin0 - pp01; left = pc2 - coff; }
+    const bool half = HALF && left < BK;   // the source's last 32 channels: a half k-tile (wave-uniform)
     c.rsrc_a = __builtin_amdgcn_make_buffer_rsrc((void*)src, 0, OOB, 0x00020000);
     c.a_soff = ((K3 && !UP) ? (ld_ky * pWin + ld_kx) * ld + coff : coff) * 2;
-    c.b_soff = ld_kt * (BK * 2);
-    c.tapbit = 1u << ld_tap; c.ky = ld_ky; c.kx = ld_kx;
+    c.b_soff = HALF ? ld_boff : ld_kt * (BK * 2);
+    c.tapbit = 1u << (half ? ld_tap + 9 : ld_tap); c.ky = ld_ky; c.kx = ld_kx;
+    c.half = half ? OOB : 0;
     c.lds = stage * STAGE_BYTES;
     if (ld_kt + 1 < kt_end) {      // advance (wave-uniform)
       ++ld_kt;
+      if constexpr (HALF) ld_boff += half ? BKH * 2 : BK * 2;
       if constexpr (K3) {
         ++ld_tap;
         if (++ld_kx == 3) { ld_kx = 0; ++ld_ky; }
@@ -179,14 +197,17 @@ __global__ void __launch_bounds__(WARPS_M* WARPS_N * 64) igemm_kernel(const IGem
     int v;
     if constexpr (UP) v = a_ro[i][c.ky] + a_co[i][c.kx];
     else v = a_off[i];
-    if constexpr (K3) v = (a_mask[i] & c.tapbit) ? v : OOB;
+    if constexpr (K3) v = (a_mask[i] & c.tapbit) ? v : OOB;      // (a half tile tests bits 9..17: clear in chunk lanes 4..7)
+    else if constexpr (HALF) v |= hi_oob & c.half;
     return v;
   };
+  // ... and of weight pass i: in a half k-tile chunk lanes 4..7 would read the next tile's columns (past the buffer behind the last row)
+  auto b_voff = [&](const TileCursor& c, int i) -> int { return HALF ? (b_off[i] | (hi_oob & c.half)) : b_off[i]; };
   auto issue_piece = [&](const TileCursor& c, int q) {     // LDS-DMA: wave-uniform LDS base + lane * 16
     const unsigned row0 = (q < A_PASSES ? q * RPP : BM + (q - A_PASSES) * RPP) + wave_u * 8;
     auto dst = (__attribute__((address_space(3))) void*)(smem + c.lds + row0 * 128);
     if (q < A_PASSES) __builtin_amdgcn_raw_ptr_buffer_load_lds(c.rsrc_a, dst, 16, a_voff(c, q), c.a_soff, 0, 0);
-    else __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_w, dst, 16, b_off[q - A_PASSES], c.b_soff, 0, SDMI_W_AUX);
+    else __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_w, dst, 16, b_voff(c, q - A_PASSES), c.b_soff, 0, SDMI_W_AUX);
   };
   auto issue_loads = [&](int stage) {
     const TileCursor c = next_tile(stage);
@@ -198,7 +219,7 @@ __global__ void __launch_bounds__(WARPS_M* WARPS_N * 64) igemm_kernel(const IGem
         typedef int i32x4 __attribute__((ext_vector_type(4)));
         i32x4 v;
         if (q < A_PASSES) v = __builtin_amdgcn_raw_buffer_load_b128(c.rsrc_a, a_voff(c, q), c.a_soff, 0);
-        else v = __builtin_amdgcn_raw_buffer_load_b128(rsrc_w, b_off[q - A_PASSES], c.b_soff, 0);
+        else v = __builtin_amdgcn_raw_buffer_load_b128(rsrc_w, b_voff(c, q - A_PASSES), c.b_soff, 0);
         if (q < A_PASSES) regA[q] = __builtin_bit_cast(f16x8, v);
         else regB[q - A_PASSES] = __builtin_bit_cast(f16x8, v);
       }
@@ -335,13 +356,15 @@ __global__ void __launch_bounds__(WARPS_M* WARPS_N * 64) igemm_kernel(const IGem
 #endif  // __HIP_DEVICE_COMPILE__
 }
 
-template <int BM, int BN, int WARPS_M, int WARPS_N, int NS>
+template <int BM, int BN, int WARPS_M, int WARPS_N, int NS, bool HALF = false>
 int launch_cfg(const IGemmParams& p, bool dma, int splitk, hipStream_t stream) {
+  SDMI_CHECK(HALF || (p.c0 % BK == 0 && p.c1 % BK == 0 && p.c2 % BK == 0), "internal: a half k-tile launch on the whole-chunk kernel");
   const int tiles_m = cdiv(p.M, BM), tiles_n = cdiv(p.N, BN);
-  const int nkt = p.K / BK;
+  const int nkt = igemm_nkt(p);
   const int kt_per_split = cdiv(nkt, splitk);
   const int nsplit = cdiv(nkt, kt_per_split);
   IGemmParams q = p;
+  q.nkt = nkt;
   q.splitk = nsplit;
   q.tile_n_fastest = tile_order_n_fastest(p);
   q.splitk_fused = 0;
@@ -355,7 +378,7 @@ int launch_cfg(const IGemmParams& p, bool dma, int splitk, hipStream_t stream) {
   dim3 grid(tiles_m * tiles_n * nsplit), block(WARPS_M * WARPS_N * 64);
   static const int by_shape = env_int("SDMI_PROF_SHAPES", 0);
   std::string pname = std::string("igemm_") + std::to_string(BM) + "x" + std::to_string(BN) + "w" +
-                      std::to_string(WARPS_M * WARPS_N) + "s" + std::to_string(NS);
+                      std::to_string(WARPS_M * WARPS_N) + "s" + std::to_string(NS) + (HALF ? "h" : "");
   if (by_shape && prof_enabled())
     pname += "_M" + std::to_string(p.M) + "_N" + std::to_string(p.N) + "_K" + std::to_string(p.K) + "_k" +
              std::to_string(p.ksize) + "_m" + std::to_string(p.mode) + "_s" + std::to_string(nsplit);
@@ -373,9 +396,9 @@ int launch_cfg(const IGemmParams& p, bool dma, int splitk, hipStream_t stream) {
   const int kind = p.ksize == 1 ? KIND_1X1 : (p.up ? KIND_3X3_UP : KIND_3X3);
 #define SDMI_LAUNCH_KIND(K_)                                                                                        \
   do {                                                                                                              \
-    if (dma) SDMI_LAUNCH((igemm_kernel<BM, BN, WARPS_M, WARPS_N, true, NS, K_>), grid, block, 0, stream, q,   \
+    if (dma) SDMI_LAUNCH((igemm_kernel<BM, BN, WARPS_M, WARPS_N, true, NS, K_, HALF>), grid, block, 0, stream, q,   \
                                 tiles_m, tiles_n, kt_per_split);                                                    \
-    else SDMI_LAUNCH((igemm_kernel<BM, BN, WARPS_M, WARPS_N, false, 2, K_>), grid, block, 0, stream, q,       \
+    else SDMI_LAUNCH((igemm_kernel<BM, BN, WARPS_M, WARPS_N, false, 2, K_, HALF>), grid, block, 0, stream, q,       \
                             tiles_m, tiles_n, kt_per_split);                                                        \
   } while (0)
   if (kind == KIND_1X1) SDMI_LAUNCH_KIND(KIND_1X1);

@@ -351,6 +351,29 @@ __global__ void pack_conv_split3_kernel(const float* w, f16* dst, int O, int I, 
   const f16 hi = (f16)v;
   dst[idx] = part < 2 ? hi : (f16)(v - (float)hi);
 }
+// The same K order for A sources that are multiples of 32 channels (igemm_kernel's half k-tile): the chunks are numbered PER SOURCE
+// (c0 | c1 | c2 input channels), 64 channels each but for the last chunk of a source of 32 (mod 64) channels, which is 32 wide -- K stays
+// dense (KH * KW * I columns).  split3: the three sources are the SAME I input channels, [w_hi | w_hi | w_lo] (pack_conv_split3_kernel).
+// With every source a multiple of 64 this writes what pack_conv_kernel / pack_conv_split3_kernel write.
+__global__ void pack_conv_src_kernel(const float* w, f16* dst, int O, int I, int KH, int KW, int c0, int c1, int c2, int split3) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int taps = KH * KW;
+  const int64_t K = (int64_t)(c0 + c1 + c2) * taps;
+  if (idx >= (int64_t)O * K) return;
+  const int o = (int)(idx / K);
+  const int k = (int)(idx - (int64_t)o * K);
+  const int src = k < taps * c0 ? 0 : (k < taps * (c0 + c1) ? 1 : 2);
+  const int cs = src == 0 ? c0 : (src == 1 ? c1 : c2), base = src == 0 ? 0 : (src == 1 ? c0 : c0 + c1);
+  const int ks = k - taps * base;
+  const int chunk = ks / (64 * taps);
+  const int rem = ks - chunk * 64 * taps;
+  const int wd = min(64, cs - chunk * 64);                // 64, or 32: the source's last chunk
+  const int tap = rem / wd, ci = chunk * 64 + rem % wd, ky = tap / KW, kx = tap % KW;
+  const int i = split3 ? ci : base + ci;
+  const float v = w[(((int64_t)o * I + i) * KH + ky) * KW + kx];
+  const f16 hi = (f16)v;
+  dst[idx] = (!split3 || src < 2) ? hi : (f16)(v - (float)hi);
+}
 __global__ void pack_conv_f32_kernel(const float* w, float* dst, int O, int I, int KH, int KW) {
   const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t total = (int64_t)O * I * KH * KW;
@@ -639,7 +662,16 @@ int launch_softmax_rows(const float* S, f16* P, int rows, int cols, int lds, int
   return 0;
 }
 
+int launch_pack_conv_weight_src(const float* w, f16* dst, int O, int I, int KH, int KW, int c0, int c1, int c2, hipStream_t s) {
+  SDMI_CHECK(c0 > 0 && c1 >= 0 && c2 >= 0 && c0 + c1 + c2 == I && (c2 == 0 || c1 > 0), "conv pack: the source split must add up to the input channels");
+  SDMI_CHECK(c0 % 32 == 0 && c1 % 32 == 0 && c2 % 32 == 0, "conv pack: every A source must be a multiple of 32 channels");
+  const int64_t total = (int64_t)O * I * KH * KW;
+  SDMI_LAUNCH(pack_conv_src_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, w, dst, O, I, KH, KW, c0, c1, c2, 0);
+  SDMI_HIP_OK(hipGetLastError());
+  return 0;
+}
 int launch_pack_conv_weight(const float* w, f16* dst, int O, int I, int KH, int KW, hipStream_t s) {
+  if (KH * KW > 1 && I % 64 != 0) return launch_pack_conv_weight_src(w, dst, O, I, KH, KW, I, 0, 0, s);   // one source that ends in a half chunk
   const int64_t total = (int64_t)O * I * KH * KW;
   SDMI_LAUNCH(pack_conv_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, w, dst, O, I, KH, KW);
   SDMI_HIP_OK(hipGetLastError());
@@ -662,8 +694,13 @@ int launch_prefetch_lines(const void* ptr, int64_t bytes, hipStream_t s) {
 }
 
 int launch_pack_conv_split3(const float* w, f16* dst, int O, int I, int KH, int KW, hipStream_t s) {
-  SDMI_CHECK(I % 64 == 0, "split-fp16 conv pack: input channels % 64");
+  SDMI_CHECK(I % 32 == 0, "split-fp16 conv pack: input channels % 64 must be 0, or 32 (a half k-tile)");
   const int64_t total = (int64_t)O * 3 * I * KH * KW;
+  if (I % 64 != 0) {               // three sources of I channels, each ending in a half chunk
+    SDMI_LAUNCH(pack_conv_src_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, w, dst, O, I, KH, KW, I, I, I, 1);
+    SDMI_HIP_OK(hipGetLastError());
+    return 0;
+  }
   SDMI_LAUNCH(pack_conv_split3_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, w, dst, O, I, KH, KW);
   SDMI_HIP_OK(hipGetLastError());
   return 0;

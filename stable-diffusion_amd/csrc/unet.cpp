@@ -63,8 +63,10 @@ int UNet::build(const sdmi_unet_cfg& c, int precision, const sdmi_unet_ext* ext,
   cfg_ = c;
   precision_ = precision;
   if (ext) ext_ = *ext;
-  SDMI_CHECK((flags & ~(unsigned)SDMI_UNET_SCALE_SHIFT_NORM) == 0, "unknown UNet creation flag");
+  SDMI_CHECK((flags & ~((unsigned)SDMI_UNET_SCALE_SHIFT_NORM | (unsigned)SDMI_UNET_NUM_HEAD_CHANNELS_MASK)) == 0, "unknown UNet creation flag");
   scale_shift_ = (flags & SDMI_UNET_SCALE_SHIFT_NORM) != 0;
+  // num_head_channels (openaimodel.py:532-535,561-563: heads = ch // num_head_channels per AttentionBlock) rides in the flag word
+  num_head_channels_ = (int)((flags & SDMI_UNET_NUM_HEAD_CHANNELS_MASK) >> SDMI_UNET_NUM_HEAD_CHANNELS_SHIFT);
   // (the family this executor path is validated for: the unconditional LDMs -- AttentionBlocks and resampling ResBlocks)
   SDMI_CHECK(!scale_shift_ || (ext_.attention_block == 1 && ext_.resblock_updown == 1),
              "SDMI_UNET_SCALE_SHIFT_NORM needs attention_block = 1 and resblock_updown = 1");
@@ -72,10 +74,15 @@ int UNet::build(const sdmi_unet_cfg& c, int precision, const sdmi_unet_ext* ext,
   SDMI_CHECK(ext_.resblock_updown == 0 || ext_.resblock_updown == 1, "resblock_updown must be 0 or 1");
   SDMI_CHECK(c.n_levels >= 1 && c.n_levels <= 8 && c.n_attention_resolutions >= 0 && c.n_attention_resolutions <= 8,
              "bad level / attention_resolutions count");
-  SDMI_CHECK(c.model_channels % 64 == 0, "model_channels must be a multiple of 64 on this path");
+  SDMI_CHECK(num_head_channels_ == 0 || ext_.attention_block == 1,
+             "num_head_channels is expressed for the AttentionBlock family only (attention_block = 1); a SpatialTransformer takes num_heads");
+  // AttentionBlock UNets: every GEMM source is a multiple of 32 channels (a source of 32 (mod 64) ends in a half k-tile, igemm_kernel.h);
+  // the SpatialTransformer's row-strip chains and LayerNorm fold keep whole 64-channel chunks
+  if (ext_.attention_block == 1) SDMI_CHECK(c.model_channels > 0 && c.model_channels % 32 == 0, "model_channels must be a multiple of 32 on this path");
+  else SDMI_CHECK(c.model_channels % 64 == 0, "model_channels must be a multiple of 64 on this path (SpatialTransformer family)");
   if (has_ctx()) SDMI_CHECK(c.context_dim % 64 == 0, "context_dim must be a multiple of 64 on this path");
   else SDMI_CHECK(c.context_dim == 0, "a UNet of AttentionBlocks has no cross-attention: context_dim must be 0");
-  SDMI_CHECK(c.num_heads >= 1 && c.transformer_depth >= 1, "num_heads / transformer_depth");
+  SDMI_CHECK((c.num_heads >= 1 || num_head_channels_ > 0) && c.transformer_depth >= 1, "num_heads / transformer_depth");
   const int mc = c.model_channels;
   te_ = 4 * mc;
   if (const char* e = getenv("SDMI_FUSE_GN_STATS")) fuse_gn_stats_ = atoi(e) != 0;
@@ -87,11 +94,13 @@ int UNet::build(const sdmi_unet_cfg& c, int precision, const sdmi_unet_ext* ext,
     Layer L; L.kind = L_RES; L.prefix = p; L.cin = cin; L.cout = cout;
     L.emb_off = emb_total_; emb_total_ += scale_shift_ ? 2 * cout : cout;      // (scale-shift: [scale | shift], th.chunk(emb_out, 2, dim=1))
     L.p1x1 = full() || (precise_1x1_ && cur_ds < precise_1x1_max_ds_);
-    L.precise3 = full();        // (build() requires model_channels % 64 == 0: every ResBlock's channel counts are multiples of 64)
+    L.precise3 = full();        // (every ResBlock's channel counts are multiples of 32: the split-fp16 3x3 conv takes them)
     return L;
   };
   auto add_attn = [&](const std::string& p, int ch) {
-    Layer L; L.kind = has_ctx() ? L_ATTN : L_ATTN_LEGACY; L.prefix = p; L.cin = ch; L.cout = ch; L.heads = c.num_heads; L.dh = ch / c.num_heads;
+    Layer L; L.kind = has_ctx() ? L_ATTN : L_ATTN_LEGACY; L.prefix = p; L.cin = ch; L.cout = ch;
+    if (num_head_channels_ > 0) { L.heads = ch / num_head_channels_; L.dh = num_head_channels_; }
+    else { L.heads = c.num_heads; L.dh = ch / c.num_heads; }
     L.attn_index = n_attn_++;
     L.p1x1 = full() || (precise_1x1_ && cur_ds < precise_1x1_max_ds_);
     return L;
@@ -164,7 +173,10 @@ int UNet::build(const sdmi_unet_cfg& c, int precision, const sdmi_unet_ext* ext,
         return 0;
       }
       if (L.kind != L_ATTN_LEGACY) return 0;
-      SDMI_CHECK(L.cin % c.num_heads == 0, L.prefix + ": channels not divisible by num_heads");
+      if (num_head_channels_ > 0)
+        SDMI_CHECK(L.cin % num_head_channels_ == 0, L.prefix + ": " + std::to_string(L.cin) + " channels not divisible by num_head_channels " +
+                   std::to_string(num_head_channels_));
+      else SDMI_CHECK(L.cin % c.num_heads == 0, L.prefix + ": channels not divisible by num_heads");
       SDMI_CHECK(L.dh == 24 || L.dh == 32 || L.dh == 40 || L.dh == 48 || L.dh == 64 || L.dh == 80 || L.dh == 96 || L.dh == 128 || L.dh == 160,
                  L.prefix + ": attention head dim " + std::to_string(L.dh) + " not instantiated (24/32/40/48/64/80/96/128/160)");
       return 0;
@@ -175,8 +187,7 @@ int UNet::build(const sdmi_unet_cfg& c, int precision, const sdmi_unet_ext* ext,
   }
 
   // the last ResBlock (output_blocks.<last>.0: its two 3x3 convs are the largest single contributors to the eps error)
-  if (precise_last_res_ && !output_blocks_.empty() && output_blocks_.back()[0].kind == L_RES && output_blocks_.back()[0].cin % 64 == 0 &&
-      output_blocks_.back()[0].cout % 64 == 0)
+  if (precise_last_res_ && !output_blocks_.empty() && output_blocks_.back()[0].kind == L_RES)
     output_blocks_.back()[0].precise3 = true;
 
   // ---- expected state_dict entries and where each one is packed to -------------------
@@ -507,6 +518,8 @@ struct PackedHeader {
   int64_t total_bytes;
 };
 constexpr int64_t PK_ALIGN = 256;
+constexpr int PK_NHC_SHIFT = 16;     // PackedHeader::reserved bits 16..27: num_head_channels of the handle that wrote the blob (the qkv rows are permuted per head)
+constexpr int32_t PK_NHC_MASK = 0xfff << PK_NHC_SHIFT;
 constexpr int32_t PK_FULL = 4;      // PackedHeader::reserved: written by a full-precision handle (its packed weights are split-fp16)
 }  // namespace
 
@@ -535,6 +548,7 @@ int UNet::export_packed(void* host_buf, int64_t bytes, hipStream_t stream) {
   h.abi = SDMI_ABI_VERSION; h.precise_1x1 = precise_1x1_ ? 1 : 0; h.n_buffers = (int32_t)bufs.size(); h.cfg = cfg_;
   h.reserved = (precise_kv_ ? 1 : 0) | (precise_last_res_ ? 2 : 0) | (precise_1x1_max_ds_ << 8);      // (ABI 17: the precision allocation)
   h.reserved |= (ext_.attention_block << 4) | (ext_.resblock_updown << 5) | ((scale_shift_ ? 1 : 0) << 6);   // (sdmi_unet_ext, creation flags: 0 for SD v1)
+  h.reserved |= num_head_channels_ << PK_NHC_SHIFT;       // (0 = heads by num_heads)
   if (full()) h.reserved |= PK_FULL;
   h.total_bytes = total;
   memcpy(host_buf, &h, sizeof(h));
@@ -560,7 +574,10 @@ int UNet::import_packed(const void* host_buf, int64_t bytes, hipStream_t stream)
   SDMI_CHECK((h.precise_1x1 != 0) == precise_1x1_, "packed blob was written with a different precision allocation (split-fp16 1x1 convs)");
   SDMI_CHECK((h.reserved & (7 << 4)) == ((ext_.attention_block << 4) | (ext_.resblock_updown << 5) | ((scale_shift_ ? 1 : 0) << 6)),
              "packed blob was written for a different UNet family (attention_block / resblock_updown / scale-shift norm)");
-  SDMI_CHECK((h.reserved & ~PK_FULL & ~(7 << 4)) == ((precise_kv_ ? 1 : 0) | (precise_last_res_ ? 2 : 0) | (precise_1x1_max_ds_ << 8)),
+  SDMI_CHECK(((h.reserved & PK_NHC_MASK) >> PK_NHC_SHIFT) == num_head_channels_,
+             "packed blob was written for num_head_channels " + std::to_string((h.reserved & PK_NHC_MASK) >> PK_NHC_SHIFT) + ", this handle has " +
+             std::to_string(num_head_channels_) + ": repack it");
+  SDMI_CHECK((h.reserved & ~PK_FULL & ~(7 << 4) & ~PK_NHC_MASK) == ((precise_kv_ ? 1 : 0) | (precise_last_res_ ? 2 : 0) | (precise_1x1_max_ds_ << 8)),
              "packed blob was written with a different precision allocation (context K / V, last ResBlock, 1x1 conv levels)");
   std::vector<std::pair<void**, size_t>> bufs;
   int64_t total = 0;
@@ -1083,6 +1100,7 @@ struct Fwd : FwdBase {
       IGemmParams p = dense1x1(ao, ao_lo, M, C, L.w16[1], C, N, fm);
       p.bias = L.f32[3]; p.residual = x.p; p.ldr = C; p.out_f32 = out.p; p.ldo = C;
       attach_gn_targets(p, out);
+      attach_f16_copy(p, out);             // ... and the fp16 copy a Downsample / Upsample convolution behind this block wants (resblock_updown = 0)
       gemm(p);
     }
     scratch.off = mark;

@@ -158,7 +158,7 @@ struct FwdBase {
     IGemmParams p = dense(hi, M, K, w, N, rows_per_batch);
     if (precise) {
       static const bool family = !(getenv("SDMI_SPLIT16_KERNEL") && atoi(getenv("SDMI_SPLIT16_KERNEL")) == 0);
-      if (family && K % 64 == 0) {
+      if (family && K % 32 == 0) {
         p.a1 = lo; p.lda1 = K; p.split16 = 1; p.ldw = 3 * K;
       } else {
         p.a1 = lo; p.c1 = K; p.lda1 = K; p.a2 = hi; p.c2 = K; p.lda2 = K; p.K = 3 * K; p.k_alg = K;
@@ -294,6 +294,9 @@ class UNet {
   // SDMI_UNET_SCALE_SHIFT_NORM (sdmi_unet_create_flags): every ResBlock is a use_scale_shift_norm one (openaimodel.py:267-271) -- its
   // emb_layers output is 2 cout wide [scale | shift] and modulates out_layers' GroupNorm instead of being added behind conv1
   bool scale_shift_ = false;
+  // SDMI_UNET_NUM_HEAD_CHANNELS(n) (sdmi_unet_create_flags): every AttentionBlock has ch / n heads of n channels (openaimodel.py:561-563);
+  // 0 = cfg.num_heads heads of ch / num_heads channels
+  int num_head_channels_ = 0;
   // SDMI_PRECISION_FULL: every MFMA operand split-fp16 (every Layer::p1x1 / precise3, split-fp16 linears, resamplers and attention;
   // the row-strip chains and the LayerNorm / GroupNorm folds off).  Fixed by build(); the packed weights depend on it.
   int precision_ = SDMI_PRECISION_MIXED;

@@ -197,3 +197,27 @@ def synthetic_churches_unet_state_dict(seed=0, unet_kwargs=None):
     from .unet import UNetModelHIP
     m = UNetModelHIP(**(unet_kwargs or CHURCHES_UNET_KWARGS))
     return synthetic_named_state_dict([(k, tuple(v.shape)) for k, v in m.state_dict().items()], seed)
+
+
+# ---- the face / bedroom models (models/ldm/celeba256, ffhq256, lsun_beds256: one unet_config) and bsr_sr's UNet -----------------
+FACES_UNET_KWARGS = dict(image_size=64, in_channels=3, out_channels=3, model_channels=224, attention_resolutions=[8, 4, 2],
+                         num_res_blocks=2, channel_mult=[1, 2, 3, 4], num_head_channels=32)                # celeba256 yaml:17-33
+FACES_VQ_KWARGS = dict(embed_dim=3, n_embed=8192, ddconfig=CIN_VQ_DDCONFIG)                               # yaml:34-52: VQ-f4, mid-block attention on
+FACES_SCHEDULE = dict(timesteps=1000, linear_start=0.0015, linear_end=0.0195, conditioning_key=None)      # yaml:5-6,9; __is_unconditional__
+BSR_UNET_KWARGS = dict(image_size=64, in_channels=6, out_channels=3, model_channels=160, attention_resolutions=[16, 8],
+                       num_res_blocks=2, channel_mult=[1, 2, 2, 4], num_head_channels=32)                  # bsr_sr yaml:16-31
+BSR_SCHEDULE = dict(timesteps=1000, linear_start=0.0015, linear_end=0.0155, conditioning_key='concat')    # yaml:5-6,8,14 (concat_mode)
+
+
+def synthetic_faces_unet_state_dict(seed=0, unet_kwargs=None):
+    """CPU state_dict (reference UNetModel key names) of a seeded random face / bedroom UNet (or, with BSR_UNET_KWARGS, bsr_sr's)."""
+    from .unet import UNetModelHIP
+    m = UNetModelHIP(**(unet_kwargs or FACES_UNET_KWARGS))
+    return synthetic_named_state_dict([(k, tuple(v.shape)) for k, v in m.state_dict().items()], seed)
+
+
+def synthetic_faces_vq_state_dict(seed=0, vq_kwargs=None):
+    """CPU state_dict (reference VQModelInterface key names, without loss.*) of a seeded random VQ-f4 first stage of the face models."""
+    from .vae import VQModelInterfaceHIP
+    m = VQModelInterfaceHIP(**(vq_kwargs or FACES_VQ_KWARGS))
+    return synthetic_named_state_dict([(k, tuple(v.shape)) for k, v in m.state_dict().items()], seed)

@@ -48,6 +48,13 @@ PRECISIONS = {'mixed': 0, 'full': 1}      # SDMI_PRECISION_MIXED / SDMI_PRECISIO
 UNET_SCALE_SHIFT_NORM = 1                 # SDMI_UNET_SCALE_SHIFT_NORM (sdmi_unet_create_flags)
 
 
+def unet_num_head_channels_flag(n):
+    """SDMI_UNET_NUM_HEAD_CHANNELS(n) (include/sdmi.h): num_head_channels rides in bits 16..27 of the creation flag word"""
+    if not 0 < int(n) < 4096:
+        raise ValueError(f'num_head_channels must be 1..4095, got {n}')
+    return int(n) << 16
+
+
 class _Handle:
     """Owns one sdmi_unet*."""
 
@@ -110,6 +117,10 @@ class UNetModelHIP(nn.Module):
         #   unconditional LSUN-Churches (models/ldm/lsun_churches256/config.yaml:33-52): the inpainting family's blocks with
         #   use_scale_shift_norm (openaimodel.py:267-271), nothing concatenated (in_channels == out_channels), five levels, attention
         #   at every resolution down to the full latent one (head dims 24 / 48 / 96)
+        #   faces / bedrooms / super-resolution (models/ldm/celeba256, ffhq256, lsun_beds256: one unet_config, model_channels 224;
+        #   models/ldm/bsr_sr: 160): legacy AttentionBlocks with num_head_channels=32 and num_heads left at -1 (openaimodel.py:561-563:
+        #   heads = ch // 32 -> 14 / 21 / 28, 20), plain Downsample / Upsample convolutions, no scale-shift norm; widths that are
+        #   multiples of 32, not of 64 (the GEMM kernels' half k-tile).  num_head_channels with a spatial transformer stays refused.
         self.use_spatial_transformer = bool(use_spatial_transformer)
         unsupported = []
         if use_spatial_transformer:
@@ -121,7 +132,20 @@ class UNetModelHIP(nn.Module):
             if context_dim is not None: unsupported.append('context_dim=None without a spatial transformer')
             if not legacy: unsupported.append('legacy=True without a spatial transformer')
             if use_new_attention_order: unsupported.append('use_new_attention_order=False (QKVAttentionLegacy)')
-        if num_heads == -1 or num_head_channels != -1: unsupported.append('num_heads (not num_head_channels)')
+        nhc = num_head_channels != -1
+        if use_spatial_transformer:
+            if num_heads == -1 or nhc: unsupported.append('num_heads (not num_head_channels) with a spatial transformer')
+        elif nhc:
+            # the reference asserts exactly one of the two is set (openaimodel.py:489-493) and lets num_head_channels win where both are
+            if num_heads != -1: unsupported.append('num_head_channels with num_heads == -1 (one of the two, as the shipped configs)')
+            chans = [model_channels * m for i, m in enumerate(channel_mult) if 2 ** i in list(attention_resolutions)]
+            chans.append(model_channels * list(channel_mult)[-1])       # (the middle block)
+            if num_head_channels < 1 or any(c % num_head_channels for c in chans):
+                unsupported.append(f'num_head_channels={num_head_channels} dividing every attention level ({sorted(set(chans))})')
+        elif num_heads == -1:
+            unsupported.append('num_heads or num_head_channels')
+        if model_channels % 32 or (use_spatial_transformer and model_channels % 64):
+            unsupported.append('model_channels a multiple of 64 (of 32 without a spatial transformer), got %d' % model_channels)
         if num_heads_upsample not in (-1, num_heads): unsupported.append('num_heads_upsample == num_heads')
         if dims != 2 or not conv_resample: unsupported.append('dims=2, conv_resample')
         if use_scale_shift_norm:
@@ -138,7 +162,8 @@ class UNetModelHIP(nn.Module):
         if num_classes is not None or n_embed is not None: unsupported.append('no class conditioning / codebook head')
         if dropout != 0: unsupported.append('dropout=0')
         if unsupported:
-            raise NotImplementedError('UNetModelHIP supports the SD-v1, latent-inpainting and unconditional UNet families only; needs: ' +
+            raise NotImplementedError('UNetModelHIP supports the SD-v1, latent-inpainting, unconditional and num_head_channels AttentionBlock '
+                                      'UNet families only; needs: ' +
                                       '; '.join(unsupported))
         if use_spatial_transformer and hip_precision == 'full':
             # heads wider than 160 run on the wide-head kernel (csrc/attn_wide.hip), which has no split-fp16 form
@@ -166,7 +191,9 @@ class UNetModelHIP(nn.Module):
         if not use_spatial_transformer or resblock_updown:
             ext = _lib.UNetExt()
             ext.attention_block, ext.resblock_updown = int(not use_spatial_transformer), int(bool(resblock_updown))
-        self._handle = _Handle(self._cfg, hip_precision, ext, UNET_SCALE_SHIFT_NORM if use_scale_shift_norm else 0)
+        self.num_head_channels = num_head_channels
+        flags = (UNET_SCALE_SHIFT_NORM if use_scale_shift_norm else 0) | (unet_num_head_channels_flag(num_head_channels) if nhc else 0)
+        self._handle = _Handle(self._cfg, hip_precision, ext, flags)
         self._specs = self._handle.weight_specs()
         for key, shape in self._specs:
             *path, leaf = key.split('.')

@@ -10,7 +10,8 @@ stand-alone sweep of one shape does not reproduce.  The resulting table is commi
 split-K summation order, i.e. the exact output bits) is fixed.
 
 --append-new: the table at --out keeps every row it has; only shapes whose key is not in it yet are appended (a model added
-later brings its own shapes and changes no other model's tiles): `--workloads churches32b8,churches32b2 --append-new`.
+later brings its own shapes and changes no other model's tiles): `--workloads churches32b8,churches32b2 --append-new`,
+`--workloads faces64b8,faces64b2,bsr64b8,bsr64b2 --append-new`.
 """
 import argparse
 import ctypes as C
@@ -81,7 +82,21 @@ def main():
         t = torch.full((B,), 481, device=dev)
         return lambda: churches(x, t)
 
+    lowwidth = {}
+
+    def faces_fn(which, B):          # the face / bedroom UNet (224 wide) and bsr_sr's (160) at their native 64 x 64 latent: half k-tiles
+        from stable_diffusion_amd.synthetic import BSR_UNET_KWARGS, FACES_UNET_KWARGS
+        kw = FACES_UNET_KWARGS if which == 'faces' else BSR_UNET_KWARGS
+        if which not in lowwidth:
+            lowwidth[which] = randomize_(UNetModelHIP(**kw).to(dev).eval(), 0)
+        m = lowwidth[which]
+        x = torch.randn(B, kw['in_channels'], 64, 64, generator=g).to(dev)
+        t = torch.full((B,), 481, device=dev)
+        return lambda: m(x, t)
+
     makers = {
+        'faces64b8': lambda: faces_fn('faces', 8), 'faces64b2': lambda: faces_fn('faces', 2),
+        'bsr64b8': lambda: faces_fn('bsr', 8), 'bsr64b2': lambda: faces_fn('bsr', 2),
         'churches32b8': lambda: churches_fn(8), 'churches32b2': lambda: churches_fn(2),
         'unet64': lambda: unet_fn(2, 64), 'unet96': lambda: unet_fn(2, 96), 'unet32': lambda: unet_fn(2, 32),
         'unet64b4': lambda: unet_fn(4, 64), 'unet64b6': lambda: unet_fn(6, 64), 'unet64b8': lambda: unet_fn(8, 64),
