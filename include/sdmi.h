@@ -464,6 +464,22 @@ int sdmi_k_vq_quantize(const float* z, float z_scale, const float* codebook, flo
 /* 2x2 average pool (dir 1) / nearest x2 (dir -1) of fp32 NHWC [B, H, W, C] (C % 4 == 0): out_f32 and / or out_f16 (+ out_lo =
  * fp16(v - out_f16)), the resampling of the inpainting UNet's ResBlocks (openaimodel.py:253-259) */
 int sdmi_k_resample2(const float* x, float* out_f32, void* out_f16, void* out_lo, int B, int H, int W, int C, int dir, void* stream);
+/* The sliding windows of LatentDiffusion.split_input_params (ddpm.py:601-651, 902-984; additive, ABI 17).
+ * sdmi_k_patch_unfold: windows l in [l0, l0 + nl) of x fp32 NCHW [B, Cx, H, W] -- and of c [B, Cc, H, W] behind them on the channel axis (the
+ * torch.cat([x] + c_concat, 1) of DiffusionWrapper.forward; c NULL with Cc = 0) -- as rows (l - l0) * B + b of out [nl * B, Cx + Cc, kh, kw].
+ * Window l starts at ((l / Lx) sy, (l % Lx) sx), Ly = (H - kh) / sy + 1, Lx = (W - kw) / sx + 1.  A copy: bit-exact.
+ * sdmi_k_patch_fold: out [B, C, H uf / df, W uf / df] = sum_l w[l] o[l * B + b] / sum_l w[l] over the windows that cover an element, in
+ * ascending l, fp32, no atomics (two runs give the same bits).  o [Ly Lx B, C, kh', kw'], w [Ly Lx, kh', kw'] with kh' = kh uf / df (window,
+ * stride and output scaled alike: uf = vqf for decode_first_stage, df = vqf for encode_first_stage, both 1 for apply_model).  norm_only: o is
+ * not read and out [H uf / df, W uf / df] = sum_l w[l] (the reference's `normalization`).
+ * 16-byte accesses when W, kw, sx (scaled) are multiples of 4 and the pointers are 16-byte aligned, element-wise otherwise.
+ * Refused (-1, nothing launched): kh > H or kw > W; (H - kh) % sy or (W - kw) % sx != 0 (the reference leaves uncovered pixels: 0 / 0);
+ * uf > 1 and df > 1; a non-square window with uf != 1 or df != 1 (get_fold_unfold scales kernel_size[0] on both axes); df not dividing
+ * H, W, kh, kw, sy, sx; a window range outside [0, Ly Lx). */
+int sdmi_k_patch_unfold(const float* x, const float* c, float* out, int B, int Cx, int Cc, int H, int W, int kh, int kw, int sy, int sx,
+                        int l0, int nl, void* stream);
+int sdmi_k_patch_fold(const float* o, const float* w, float* out, int B, int C, int H, int W, int kh, int kw, int sy, int sx, int uf, int df,
+                      int norm_only, void* stream);
 int sdmi_k_gelu_erf(const float* x, void* out_f16, int64_t n, void* stream);
 int sdmi_k_pack_geglu(const float* w, const float* bias, void* wdst_f16, float* bdst, int N, int K, void* stream);
 /* Host post-processing of scripts/txt2img.py:313-324, on the device: img fp32 [B, C, H, W] (the

@@ -96,6 +96,8 @@ _SIGS = {
     'sdmi_vae_create_ext': (C.c_int, [C.POINTER(VaeCfg), C.POINTER(VaeExt), C.c_int, C.POINTER(c_ptr)]),
     'sdmi_vae_decode_vq': (C.c_int, [c_ptr, c_ptr, C.c_float, C.c_int, c_ptr, C.c_int, C.c_int, C.c_int, c_ptr, C.c_int64, c_ptr]),
     'sdmi_k_vq_quantize': (C.c_int, [c_ptr, C.c_float, c_ptr, c_ptr, C.c_int, C.c_int, c_ptr, c_ptr, C.c_int, C.c_int, c_ptr]),
+    'sdmi_k_patch_unfold': (C.c_int, [c_ptr, c_ptr, c_ptr] + [C.c_int] * 11 + [c_ptr]),
+    'sdmi_k_patch_fold': (C.c_int, [c_ptr, c_ptr, c_ptr] + [C.c_int] * 11 + [c_ptr]),
     'sdmi_k_resample2': (C.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_ptr]),
     'sdmi_vae_num_weights': (C.c_int, [c_ptr]),
     'sdmi_vae_weight_info': (C.c_int, [c_ptr, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int)]),

@@ -314,6 +314,14 @@ int sdmi_k_vq_quantize(const float* z, float z_scale, const float* codebook, flo
 int sdmi_k_resample2(const float* x, float* out_f32, void* out_f16, void* out_lo, int B, int H, int W, int C, int dir, void* stream) {
   return launch_resample2(x, out_f32, (f16*)out_f16, (f16*)out_lo, B, H, W, C, dir, (hipStream_t)stream);
 }
+int sdmi_k_patch_unfold(const float* x, const float* c, float* out, int B, int Cx, int Cc, int H, int W, int kh, int kw, int sy, int sx,
+                        int l0, int nl, void* stream) {
+  return launch_patch_unfold(x, c, out, B, Cx, Cc, H, W, kh, kw, sy, sx, l0, nl, (hipStream_t)stream);
+}
+int sdmi_k_patch_fold(const float* o, const float* w, float* out, int B, int C, int H, int W, int kh, int kw, int sy, int sx, int uf, int df,
+                      int norm_only, void* stream) {
+  return launch_patch_fold(o, w, out, B, C, H, W, kh, kw, sy, sx, uf, df, norm_only, (hipStream_t)stream);
+}
 int sdmi_k_gelu_erf(const float* x, void* out_f16, int64_t n, void* stream) {
   return launch_gelu_erf(x, (f16*)out_f16, n, (hipStream_t)stream);
 }

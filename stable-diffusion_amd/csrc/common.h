@@ -457,6 +457,15 @@ int launch_vq_norms(const float* e, float* se, int n_embed, int D, hipStream_t s
 int launch_vq_quantize(const float* z, float z_scale, const float* e, const float* se, int n_embed, int D, float* zq, int* idx, int B,
                        int HW, hipStream_t s);
 
+// sliding windows of LatentDiffusion.split_input_params (patch.hip)
+// rows (l, b), l in [l0, l0 + nl), of [nl * B][Cx + Cc][kh][kw] <- windows of x [B][Cx][H][W] and c [B][Cc][H][W] (c may be null with Cc = 0)
+int launch_patch_unfold(const float* x, const float* c, float* out, int B, int Cx, int Cc, int H, int W, int kh, int kw, int sy, int sx,
+                        int l0, int nl, hipStream_t s);
+// out [B][C][H uf / df][W uf / df] = sum_l w[l] o[(l, b)] / sum_l w[l] over the covering windows (window and stride scaled by uf / df);
+// norm_only: out [H uf / df][W uf / df] = sum_l w[l]
+int launch_patch_fold(const float* o, const float* w, float* out, int B, int C, int H, int W, int kh, int kw, int sy, int sx, int uf, int df,
+                      int norm_only, hipStream_t s);
+
 // cache hint (small.hip): touch every 128-byte line of a device range
 int launch_prefetch_lines(const void* ptr, int64_t bytes, hipStream_t s);
 

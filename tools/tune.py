@@ -11,7 +11,8 @@ split-K summation order, i.e. the exact output bits) is fixed.
 
 --append-new: the table at --out keeps every row it has; only shapes whose key is not in it yet are appended (a model added
 later brings its own shapes and changes no other model's tiles): `--workloads churches32b8,churches32b2 --append-new`,
-`--workloads faces64b8,faces64b2,bsr64b8,bsr64b2 --append-new`.
+`--workloads faces64b8,faces64b2,bsr64b8,bsr64b2 --append-new`, `--workloads bsr128b8,bsr128b1 --append-new` (bsr_sr's 128 x 128
+windows, nine of them as 8 + 1 rows; profiles/tune_candidates_bsr128.txt).
 """
 import argparse
 import ctypes as C
@@ -84,19 +85,20 @@ def main():
 
     lowwidth = {}
 
-    def faces_fn(which, B):          # the face / bedroom UNet (224 wide) and bsr_sr's (160) at their native 64 x 64 latent: half k-tiles
+    def faces_fn(which, B, H=64):    # the face / bedroom UNet (224 wide) and bsr_sr's (160) at their native 64 x 64 latent: half k-tiles
         from stable_diffusion_amd.synthetic import BSR_UNET_KWARGS, FACES_UNET_KWARGS
         kw = FACES_UNET_KWARGS if which == 'faces' else BSR_UNET_KWARGS
         if which not in lowwidth:
             lowwidth[which] = randomize_(UNetModelHIP(**kw).to(dev).eval(), 0)
         m = lowwidth[which]
-        x = torch.randn(B, kw['in_channels'], 64, 64, generator=g).to(dev)
+        x = torch.randn(B, kw['in_channels'], H, H, generator=g).to(dev)
         t = torch.full((B,), 481, device=dev)
         return lambda: m(x, t)
 
     makers = {
         'faces64b8': lambda: faces_fn('faces', 8), 'faces64b2': lambda: faces_fn('faces', 2),
         'bsr64b8': lambda: faces_fn('bsr', 8), 'bsr64b2': lambda: faces_fn('bsr', 2),
+        'bsr128b8': lambda: faces_fn('bsr', 8, 128), 'bsr128b1': lambda: faces_fn('bsr', 1, 128),
         'churches32b8': lambda: churches_fn(8), 'churches32b2': lambda: churches_fn(2),
         'unet64': lambda: unet_fn(2, 64), 'unet96': lambda: unet_fn(2, 96), 'unet32': lambda: unet_fn(2, 32),
         'unet64b4': lambda: unet_fn(4, 64), 'unet64b6': lambda: unet_fn(6, 64), 'unet64b8': lambda: unet_fn(8, 64),
