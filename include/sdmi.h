@@ -205,6 +205,15 @@ typedef struct sdmi_vae_ext {
   int32_t n_embed;
 } sdmi_vae_ext;
 int sdmi_vae_create_ext(const sdmi_vae_cfg* cfg, const sdmi_vae_ext* ext, int parts, sdmi_vae** out);
+/* The first stage's precision, fixed for the handle's lifetime (additive; sdmi_vae_cfg and sdmi_vae_ext are unchanged):
+ *   SDMI_PRECISION_MIXED  what sdmi_vae_create / sdmi_vae_create_ext create: fp16 MFMA operands, fp32 accumulation and stream
+ *   SDMI_PRECISION_FULL   every MFMA operand of the ResBlocks, the Upsample / Downsample convs and the mid-block attention is a
+ *                         split-fp16 pair (three MFMA passes); the attention is one split-fp16 flash launch at d = the mid width
+ *                         (sdmi_k_attention_split16's head dims).  A mid width with mid_attn = 1 that no split-fp16 attention
+ *                         kernel instantiates is refused here, by name.  Same weight keys and shapes, a larger workspace.
+ * ext = NULL is {1, 1, 0}.  sdmi_vae_create_ext(cfg, ext, parts, out) = sdmi_vae_create_precision(cfg, ext, parts, SDMI_PRECISION_MIXED, out). */
+int sdmi_vae_create_precision(const sdmi_vae_cfg* cfg, const sdmi_vae_ext* ext, int parts, int precision, sdmi_vae** out);
+int sdmi_vae_precision(const sdmi_vae* h);        /* SDMI_PRECISION_*, or -1 for a null handle */
 /* VQModelInterface.decode(h, force_not_quantize) (autoencoder.py:274-283): quantize = 1 replaces z_scale * z by its nearest
  * codebook entry first (sdmi_k_vq_quantize's arithmetic), then post_quant_conv -> decoder; quantize = 0 is sdmi_vae_decode.
  * The workspace is sdmi_vae_decode_workspace_bytes. */
@@ -404,7 +413,10 @@ int sdmi_k_ln_fold_prep(const void* w_f16, int N, int K, int ldw, const float* g
 int sdmi_k_attention(const void* q, const void* k, const void* vt, void* out, int BH, int heads, int nq, int nkv,
                      int nkv_pad, int d, float scale, void* stream);
 /* split-fp16 attention (the full-precision mode): q / k / vt and their low halves q_lo / k_lo / vt_lo in the layouts above,
- * out / out_lo fp16 [BH/heads, nq, heads*d] = hi / lo of the fp32 result; d in {24, 32, 40, 48, 64, 80, 96, 128, 160} */
+ * out / out_lo fp16 [BH/heads, nq, heads*d] = hi / lo of the fp32 result; d in {24, 32, 40, 48, 64, 80, 96, 128, 160} (csrc/attn_split16.hip)
+ * or 192 .. 1024 in steps of 64 (csrc/attn_wide_split16.hip: four waves split d and sum their partial scores in a fixed order; like the
+ * wide-head kernel of sdmi_k_attention it replaces the V^T pad columns nkv .. nkv_pad, hi and lo, by zeros itself).  Any other d fails
+ * with a message that names it. */
 int sdmi_k_attention_split16(const void* q, const void* q_lo, const void* k, const void* k_lo, const void* vt, const void* vt_lo, void* out,
                              void* out_lo, int BH, int heads, int nq, int nkv, int nkv_pad, int d, float scale, void* stream);
 /* same with a causal mask (query i attends to keys <= i; nq == nkv): CLIPTextModel's self-attention */

@@ -94,6 +94,8 @@ _SIGS = {
     'sdmi_vae_create': (C.c_int, [C.POINTER(VaeCfg), C.c_int, C.POINTER(c_ptr)]),
     'sdmi_vae_destroy': (C.c_int, [c_ptr]),
     'sdmi_vae_create_ext': (C.c_int, [C.POINTER(VaeCfg), C.POINTER(VaeExt), C.c_int, C.POINTER(c_ptr)]),
+    'sdmi_vae_create_precision': (C.c_int, [C.POINTER(VaeCfg), C.POINTER(VaeExt), C.c_int, C.c_int, C.POINTER(c_ptr)]),
+    'sdmi_vae_precision': (C.c_int, [c_ptr]),
     'sdmi_vae_decode_vq': (C.c_int, [c_ptr, c_ptr, C.c_float, C.c_int, c_ptr, C.c_int, C.c_int, C.c_int, c_ptr, C.c_int64, c_ptr]),
     'sdmi_k_vq_quantize': (C.c_int, [c_ptr, C.c_float, c_ptr, c_ptr, C.c_int, C.c_int, c_ptr, c_ptr, C.c_int, C.c_int, c_ptr]),
     'sdmi_k_patch_unfold': (C.c_int, [c_ptr, c_ptr, c_ptr] + [C.c_int] * 11 + [c_ptr]),

@@ -165,20 +165,24 @@ int sdmi_dpm_solver_step(const float* eps_model, int cfg, float scale, const flo
 
 // ---- first stage --------------------------------------------------------------------------------------
 int sdmi_vae_create(const sdmi_vae_cfg* cfg, int parts, sdmi_vae** out) {
+  return sdmi_vae_create_precision(cfg, nullptr, parts, SDMI_PRECISION_MIXED, out);
+}
+int sdmi_vae_create_ext(const sdmi_vae_cfg* cfg, const sdmi_vae_ext* ext, int parts, sdmi_vae** out) {
+  return sdmi_vae_create_precision(cfg, ext, parts, SDMI_PRECISION_MIXED, out);
+}
+int sdmi_vae_create_precision(const sdmi_vae_cfg* cfg, const sdmi_vae_ext* ext, int parts, int precision, sdmi_vae** out) {
   SDMI_CHECK(cfg && out, "null argument");
+  SDMI_CHECK(precision == SDMI_PRECISION_MIXED || precision == SDMI_PRECISION_FULL,
+             "precision must be SDMI_PRECISION_MIXED (0) or SDMI_PRECISION_FULL (1), got " + std::to_string(precision));
   sdmi_vae* h = new (std::nothrow) sdmi_vae();
   SDMI_CHECK(h != nullptr, "out of host memory");
-  if (h->impl.build(*cfg, parts)) { delete h; return -1; }
+  if (h->impl.build(*cfg, parts, ext, precision)) { delete h; return -1; }
   *out = h;
   return 0;
 }
-int sdmi_vae_create_ext(const sdmi_vae_cfg* cfg, const sdmi_vae_ext* ext, int parts, sdmi_vae** out) {
-  SDMI_CHECK(cfg && out, "null argument");
-  sdmi_vae* h = new (std::nothrow) sdmi_vae();
-  SDMI_CHECK(h != nullptr, "out of host memory");
-  if (h->impl.build(*cfg, parts, ext)) { delete h; return -1; }
-  *out = h;
-  return 0;
+int sdmi_vae_precision(const sdmi_vae* h) {
+  if (!h) { fail("null handle"); return -1; }
+  return h->impl.precision_;
 }
 int sdmi_vae_destroy(sdmi_vae* h) { delete h; return 0; }
 int sdmi_vae_num_weights(const sdmi_vae* h) { return h ? (int)h->impl.slots().size() : fail("null handle"); }

@@ -225,7 +225,10 @@ int launch_attention_split16(const AttnSplitParams& p, hipStream_t stream) {
     case 96: return launch_d<96>(p, stream);
     case 128: return launch_d<128>(p, stream);
     case 160: return launch_d<160>(p, stream);
-    default: return fail("split-fp16 attention: head dim " + std::to_string(p.d) + " has no instantiation (24, 32, 40, 48, 64, 80, 96, 128, 160)");
+    default:
+      if (p.d > 160 && p.d <= 1024 && p.d % 64 == 0) return launch_attention_wide_split16(p, stream);     // attn_wide_split16.hip
+      return fail("split-fp16 attention: head dim " + std::to_string(p.d) +
+                  " has no instantiation (24, 32, 40, 48, 64, 80, 96, 128, 160, and 192 .. 1024 in steps of 64)");
   }
 }
 

@@ -17,6 +17,9 @@ struct AttnSplitParams {
   float scale = 1.f;
 };
 int launch_attention_split16(const AttnSplitParams& p, hipStream_t stream);
+// ... its wide-head form (attn_wide_split16.hip: d = 192 .. 1024 in steps of 64; the V^T pad columns may hold anything there).
+// launch_attention_split16 checks the operands and dispatches to it by d: call that one.
+int launch_attention_wide_split16(const AttnSplitParams& p, hipStream_t stream);
 
 // The producers of the split operands (split_ops.hip).  Each reads an fp32 GEMM output and writes hi / lo.
 // Per-head scatter of columns [col0, col0 + heads * dh) of src [B * ntok][ld]:

@@ -10,7 +10,15 @@
 // the following implicit-GEMM conv; nin_shortcut (1x1 on the raw stream) runs as a 3-pass split-fp16 GEMM; the first
 // (z -> 512) and last (128 -> 3) convs and the two 1x1 "quant" convs are fp32.  Attention over N = H*W tokens with
 // d = C = 512 is three GEMMs (q k^T, softmax rows, P v) on the igemm kernel, in query chunks so S stays cache-sized.
+//
+// A handle created with SDMI_PRECISION_FULL (sdmi_vae_create_precision) runs the same layers with every MFMA operand as a split-fp16
+// pair, as the UNet's full-precision mode does (unet.cpp: Fwd::res_block / resample / attn_block_full): GroupNorm writes hi | lo, the
+// 3x3 convs are 3-pass split convs against weights packed [w_hi | w_hi | w_lo], q / k / v / proj_out are split GEMMs into fp32 and the
+// attention is one split-fp16 flash launch (attn_split16.hip up to d = 160, attn_wide_split16.hip for 192 .. 1024): no S / P buffer, no
+// query chunks.  The fp32 ends (conv_in, conv_out, the quant convs, the codebook quantizer) are the same launches in both modes.
 #include "vae.h"
+
+#include "split16.h"
 
 #include <math.h>
 
@@ -25,8 +33,8 @@ void Vae::expect(const std::string& key, std::vector<int64_t> shape, VWKind kind
   slots_.push_back(std::move(s));
 }
 
-int Vae::build(const sdmi_vae_cfg& c, int parts, const sdmi_vae_ext* ext) {
-  cfg_ = c; parts_ = parts;
+int Vae::build(const sdmi_vae_cfg& c, int parts, const sdmi_vae_ext* ext, int precision) {
+  cfg_ = c; parts_ = parts; precision_ = precision;
   if (ext) ext_ = *ext;
   SDMI_CHECK((ext_.double_z == 0 || ext_.double_z == 1) && (ext_.mid_attn == 0 || ext_.mid_attn == 1) && ext_.n_embed >= 0,
              "first-stage extension: double_z and mid_attn are 0 or 1, n_embed >= 0");
@@ -39,6 +47,14 @@ int Vae::build(const sdmi_vae_cfg& c, int parts, const sdmi_vae_ext* ext) {
                  c.embed_dim <= 8 && c.out_ch >= 1 && c.out_ch <= 8,
              "in_channels <= 16, z_channels <= 4, embed_dim <= 8, out_ch <= 8 on this path");
   const int n = c.n_levels;
+  if (full() && ext_.mid_attn) {       // the mid-block attention is single-headed at d = the mid width
+    const int d = c.ch * c.ch_mult[n - 1];
+    const bool narrow = d == 64 || d == 128, wide = d > 160 && d <= 1024 && d % 64 == 0;
+    SDMI_CHECK(narrow || wide, "full-precision first stage: mid-block attention width " + std::to_string(d) +
+               " has no split-fp16 attention kernel (64, 128, and 192 .. 1024 in steps of 64)");
+  }
+  const VWKind conv_kind = full() ? VW_CONV_SPLIT3 : VW_CONV;
+  const VWKind lin_kind = full() ? VW_SPLIT3 : VW_PLAIN16;
   auto res = [&](const std::string& p, int ci, int co) { VLayer L; L.kind = V_RES; L.prefix = p; L.cin = ci; L.cout = co; return L; };
   auto one = [&](VKind k, const std::string& p, int ch) { VLayer L; L.kind = k; L.prefix = p; L.cin = ch; L.cout = ch; return L; };
 
@@ -81,14 +97,14 @@ int Vae::build(const sdmi_vae_cfg& c, int parts, const sdmi_vae_ext* ext) {
       case V_RES:
         expect(p + ".norm1.weight", {ci}, VW_F32, (void**)&L.f32[0]);
         expect(p + ".norm1.bias", {ci}, VW_F32, (void**)&L.f32[1]);
-        expect(p + ".conv1.weight", {co, ci, 3, 3}, VW_CONV, (void**)&L.w16[0]);
+        expect(p + ".conv1.weight", {co, ci, 3, 3}, conv_kind, (void**)&L.w16[0]);
         expect(p + ".conv1.bias", {co}, VW_F32, (void**)&L.f32[2]);
         expect(p + ".norm2.weight", {co}, VW_F32, (void**)&L.f32[3]);
         expect(p + ".norm2.bias", {co}, VW_F32, (void**)&L.f32[4]);
-        expect(p + ".conv2.weight", {co, co, 3, 3}, VW_CONV, (void**)&L.w16[1]);
+        expect(p + ".conv2.weight", {co, co, 3, 3}, conv_kind, (void**)&L.w16[1]);
         expect(p + ".conv2.bias", {co}, VW_F32, (void**)&L.f32[5]);
         if (ci != co) {
-          expect(p + ".nin_shortcut.weight", {co, ci, 1, 1}, precise_1x1_ ? VW_SPLIT3 : VW_PLAIN16, (void**)&L.w16[2]);
+          expect(p + ".nin_shortcut.weight", {co, ci, 1, 1}, (precise_1x1_ || full()) ? VW_SPLIT3 : VW_PLAIN16, (void**)&L.w16[2]);
           expect(p + ".nin_shortcut.bias", {co}, VW_F32, (void**)&L.f32[6]);
         }
         break;
@@ -97,14 +113,14 @@ int Vae::build(const sdmi_vae_cfg& c, int parts, const sdmi_vae_ext* ext) {
         expect(p + ".norm.bias", {ci}, VW_F32, (void**)&L.f32[1]);
         const char* names[4] = {"q", "k", "v", "proj_out"};
         for (int i = 0; i < 4; ++i) {
-          expect(p + "." + names[i] + ".weight", {ci, ci, 1, 1}, VW_PLAIN16, (void**)&L.w16[i]);
+          expect(p + "." + names[i] + ".weight", {ci, ci, 1, 1}, lin_kind, (void**)&L.w16[i]);
           expect(p + "." + names[i] + ".bias", {ci}, VW_F32, (void**)&L.f32[2 + i]);
         }
         break;
       }
       case V_UP:
       case V_DOWN:
-        expect(p + ".conv.weight", {co, ci, 3, 3}, VW_CONV, (void**)&L.w16[0]);
+        expect(p + ".conv.weight", {co, ci, 3, 3}, conv_kind, (void**)&L.w16[0]);
         expect(p + ".conv.bias", {co}, VW_F32, (void**)&L.f32[0]);
         break;
     }
@@ -170,6 +186,10 @@ int Vae::set_weight(const char* key, const float* ptr, const int64_t* shape, int
       rc = dev_alloc(s.dst, numel * sizeof(f16));
       if (!rc) rc = launch_pack_conv_weight(dptr, (f16*)*s.dst, (int)shape[0], (int)shape[1], (int)shape[2], (int)shape[3], stream);
       break;
+    case VW_CONV_SPLIT3:
+      rc = dev_alloc(s.dst, 3 * numel * sizeof(f16));
+      if (!rc) rc = launch_pack_conv_split3(dptr, (f16*)*s.dst, (int)shape[0], (int)shape[1], (int)shape[2], (int)shape[3], stream);
+      break;
     case VW_SPLIT3:
       rc = dev_alloc(s.dst, 3 * numel * sizeof(f16));
       if (!rc) rc = launch_pack_split3(dptr, (f16*)*s.dst, (int)shape[0], (int)shape[1], stream);
@@ -213,6 +233,105 @@ int Vae::finalize() {
 // ------------------------------------------------------------------------------------------------------
 struct VFwd : FwdBase {
   static constexpr float EPS = 1e-6f;        // Normalize(): GroupNorm(32, eps=1e-6)   model.py:37-38
+  bool full = false;                         // the handle's precision (Vae::full())
+
+  // ---- SDMI_PRECISION_FULL: split-fp16 operands [hi | lo | hi] against weights packed [w_hi | w_hi | w_lo] ----
+  static void split3(IGemmParams& q, const f16* hi, const f16* lo, int C) {
+    q.a0 = hi; q.c0 = C; q.lda0 = C; q.a1 = lo; q.c1 = C; q.lda1 = C; q.a2 = hi; q.c2 = C; q.lda2 = C; q.K = 27 * C; q.k_alg = 9 * C;
+  }
+
+  // no split-K in this mode: every output element is then summed over K in one fixed order whatever M is, so a sample's result does
+  // not depend on the batch it is decoded in (the split is otherwise chosen from the number of workgroups)
+  void gemm_full(IGemmParams& p) { p.splitk = 1; gemm(p); }
+
+  Act res_block_full(VLayer& L, const Act& x) {
+    const int H = x.H, W = x.W, M = B * H * W, Cin = L.cin, Cout = L.cout;
+    if (x.C != Cin) ok(fail("res block channel mismatch at " + L.prefix));
+    const size_t mark = scratch.off;
+    const bool nin = Cin != Cout;
+    f16* a = S<f16>((size_t)M * Cin); f16* a_lo = S<f16>((size_t)M * Cin);
+    f16* raw = nin ? S<f16>((size_t)M * Cin) : nullptr;
+    f16* raw_lo = nin ? S<f16>((size_t)M * Cin) : nullptr;
+    float* h = S<float>((size_t)M * Cout);
+    Act out; out.p = P<float>((size_t)M * Cout); out.C = Cout; out.H = H; out.W = W;
+    groupnorm(x, nullptr, L.f32[0], L.f32[1], EPS, 1, a, nullptr, raw, a_lo, raw_lo);
+    {
+      IGemmParams p = conv3(a, Cin, H, W, H, W, 1, 0, L.w16[0], Cout);
+      split3(p, a, a_lo, Cin);
+      p.bias = L.f32[2]; p.out_f32 = h; p.ldo = Cout;
+      gemm_full(p);
+    }
+    const float* residual = x.p;
+    if (nin) {
+      IGemmParams p = dense1x1(raw, raw_lo, M, Cin, L.w16[2], Cout, H * W, true);
+      p.bias = L.f32[6]; p.out_f32 = out.p; p.ldo = Cout;
+      gemm_full(p);
+      residual = out.p;
+    }
+    Act hact; hact.p = h; hact.C = Cout; hact.H = H; hact.W = W;
+    f16* a2 = S<f16>((size_t)M * Cout); f16* a2_lo = S<f16>((size_t)M * Cout);
+    groupnorm(hact, nullptr, L.f32[3], L.f32[4], EPS, 1, a2, nullptr, nullptr, a2_lo, nullptr);
+    {
+      IGemmParams p = conv3(a2, Cout, H, W, H, W, 1, 0, L.w16[1], Cout);
+      split3(p, a2, a2_lo, Cout);
+      p.bias = L.f32[5]; p.residual = residual; p.ldr = Cout; p.out_f32 = out.p; p.ldo = Cout;
+      gemm_full(p);
+    }
+    scratch.off = mark;
+    return out;
+  }
+
+  // AttnBlock with one head of d = C: q, k, v (bias inside its GEMM) as split GEMMs into fp32, scattered to q / k / V^T hi | lo, one
+  // split-fp16 flash attention launch, proj_out as a split GEMM with the residual
+  Act attn_block_full(VLayer& L, const Act& x) {
+    const int H = x.H, W = x.W, N = H * W, M = B * N, C = L.cin;
+    const int Np = (int)round_up(N, 8);
+    const size_t mark = scratch.off;
+    f16* a = S<f16>((size_t)M * C); f16* a_lo = S<f16>((size_t)M * C);          // GroupNorm output, then the attention output
+    float* y = S<float>((size_t)M * C);
+    f16* qkv[3]; f16* qkv_lo[3];
+    for (int i = 0; i < 3; ++i) {
+      const size_t n = i == 2 ? (size_t)B * C * Np : (size_t)M * C;
+      qkv[i] = S<f16>(n); qkv_lo[i] = S<f16>(n);
+    }
+    groupnorm(x, nullptr, L.f32[0], L.f32[1], EPS, 0, a, nullptr, nullptr, a_lo, nullptr);
+    for (int i = 0; i < 3; ++i) {
+      IGemmParams p = dense1x1(a, a_lo, M, C, L.w16[i], C, N, true);
+      p.bias = L.f32[2 + i]; p.out_f32 = y; p.ldo = C;
+      gemm_full(p);
+      if (!dry && !rc) ok(launch_split_heads(y, C, 0, qkv[i], qkv_lo[i], i == 2 ? 1 : 0, B, N, Np, 1, C, s));
+    }
+    AttnSplitParams ap = AttnSplitParams();
+    ap.q = qkv[0]; ap.q_lo = qkv_lo[0]; ap.k = qkv[1]; ap.k_lo = qkv_lo[1]; ap.vt = qkv[2]; ap.vt_lo = qkv_lo[2]; ap.out = a; ap.out_lo = a_lo;
+    ap.BH = B; ap.heads = 1; ap.nq = N; ap.nkv = N; ap.nkv_pad = Np; ap.d = C; ap.scale = 1.0f / sqrtf((float)C);
+    if (!dry && !rc) ok(launch_attention_split16(ap, s));
+    Act out; out.p = P<float>((size_t)M * C); out.C = C; out.H = H; out.W = W;
+    {
+      IGemmParams p = dense1x1(a, a_lo, M, C, L.w16[3], C, N, true);
+      p.bias = L.f32[5]; p.residual = x.p; p.ldr = C; p.out_f32 = out.p; p.ldo = C;
+      gemm_full(p);
+    }
+    scratch.off = mark;
+    return out;
+  }
+
+  Act resample_full(VLayer& L, const Act& x, bool up) {
+    const int Hin = x.H, Win = x.W, C = x.C;
+    if (!up && ((Hin | Win) & 1)) ok(fail("first-stage Downsample needs even H and W"));
+    const int Hout = up ? 2 * Hin : Hin / 2, Wout = up ? 2 * Win : Win / 2;
+    const size_t mark = scratch.off;
+    const int64_t n = (int64_t)B * Hin * Win * C;
+    f16* hi = S<f16>((size_t)n); f16* lo = S<f16>((size_t)n);
+    if (!dry && !rc) ok(launch_cast_f16(x.p, hi, lo, n, s));
+    Act out; out.p = P<float>((size_t)B * Hout * Wout * C); out.C = C; out.H = Hout; out.W = Wout;
+    IGemmParams p = conv3(hi, C, Hin, Win, Hout, Wout, up ? 1 : 2, up ? 1 : 0, L.w16[0], C);
+    split3(p, hi, lo, C);
+    if (!up) p.pad = 0;                   // F.pad(x, (0,1,0,1)) + conv(stride 2, padding 0)
+    p.bias = L.f32[0]; p.out_f32 = out.p; p.ldo = C;
+    gemm_full(p);
+    scratch.off = mark;
+    return out;
+  }
 
   Act res_block(VLayer& L, const Act& x) {   // model.py:119-141
     const int H = x.H, W = x.W, M = B * H * W, Cin = L.cin, Cout = L.cout;
@@ -316,6 +435,15 @@ struct VFwd : FwdBase {
   }
 
   Act run_layer(VLayer& L, const Act& x) {
+    if (full) {
+      switch (L.kind) {
+        case V_RES: return res_block_full(L, x);
+        case V_ATTN: return attn_block_full(L, x);
+        case V_UP: return resample_full(L, x, true);
+        case V_DOWN: return resample_full(L, x, false);
+      }
+      return x;
+    }
     switch (L.kind) {
       case V_RES: return res_block(L, x);
       case V_ATTN: return attn_block(L, x);
@@ -366,7 +494,7 @@ int Vae::decode(const float* z, float z_scale, float* img, int B, int H, int W, 
   SDMI_CHECK(H >= 1 && W >= 1, "bad shape");
   SDMI_CHECK(dry || (z != nullptr && img != nullptr), "z / img is NULL");
   VFwd f;
-  f.s = stream; f.B = B; f.zero = zero_; f.precise_1x1 = precise_1x1_;
+  f.s = stream; f.B = B; f.zero = zero_; f.precise_1x1 = precise_1x1_; f.full = full();
   const int n = cfg_.n_levels, c_in = cfg_.ch * cfg_.ch_mult[n - 1];
   return run_two_pass(f, dry, workspace, ws_bytes, bytes_needed, [&](VFwd& f) -> int {
     const bool d = f.dry;
@@ -397,7 +525,7 @@ int Vae::encode(const float* img, float* moments, int B, int H, int W, void* wor
   SDMI_CHECK(H >= fct && W >= fct && H % fct == 0 && W % fct == 0, "H and W must be multiples of 2^(levels-1)");
   SDMI_CHECK(dry || (img != nullptr && moments != nullptr), "img / moments is NULL");
   VFwd f;
-  f.s = stream; f.B = B; f.zero = zero_; f.precise_1x1 = precise_1x1_;
+  f.s = stream; f.B = B; f.zero = zero_; f.precise_1x1 = precise_1x1_; f.full = full();
   return run_two_pass(f, dry, workspace, ws_bytes, bytes_needed, [&](VFwd& f) -> int {
     const bool d = f.dry;
     Act x; x.p = f.P<float>((size_t)B * H * W * cfg_.ch); x.C = cfg_.ch; x.H = H; x.W = W;

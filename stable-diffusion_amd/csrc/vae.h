@@ -11,7 +11,8 @@
 namespace sdmi {
 
 enum VKind { V_RES, V_ATTN, V_UP, V_DOWN };
-enum VWKind { VW_F32, VW_CONV, VW_SPLIT3, VW_PLAIN16, VW_CONV_OUT };
+// VW_CONV_SPLIT3: the 3x3 conv weights of a full-precision handle, packed [w_hi | w_hi | w_lo] (launch_pack_conv_split3)
+enum VWKind { VW_F32, VW_CONV, VW_SPLIT3, VW_PLAIN16, VW_CONV_OUT, VW_CONV_SPLIT3 };
 
 struct VLayer {
   VKind kind = V_RES;
@@ -39,7 +40,7 @@ class Vae {
   Vae(const Vae&) = delete;
   Vae& operator=(const Vae&) = delete;
 
-  int build(const sdmi_vae_cfg& cfg, int parts, const sdmi_vae_ext* ext = nullptr);
+  int build(const sdmi_vae_cfg& cfg, int parts, const sdmi_vae_ext* ext = nullptr, int precision = SDMI_PRECISION_MIXED);
   int set_weight(const char* key, const float* ptr, const int64_t* shape, int ndim, hipStream_t stream);
   int finalize();
   // z [B, embed_dim, H, W] fp32 NCHW -> img [B, out_ch, H*f, W*f] fp32 NCHW; z is multiplied by z_scale first
@@ -60,6 +61,10 @@ class Vae {
   int enc_ed() const { return ext_.double_z ? 2 * cfg_.embed_dim : cfg_.embed_dim; }      // quant_conv output channels
   f16* zero_ = nullptr;
   bool precise_1x1_ = true;
+  // SDMI_PRECISION_FULL: every MFMA operand of the ResBlocks, the resampling convs and the mid-block attention is a split-fp16 pair
+  // (vae.cpp: VFwd::*_full); fixed at creation, the weights are packed for it
+  int precision_ = SDMI_PRECISION_MIXED;
+  bool full() const { return precision_ == SDMI_PRECISION_FULL; }
 
  private:
   friend struct VFwd;

@@ -48,7 +48,8 @@ class SuperResolutionHIP(LatentDiffusionHIP):
         if not p.get('concat_mode') or p.get('cond_stage_key') != 'LR_image':
             raise NotImplementedError('SuperResolutionHIP: a concat_mode model conditioned on LR_image')
         return cls(split_input_params, dict(p['unet_config']['params']),
-                   dict(embed_dim=fs['embed_dim'], n_embed=fs['n_embed'], ddconfig=dict(fs['ddconfig'])),
+                   dict(embed_dim=fs['embed_dim'], n_embed=fs['n_embed'], ddconfig=dict(fs['ddconfig']),
+                        **({'hip_precision': fs['hip_precision']} if 'hip_precision' in fs else {})),     # (the first stage's own mode)
                    dict(timesteps=p['timesteps'], linear_start=p['linear_start'], linear_end=p['linear_end'], conditioning_key='concat'),
                    hip_precision)
 

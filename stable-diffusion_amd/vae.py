@@ -20,7 +20,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .unet import _Node
+from .unet import PRECISIONS, _Node
 
 
 class DiagonalGaussianDistributionHIP:
@@ -49,6 +49,12 @@ def _posterior(moments):
         return DiagonalGaussianDistribution(moments)
     except ImportError:
         return DiagonalGaussianDistributionHIP(moments)
+
+
+def _check_precision(hip_precision):
+    if hip_precision not in PRECISIONS:
+        raise ValueError(f"hip_precision must be one of {sorted(PRECISIONS)}, got {hip_precision!r}")
+    return hip_precision
 
 
 def make_vae_cfg(ddconfig, embed_dim, vq=False):
@@ -84,13 +90,12 @@ def make_vae_cfg(ddconfig, embed_dim, vq=False):
 class _VaeHandle:
     """Owns one sdmi_vae*."""
 
-    def __init__(self, cfg, parts, ext=None):
+    def __init__(self, cfg, parts, ext=None, precision='mixed'):
         self.lib = _lib.load()
+        self.h = None
         h = C.c_void_p()
-        if ext is None:
-            _lib.check(self.lib.sdmi_vae_create(C.byref(cfg), parts, C.byref(h)))
-        else:
-            _lib.check(self.lib.sdmi_vae_create_ext(C.byref(cfg), C.byref(ext), parts, C.byref(h)))
+        _lib.check(self.lib.sdmi_vae_create_precision(C.byref(cfg), None if ext is None else C.byref(ext), parts,
+                                                      PRECISIONS[precision], C.byref(h)))
         self.h = h
 
     def weight_specs(self):
@@ -117,14 +122,18 @@ class AutoencoderKLHIP(nn.Module):
     MAX_BATCH = 8     # images per library call (larger batches are looped)
 
     def __init__(self, ddconfig, lossconfig=None, embed_dim=4, ckpt_path=None, ignore_keys=[], image_key='image',
-                 colorize_nlabels=None, monitor=None, parts=3):
+                 colorize_nlabels=None, monitor=None, parts=3, hip_precision='mixed'):
+        """`hip_precision` (not a keyword of the reference AutoencoderKL): 'mixed' (default) = fp16 MFMA operands; 'full' = every MFMA
+        operand of the ResBlocks, the resampling convs and the mid-block attention is a split-fp16 pair (three MFMA passes), as in
+        UNetModelHIP's full mode.  Fixed for the module's lifetime; the state_dict keys are the same in both modes."""
         super().__init__()
+        self.hip_precision = _check_precision(hip_precision)
         self.image_key = image_key
         self.embed_dim = int(embed_dim)
         self.ddconfig = dict(ddconfig)
         self._cfg = make_vae_cfg(ddconfig, embed_dim)
         self._parts = parts
-        self._handle = _VaeHandle(self._cfg, parts)
+        self._handle = _VaeHandle(self._cfg, parts, None, hip_precision)
         self._specs = self._handle.weight_specs()
         for key, shape in self._specs:
             *path, leaf = key.split('.')
@@ -292,7 +301,7 @@ class VQModelInterfaceHIP(AutoencoderKLHIP):
 
     def __init__(self, embed_dim, ddconfig=None, n_embed=None, lossconfig=None, ckpt_path=None, ignore_keys=[],
                  image_key='image', colorize_nlabels=None, monitor=None, batch_resize_range=None, scheduler_config=None,
-                 lr_g_factor=1.0, remap=None, sane_index_shape=False, use_ema=False):
+                 lr_g_factor=1.0, remap=None, sane_index_shape=False, use_ema=False, hip_precision='mixed'):
         if ddconfig is None or n_embed is None:
             raise TypeError('VQModelInterfaceHIP needs ddconfig and n_embed')
         unsupported = []
@@ -303,6 +312,7 @@ class VQModelInterfaceHIP(AutoencoderKLHIP):
                                       '; '.join(unsupported))
         self.n_embed = int(n_embed)
         nn.Module.__init__(self)
+        self.hip_precision = _check_precision(hip_precision)      # (as AutoencoderKLHIP's)
         self.image_key = image_key
         self.embed_dim = int(embed_dim)
         self.ddconfig = dict(ddconfig)
@@ -310,7 +320,7 @@ class VQModelInterfaceHIP(AutoencoderKLHIP):
         ext = _lib.VaeExt()
         ext.double_z, ext.mid_attn, ext.n_embed = 0, int(self.ddconfig.get('attn_type', 'vanilla') != 'none'), self.n_embed
         self._parts = 3
-        self._handle = _VaeHandle(self._cfg, 3, ext)
+        self._handle = _VaeHandle(self._cfg, 3, ext, hip_precision)
         self._specs = self._handle.weight_specs()
         self.add_module('quantize', _QuantizerHIP(self._quantize))
         for key, shape in self._specs:

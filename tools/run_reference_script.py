@@ -28,6 +28,8 @@ What this launcher does (nothing in the reference tree is edited or copied):
   * `--hip --hip-precision full`: also writes `hip_precision: full` into that copy's `unet_config.params` (UNetModelHIP's
     full-precision mode: every MFMA operand split-fp16).  The script's own `--precision full` is NOT mapped onto it -- pass both
     to get the reference's fp32 semantics on the HIP UNet;
+  * `--hip --hip-first-stage-precision full`: writes `hip_precision: full` into that copy's `first_stage_config.params`
+    (AutoencoderKLHIP's full-precision mode); independent of `--hip-precision`, which leaves `first_stage_config` alone;
   * on a GPU-less host (BASELINE.json configs[0], the CPU plumbing check) it neutralises the hard-coded
     `.cuda()` / `torch.device("cuda")` uses (`txt2img.py:64`, `plms.py:18-22`); use `--precision full` there.
 Then it `runpy`-executes the script with the remaining arguments.
@@ -371,11 +373,37 @@ def patch_torch_load():
     torch.load = load
 
 
+FIRST_STAGE_TARGETS = ('stable_diffusion_amd.vae.AutoencoderKLHIP', 'stable_diffusion_amd.vae.VQModelInterfaceHIP')
+
+
 def add_hip_precision(text, precision):
     """`hip_precision: <precision>` as the first entry of the (patched) unet_config's params block; other lines unchanged"""
+    return _add_precision_under(text, precision, ('stable_diffusion_amd.unet.UNetModelHIP',), 'the UNetModelHIP target')
+
+
+def add_first_stage_precision(text, precision):
+    """`hip_precision: <precision>` as the first entry of the (patched) first_stage_config's params block (AutoencoderKLHIP /
+    VQModelInterfaceHIP); other lines unchanged.  A cond stage that is the first stage (`__is_first_stage__`) follows it."""
     lines = text.splitlines(keepends=True)
     ind = [len(l) - len(l.lstrip()) for l in lines]
-    at = next(i for i, l in enumerate(lines) if l.strip() == 'target: stable_diffusion_amd.unet.UNetModelHIP')
+    for i, l in enumerate(lines):
+        if l.strip() == 'first_stage_config:':
+            j = i + 1
+            while j < len(lines) and (not lines[j].strip() or ind[j] > ind[i]):
+                j += 1
+            block = ''.join(lines[i:j])
+            return ''.join(lines[:i]) + _add_precision_under(block, precision, FIRST_STAGE_TARGETS, 'a HIP first-stage target') + \
+                ''.join(lines[j:])
+    raise ValueError('no first_stage_config block')
+
+
+def _add_precision_under(text, precision, targets, what):
+    lines = text.splitlines(keepends=True)
+    ind = [len(l) - len(l.lstrip()) for l in lines]
+    try:
+        at = next(i for i, l in enumerate(lines) if l.strip() in tuple('target: ' + t for t in targets))
+    except StopIteration:
+        raise ValueError('no ' + what) from None
     parent = next(i for i in range(at - 1, -1, -1) if lines[i].strip() and ind[i] < ind[at])       # unet_config:
     i = parent + 1
     while i < len(lines) and (not lines[i].strip() or ind[i] > ind[parent]):
@@ -384,7 +412,7 @@ def add_hip_precision(text, precision):
             pad = ind[inner] if inner is not None and ind[inner] > ind[i] else ind[i] + 2
             return ''.join(lines[:i + 1] + [' ' * pad + f'hip_precision: {precision}\n'] + lines[i + 1:])
         i += 1
-    raise ValueError('no params block under the UNetModelHIP target')
+    raise ValueError('no params block under ' + what)
 
 
 def main():
@@ -394,6 +422,9 @@ def main():
     ap.add_argument('--hip-precision', choices=['mixed', 'full'], default=None,
                     help="with --hip: UNetModelHIP's hip_precision ('full' = split-fp16 on every MFMA operand); the default leaves the yaml "
                          "without the key (= 'mixed')")
+    ap.add_argument('--hip-first-stage-precision', choices=['mixed', 'full'], default=None,
+                    help="with --hip: the first stage's hip_precision (AutoencoderKLHIP: 'full' = split-fp16 on every MFMA operand of the "
+                         "decoder and encoder); the default leaves the yaml without the key (= 'mixed')")
     ap.add_argument('--offline-stubs', action='store_true',
                     help='allow seeded stand-ins for the CLIP tokenizer / text model / safety checker when the HF hub is '
                          'unreachable (synthetic checkpoints only; each substitution prints a warning)')
@@ -402,6 +433,8 @@ def main():
     args = ap.parse_args()
     if args.hip_precision and not args.hip:
         ap.error('--hip-precision needs --hip')
+    if args.hip_first_stage_precision and not args.hip:
+        ap.error('--hip-first-stage-precision needs --hip')
     rest = args.rest[1:] if args.rest[:1] == ['--'] else args.rest
     ref = os.path.abspath(args.reference)
     if not os.path.isdir(os.path.join(ref, 'ldm')) and os.path.isdir(os.path.join(BUNDLE, 'ldm')):
@@ -452,6 +485,9 @@ def main():
         if args.hip_precision:
             text = add_hip_precision(text, args.hip_precision)
             print(f'run_reference_script: unet_config.params.hip_precision = {args.hip_precision}', flush=True)
+        if args.hip_first_stage_precision:
+            text = add_first_stage_precision(text, args.hip_first_stage_precision)
+            print(f'run_reference_script: first_stage_config.params.hip_precision = {args.hip_first_stage_precision}', flush=True)
         tmp.write(text)
         tmp.close()
         rest = ['--config', tmp.name] + rest
