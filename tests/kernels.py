@@ -212,11 +212,11 @@ def gn_acc_sums(acc):
     return s, ss
 
 
-def ln_fold_prep(w16, K, gamma, beta, bias=None):
-    """column terms of a LayerNorm-folding GEMM from the packed fp16 weights w16 [N, ldw >= K]: (cs, d) fp32 [N]"""
+def ln_fold_prep(w16, K, gamma, beta, bias=None, out=None):
+    """column terms of a LayerNorm-folding GEMM from the packed fp16 weights w16 [N, ldw >= K]: (cs, d) fp32 [N]; `out` = the caller's
+    (cs, d), e.g. in guarded buffers (tests/guard.py)"""
     N = w16.shape[0]
-    cs = torch.empty((N,), dtype=torch.float32, device=w16.device)
-    dn = torch.empty((N,), dtype=torch.float32, device=w16.device)
+    cs, dn = out if out is not None else (torch.empty((N,), dtype=torch.float32, device=w16.device) for _ in range(2))
     _lib.check(_lib.load().sdmi_k_ln_fold_prep(w16.data_ptr(), N, K, w16.stride(0), gamma.data_ptr(), beta.data_ptr(),
                                                _lib.ptr(bias), cs.data_ptr(), dn.data_ptr(), _s()))
     return cs, dn

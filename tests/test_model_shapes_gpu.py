@@ -19,11 +19,11 @@ there the concat is launched as two sources a0 | a1, the skip conv also carries 
 at a pitch of N + 8, so that a store past the N tail of a row lands in a gap).
 NOT run here -- these launch variants of the executor stay covered by the whole-UNet goldens (and, at SD's shapes only, by their own
 kernel tests): GroupNorm + SiLU applied inside the split-K reduction of a ResBlock's conv1 (pgn_*; test_igemm_splitk_reduce_groupnorm_
-behind_a_grid_barrier runs 40 / 20 / 16 channels per group, the new models have 18 .. 32); the LayerNorm fold of the transformer blocks
-with >= 512 rows (f16_scale + lnp_out producers, lnf_* consumers without bias, out_lo of the last FF-out; test_layernorm_folded_into_
-consumer knows C = 320, CIN has 384 and 576) -- the dense cases here run the plain bias / residual epilogues; the one-token context
+behind_a_grid_barrier runs 40 / 20 / 16 channels per group, the new models have 18 .. 32); out_lo of the last FF-out; the one-token context
 broadcast that replaces to_q and the nkv = 1 attention in CIN by default (SDMI_CTX1; the general path it replaces IS run here); and the
 statistics conv_in emits itself (the C ABI of sdmi_k_conv_in has no statistics arguments; the walk lists its targets).
+The LayerNorm fold of the transformer blocks (f16_scale + lnp_out producers, lnf_* consumers without bias) is run by tests/test_ln_fold_gpu.py,
+at every transformer width of these models; the dense cases here run the plain bias / residual epilogues.
 The split-fp16 bar is 3e-5 up to K = 1920 and grows as sqrt(K) beyond (_tol_split: derivation and the one case it matters for).
 After every launch every buffer's guards are checked, the split-K tile counters must be zero again, and inputs must be unchanged bits.
 

@@ -210,9 +210,13 @@ def _st_head_launches(c):
     return t, q, k, vt, cs, dn
 
 
-@pytest.mark.parametrize('B,ntok', [(2, 4096), (1, 64), (3, 128), (2, 9216)])
-def test_st_head_is_bit_identical_to_the_three_launches(B, ntok):
-    c = _st_head_case(B, ntok, 4321 + ntok)
+# the head layouts st_head_supported accepts at C = 320 next to the 8 x 40 of the SD blocks (heads * dh = C, dh % 4 == 0)
+HEAD_LAYOUTS = [5, 10, 4]
+HEAD_LAYOUT_IDS = ['5x64', '10x32', '4x80']
+
+
+def _check_st_head(B, ntok, heads=8):
+    c = _st_head_case(B, ntok, 4321 + ntok + (heads - 8), heads)        # (the 8-head cases keep their seeds)
     M, C_, heads, dh = c['M'], c['C'], c['heads'], c['dh']
     t0, q0, k0, vt0, cs, dn = _st_head_launches(c)
     t, q, k, vt = _st_head_outputs(c)
@@ -236,6 +240,17 @@ def test_st_head_is_bit_identical_to_the_three_launches(B, ntok):
     assert all(same)
 
 
+@pytest.mark.parametrize('B,ntok', [(2, 4096), (1, 64), (3, 128), (2, 9216)])
+def test_st_head_is_bit_identical_to_the_three_launches(B, ntok):
+    _check_st_head(B, ntok)
+
+
+@pytest.mark.parametrize('B,ntok', [(1, 64), (3, 128)])
+@pytest.mark.parametrize('heads', HEAD_LAYOUTS, ids=HEAD_LAYOUT_IDS)
+def test_st_head_head_layouts_are_bit_identical_to_the_three_launches(heads, B, ntok):
+    _check_st_head(B, ntok, heads)
+
+
 def test_st_head_repeats_bit_identically_next_to_other_work():
     c = _st_head_case(2, 4096, 11)
     M, C_, heads, dh = c['M'], c['C'], c['heads'], c['dh']
@@ -254,11 +269,9 @@ def test_st_head_repeats_bit_identically_next_to_other_work():
             assert all(torch.equal(a, b) for a, b in zip((t, q, k, vt), ref)), i
 
 
-@pytest.mark.parametrize('B,ntok', [(2, 4096), (1, 64), (3, 128), (2, 9216)])
-def test_st_mid_is_bit_identical_to_the_two_launches(B, ntok):
-    """out-projection of attn1 (+ residual, in place) and attn2's to_q over norm2 (attention.py:212-213) as one launch"""
-    g = _g(977 + ntok)
-    C_, heads = 320, 8
+def _check_st_mid(B, ntok, heads=8):
+    g = _g(977 + ntok + (heads - 8))        # (the 8-head cases keep their seeds)
+    C_ = 320
     dh, M = C_ // heads, B * ntok
     d = lambda t: t.to(DEV)
     ao = (torch.randn(M, C_, generator=g) * 0.7).half()
@@ -285,6 +298,18 @@ def test_st_mid_is_bit_identical_to_the_two_launches(B, ntok):
     assert K.report(f'st_mid q B{B} n{ntok}', q.float(), q_ref, 2e-2) < 2e-2
     print(f'[st_mid vs launches] t / q equal: {torch.equal(t, t0)} {torch.equal(q, q0)}', flush=True)
     assert torch.equal(t, t0) and torch.equal(q, q0)
+
+
+@pytest.mark.parametrize('B,ntok', [(2, 4096), (1, 64), (3, 128), (2, 9216)])
+def test_st_mid_is_bit_identical_to_the_two_launches(B, ntok):
+    """out-projection of attn1 (+ residual, in place) and attn2's to_q over norm2 (attention.py:212-213) as one launch"""
+    _check_st_mid(B, ntok)
+
+
+@pytest.mark.parametrize('B,ntok', [(1, 64), (3, 128)])
+@pytest.mark.parametrize('heads', HEAD_LAYOUTS, ids=HEAD_LAYOUT_IDS)
+def test_st_mid_head_layouts_are_bit_identical_to_the_two_launches(heads, B, ntok):
+    _check_st_mid(B, ntok, heads)
 
 
 @pytest.mark.parametrize('B,ntok,nkv', [(2, 4096, 77), (1, 64, 77), (3, 128, 64), (2, 9216, 77), (2, 256, 128), (1, 32, 5)])
