@@ -22,6 +22,17 @@ struct sdmi_bert { sdmi::BertText impl; };
 
 using namespace sdmi;
 
+static int weight_info(const WeightStore& w, int idx, char* key_buf, int key_buf_len, int64_t* shape4, int* ndim) {
+  SDMI_CHECK(key_buf && shape4 && ndim, "null argument");
+  SDMI_CHECK(idx >= 0 && idx < (int)w.slots().size(), "weight index out of range");
+  const WeightSlot& s = w.slots()[idx];
+  SDMI_CHECK((int)s.key.size() + 1 <= key_buf_len, "key buffer too small");
+  memcpy(key_buf, s.key.c_str(), s.key.size() + 1);
+  *ndim = (int)s.shape.size();
+  for (int i = 0; i < 4; ++i) shape4[i] = i < *ndim ? s.shape[i] : 1;
+  return 0;
+}
+
 static void* g_zero_page[16] = {nullptr};
 static int zero_page(const f16** out) {
   int dev = 0;
@@ -70,16 +81,10 @@ int sdmi_unet_precision(const sdmi_unet* h) {
   return h->impl.precision_;
 }
 int sdmi_unet_destroy(sdmi_unet* h) { delete h; return 0; }
-int sdmi_unet_num_weights(const sdmi_unet* h) { return h ? (int)h->impl.slots().size() : fail("null handle"); }
+int sdmi_unet_num_weights(const sdmi_unet* h) { return h ? (int)h->impl.weights().slots().size() : fail("null handle"); }
 int sdmi_unet_weight_info(const sdmi_unet* h, int idx, char* key_buf, int key_buf_len, int64_t* shape4, int* ndim) {
-  SDMI_CHECK(h && key_buf && shape4 && ndim, "null argument");
-  SDMI_CHECK(idx >= 0 && idx < (int)h->impl.slots().size(), "weight index out of range");
-  const WeightSlot& s = h->impl.slots()[idx];
-  SDMI_CHECK((int)s.key.size() + 1 <= key_buf_len, "key buffer too small");
-  memcpy(key_buf, s.key.c_str(), s.key.size() + 1);
-  *ndim = (int)s.shape.size();
-  for (int i = 0; i < 4; ++i) shape4[i] = i < *ndim ? s.shape[i] : 1;
-  return 0;
+  SDMI_CHECK(h, "null argument");
+  return weight_info(h->impl.weights(), idx, key_buf, key_buf_len, shape4, ndim);
 }
 int sdmi_unet_set_weight(sdmi_unet* h, const char* key, const float* ptr, const int64_t* shape, int ndim, void* stream) {
   SDMI_CHECK(h && key && ptr && shape, "null argument");
@@ -185,16 +190,10 @@ int sdmi_vae_precision(const sdmi_vae* h) {
   return h->impl.precision_;
 }
 int sdmi_vae_destroy(sdmi_vae* h) { delete h; return 0; }
-int sdmi_vae_num_weights(const sdmi_vae* h) { return h ? (int)h->impl.slots().size() : fail("null handle"); }
+int sdmi_vae_num_weights(const sdmi_vae* h) { return h ? (int)h->impl.weights().slots().size() : fail("null handle"); }
 int sdmi_vae_weight_info(const sdmi_vae* h, int idx, char* key_buf, int key_buf_len, int64_t* shape4, int* ndim) {
-  SDMI_CHECK(h && key_buf && shape4 && ndim, "null argument");
-  SDMI_CHECK(idx >= 0 && idx < (int)h->impl.slots().size(), "weight index out of range");
-  const VWeightSlot& s = h->impl.slots()[idx];
-  SDMI_CHECK((int)s.key.size() + 1 <= key_buf_len, "key buffer too small");
-  memcpy(key_buf, s.key.c_str(), s.key.size() + 1);
-  *ndim = (int)s.shape.size();
-  for (int i = 0; i < 4; ++i) shape4[i] = i < *ndim ? s.shape[i] : 1;
-  return 0;
+  SDMI_CHECK(h, "null argument");
+  return weight_info(h->impl.weights(), idx, key_buf, key_buf_len, shape4, ndim);
 }
 int sdmi_vae_set_weight(sdmi_vae* h, const char* key, const float* ptr, const int64_t* shape, int ndim, void* stream) {
   SDMI_CHECK(h && key && ptr && shape, "null argument");
@@ -247,20 +246,10 @@ int sdmi_clip_create(const sdmi_clip_cfg* cfg, sdmi_clip** out) {
   return 0;
 }
 int sdmi_clip_destroy(sdmi_clip* h) { delete h; return 0; }
-int sdmi_clip_num_weights(const sdmi_clip* h) { return h ? (int)h->impl.slots().size() : fail("null handle"); }
-static int text_weight_info(const TextEncBase& t, int idx, char* key_buf, int key_buf_len, int64_t* shape4, int* ndim) {
-  SDMI_CHECK(key_buf && shape4 && ndim, "null argument");
-  SDMI_CHECK(idx >= 0 && idx < (int)t.slots().size(), "weight index out of range");
-  const CWeightSlot& s = t.slots()[idx];
-  SDMI_CHECK((int)s.key.size() + 1 <= key_buf_len, "key buffer too small");
-  memcpy(key_buf, s.key.c_str(), s.key.size() + 1);
-  *ndim = (int)s.shape.size();
-  for (int i = 0; i < 4; ++i) shape4[i] = i < *ndim ? s.shape[i] : 1;
-  return 0;
-}
+int sdmi_clip_num_weights(const sdmi_clip* h) { return h ? (int)h->impl.weights().slots().size() : fail("null handle"); }
 int sdmi_clip_weight_info(const sdmi_clip* h, int idx, char* key_buf, int key_buf_len, int64_t* shape4, int* ndim) {
-  SDMI_CHECK(h && key_buf && shape4 && ndim, "null argument");
-  return text_weight_info(h->impl, idx, key_buf, key_buf_len, shape4, ndim);
+  SDMI_CHECK(h, "null argument");
+  return weight_info(h->impl.weights(), idx, key_buf, key_buf_len, shape4, ndim);
 }
 int sdmi_clip_set_weight(sdmi_clip* h, const char* key, const float* ptr, const int64_t* shape, int ndim, void* stream) {
   SDMI_CHECK(h && key && ptr && shape, "null argument");
@@ -289,10 +278,10 @@ int sdmi_bert_create(const sdmi_bert_cfg* cfg, sdmi_bert** out) {
   return 0;
 }
 int sdmi_bert_destroy(sdmi_bert* h) { delete h; return 0; }
-int sdmi_bert_num_weights(const sdmi_bert* h) { return h ? (int)h->impl.slots().size() : fail("null handle"); }
+int sdmi_bert_num_weights(const sdmi_bert* h) { return h ? (int)h->impl.weights().slots().size() : fail("null handle"); }
 int sdmi_bert_weight_info(const sdmi_bert* h, int idx, char* key_buf, int key_buf_len, int64_t* shape4, int* ndim) {
-  SDMI_CHECK(h && key_buf && shape4 && ndim, "null argument");
-  return text_weight_info(h->impl, idx, key_buf, key_buf_len, shape4, ndim);
+  SDMI_CHECK(h, "null argument");
+  return weight_info(h->impl.weights(), idx, key_buf, key_buf_len, shape4, ndim);
 }
 int sdmi_bert_set_weight(sdmi_bert* h, const char* key, const float* ptr, const int64_t* shape, int ndim, void* stream) {
   SDMI_CHECK(h && key && ptr && shape, "null argument");

@@ -28,29 +28,29 @@ int BertText::build(const sdmi_bert_cfg& c) {
   SDMI_CHECK(c.depth >= 1 && c.vocab_size >= 1 && c.max_seq_len >= 1, "bad BERT config (depth, vocab_size, max_seq_len >= 1)");
   const int64_t D = c.dim, F = c.ff_inner, I = (int64_t)c.heads * dh;
   layers_.resize(c.depth);
-  expect("token_emb.weight", {c.vocab_size, D}, CW_F32, (void**)&tok_);
-  expect("pos_emb.emb.weight", {c.max_seq_len, D}, CW_F32, (void**)&pos_);
+  store_.expect("token_emb.weight", {c.vocab_size, D}, W_F32, &tok_);
+  store_.expect("pos_emb.emb.weight", {c.max_seq_len, D}, W_F32, &pos_);
   for (int i = 0; i < c.depth; ++i) {   // NOTE: slots point into layers_, which must not reallocate from here on
     BLayer& Ly = layers_[i];
     const std::string a = "attn_layers.layers." + std::to_string(2 * i) + ".";
     const std::string f = "attn_layers.layers." + std::to_string(2 * i + 1) + ".";
-    expect(a + "0.weight", {D}, CW_F32, (void**)&Ly.ln[0]);
-    expect(a + "0.bias", {D}, CW_F32, (void**)&Ly.ln[1]);
+    store_.expect(a + "0.weight", {D}, W_F32, &Ly.ln[0]);
+    store_.expect(a + "0.bias", {D}, W_F32, &Ly.ln[1]);
     const char* names[3] = {"to_q", "to_k", "to_v"};
-    for (int j = 0; j < 3; ++j) expect(a + "1." + names[j] + ".weight", {I, D}, CW_ROWS16, (void**)&Ly.wqkv, j * (int)I, 3 * (int)I);
-    expect(a + "1.to_out.weight", {D, I}, CW_ROWS16, (void**)&Ly.wo, 0, (int)D);
-    expect(a + "1.to_out.bias", {D}, CW_F32, (void**)&Ly.bo);
-    expect(f + "0.weight", {D}, CW_F32, (void**)&Ly.ln[2]);
-    expect(f + "0.bias", {D}, CW_F32, (void**)&Ly.ln[3]);
-    expect(f + "1.net.0.0.weight", {F, D}, CW_ROWS16, (void**)&Ly.w1, 0, (int)F);
-    expect(f + "1.net.0.0.bias", {F}, CW_F32, (void**)&Ly.b1);
-    expect(f + "1.net.2.weight", {D, F}, CW_ROWS16, (void**)&Ly.w2, 0, (int)D);
-    expect(f + "1.net.2.bias", {D}, CW_F32, (void**)&Ly.b2);
+    for (int j = 0; j < 3; ++j) store_.expect(a + "1." + names[j] + ".weight", {I, D}, W_ROWS16, &Ly.wqkv, j * (int)I, 3 * (int)I);
+    store_.expect(a + "1.to_out.weight", {D, I}, W_ROWS16, &Ly.wo);
+    store_.expect(a + "1.to_out.bias", {D}, W_F32, &Ly.bo);
+    store_.expect(f + "0.weight", {D}, W_F32, &Ly.ln[2]);
+    store_.expect(f + "0.bias", {D}, W_F32, &Ly.ln[3]);
+    store_.expect(f + "1.net.0.0.weight", {F, D}, W_ROWS16, &Ly.w1);
+    store_.expect(f + "1.net.0.0.bias", {F}, W_F32, &Ly.b1);
+    store_.expect(f + "1.net.2.weight", {D, F}, W_ROWS16, &Ly.w2);
+    store_.expect(f + "1.net.2.bias", {D}, W_F32, &Ly.b2);
   }
-  expect("norm.weight", {D}, CW_F32, (void**)&fln_g_);
-  expect("norm.bias", {D}, CW_F32, (void**)&fln_b_);
-  expect("to_logits.weight", {c.vocab_size, D}, CW_DROP, nullptr);
-  expect("to_logits.bias", {c.vocab_size}, CW_DROP, nullptr);
+  store_.expect("norm.weight", {D}, W_F32, &fln_g_);
+  store_.expect("norm.bias", {D}, W_F32, &fln_b_);
+  store_.expect("to_logits.weight", {c.vocab_size, D}, W_DROP, nullptr);
+  store_.expect("to_logits.bias", {c.vocab_size}, W_DROP, nullptr);
   return 0;
 }
 
@@ -67,7 +67,7 @@ int BertText::forward(const int64_t* ids, float* out, int B, int L, void* worksp
   // splits of 64 x 64 tiles = 2M floats; room for 16 splits of the widest N at up to 256 rows, 4M floats at least (CLIP's size)
   const int64_t slab_floats = std::max<int64_t>((int64_t)4 << 20, (int64_t)16 * 256 * std::max(D, 3 * I));
   FwdBase f;
-  f.s = stream; f.B = B; f.zero = zero_; f.precise_1x1 = false;
+  f.s = stream; f.B = B; f.zero = store_.zero(); f.precise_1x1 = false;
   int64_t persist_bytes = 0;
   for (int pass = 0; pass < 2; ++pass) {
     const bool d = pass == 0;

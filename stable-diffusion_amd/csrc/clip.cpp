@@ -13,13 +13,6 @@
 
 namespace sdmi {
 
-void TextEncBase::expect(const std::string& key, std::vector<int64_t> shape, CWKind kind, void** dst, int row0, int total_rows) {
-  CWeightSlot s;
-  s.key = key; s.shape = std::move(shape); s.kind = kind; s.dst = dst; s.row0 = row0; s.total_rows = total_rows;
-  slot_index_[key] = (int)slots_.size();
-  slots_.push_back(std::move(s));
-}
-
 int ClipText::build(const sdmi_clip_cfg& c) {
   cfg_ = c;
   SDMI_CHECK(c.hidden_size % 64 == 0 && c.intermediate_size % 64 == 0, "hidden / intermediate size must be multiples of 64");
@@ -30,92 +23,41 @@ int ClipText::build(const sdmi_clip_cfg& c) {
   const int64_t C = c.hidden_size, I = c.intermediate_size;
   layers_.resize(c.num_layers);
   const std::string tm = "text_model.";
-  expect(tm + "embeddings.token_embedding.weight", {c.vocab_size, C}, CW_F32, (void**)&tok_);
-  expect(tm + "embeddings.position_embedding.weight", {c.max_positions, C}, CW_F32, (void**)&pos_);
+  store_.expect(tm + "embeddings.token_embedding.weight", {c.vocab_size, C}, W_F32, &tok_);
+  store_.expect(tm + "embeddings.position_embedding.weight", {c.max_positions, C}, W_F32, &pos_);
   for (int i = 0; i < c.num_layers; ++i) {   // NOTE: slots point into layers_, which must not reallocate from here on
     CLayer& L = layers_[i];
     const std::string p = tm + "encoder.layers." + std::to_string(i) + ".";
     const char* names[3] = {"q_proj", "k_proj", "v_proj"};
     for (int j = 0; j < 3; ++j) {
-      expect(p + "self_attn." + names[j] + ".weight", {C, C}, CW_ROWS16, (void**)&L.wqkv, j * (int)C, 3 * (int)C);
-      expect(p + "self_attn." + names[j] + ".bias", {C}, CW_BIAS_ROWS, (void**)&L.bqkv, j * (int)C, 3 * (int)C);
+      store_.expect(p + "self_attn." + names[j] + ".weight", {C, C}, W_ROWS16, &L.wqkv, j * (int)C, 3 * (int)C);
+      store_.expect(p + "self_attn." + names[j] + ".bias", {C}, W_F32_ROWS, &L.bqkv, j * (int)C, 3 * (int)C);
     }
-    expect(p + "self_attn.out_proj.weight", {C, C}, CW_ROWS16, (void**)&L.wo, 0, (int)C);
-    expect(p + "self_attn.out_proj.bias", {C}, CW_F32, (void**)&L.bo);
-    expect(p + "layer_norm1.weight", {C}, CW_F32, (void**)&L.ln[0]);
-    expect(p + "layer_norm1.bias", {C}, CW_F32, (void**)&L.ln[1]);
-    expect(p + "mlp.fc1.weight", {I, C}, CW_ROWS16, (void**)&L.w1, 0, (int)I);
-    expect(p + "mlp.fc1.bias", {I}, CW_F32, (void**)&L.b1);
-    expect(p + "mlp.fc2.weight", {C, I}, CW_ROWS16, (void**)&L.w2, 0, (int)C);
-    expect(p + "mlp.fc2.bias", {C}, CW_F32, (void**)&L.b2);
-    expect(p + "layer_norm2.weight", {C}, CW_F32, (void**)&L.ln[2]);
-    expect(p + "layer_norm2.bias", {C}, CW_F32, (void**)&L.ln[3]);
+    store_.expect(p + "self_attn.out_proj.weight", {C, C}, W_ROWS16, &L.wo);
+    store_.expect(p + "self_attn.out_proj.bias", {C}, W_F32, &L.bo);
+    store_.expect(p + "layer_norm1.weight", {C}, W_F32, &L.ln[0]);
+    store_.expect(p + "layer_norm1.bias", {C}, W_F32, &L.ln[1]);
+    store_.expect(p + "mlp.fc1.weight", {I, C}, W_ROWS16, &L.w1);
+    store_.expect(p + "mlp.fc1.bias", {I}, W_F32, &L.b1);
+    store_.expect(p + "mlp.fc2.weight", {C, I}, W_ROWS16, &L.w2);
+    store_.expect(p + "mlp.fc2.bias", {C}, W_F32, &L.b2);
+    store_.expect(p + "layer_norm2.weight", {C}, W_F32, &L.ln[2]);
+    store_.expect(p + "layer_norm2.bias", {C}, W_F32, &L.ln[3]);
   }
-  expect(tm + "final_layer_norm.weight", {C}, CW_F32, (void**)&fln_g_);
-  expect(tm + "final_layer_norm.bias", {C}, CW_F32, (void**)&fln_b_);
-  return 0;
-}
-
-TextEncBase::~TextEncBase() {
-  for (void* p : owned_) (void)hipFree(p);
-}
-
-int TextEncBase::dev_alloc(void** dst, size_t bytes) {
-  if (*dst) return 0;
-  SDMI_HIP_OK(hipMalloc(dst, bytes));
-  owned_.push_back(*dst);
+  store_.expect(tm + "final_layer_norm.weight", {C}, W_F32, &fln_g_);
+  store_.expect(tm + "final_layer_norm.bias", {C}, W_F32, &fln_b_);
   return 0;
 }
 
 int TextEncBase::set_weight(const char* key, const float* ptr, const int64_t* shape, int ndim, hipStream_t stream) {
-  auto it = slot_index_.find(key);
-  if (it == slot_index_.end()) return fail(std::string("unexpected weight key: ") + key);
-  CWeightSlot& s = slots_[it->second];
-  SDMI_CHECK((int)s.shape.size() == ndim, std::string("rank mismatch for ") + key);
-  int64_t numel = 1;
-  for (int i = 0; i < ndim; ++i) {
-    SDMI_CHECK(shape[i] == s.shape[i], std::string("shape mismatch for ") + key);
-    numel *= shape[i];
-  }
-  if (s.kind == CW_DROP) {
-    s.set = true;
-    return 0;
-  }
-  DevStage st;
-  if (st.acquire(ptr, numel, stream)) return -1;
-  int rc = 0;
-  switch (s.kind) {
-    case CW_F32:
-      rc = dev_alloc(s.dst, numel * sizeof(float));
-      if (!rc) SDMI_HIP_OK(hipMemcpyAsync(*s.dst, st.dptr, numel * sizeof(float), hipMemcpyDeviceToDevice, stream));
-      break;
-    case CW_ROWS16:      // rows [row0, row0 + rows) of an fp16 [total_rows][cols] matrix (q | k | v concatenation)
-      rc = dev_alloc(s.dst, (size_t)s.total_rows * shape[1] * sizeof(f16));
-      if (!rc) rc = launch_pack_rows(st.dptr, (f16*)*s.dst, (int)shape[0], (int)shape[1], s.row0, (int)shape[1], stream);
-      break;
-    case CW_BIAS_ROWS:   // slice [row0, row0 + n) of a concatenated fp32 bias
-      rc = dev_alloc(s.dst, (size_t)s.total_rows * sizeof(float));
-      if (!rc)
-        SDMI_HIP_OK(hipMemcpyAsync((float*)*s.dst + s.row0, st.dptr, numel * sizeof(float), hipMemcpyDeviceToDevice, stream));
-      break;
-    case CW_DROP:
-      break;
-  }
-  if (st.release(stream)) return -1;
-  if (rc) return rc;
-  s.set = true;
+  if (int rc = store_.set(key, ptr, shape, ndim, stream)) return rc;
   finalized_ = false;
   return 0;
 }
 
 int TextEncBase::finalize() {
-  for (auto& s : slots_)
-    if (!s.set && s.kind != CW_DROP) return fail("weight not set: " + s.key);
-  if (!zero_) {
-    SDMI_HIP_OK(hipMalloc((void**)&zero_, 4096));
-    owned_.push_back(zero_);
-    SDMI_HIP_OK(hipMemset(zero_, 0, 4096));
-  }
+  if (const WeightSlot* m = store_.missing()) return fail("weight not set: " + m->key);
+  if (store_.zero_page()) return -1;
   finalized_ = true;
   return 0;
 }
@@ -129,7 +71,7 @@ int ClipText::forward(const int64_t* ids, float* out, int B, int L, void* worksp
   const int M = B * L, Lp = (int)round_up(L, 8);
   const float scale = 1.0f / sqrtf((float)dh);
   FwdBase f;
-  f.s = stream; f.B = B; f.zero = zero_; f.precise_1x1 = false;
+  f.s = stream; f.B = B; f.zero = store_.zero(); f.precise_1x1 = false;
   int64_t persist_bytes = 0;
   for (int pass = 0; pass < 2; ++pass) {
     const bool d = pass == 0;

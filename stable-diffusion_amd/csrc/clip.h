@@ -1,7 +1,6 @@
 // Text-encoder executor state: HF CLIPTextModel as wrapped by FrozenCLIPEmbedder (clip.cpp) and the LAION-400M model's
 // BERTEmbedder transformer (bert.cpp).
 #pragma once
-#include <map>
 #include <string>
 #include <vector>
 
@@ -11,9 +10,6 @@
 
 namespace sdmi {
 
-// CW_DROP: accepted (shape-checked) and never uploaded -- a checkpoint tensor the forward does not use
-enum CWKind { CW_F32, CW_ROWS16, CW_BIAS_ROWS, CW_DROP };
-
 struct CLayer {   // CLIPEncoderLayer
   f16* wqkv = nullptr; float* bqkv = nullptr;     // [3C][C], [3C]   q_proj | k_proj | v_proj
   f16* wo = nullptr; float* bo = nullptr;
@@ -22,34 +18,15 @@ struct CLayer {   // CLIPEncoderLayer
   float* ln[4] = {nullptr, nullptr, nullptr, nullptr};   // layer_norm1.{weight,bias}, layer_norm2.{weight,bias}
 };
 
-struct CWeightSlot {
-  std::string key;
-  std::vector<int64_t> shape;
-  CWKind kind = CW_F32;
-  void** dst = nullptr; int row0 = 0, total_rows = 0;
-  bool set = false;
-};
-
-// Host plumbing shared by the text encoders: the weight-slot table (key -> shape, packing kind, device destination), staging of
-// caller tensors, device allocation and the all-set check.  No device code of its own.
+// Host plumbing shared by the text encoders: the weight store and the all-set check.  No device code of its own.
 class TextEncBase {
  public:
-  TextEncBase() = default;
-  ~TextEncBase();
-  TextEncBase(const TextEncBase&) = delete;
-  TextEncBase& operator=(const TextEncBase&) = delete;
-
   int set_weight(const char* key, const float* ptr, const int64_t* shape, int ndim, hipStream_t stream);
   int finalize();
-  const std::vector<CWeightSlot>& slots() const { return slots_; }
+  const WeightStore& weights() const { return store_; }
 
  protected:
-  void expect(const std::string& key, std::vector<int64_t> shape, CWKind kind, void** dst, int row0 = 0, int total_rows = 0);
-  int dev_alloc(void** dst, size_t bytes);
-  std::vector<CWeightSlot> slots_;
-  std::map<std::string, int> slot_index_;
-  std::vector<void*> owned_;
-  f16* zero_ = nullptr;
+  WeightStore store_;           // (slots point into the layer objects of the derived class)
   bool finalized_ = false;
 };
 

@@ -31,14 +31,6 @@ static bool in_list(const int* v, int n, int x) {
   return false;
 }
 
-void UNet::expect(const std::string& key, std::vector<int64_t> shape, WKind kind, void** dst, int row0, int ld,
-                  void** dst2) {
-  WeightSlot s;
-  s.key = key; s.shape = std::move(shape); s.kind = kind; s.dst = dst; s.row0 = row0; s.ld = ld; s.dst2 = dst2;
-  slot_index_[key] = (int)slots_.size();
-  slots_.push_back(std::move(s));
-}
-
 thread_local Tape* g_tape_rec = nullptr;
 
 namespace {
@@ -166,8 +158,10 @@ int UNet::build(const sdmi_unet_cfg& c, int precision, const sdmi_unet_ext* ext,
   }
 
   {                          // (the attention kernels are instantiated per head dim)
-    auto check = [&](const Layer& L) -> int {
-      if (L.kind == L_ATTN) {      // wide heads (num_heads = 1: d_head = C) run on attn_wide.hip, which has no split-fp16 form yet
+    if (for_each_layer([&](const Layer& L) -> int {
+      // wide heads (num_heads = 1: d_head = C) run on attn_wide.hip; its split-fp16 form attn_wide_split16.hip exists, but this executor
+      // does not dispatch to it
+      if (L.kind == L_ATTN) {
         SDMI_CHECK(!(full() && L.dh > 160), L.prefix + ": attention head dim " + std::to_string(L.dh) +
                    " has no full-precision kernel (split-fp16 attention is instantiated up to head dim 160)");
         return 0;
@@ -180,10 +174,7 @@ int UNet::build(const sdmi_unet_cfg& c, int precision, const sdmi_unet_ext* ext,
       SDMI_CHECK(L.dh == 24 || L.dh == 32 || L.dh == 40 || L.dh == 48 || L.dh == 64 || L.dh == 80 || L.dh == 96 || L.dh == 128 || L.dh == 160,
                  L.prefix + ": attention head dim " + std::to_string(L.dh) + " not instantiated (24/32/40/48/64/80/96/128/160)");
       return 0;
-    };
-    for (auto& blk : input_blocks_) for (auto& L : blk) if (check(L)) return -1;
-    for (auto& L : middle_) if (check(L)) return -1;
-    for (auto& blk : output_blocks_) for (auto& L : blk) if (check(L)) return -1;
+    })) return -1;
   }
 
   // the last ResBlock (output_blocks.<last>.0: its two 3x3 convs are the largest single contributors to the eps error)
@@ -192,269 +183,122 @@ int UNet::build(const sdmi_unet_cfg& c, int precision, const sdmi_unet_ext* ext,
 
   // ---- expected state_dict entries and where each one is packed to -------------------
   const int64_t TE = te_;
-  expect("time_embed.0.weight", {TE, mc}, W_F32, (void**)&te_w0_);
-  expect("time_embed.0.bias", {TE}, W_F32, (void**)&te_b0_);
-  expect("time_embed.2.weight", {TE, TE}, W_F32, (void**)&te_w2_);
-  expect("time_embed.2.bias", {TE}, W_F32, (void**)&te_b2_);
-  auto visit = [&](Layer& L) {
+  store_.expect("time_embed.0.weight", {TE, mc}, W_F32, &te_w0_);
+  store_.expect("time_embed.0.bias", {TE}, W_F32, &te_b0_);
+  store_.expect("time_embed.2.weight", {TE, TE}, W_F32, &te_w2_);
+  store_.expect("time_embed.2.bias", {TE}, W_F32, &te_b2_);
+  for_each_layer([&](Layer& L) -> int {
     const std::string& p = L.prefix;
     const int64_t ci = L.cin, co = L.cout;
     switch (L.kind) {
       case L_CONV_IN:
-        expect(p + ".weight", {co, ci, 3, 3}, W_F32, (void**)&L.w32[0]);
-        expect(p + ".bias", {co}, W_F32, (void**)&L.f32[0]);
+        store_.expect(p + ".weight", {co, ci, 3, 3}, W_F32, &L.w32[0]);
+        store_.expect(p + ".bias", {co}, W_F32, &L.f32[0]);
         break;
       case L_RES:
-        expect(p + ".in_layers.0.weight", {ci}, W_F32, (void**)&L.f32[0]);
-        expect(p + ".in_layers.0.bias", {ci}, W_F32, (void**)&L.f32[1]);
-        expect(p + ".in_layers.2.weight", {co, ci, 3, 3}, L.precise3 ? W_CONV_SPLIT3 : W_CONV, (void**)&L.w16[0]);
-        expect(p + ".in_layers.2.bias", {co}, W_F32, (void**)&L.f32[2]);
-        expect(p + ".emb_layers.1.weight", {scale_shift_ ? 2 * co : co, TE}, W_F32_ROWS, (void**)&emb_w_, L.emb_off, te_);
-        expect(p + ".emb_layers.1.bias", {scale_shift_ ? 2 * co : co}, W_F32_ROWS, (void**)&emb_b_, L.emb_off, 1);
-        expect(p + ".out_layers.0.weight", {co}, W_F32, (void**)&L.f32[3]);
-        expect(p + ".out_layers.0.bias", {co}, W_F32, (void**)&L.f32[4]);
-        expect(p + ".out_layers.3.weight", {co, co, 3, 3}, L.precise3 ? W_CONV_SPLIT3 : W_CONV, (void**)&L.w16[1]);
-        expect(p + ".out_layers.3.bias", {co}, W_F32, (void**)&L.f32[5]);
+        store_.expect(p + ".in_layers.0.weight", {ci}, W_F32, &L.f32[0]);
+        store_.expect(p + ".in_layers.0.bias", {ci}, W_F32, &L.f32[1]);
+        store_.expect(p + ".in_layers.2.weight", {co, ci, 3, 3}, L.precise3 ? W_CONV_SPLIT3 : W_CONV, &L.w16[0]);
+        store_.expect(p + ".in_layers.2.bias", {co}, W_F32, &L.f32[2]);
+        store_.expect(p + ".emb_layers.1.weight", {scale_shift_ ? 2 * co : co, TE}, W_F32_ROWS, &emb_w_, L.emb_off, emb_total_);
+        store_.expect(p + ".emb_layers.1.bias", {scale_shift_ ? 2 * co : co}, W_F32_ROWS, &emb_b_, L.emb_off, emb_total_);
+        store_.expect(p + ".out_layers.0.weight", {co}, W_F32, &L.f32[3]);
+        store_.expect(p + ".out_layers.0.bias", {co}, W_F32, &L.f32[4]);
+        store_.expect(p + ".out_layers.3.weight", {co, co, 3, 3}, L.precise3 ? W_CONV_SPLIT3 : W_CONV, &L.w16[1]);
+        store_.expect(p + ".out_layers.3.bias", {co}, W_F32, &L.f32[5]);
         if (ci != co) {
-          expect(p + ".skip_connection.weight", {co, ci, 1, 1}, L.p1x1 ? W_SPLIT3 : W_CONV, (void**)&L.w16[2]);
-          expect(p + ".skip_connection.bias", {co}, W_F32, (void**)&L.f32[6]);
+          store_.expect(p + ".skip_connection.weight", {co, ci, 1, 1}, L.p1x1 ? W_SPLIT3 : W_CONV, &L.w16[2]);
+          store_.expect(p + ".skip_connection.bias", {co}, W_F32, &L.f32[6]);
         }
         break;
       case L_ATTN: {
         const int64_t C = ci, CD = cfg_.context_dim;
-        expect(p + ".norm.weight", {C}, W_F32, (void**)&L.f32[0]);
-        expect(p + ".norm.bias", {C}, W_F32, (void**)&L.f32[1]);
-        expect(p + ".proj_in.weight", {C, C, 1, 1}, L.p1x1 ? W_SPLIT3 : W_CONV, (void**)&L.w16[0]);
-        expect(p + ".proj_in.bias", {C}, W_F32, (void**)&L.f32[2]);
-        expect(p + ".proj_out.weight", {C, C, 1, 1}, L.p1x1 ? W_SPLIT3 : W_CONV, (void**)&L.w16[1]);
-        expect(p + ".proj_out.bias", {C}, W_F32, (void**)&L.f32[3]);
+        store_.expect(p + ".norm.weight", {C}, W_F32, &L.f32[0]);
+        store_.expect(p + ".norm.bias", {C}, W_F32, &L.f32[1]);
+        store_.expect(p + ".proj_in.weight", {C, C, 1, 1}, L.p1x1 ? W_SPLIT3 : W_CONV, &L.w16[0]);
+        store_.expect(p + ".proj_in.bias", {C}, W_F32, &L.f32[2]);
+        store_.expect(p + ".proj_out.weight", {C, C, 1, 1}, L.p1x1 ? W_SPLIT3 : W_CONV, &L.w16[1]);
+        store_.expect(p + ".proj_out.bias", {C}, W_F32, &L.f32[3]);
         L.tb.resize(cfg_.transformer_depth);
         for (int d = 0; d < cfg_.transformer_depth; ++d) {
           TBlock& T = L.tb[d];
           const std::string t = p + ".transformer_blocks." + std::to_string(d);
           // full mode: every linear split-fp16 ([rows][3 K] = [hi | hi | lo]), the GEGLU projection in the reference's column order
           const WKind lin = full() ? W_SPLIT3_ROWS : W_ROWS16;
-          expect(t + ".attn1.to_q.weight", {C, C}, lin, (void**)&T.wqkv, 0, (int)C);
-          expect(t + ".attn1.to_k.weight", {C, C}, lin, (void**)&T.wqkv, (int)C, (int)C);
-          expect(t + ".attn1.to_v.weight", {C, C}, lin, (void**)&T.wqkv, 2 * (int)C, (int)C);
-          expect(t + ".attn1.to_out.0.weight", {C, C}, lin, (void**)&T.wo1, 0, (int)C);
-          expect(t + ".attn1.to_out.0.bias", {C}, W_F32, (void**)&T.bo1);
-          expect(t + ".attn2.to_q.weight", {C, C}, lin, (void**)&T.wq2, 0, (int)C);
+          store_.expect(t + ".attn1.to_q.weight", {C, C}, lin, &T.wqkv, 0, 3 * (int)C);
+          store_.expect(t + ".attn1.to_k.weight", {C, C}, lin, &T.wqkv, (int)C, 3 * (int)C);
+          store_.expect(t + ".attn1.to_v.weight", {C, C}, lin, &T.wqkv, 2 * (int)C, 3 * (int)C);
+          store_.expect(t + ".attn1.to_out.0.weight", {C, C}, lin, &T.wo1);
+          store_.expect(t + ".attn1.to_out.0.bias", {C}, W_F32, &T.bo1);
+          store_.expect(t + ".attn2.to_q.weight", {C, C}, lin, &T.wq2);
           // round 6: the context K / V projections as 3-pass split-fp16 (k_hi w_hi + k_lo w_hi + k_hi w_lo, one K-concatenated GEMM): the
           // context is the one operand of the call with channel outliers by construction (CLIP's last_hidden_state has channels at
           // |x| ~ 30) and its fp16 rounding was the error class that grew most (11x) on the outlier goldens (tools/precision_emul.py);
           // computed once per prompt and cached for all 51 calls, so the extra passes cost nothing per UNet call
-          expect(t + ".attn2.to_k.weight", {C, CD}, precise_kv_ ? W_SPLIT3_ROWS : W_ROWS16, (void**)&T.wkv2, 0, (int)CD);
-          expect(t + ".attn2.to_v.weight", {C, CD}, precise_kv_ ? W_SPLIT3_ROWS : W_ROWS16, (void**)&T.wkv2, (int)C, (int)CD);
-          expect(t + ".attn2.to_out.0.weight", {C, C}, lin, (void**)&T.wo2, 0, (int)C);
-          expect(t + ".attn2.to_out.0.bias", {C}, W_F32, (void**)&T.bo2);
-          expect(t + ".ff.net.0.proj.weight", {8 * C, C}, full() ? W_SPLIT3 : W_GEGLU_W, (void**)&T.wgg);
-          expect(t + ".ff.net.0.proj.bias", {8 * C}, full() ? W_F32 : W_GEGLU_B, (void**)&T.bgg);
-          expect(t + ".ff.net.2.weight", {C, 4 * C}, lin, (void**)&T.wff2, 0, 4 * (int)C);
-          expect(t + ".ff.net.2.bias", {C}, W_F32, (void**)&T.bff2);
-          expect(t + ".norm1.weight", {C}, W_F32, (void**)&T.ln[0]);
-          expect(t + ".norm1.bias", {C}, W_F32, (void**)&T.ln[1]);
-          expect(t + ".norm2.weight", {C}, W_F32, (void**)&T.ln[2]);
-          expect(t + ".norm2.bias", {C}, W_F32, (void**)&T.ln[3]);
-          expect(t + ".norm3.weight", {C}, W_F32, (void**)&T.ln[4]);
-          expect(t + ".norm3.bias", {C}, W_F32, (void**)&T.ln[5]);
+          store_.expect(t + ".attn2.to_k.weight", {C, CD}, precise_kv_ ? W_SPLIT3_ROWS : W_ROWS16, &T.wkv2, 0, 2 * (int)C);
+          store_.expect(t + ".attn2.to_v.weight", {C, CD}, precise_kv_ ? W_SPLIT3_ROWS : W_ROWS16, &T.wkv2, (int)C, 2 * (int)C);
+          store_.expect(t + ".attn2.to_out.0.weight", {C, C}, lin, &T.wo2);
+          store_.expect(t + ".attn2.to_out.0.bias", {C}, W_F32, &T.bo2);
+          store_.expect(t + ".ff.net.0.proj.weight", {8 * C, C}, full() ? W_SPLIT3 : W_GEGLU_W, &T.wgg);
+          store_.expect(t + ".ff.net.0.proj.bias", {8 * C}, full() ? W_F32 : W_GEGLU_B, &T.bgg);
+          store_.expect(t + ".ff.net.2.weight", {C, 4 * C}, lin, &T.wff2);
+          store_.expect(t + ".ff.net.2.bias", {C}, W_F32, &T.bff2);
+          store_.expect(t + ".norm1.weight", {C}, W_F32, &T.ln[0]);
+          store_.expect(t + ".norm1.bias", {C}, W_F32, &T.ln[1]);
+          store_.expect(t + ".norm2.weight", {C}, W_F32, &T.ln[2]);
+          store_.expect(t + ".norm2.bias", {C}, W_F32, &T.ln[3]);
+          store_.expect(t + ".norm3.weight", {C}, W_F32, &T.ln[4]);
+          store_.expect(t + ".norm3.bias", {C}, W_F32, &T.ln[5]);
         }
         break;
       }
       case L_ATTN_LEGACY: {      // AttentionBlock (openaimodel.py:302-312): conv1d weights [out][in][1]
         const int64_t C = ci;
         const bool pq = L.p1x1;              // qkv as split-fp16 (the GroupNorm writes hi | lo) where the 1x1 allocation says so
-        expect(p + ".norm.weight", {C}, W_F32, (void**)&L.f32[0]);
-        expect(p + ".norm.bias", {C}, W_F32, (void**)&L.f32[1]);
-        expect(p + ".qkv.weight", {3 * C, C, 1}, W_QKV_LEGACY, (void**)&L.w16[0], L.heads, pq ? 1 : 0);
-        expect(p + ".qkv.bias", {3 * C}, W_QKV_LEGACY_B, (void**)&L.f32[2], L.heads, 0);
+        store_.expect(p + ".norm.weight", {C}, W_F32, &L.f32[0]);
+        store_.expect(p + ".norm.bias", {C}, W_F32, &L.f32[1]);
+        WeightSlot& qkv = store_.expect(p + ".qkv.weight", {3 * C, C, 1}, W_QKV_LEGACY, &L.w16[0]);
+        qkv.heads = L.heads; qkv.split = pq;
+        store_.expect(p + ".qkv.bias", {3 * C}, W_QKV_LEGACY_B, &L.f32[2]).heads = L.heads;
         // proj_out reads the attention output: fp16 in the mixed mode, hi | lo in the full mode
-        expect(p + ".proj_out.weight", {C, C, 1}, full() ? W_SPLIT3 : W_ROWS16, (void**)&L.w16[1], 0, (int)C);
-        expect(p + ".proj_out.bias", {C}, W_F32, (void**)&L.f32[3]);
+        store_.expect(p + ".proj_out.weight", {C, C, 1}, full() ? W_SPLIT3 : W_ROWS16, &L.w16[1]);
+        store_.expect(p + ".proj_out.bias", {C}, W_F32, &L.f32[3]);
         break;
       }
       case L_DOWN:
-        expect(p + ".op.weight", {co, ci, 3, 3}, full() ? W_CONV_SPLIT3 : W_CONV, (void**)&L.w16[0]);
-        expect(p + ".op.bias", {co}, W_F32, (void**)&L.f32[0]);
+        store_.expect(p + ".op.weight", {co, ci, 3, 3}, full() ? W_CONV_SPLIT3 : W_CONV, &L.w16[0]);
+        store_.expect(p + ".op.bias", {co}, W_F32, &L.f32[0]);
         break;
       case L_UP:
-        expect(p + ".conv.weight", {co, ci, 3, 3}, full() ? W_CONV_SPLIT3 : W_CONV, (void**)&L.w16[0]);
-        expect(p + ".conv.bias", {co}, W_F32, (void**)&L.f32[0]);
+        store_.expect(p + ".conv.weight", {co, ci, 3, 3}, full() ? W_CONV_SPLIT3 : W_CONV, &L.w16[0]);
+        store_.expect(p + ".conv.bias", {co}, W_F32, &L.f32[0]);
         break;
     }
-  };
-  // NOTE: slots hold pointers into the Layer objects, so the containers must not reallocate after this point.
-  for (auto& blk : input_blocks_) for (auto& L : blk) visit(L);
-  for (auto& L : middle_) visit(L);
-  for (auto& blk : output_blocks_) for (auto& L : blk) visit(L);
-  expect("out.0.weight", {mc}, W_F32, (void**)&out_gamma_);
-  expect("out.0.bias", {mc}, W_F32, (void**)&out_beta_);
-  expect("out.2.weight", {c.out_channels, mc, 3, 3}, W_CONV_OUT, (void**)&out_w_);
-  expect("out.2.bias", {c.out_channels}, W_F32, (void**)&out_b_);
-  return 0;
-}
-
-int DevStage::acquire(const float* ptr, int64_t numel, hipStream_t stream) {
-  dptr = ptr;
-  hipPointerAttribute_t attr;
-  hipError_t e = hipPointerGetAttributes(&attr, ptr);
-  const bool on_device = (e == hipSuccess) && (attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged);
-  if (e != hipSuccess) (void)hipGetLastError();
-  if (!on_device) {
-    SDMI_HIP_OK(hipMalloc((void**)&staged, numel * sizeof(float)));
-    SDMI_HIP_OK(hipMemcpyAsync(staged, ptr, numel * sizeof(float), hipMemcpyHostToDevice, stream));
-    dptr = staged;
-  }
-  return 0;
-}
-int DevStage::release(hipStream_t stream) {
-  if (staged) {
-    SDMI_HIP_OK(hipStreamSynchronize(stream));
-    (void)hipFree(staged);
-    staged = nullptr;
-  }
+    return 0;
+  });       // NOTE: slots hold pointers into the Layer objects, so the containers must not reallocate after this point.
+  store_.expect("out.0.weight", {mc}, W_F32, &out_gamma_);
+  store_.expect("out.0.bias", {mc}, W_F32, &out_beta_);
+  store_.expect("out.2.weight", {c.out_channels, mc, 3, 3}, W_CONV_OUT, &out_w_);
+  store_.expect("out.2.bias", {c.out_channels}, W_F32, &out_b_);
   return 0;
 }
 
 UNet::~UNet() {
-  for (void* p : owned_) (void)hipFree(p);
   if (emb_tab_) (void)hipFree(emb_tab_);
   if (emb_tab_tdev_) (void)hipFree(emb_tab_tdev_);
-  auto drop_ctx = [](Layer& L) {            // cross-attention K / V^T caches (ensure_ctx_cache)
+  for_each_layer([](Layer& L) -> int {      // cross-attention K / V^T caches (ensure_ctx_cache)
     for (auto& T : L.tb) {
       if (T.ck) (void)hipFree(T.ck);
       if (T.cvt) (void)hipFree(T.cvt);
       if (T.ck_lo) (void)hipFree(T.ck_lo);
       if (T.cvt_lo) (void)hipFree(T.cvt_lo);
     }
-  };
-  for (auto& blk : input_blocks_) for (auto& L : blk) drop_ctx(L);
-  for (auto& L : middle_) drop_ctx(L);
-  for (auto& blk : output_blocks_) for (auto& L : blk) drop_ctx(L);
-}
-
-int UNet::dev_alloc(void** dst, size_t bytes) {
-  if (*dst) return 0;
-  SDMI_HIP_OK(hipMalloc(dst, bytes));
-  owned_.push_back(*dst);
-  return 0;
-}
-
-// bytes of the packed device buffer a slot writes into (several slots may share one buffer: q|k|v rows, emb_layers rows)
-size_t UNet::slot_bytes(const WeightSlot& s) const {
-  size_t numel = 1;
-  for (int64_t d : s.shape) numel *= (size_t)d;
-  switch (s.kind) {
-    case W_F32: case W_CONV_OUT: case W_GEGLU_B: case W_QKV_LEGACY_B: return numel * sizeof(float);
-    case W_QKV_LEGACY: return numel * sizeof(f16) * (s.ld ? 3 : 1);
-    case W_F32_ROWS: return (size_t)emb_total_ * s.ld * sizeof(float);
-    case W_CONV: case W_GEGLU_W: return numel * sizeof(f16);
-    case W_SPLIT3: case W_CONV_SPLIT3: return 3 * numel * sizeof(f16);
-    case W_SPLIT3_ROWS: case W_ROWS16: {       // (row blocks of one buffer: to_q | to_k | to_v of attn1, to_k | to_v of attn2)
-      size_t total_rows = (size_t)s.shape[0];
-      if (s.key.find(".attn1.to_") != std::string::npos && s.key.find("to_out") == std::string::npos) total_rows *= 3;
-      if (s.key.find(".attn2.to_k") != std::string::npos || s.key.find(".attn2.to_v") != std::string::npos) total_rows *= 2;
-      return total_rows * s.ld * sizeof(f16) * (s.kind == W_SPLIT3_ROWS ? 3 : 1);
-    }
-  }
-  return 0;
+    return 0;
+  });
 }
 
 int UNet::set_weight(const char* key, const float* ptr, const int64_t* shape, int ndim, hipStream_t stream) {
-  auto it = slot_index_.find(key);
-  if (it == slot_index_.end()) return fail(std::string("unexpected weight key: ") + key);
-  WeightSlot& s = slots_[it->second];
-  SDMI_CHECK((int)s.shape.size() == ndim, std::string("rank mismatch for ") + key);
-  int64_t numel = 1;
-  for (int i = 0; i < ndim; ++i) {
-    SDMI_CHECK(shape[i] == s.shape[i], std::string("shape mismatch for ") + key);
-    numel *= shape[i];
-  }
-  DevStage st;
-  if (st.acquire(ptr, numel, stream)) return -1;
-  const float* dptr = st.dptr;
-  int rc = 0;
-  switch (s.kind) {
-    case W_F32:
-      rc = dev_alloc(s.dst, slot_bytes(s));
-      if (!rc) SDMI_HIP_OK(hipMemcpyAsync(*s.dst, dptr, numel * sizeof(float), hipMemcpyDeviceToDevice, stream));
-      break;
-    case W_F32_ROWS: {   // rows of a concatenated fp32 matrix (the 22 emb_layers)
-      rc = dev_alloc(s.dst, slot_bytes(s));
-      if (!rc)
-        SDMI_HIP_OK(hipMemcpyAsync((float*)*s.dst + (size_t)s.row0 * s.ld, dptr, numel * sizeof(float),
-                                   hipMemcpyDeviceToDevice, stream));
-      break;
-    }
-    case W_CONV:
-      rc = dev_alloc(s.dst, slot_bytes(s));
-      if (!rc) rc = launch_pack_conv_weight(dptr, (f16*)*s.dst, (int)shape[0], (int)shape[1], (int)shape[2], (int)shape[3], stream);
-      break;
-    case W_SPLIT3:
-      rc = dev_alloc(s.dst, slot_bytes(s));
-      if (!rc) rc = launch_pack_split3(dptr, (f16*)*s.dst, (int)shape[0], (int)shape[1], stream);
-      break;
-    case W_CONV_SPLIT3:
-      rc = dev_alloc(s.dst, slot_bytes(s));
-      if (!rc) rc = launch_pack_conv_split3(dptr, (f16*)*s.dst, (int)shape[0], (int)shape[1], (int)shape[2], (int)shape[3], stream);
-      break;
-    case W_SPLIT3_ROWS:  // rows [row0, row0 + rows) of a split-fp16 [*][3 ld] matrix
-      rc = dev_alloc(s.dst, slot_bytes(s));
-      if (!rc) rc = launch_pack_split3(dptr, (f16*)*s.dst + (size_t)s.row0 * 3 * s.ld, (int)shape[0], (int)shape[1], stream);
-      break;
-    case W_CONV_OUT:
-      rc = dev_alloc(s.dst, slot_bytes(s));
-      if (!rc) rc = launch_pack_conv_out(dptr, (float*)*s.dst, (int)shape[0], (int)shape[1], stream);
-      break;
-    case W_ROWS16: {     // rows [row0, row0+rows) of an fp16 [*, ld] matrix (q|k|v and k|v concatenations)
-      const int rows = (int)shape[0];
-      rc = dev_alloc(s.dst, slot_bytes(s));
-      if (!rc) rc = launch_pack_rows(dptr, (f16*)*s.dst, rows, (int)shape[1], s.row0, s.ld, stream);
-      break;
-    }
-    case W_QKV_LEGACY:
-    case W_QKV_LEGACY_B: {
-      // QKVAttentionLegacy (openaimodel.py:361-366) reads the qkv rows as [head][q | k | v][channel]: reference row h * 3d + j * d + i
-      // becomes packed row j * C + h * d + i, the [q | k | v] head-major order of the SpatialTransformer's fused projection
-      const int R = (int)shape[0], K = s.kind == W_QKV_LEGACY ? (int)shape[1] : 1, heads = s.row0, C = R / 3, d = C / heads;
-      float* perm = nullptr;
-      rc = dev_alloc(s.dst, slot_bytes(s));
-      if (!rc && s.kind == W_QKV_LEGACY) SDMI_HIP_OK(hipMalloc((void**)&perm, (size_t)R * K * sizeof(float)));
-      float* dst = s.kind == W_QKV_LEGACY ? perm : (float*)*s.dst;
-      for (int h = 0; !rc && h < heads; ++h)
-        for (int j = 0; j < 3; ++j)
-          SDMI_HIP_OK(hipMemcpyAsync(dst + ((size_t)j * C + (size_t)h * d) * K, dptr + ((size_t)h * 3 * d + (size_t)j * d) * K,
-                                     (size_t)d * K * sizeof(float), hipMemcpyDeviceToDevice, stream));
-      if (!rc && s.kind == W_QKV_LEGACY)
-        rc = s.ld ? launch_pack_split3(perm, (f16*)*s.dst, R, K, stream) : launch_pack_rows(perm, (f16*)*s.dst, R, K, 0, K, stream);
-      if (perm) {
-        SDMI_HIP_OK(hipStreamSynchronize(stream));
-        (void)hipFree(perm);
-      }
-      break;
-    }
-    case W_GEGLU_W: {
-      // weight and bias arrive separately; the weight packer does not need the bias (and vice versa)
-      rc = dev_alloc(s.dst, slot_bytes(s));
-      if (!rc) rc = launch_pack_geglu(dptr, nullptr, (f16*)*s.dst, nullptr, (int)shape[0], (int)shape[1], stream);
-      break;
-    }
-    case W_GEGLU_B: {
-      rc = dev_alloc(s.dst, slot_bytes(s));
-      // permute the bias with the same 32-row interleave: reuse the packer with K = 1 on a [N][1] "matrix"
-      if (!rc) {
-        f16* tmp = nullptr;
-        SDMI_HIP_OK(hipMalloc((void**)&tmp, numel * sizeof(f16)));
-        rc = launch_pack_geglu(dptr, dptr, tmp, (float*)*s.dst, (int)shape[0], 1, stream);
-        SDMI_HIP_OK(hipStreamSynchronize(stream));
-        (void)hipFree(tmp);
-      }
-      break;
-    }
-  }
-  if (st.release(stream)) return -1;
-  if (rc) return rc;
-  s.set = true;
+  if (int rc = store_.set(key, ptr, shape, ndim, stream)) return rc;
   ++weights_gen_;            // (recorded launch tapes point into the packed buffers / were planned for them)
   finalized_ = false;
   ctx_valid_ = false;      // cached cross-attention K/V were computed with the previous to_k / to_v weights
@@ -463,18 +307,13 @@ int UNet::set_weight(const char* key, const float* ptr, const int64_t* shape, in
 }
 
 int UNet::finalize() {
-  for (auto& s : slots_)
-    if (!s.set) return fail("weight not set: " + s.key);
-  if (!zero_) {
-    SDMI_HIP_OK(hipMalloc((void**)&zero_, 4096));
-    owned_.push_back(zero_);
-    SDMI_HIP_OK(hipMemset(zero_, 0, 4096));
-  }
+  if (const WeightSlot* m = store_.missing()) return fail("weight not set: " + m->key);
+  if (store_.zero_page()) return -1;
   if (reserve_ctx_cache(8, 77)) return -1;       // default K/V capacity (a no-op once reserved)
   // column terms of the GEMMs that fold a LayerNorm of their input rows (derived from the packed weights: not part of the blob)
   {
     SDMI_HIP_OK(hipDeviceSynchronize());          // (the packing kernels ran on the caller's streams; finalize is off the hot path)
-    auto each = [&](Layer& L) -> int {
+    if (for_each_layer([&](Layer& L) -> int {
       if (L.kind != L_ATTN || full()) return 0;        // (full mode: no LayerNorm fold, and its weights are split-fp16)
       const int C = L.cin;
       for (auto& T : L.tb) {
@@ -482,12 +321,12 @@ int UNet::finalize() {
         const f16* w_[3] = {T.wqkv, T.wq2, T.wgg};
         const float* b_[3] = {nullptr, nullptr, T.bgg};
         for (int i = 0; i < 3; ++i) {
-          if (dev_alloc((void**)&T.lnf[2 * i], (size_t)n_[i] * sizeof(float)) || dev_alloc((void**)&T.lnf[2 * i + 1], (size_t)n_[i] * sizeof(float)))
+          if (store_.alloc((void**)&T.lnf[2 * i], (size_t)n_[i] * sizeof(float)) || store_.alloc((void**)&T.lnf[2 * i + 1], (size_t)n_[i] * sizeof(float)))
             return -1;
           if (launch_ln_fold_prep(w_[i], n_[i], C, C, T.ln[2 * i], T.ln[2 * i + 1], b_[i], T.lnf[2 * i], T.lnf[2 * i + 1], nullptr)) return -1;
         }
         if (ff_tail_supported(C, 32, 32)) {            // (geometry only: rows are checked per call)
-          if (dev_alloc((void**)&T.lnf_csd, (size_t)16 * C * sizeof(float))) return -1;
+          if (store_.alloc((void**)&T.lnf_csd, (size_t)16 * C * sizeof(float))) return -1;
           for (int h = 0; h < 4; ++h) {                 // (default stream, behind the prep kernels above)
             SDMI_HIP_OK(hipMemcpyAsync(T.lnf_csd + (size_t)h * 4 * C, T.lnf[4] + (size_t)h * 2 * C, (size_t)2 * C * sizeof(float), hipMemcpyDeviceToDevice, nullptr));
             SDMI_HIP_OK(hipMemcpyAsync(T.lnf_csd + (size_t)h * 4 * C + 2 * C, T.lnf[5] + (size_t)h * 2 * C, (size_t)2 * C * sizeof(float), hipMemcpyDeviceToDevice, nullptr));
@@ -495,10 +334,7 @@ int UNet::finalize() {
         }
       }
       return 0;
-    };
-    for (auto& blk : input_blocks_) for (auto& L : blk) if (each(L)) return -1;
-    for (auto& L : middle_) if (each(L)) return -1;
-    for (auto& blk : output_blocks_) for (auto& L : blk) if (each(L)) return -1;
+    })) return -1;
     SDMI_HIP_OK(hipDeviceSynchronize());
   }
   ++weights_gen_;
@@ -524,14 +360,10 @@ constexpr int32_t PK_FULL = 4;      // PackedHeader::reserved: written by a full
 }  // namespace
 
 int UNet::packed_layout(std::vector<std::pair<void**, size_t>>* bufs, int64_t* total) const {
-  std::vector<void**> seen;
   int64_t off = (int64_t)round_up((int64_t)sizeof(PackedHeader), PK_ALIGN);
-  for (const auto& s : slots_) {
-    if (std::find(seen.begin(), seen.end(), s.dst) != seen.end()) continue;
-    seen.push_back(s.dst);
-    const size_t b = slot_bytes(s);
-    if (bufs) bufs->push_back({s.dst, b});
-    off += (int64_t)round_up((int64_t)b, PK_ALIGN);
+  for (const auto& b : store_.buffers()) {
+    if (bufs) bufs->push_back(b);
+    off += (int64_t)round_up((int64_t)b.second, PK_ALIGN);
   }
   *total = off;
   return 0;
@@ -585,12 +417,12 @@ int UNet::import_packed(const void* host_buf, int64_t bytes, hipStream_t stream)
   SDMI_CHECK(h.n_buffers == (int32_t)bufs.size() && h.total_bytes == total && bytes >= total, "packed blob truncated or inconsistent");
   int64_t off = (int64_t)round_up((int64_t)sizeof(PackedHeader), PK_ALIGN);
   for (auto& b : bufs) {
-    if (dev_alloc(b.first, b.second)) return -1;
+    if (store_.alloc(b.first, b.second)) return -1;
     SDMI_HIP_OK(hipMemcpyAsync(*b.first, (const char*)host_buf + off, b.second, hipMemcpyHostToDevice, stream));
     off += (int64_t)round_up((int64_t)b.second, PK_ALIGN);
   }
   SDMI_HIP_OK(hipStreamSynchronize(stream));
-  for (auto& s : slots_) s.set = true;
+  store_.mark_all_set();
   ctx_valid_ = false;
   drop_timestep_table();
   return finalize();
@@ -625,9 +457,6 @@ struct Fwd : FwdBase {
     const bool p1 = L.p1x1;              // this layer's skip convolution as 3-pass split-fp16
     const bool p3 = L.precise3;          // ... and its two 3x3 convs (the last ResBlock): operands [hi | lo | hi] against packed [w_hi | w_hi | w_lo]
     f16* raw_lo = (Cin != Cout && p1) ? S<f16>((size_t)M * Cin) : nullptr;
-    auto split3 = [&](IGemmParams& q, const f16* hi, const f16* lo, int C) {
-      q.a0 = hi; q.c0 = C; q.lda0 = C; q.a1 = lo; q.c1 = C; q.lda1 = C; q.a2 = hi; q.c2 = C; q.lda2 = C; q.K = 27 * C; q.k_alg = 9 * C;
-    };
     float* h = S<float>((size_t)M * Cout);
     Act out = make_act(P<float>((size_t)M * Cout), Cout, H, W, true);
     Act hact = make_act(h, Cout, H, W, true);
@@ -715,9 +544,7 @@ struct Fwd : FwdBase {
     const int C = L.cin, Lp = (int)round_up(Lctx, 8);
     const int CD = u->cfg_.context_dim;
     IGemmParams p = dense(ctx16, B * Lctx, CD, T.wkv2, 2 * C, Lctx);
-    if (ctx16_lo) {          // split-fp16: A' = [hi | lo | hi] against W' = [hi | hi | lo]
-      p.a1 = ctx16_lo; p.c1 = CD; p.lda1 = CD; p.a2 = ctx16; p.c2 = CD; p.lda2 = CD; p.K = 3 * CD; p.k_alg = CD;
-    }
+    if (ctx16_lo) split3(p, ctx16, ctx16_lo, CD);
     if (u->full()) {         // K | V in fp32, then hi / lo per head (the V^T pad keys are written as zeros)
       const size_t mark = scratch.off;
       float* kv = S<float>((size_t)B * Lctx * 2 * C);
@@ -982,7 +809,7 @@ struct Fwd : FwdBase {
       if (!dry && !rc) ok(launch_cast_f16(x.p, hi, lo, n, s));
       Act out = make_act(P<float>((size_t)B * Hout * Wout * C), L.cout, Hout, Wout, true);
       IGemmParams p = conv3(hi, C, Hin, Win, Hout, Wout, up ? 1 : 2, up ? 1 : 0, L.w16[0], L.cout);
-      p.a1 = lo; p.c1 = C; p.lda1 = C; p.a2 = hi; p.c2 = C; p.lda2 = C; p.K = 27 * C; p.k_alg = 9 * C;
+      split3(p, hi, lo, C);
       p.bias = L.f32[0]; p.out_f32 = out.p; p.ldo = L.cout;
       attach_gn_targets(p, out);
       gemm(p);
@@ -1027,15 +854,12 @@ struct Fwd : FwdBase {
     float* xs = S<float>((size_t)M * C);                               // x_upd(x): the residual
     if (!dry && !rc) ok(launch_resample2(g, nullptr, a, a_lo, B, H, W, C, dir, s));
     if (!dry && !rc) ok(launch_resample2(x.p, xs, nullptr, nullptr, B, H, W, C, dir, s));
-    auto split3 = [&](IGemmParams& q, const f16* hi, const f16* lo) {
-      q.a1 = lo; q.c1 = C; q.lda1 = C; q.a2 = hi; q.c2 = C; q.lda2 = C; q.K = 27 * C; q.k_alg = 9 * C;
-    };
     float* h = S<float>((size_t)M * C);
     Act out = make_act(P<float>((size_t)M * C), C, Ho, Wo, true);
     Act hact = make_act(h, C, Ho, Wo, true);
     {
       IGemmParams p = conv3(a, C, Ho, Wo, Ho, Wo, 1, 0, L.w16[0], C);
-      if (p3) split3(p, a, a_lo);
+      if (p3) split3(p, a, a_lo, C);
       p.bias = L.f32[2];
       if (!ss) { p.rowvec = emb_all + L.emb_off; p.ld_rowvec = emb_ld; }
       p.out_f32 = h; p.ldo = C;
@@ -1051,7 +875,7 @@ struct Fwd : FwdBase {
         groupnorm(hact, nullptr, L.f32[3], L.f32[4], 1e-5f, 1, a2, nullptr, nullptr, a2_lo, nullptr, false, false, film, emb_ld);
       }
       IGemmParams p = conv3(a2, C, Ho, Wo, Ho, Wo, 1, 0, L.w16[1], C);
-      if (p3) split3(p, a2, a2_lo);
+      if (p3) split3(p, a2, a2_lo, C);
       p.bias = L.f32[5]; p.residual = xs; p.ldr = C; p.out_f32 = out.p; p.ldo = C;
       attach_gn_targets(p, out);
       gemm(p);
@@ -1127,7 +951,7 @@ int UNet::reserve_ctx_cache(int B, int Lctx) {
   const int64_t need = (int64_t)B * round_up(Lctx, 8);          // (B * Lctx * C <= B * Lp * C: one capacity covers K and V^T)
   if (need <= ctx_cap_) return 0;
   ++ctx_gen_;                // (the K / V^T buffers move: recorded launch tapes are stale)
-  auto each = [&](Layer& L) -> int {
+  if (for_each_layer([&](Layer& L) -> int {
     if (L.kind != L_ATTN) return 0;
     for (auto& T : L.tb) {
       if (T.ck) { (void)hipFree(T.ck); T.ck = nullptr; }
@@ -1142,10 +966,7 @@ int UNet::reserve_ctx_cache(int B, int Lctx) {
       }
     }
     return 0;
-  };
-  for (auto& blk : input_blocks_) for (auto& L : blk) if (each(L)) return -1;
-  for (auto& L : middle_) if (each(L)) return -1;
-  for (auto& blk : output_blocks_) for (auto& L : blk) if (each(L)) return -1;
+  })) return -1;
   ctx_cap_ = need; ctx_B_ = 0; ctx_L_ = 0; ctx_valid_ = false;
   return 0;
 }
@@ -1286,7 +1107,7 @@ int UNet::run(const float* x, const int64_t* t_i64, const float* t_f32, const fl
   }
 
   Fwd f;
-  f.u = this; f.s = stream; f.dry = dry; f.B = B; f.Lctx = Lctx; f.zero = zero_; f.precise_1x1 = precise_1x1_;
+  f.u = this; f.s = stream; f.dry = dry; f.B = B; f.Lctx = Lctx; f.zero = store_.zero(); f.precise_1x1 = precise_1x1_;
   {
     // (both knobs are read per call -- the tests flip them between two forwards; the row statistics ride on the 16-byte epilogue)
     const char* e_fold = getenv("SDMI_LN_FOLD"); const char* e_vec = getenv("SDMI_EPI_VEC");
@@ -1312,7 +1133,7 @@ int UNet::run(const float* x, const int64_t* t_i64, const float* t_f32, const fl
   }
   // first pass (always dry) sizes the two arenas; the persist arena sits in front of the scratch arena
   int64_t persist_bytes = 0, scratch_bytes = 0;
-  for (int pass = (dry ? 0 : 0); pass < 2; ++pass) {
+  for (int pass = 0; pass < 2; ++pass) {
     const bool d = (pass == 0) ? true : false;
     if (pass == 1 && dry) break;
     f.dry = d; f.rc = 0;
@@ -1349,10 +1170,10 @@ int UNet::run(const float* x, const int64_t* t_i64, const float* t_f32, const fl
       f.ctx16 = nullptr; f.ctx16_lo = nullptr;
     }
     if (ctx_only) {
-      auto each = [&](Layer& L) { if (L.kind == L_ATTN) for (int dd = 0; dd < (int)L.tb.size(); ++dd) f.context_kv(L, dd); };
-      for (auto& blk : input_blocks_) for (auto& L : blk) each(L);
-      for (auto& L : middle_) each(L);
-      for (auto& blk : output_blocks_) for (auto& L : blk) each(L);
+      for_each_layer([&](Layer& L) -> int {
+        if (L.kind == L_ATTN) for (int dd = 0; dd < (int)L.tb.size(); ++dd) f.context_kv(L, dd);
+        return 0;
+      });
     } else {
       // ---- time embedding (util.py:151-171, openaimodel.py:506-511,723-724) and all emb_layers at once ----
       float* temb = f.P<float>((size_t)B * mc);

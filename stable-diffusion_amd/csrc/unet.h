@@ -2,7 +2,6 @@
 #pragma once
 #include <stdlib.h>
 
-#include <map>
 #include <memory>
 #include <string>
 #include <utility>
@@ -10,6 +9,7 @@
 
 #include "../../include/sdmi.h"
 #include "common.h"
+#include "weights.h"
 
 namespace sdmi {
 
@@ -151,6 +151,12 @@ struct FwdBase {
     p.ksize = 3; p.stride = stride; p.up = up; p.w = w; p.M = B * Hout * Wout; p.N = N; p.K = 9 * C; p.splitk = 0;
     return p;
   }
+  // split-fp16 operand of a GEMM through the generic kernel: A' = [hi | lo | hi], three K-concatenated sources of C channels, against weights
+  // packed [w_hi | w_hi | w_lo] (W_SPLIT3 / W_CONV_SPLIT3); `p` comes from dense() or conv3()
+  static void split3(IGemmParams& p, const f16* hi, const f16* lo, int C) {
+    p.a0 = hi; p.c0 = C; p.lda0 = C; p.a1 = lo; p.c1 = C; p.lda1 = C; p.a2 = hi; p.c2 = C; p.lda2 = C;
+    p.k_alg = p.ksize * p.ksize * C; p.K = 3 * p.k_alg;
+  }
   // 1x1 conv on split-fp16 operands (packed W_SPLIT3 weights [N][3K] = [hi | hi | lo]) when precise: the split-fp16 GEMM family
   // (gemm_split16.hip: four operand tiles per 64-channel chunk, three MFMAs per fragment pair); SDMI_SPLIT16_KERNEL=0 = the
   // rounds-1/2 formulation, one K-concatenated GEMM A' = [hi | lo | hi] through the generic kernel (A/B)
@@ -158,11 +164,8 @@ struct FwdBase {
     IGemmParams p = dense(hi, M, K, w, N, rows_per_batch);
     if (precise) {
       static const bool family = !(getenv("SDMI_SPLIT16_KERNEL") && atoi(getenv("SDMI_SPLIT16_KERNEL")) == 0);
-      if (family && K % 32 == 0) {
-        p.a1 = lo; p.lda1 = K; p.split16 = 1; p.ldw = 3 * K;
-      } else {
-        p.a1 = lo; p.c1 = K; p.lda1 = K; p.a2 = hi; p.c2 = K; p.lda2 = K; p.K = 3 * K; p.k_alg = K;
-      }
+      if (family && K % 32 == 0) { p.a1 = lo; p.lda1 = K; p.split16 = 1; p.ldw = 3 * K; }
+      else split3(p, hi, lo, K);
     }
     return p;
   }
@@ -203,19 +206,8 @@ struct FwdBase {
   }
 };
 
-// host or device fp32 pointer -> device pointer (staged through a temporary device buffer when it is host memory)
-struct DevStage {
-  const float* dptr = nullptr; float* staged = nullptr;
-  int acquire(const float* ptr, int64_t numel, hipStream_t stream);
-  int release(hipStream_t stream);
-};
-
 // L_ATTN_LEGACY: the AttentionBlock of a UNet without spatial transformer (openaimodel.py:278-323, QKVAttentionLegacy :347-376)
 enum LayerKind { L_CONV_IN, L_RES, L_ATTN, L_DOWN, L_UP, L_ATTN_LEGACY };
-// W_QKV_LEGACY / W_QKV_LEGACY_B: the AttentionBlock's conv1d qkv weight / bias, its head-interleaved rows (head, q | k | v, channel)
-// permuted to the [q | k | v] head-major rows launch_split_heads reads (WeightSlot::row0 = heads; ld = 1: split-fp16 [hi | hi | lo])
-enum WKind { W_F32, W_F32_ROWS, W_CONV, W_CONV_OUT, W_ROWS16, W_GEGLU_W, W_GEGLU_B, W_SPLIT3, W_SPLIT3_ROWS, W_CONV_SPLIT3, W_QKV_LEGACY,
-             W_QKV_LEGACY_B };
 
 struct TBlock {   // BasicTransformerBlock (ldm/modules/attention.py:196-215)
   f16* wqkv = nullptr;   // [3C][C]   attn1 to_q | to_k | to_v
@@ -253,14 +245,6 @@ struct Layer {
   std::vector<TBlock> tb;
 };
 
-struct WeightSlot {
-  std::string key;
-  std::vector<int64_t> shape;
-  WKind kind = W_F32;
-  void** dst = nullptr; int row0 = 0, ld = 0; void** dst2 = nullptr;
-  bool set = false;
-};
-
 class UNet {
  public:
   UNet() = default;
@@ -286,7 +270,7 @@ class UNet {
   int reserve_ctx_cache(int B, int Lctx);
   int hint_timestep(int64_t t);
 
-  const std::vector<WeightSlot>& slots() const { return slots_; }
+  const WeightStore& weights() const { return store_; }
 
   sdmi_unet_cfg cfg_{};
   sdmi_unet_ext ext_{};        // (all zero: the SD-v1 family)
@@ -302,7 +286,6 @@ class UNet {
   int precision_ = SDMI_PRECISION_MIXED;
   bool full() const { return precision_ == SDMI_PRECISION_FULL; }
   int te_ = 0, emb_total_ = 0, n_attn_ = 0;
-  f16* zero_ = nullptr;
   // 1x1 convs on the residual stream (skip_connection, proj_in, proj_out) run as 3-pass split-fp16 GEMMs
   // (a_hi*w_hi + a_lo*w_hi + a_hi*w_lo): ~22-bit operands for 5 % of the FLOPs (DESIGN.md "precision")
   bool precise_1x1_ = true;
@@ -312,10 +295,13 @@ class UNet {
 
  private:
   friend struct Fwd;
-  void expect(const std::string& key, std::vector<int64_t> shape, WKind kind, void** dst, int row0 = 0, int ld = 0,
-              void** dst2 = nullptr);
-  int dev_alloc(void** dst, size_t bytes);
-  size_t slot_bytes(const WeightSlot& s) const;
+  // every layer in execution order; fn returns int, the first non-zero result ends the walk and is returned
+  template <class F> int for_each_layer(F&& fn) {
+    for (auto& blk : input_blocks_) for (auto& L : blk) if (int r = fn(L)) return r;
+    for (auto& L : middle_) if (int r = fn(L)) return r;
+    for (auto& blk : output_blocks_) for (auto& L : blk) if (int r = fn(L)) return r;
+    return 0;
+  }
   int ensure_ctx_cache(int B, int Lctx, bool may_grow);
   GnPlan gn_plan_;           // GroupNorm-statistics fusion plan of the current forward (rebuilt by its dry pass)
   bool fuse_gn_stats_ = true;   // SDMI_FUSE_GN_STATS=0: every GroupNorm runs its own statistics kernel (A/B, debugging)
@@ -354,9 +340,7 @@ class UNet {
 
   std::vector<std::vector<Layer>> input_blocks_, output_blocks_;
   std::vector<Layer> middle_;
-  std::vector<WeightSlot> slots_;
-  std::map<std::string, int> slot_index_;
-  std::vector<void*> owned_;
+  WeightStore store_;           // (slots point into the Layer objects and the members below)
   float *te_w0_ = nullptr, *te_b0_ = nullptr, *te_w2_ = nullptr, *te_b2_ = nullptr;
   float *emb_w_ = nullptr, *emb_b_ = nullptr;       // concatenated emb_layers [emb_total][te], [emb_total]
   float *out_gamma_ = nullptr, *out_beta_ = nullptr, *out_w_ = nullptr, *out_b_ = nullptr;

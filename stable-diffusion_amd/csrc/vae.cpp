@@ -26,13 +26,6 @@
 
 namespace sdmi {
 
-void Vae::expect(const std::string& key, std::vector<int64_t> shape, VWKind kind, void** dst) {
-  VWeightSlot s;
-  s.key = key; s.shape = std::move(shape); s.kind = kind; s.dst = dst;
-  slot_index_[key] = (int)slots_.size();
-  slots_.push_back(std::move(s));
-}
-
 int Vae::build(const sdmi_vae_cfg& c, int parts, const sdmi_vae_ext* ext, int precision) {
   cfg_ = c; parts_ = parts; precision_ = precision;
   if (ext) ext_ = *ext;
@@ -53,8 +46,8 @@ int Vae::build(const sdmi_vae_cfg& c, int parts, const sdmi_vae_ext* ext, int pr
     SDMI_CHECK(narrow || wide, "full-precision first stage: mid-block attention width " + std::to_string(d) +
                " has no split-fp16 attention kernel (64, 128, and 192 .. 1024 in steps of 64)");
   }
-  const VWKind conv_kind = full() ? VW_CONV_SPLIT3 : VW_CONV;
-  const VWKind lin_kind = full() ? VW_SPLIT3 : VW_PLAIN16;
+  const WKind conv_kind = full() ? W_CONV_SPLIT3 : W_CONV;
+  const WKind lin_kind = full() ? W_SPLIT3 : W_ROWS16;
   auto res = [&](const std::string& p, int ci, int co) { VLayer L; L.kind = V_RES; L.prefix = p; L.cin = ci; L.cout = co; return L; };
   auto one = [&](VKind k, const std::string& p, int ch) { VLayer L; L.kind = k; L.prefix = p; L.cin = ch; L.cout = ch; return L; };
 
@@ -95,131 +88,74 @@ int Vae::build(const sdmi_vae_cfg& c, int parts, const sdmi_vae_ext* ext, int pr
     const int64_t ci = L.cin, co = L.cout;
     switch (L.kind) {
       case V_RES:
-        expect(p + ".norm1.weight", {ci}, VW_F32, (void**)&L.f32[0]);
-        expect(p + ".norm1.bias", {ci}, VW_F32, (void**)&L.f32[1]);
-        expect(p + ".conv1.weight", {co, ci, 3, 3}, conv_kind, (void**)&L.w16[0]);
-        expect(p + ".conv1.bias", {co}, VW_F32, (void**)&L.f32[2]);
-        expect(p + ".norm2.weight", {co}, VW_F32, (void**)&L.f32[3]);
-        expect(p + ".norm2.bias", {co}, VW_F32, (void**)&L.f32[4]);
-        expect(p + ".conv2.weight", {co, co, 3, 3}, conv_kind, (void**)&L.w16[1]);
-        expect(p + ".conv2.bias", {co}, VW_F32, (void**)&L.f32[5]);
+        store_.expect(p + ".norm1.weight", {ci}, W_F32, &L.f32[0]);
+        store_.expect(p + ".norm1.bias", {ci}, W_F32, &L.f32[1]);
+        store_.expect(p + ".conv1.weight", {co, ci, 3, 3}, conv_kind, &L.w16[0]);
+        store_.expect(p + ".conv1.bias", {co}, W_F32, &L.f32[2]);
+        store_.expect(p + ".norm2.weight", {co}, W_F32, &L.f32[3]);
+        store_.expect(p + ".norm2.bias", {co}, W_F32, &L.f32[4]);
+        store_.expect(p + ".conv2.weight", {co, co, 3, 3}, conv_kind, &L.w16[1]);
+        store_.expect(p + ".conv2.bias", {co}, W_F32, &L.f32[5]);
         if (ci != co) {
-          expect(p + ".nin_shortcut.weight", {co, ci, 1, 1}, (precise_1x1_ || full()) ? VW_SPLIT3 : VW_PLAIN16, (void**)&L.w16[2]);
-          expect(p + ".nin_shortcut.bias", {co}, VW_F32, (void**)&L.f32[6]);
+          store_.expect(p + ".nin_shortcut.weight", {co, ci, 1, 1}, (precise_1x1_ || full()) ? W_SPLIT3 : W_ROWS16, &L.w16[2]);
+          store_.expect(p + ".nin_shortcut.bias", {co}, W_F32, &L.f32[6]);
         }
         break;
       case V_ATTN: {
-        expect(p + ".norm.weight", {ci}, VW_F32, (void**)&L.f32[0]);
-        expect(p + ".norm.bias", {ci}, VW_F32, (void**)&L.f32[1]);
+        store_.expect(p + ".norm.weight", {ci}, W_F32, &L.f32[0]);
+        store_.expect(p + ".norm.bias", {ci}, W_F32, &L.f32[1]);
         const char* names[4] = {"q", "k", "v", "proj_out"};
         for (int i = 0; i < 4; ++i) {
-          expect(p + "." + names[i] + ".weight", {ci, ci, 1, 1}, lin_kind, (void**)&L.w16[i]);
-          expect(p + "." + names[i] + ".bias", {ci}, VW_F32, (void**)&L.f32[2 + i]);
+          store_.expect(p + "." + names[i] + ".weight", {ci, ci, 1, 1}, lin_kind, &L.w16[i]);
+          store_.expect(p + "." + names[i] + ".bias", {ci}, W_F32, &L.f32[2 + i]);
         }
         break;
       }
       case V_UP:
       case V_DOWN:
-        expect(p + ".conv.weight", {co, ci, 3, 3}, conv_kind, (void**)&L.w16[0]);
-        expect(p + ".conv.bias", {co}, VW_F32, (void**)&L.f32[0]);
+        store_.expect(p + ".conv.weight", {co, ci, 3, 3}, conv_kind, &L.w16[0]);
+        store_.expect(p + ".conv.bias", {co}, W_F32, &L.f32[0]);
         break;
     }
   };
   // NOTE: slots hold pointers into the VLayer objects: dec_ / enc_ must not reallocate after this point.
   if (parts & 2) {
-    expect("encoder.conv_in.weight", {c.ch, c.in_channels, 3, 3}, VW_F32, (void**)&eci_w_);
-    expect("encoder.conv_in.bias", {c.ch}, VW_F32, (void**)&eci_b_);
+    store_.expect("encoder.conv_in.weight", {c.ch, c.in_channels, 3, 3}, W_F32, &eci_w_);
+    store_.expect("encoder.conv_in.bias", {c.ch}, W_F32, &eci_b_);
     for (auto& L : enc_) visit(L);
-    expect("encoder.norm_out.weight", {enc_c_end_}, VW_F32, (void**)&eno_g_);
-    expect("encoder.norm_out.bias", {enc_c_end_}, VW_F32, (void**)&eno_b_);
-    expect("encoder.conv_out.weight", {enc_zc(), enc_c_end_, 3, 3}, VW_CONV_OUT, (void**)&eco_w_);
-    expect("encoder.conv_out.bias", {enc_zc()}, VW_F32, (void**)&eco_b_);
-    expect("quant_conv.weight", {enc_ed(), enc_zc(), 1, 1}, VW_F32, (void**)&q_w_);
-    expect("quant_conv.bias", {enc_ed()}, VW_F32, (void**)&q_b_);
+    store_.expect("encoder.norm_out.weight", {enc_c_end_}, W_F32, &eno_g_);
+    store_.expect("encoder.norm_out.bias", {enc_c_end_}, W_F32, &eno_b_);
+    store_.expect("encoder.conv_out.weight", {enc_zc(), enc_c_end_, 3, 3}, W_CONV_OUT, &eco_w_);
+    store_.expect("encoder.conv_out.bias", {enc_zc()}, W_F32, &eco_b_);
+    store_.expect("quant_conv.weight", {enc_ed(), enc_zc(), 1, 1}, W_F32, &q_w_);
+    store_.expect("quant_conv.bias", {enc_ed()}, W_F32, &q_b_);
   }
   if (parts & 1) {
-    if (ext_.n_embed > 0) expect("quantize.embedding.weight", {ext_.n_embed, c.embed_dim}, VW_F32, (void**)&cb_);
-    expect("post_quant_conv.weight", {c.z_channels, c.embed_dim, 1, 1}, VW_F32, (void**)&pq_w_);
-    expect("post_quant_conv.bias", {c.z_channels}, VW_F32, (void**)&pq_b_);
-    expect("decoder.conv_in.weight", {c.ch * c.ch_mult[n - 1], c.z_channels, 3, 3}, VW_F32, (void**)&dci_w_);
-    expect("decoder.conv_in.bias", {c.ch * c.ch_mult[n - 1]}, VW_F32, (void**)&dci_b_);
+    if (ext_.n_embed > 0) store_.expect("quantize.embedding.weight", {ext_.n_embed, c.embed_dim}, W_F32, &cb_);
+    store_.expect("post_quant_conv.weight", {c.z_channels, c.embed_dim, 1, 1}, W_F32, &pq_w_);
+    store_.expect("post_quant_conv.bias", {c.z_channels}, W_F32, &pq_b_);
+    store_.expect("decoder.conv_in.weight", {c.ch * c.ch_mult[n - 1], c.z_channels, 3, 3}, W_F32, &dci_w_);
+    store_.expect("decoder.conv_in.bias", {c.ch * c.ch_mult[n - 1]}, W_F32, &dci_b_);
     for (auto& L : dec_) visit(L);
-    expect("decoder.norm_out.weight", {dec_c_end_}, VW_F32, (void**)&dno_g_);
-    expect("decoder.norm_out.bias", {dec_c_end_}, VW_F32, (void**)&dno_b_);
-    expect("decoder.conv_out.weight", {c.out_ch, dec_c_end_, 3, 3}, VW_CONV_OUT, (void**)&dco_w_);
-    expect("decoder.conv_out.bias", {c.out_ch}, VW_F32, (void**)&dco_b_);
+    store_.expect("decoder.norm_out.weight", {dec_c_end_}, W_F32, &dno_g_);
+    store_.expect("decoder.norm_out.bias", {dec_c_end_}, W_F32, &dno_b_);
+    store_.expect("decoder.conv_out.weight", {c.out_ch, dec_c_end_, 3, 3}, W_CONV_OUT, &dco_w_);
+    store_.expect("decoder.conv_out.bias", {c.out_ch}, W_F32, &dco_b_);
   }
-  return 0;
-}
-
-Vae::~Vae() {
-  for (void* p : owned_) (void)hipFree(p);
-}
-
-int Vae::dev_alloc(void** dst, size_t bytes) {
-  if (*dst) return 0;
-  SDMI_HIP_OK(hipMalloc(dst, bytes));
-  owned_.push_back(*dst);
   return 0;
 }
 
 int Vae::set_weight(const char* key, const float* ptr, const int64_t* shape, int ndim, hipStream_t stream) {
-  auto it = slot_index_.find(key);
-  if (it == slot_index_.end()) return fail(std::string("unexpected weight key: ") + key);
-  VWeightSlot& s = slots_[it->second];
-  SDMI_CHECK((int)s.shape.size() == ndim, std::string("rank mismatch for ") + key);
-  int64_t numel = 1;
-  for (int i = 0; i < ndim; ++i) {
-    SDMI_CHECK(shape[i] == s.shape[i], std::string("shape mismatch for ") + key);
-    numel *= shape[i];
-  }
-  DevStage st;
-  if (st.acquire(ptr, numel, stream)) return -1;
-  const float* dptr = st.dptr;
-  int rc = 0;
-  switch (s.kind) {
-    case VW_F32:
-      rc = dev_alloc(s.dst, numel * sizeof(float));
-      if (!rc) SDMI_HIP_OK(hipMemcpyAsync(*s.dst, dptr, numel * sizeof(float), hipMemcpyDeviceToDevice, stream));
-      break;
-    case VW_CONV:
-      rc = dev_alloc(s.dst, numel * sizeof(f16));
-      if (!rc) rc = launch_pack_conv_weight(dptr, (f16*)*s.dst, (int)shape[0], (int)shape[1], (int)shape[2], (int)shape[3], stream);
-      break;
-    case VW_CONV_SPLIT3:
-      rc = dev_alloc(s.dst, 3 * numel * sizeof(f16));
-      if (!rc) rc = launch_pack_conv_split3(dptr, (f16*)*s.dst, (int)shape[0], (int)shape[1], (int)shape[2], (int)shape[3], stream);
-      break;
-    case VW_SPLIT3:
-      rc = dev_alloc(s.dst, 3 * numel * sizeof(f16));
-      if (!rc) rc = launch_pack_split3(dptr, (f16*)*s.dst, (int)shape[0], (int)shape[1], stream);
-      break;
-    case VW_PLAIN16:
-      rc = dev_alloc(s.dst, numel * sizeof(f16));
-      if (!rc) rc = launch_pack_rows(dptr, (f16*)*s.dst, (int)shape[0], (int)shape[1], 0, (int)shape[1], stream);
-      break;
-    case VW_CONV_OUT:
-      rc = dev_alloc(s.dst, numel * sizeof(float));
-      if (!rc) rc = launch_pack_conv_out(dptr, (float*)*s.dst, (int)shape[0], (int)shape[1], stream);
-      break;
-  }
-  if (st.release(stream)) return -1;
-  if (rc) return rc;
-  s.set = true;
+  if (int rc = store_.set(key, ptr, shape, ndim, stream)) return rc;
   finalized_ = false;
   return 0;
 }
 
 int Vae::finalize() {
-  for (auto& s : slots_)
-    if (!s.set) return fail("weight not set: " + s.key);
-  if (!zero_) {
-    SDMI_HIP_OK(hipMalloc((void**)&zero_, 4096));
-    owned_.push_back(zero_);
-    SDMI_HIP_OK(hipMemset(zero_, 0, 4096));
-  }
+  if (const WeightSlot* m = store_.missing()) return fail("weight not set: " + m->key);
+  if (store_.zero_page()) return -1;
   if (cb_) {          // sum e^2 of every code, once per set of weights (the quantizer's distance expression)
-    if (dev_alloc((void**)&cb_norm_, (size_t)ext_.n_embed * sizeof(float))) return -1;
+    if (store_.alloc((void**)&cb_norm_, (size_t)ext_.n_embed * sizeof(float))) return -1;
     SDMI_HIP_OK(hipDeviceSynchronize());         // (set_weight copied the codebook on the caller's stream)
     if (launch_vq_norms(cb_, cb_norm_, ext_.n_embed, cfg_.embed_dim, nullptr)) return -1;
     SDMI_HIP_OK(hipDeviceSynchronize());
@@ -235,51 +171,11 @@ struct VFwd : FwdBase {
   static constexpr float EPS = 1e-6f;        // Normalize(): GroupNorm(32, eps=1e-6)   model.py:37-38
   bool full = false;                         // the handle's precision (Vae::full())
 
-  // ---- SDMI_PRECISION_FULL: split-fp16 operands [hi | lo | hi] against weights packed [w_hi | w_hi | w_lo] ----
-  static void split3(IGemmParams& q, const f16* hi, const f16* lo, int C) {
-    q.a0 = hi; q.c0 = C; q.lda0 = C; q.a1 = lo; q.c1 = C; q.lda1 = C; q.a2 = hi; q.c2 = C; q.lda2 = C; q.K = 27 * C; q.k_alg = 9 * C;
-  }
-
-  // no split-K in this mode: every output element is then summed over K in one fixed order whatever M is, so a sample's result does
-  // not depend on the batch it is decoded in (the split is otherwise chosen from the number of workgroups)
-  void gemm_full(IGemmParams& p) { p.splitk = 1; gemm(p); }
-
-  Act res_block_full(VLayer& L, const Act& x) {
-    const int H = x.H, W = x.W, M = B * H * W, Cin = L.cin, Cout = L.cout;
-    if (x.C != Cin) ok(fail("res block channel mismatch at " + L.prefix));
-    const size_t mark = scratch.off;
-    const bool nin = Cin != Cout;
-    f16* a = S<f16>((size_t)M * Cin); f16* a_lo = S<f16>((size_t)M * Cin);
-    f16* raw = nin ? S<f16>((size_t)M * Cin) : nullptr;
-    f16* raw_lo = nin ? S<f16>((size_t)M * Cin) : nullptr;
-    float* h = S<float>((size_t)M * Cout);
-    Act out; out.p = P<float>((size_t)M * Cout); out.C = Cout; out.H = H; out.W = W;
-    groupnorm(x, nullptr, L.f32[0], L.f32[1], EPS, 1, a, nullptr, raw, a_lo, raw_lo);
-    {
-      IGemmParams p = conv3(a, Cin, H, W, H, W, 1, 0, L.w16[0], Cout);
-      split3(p, a, a_lo, Cin);
-      p.bias = L.f32[2]; p.out_f32 = h; p.ldo = Cout;
-      gemm_full(p);
-    }
-    const float* residual = x.p;
-    if (nin) {
-      IGemmParams p = dense1x1(raw, raw_lo, M, Cin, L.w16[2], Cout, H * W, true);
-      p.bias = L.f32[6]; p.out_f32 = out.p; p.ldo = Cout;
-      gemm_full(p);
-      residual = out.p;
-    }
-    Act hact; hact.p = h; hact.C = Cout; hact.H = H; hact.W = W;
-    f16* a2 = S<f16>((size_t)M * Cout); f16* a2_lo = S<f16>((size_t)M * Cout);
-    groupnorm(hact, nullptr, L.f32[3], L.f32[4], EPS, 1, a2, nullptr, nullptr, a2_lo, nullptr);
-    {
-      IGemmParams p = conv3(a2, Cout, H, W, H, W, 1, 0, L.w16[1], Cout);
-      split3(p, a2, a2_lo, Cout);
-      p.bias = L.f32[5]; p.residual = residual; p.ldr = Cout; p.out_f32 = out.p; p.ldo = Cout;
-      gemm_full(p);
-    }
-    scratch.off = mark;
-    return out;
-  }
+  // SDMI_PRECISION_FULL: the 3x3 convs take split-fp16 operands (FwdBase::split3 against weights packed W_CONV_SPLIT3; the `_lo` buffers
+  // below are null in the mixed mode), and no GEMM is split along K: every output element is then summed over K in one fixed order
+  // whatever M is, so a sample's result does not depend on the batch it is decoded in (the split is otherwise chosen from the number
+  // of workgroups)
+  void gemm(IGemmParams& p) { if (full) p.splitk = 1; FwdBase::gemm(p); }
 
   // AttnBlock with one head of d = C: q, k, v (bias inside its GEMM) as split GEMMs into fp32, scattered to q / k / V^T hi | lo, one
   // split-fp16 flash attention launch, proj_out as a split GEMM with the residual
@@ -298,7 +194,7 @@ struct VFwd : FwdBase {
     for (int i = 0; i < 3; ++i) {
       IGemmParams p = dense1x1(a, a_lo, M, C, L.w16[i], C, N, true);
       p.bias = L.f32[2 + i]; p.out_f32 = y; p.ldo = C;
-      gemm_full(p);
+      gemm(p);
       if (!dry && !rc) ok(launch_split_heads(y, C, 0, qkv[i], qkv_lo[i], i == 2 ? 1 : 0, B, N, Np, 1, C, s));
     }
     AttnSplitParams ap = AttnSplitParams();
@@ -309,26 +205,8 @@ struct VFwd : FwdBase {
     {
       IGemmParams p = dense1x1(a, a_lo, M, C, L.w16[3], C, N, true);
       p.bias = L.f32[5]; p.residual = x.p; p.ldr = C; p.out_f32 = out.p; p.ldo = C;
-      gemm_full(p);
+      gemm(p);
     }
-    scratch.off = mark;
-    return out;
-  }
-
-  Act resample_full(VLayer& L, const Act& x, bool up) {
-    const int Hin = x.H, Win = x.W, C = x.C;
-    if (!up && ((Hin | Win) & 1)) ok(fail("first-stage Downsample needs even H and W"));
-    const int Hout = up ? 2 * Hin : Hin / 2, Wout = up ? 2 * Win : Win / 2;
-    const size_t mark = scratch.off;
-    const int64_t n = (int64_t)B * Hin * Win * C;
-    f16* hi = S<f16>((size_t)n); f16* lo = S<f16>((size_t)n);
-    if (!dry && !rc) ok(launch_cast_f16(x.p, hi, lo, n, s));
-    Act out; out.p = P<float>((size_t)B * Hout * Wout * C); out.C = C; out.H = Hout; out.W = Wout;
-    IGemmParams p = conv3(hi, C, Hin, Win, Hout, Wout, up ? 1 : 2, up ? 1 : 0, L.w16[0], C);
-    split3(p, hi, lo, C);
-    if (!up) p.pad = 0;                   // F.pad(x, (0,1,0,1)) + conv(stride 2, padding 0)
-    p.bias = L.f32[0]; p.out_f32 = out.p; p.ldo = C;
-    gemm_full(p);
     scratch.off = mark;
     return out;
   }
@@ -338,29 +216,34 @@ struct VFwd : FwdBase {
     if (x.C != Cin) ok(fail("res block channel mismatch at " + L.prefix));
     const size_t mark = scratch.off;
     const bool nin = Cin != Cout;
+    const bool p1 = precise_1x1 || full;       // nin_shortcut as a split-fp16 GEMM
     f16* a = S<f16>((size_t)M * Cin);
+    f16* a_lo = full ? S<f16>((size_t)M * Cin) : nullptr;
     f16* raw = nin ? S<f16>((size_t)M * Cin) : nullptr;
-    f16* raw_lo = (nin && precise_1x1) ? S<f16>((size_t)M * Cin) : nullptr;
+    f16* raw_lo = (nin && p1) ? S<f16>((size_t)M * Cin) : nullptr;
     float* h = S<float>((size_t)M * Cout);
     Act out; out.p = P<float>((size_t)M * Cout); out.C = Cout; out.H = H; out.W = W;
-    groupnorm(x, nullptr, L.f32[0], L.f32[1], EPS, 1, a, nullptr, raw, nullptr, raw_lo);
+    groupnorm(x, nullptr, L.f32[0], L.f32[1], EPS, 1, a, nullptr, raw, a_lo, raw_lo);
     {
       IGemmParams p = conv3(a, Cin, H, W, H, W, 1, 0, L.w16[0], Cout);
+      if (full) split3(p, a, a_lo, Cin);
       p.bias = L.f32[2]; p.out_f32 = h; p.ldo = Cout;
       gemm(p);
     }
     const float* residual = x.p;
     if (nin) {
-      IGemmParams p = dense1x1(raw, raw_lo, M, Cin, L.w16[2], Cout, H * W, precise_1x1);
+      IGemmParams p = dense1x1(raw, raw_lo, M, Cin, L.w16[2], Cout, H * W, p1);
       p.bias = L.f32[6]; p.out_f32 = out.p; p.ldo = Cout;
       gemm(p);
       residual = out.p;
     }
     Act hact; hact.p = h; hact.C = Cout; hact.H = H; hact.W = W;
     f16* a2 = S<f16>((size_t)M * Cout);
-    groupnorm(hact, nullptr, L.f32[3], L.f32[4], EPS, 1, a2, nullptr, nullptr);
+    f16* a2_lo = full ? S<f16>((size_t)M * Cout) : nullptr;
+    groupnorm(hact, nullptr, L.f32[3], L.f32[4], EPS, 1, a2, nullptr, nullptr, a2_lo, nullptr);
     {
       IGemmParams p = conv3(a2, Cout, H, W, H, W, 1, 0, L.w16[1], Cout);
+      if (full) split3(p, a2, a2_lo, Cout);
       p.bias = L.f32[5]; p.residual = residual; p.ldr = Cout; p.out_f32 = out.p; p.ldo = Cout;
       gemm(p);
     }
@@ -423,10 +306,13 @@ struct VFwd : FwdBase {
     if (!up && ((Hin | Win) & 1)) ok(fail("first-stage Downsample needs even H and W"));
     const int Hout = up ? 2 * Hin : Hin / 2, Wout = up ? 2 * Win : Win / 2;
     const size_t mark = scratch.off;
-    f16* x16 = S<f16>((size_t)B * Hin * Win * C);
-    if (!dry && !rc) ok(launch_cast_f16(x.p, x16, nullptr, (int64_t)B * Hin * Win * C, s));
+    const int64_t n = (int64_t)B * Hin * Win * C;
+    f16* x16 = S<f16>((size_t)n);
+    f16* x16_lo = full ? S<f16>((size_t)n) : nullptr;
+    if (!dry && !rc) ok(launch_cast_f16(x.p, x16, x16_lo, n, s));
     Act out; out.p = P<float>((size_t)B * Hout * Wout * C); out.C = C; out.H = Hout; out.W = Wout;
     IGemmParams p = conv3(x16, C, Hin, Win, Hout, Wout, up ? 1 : 2, up ? 1 : 0, L.w16[0], C);
+    if (full) split3(p, x16, x16_lo, C);
     if (!up) p.pad = 0;                   // F.pad(x, (0,1,0,1)) + conv(stride 2, padding 0)
     p.bias = L.f32[0]; p.out_f32 = out.p; p.ldo = C;
     gemm(p);
@@ -435,18 +321,9 @@ struct VFwd : FwdBase {
   }
 
   Act run_layer(VLayer& L, const Act& x) {
-    if (full) {
-      switch (L.kind) {
-        case V_RES: return res_block_full(L, x);
-        case V_ATTN: return attn_block_full(L, x);
-        case V_UP: return resample_full(L, x, true);
-        case V_DOWN: return resample_full(L, x, false);
-      }
-      return x;
-    }
     switch (L.kind) {
       case V_RES: return res_block(L, x);
-      case V_ATTN: return attn_block(L, x);
+      case V_ATTN: return full ? attn_block_full(L, x) : attn_block(L, x);
       case V_UP: return resample(L, x, true);
       case V_DOWN: return resample(L, x, false);
     }
@@ -494,7 +371,7 @@ int Vae::decode(const float* z, float z_scale, float* img, int B, int H, int W, 
   SDMI_CHECK(H >= 1 && W >= 1, "bad shape");
   SDMI_CHECK(dry || (z != nullptr && img != nullptr), "z / img is NULL");
   VFwd f;
-  f.s = stream; f.B = B; f.zero = zero_; f.precise_1x1 = precise_1x1_; f.full = full();
+  f.s = stream; f.B = B; f.zero = store_.zero(); f.precise_1x1 = precise_1x1_; f.full = full();
   const int n = cfg_.n_levels, c_in = cfg_.ch * cfg_.ch_mult[n - 1];
   return run_two_pass(f, dry, workspace, ws_bytes, bytes_needed, [&](VFwd& f) -> int {
     const bool d = f.dry;
@@ -525,7 +402,7 @@ int Vae::encode(const float* img, float* moments, int B, int H, int W, void* wor
   SDMI_CHECK(H >= fct && W >= fct && H % fct == 0 && W % fct == 0, "H and W must be multiples of 2^(levels-1)");
   SDMI_CHECK(dry || (img != nullptr && moments != nullptr), "img / moments is NULL");
   VFwd f;
-  f.s = stream; f.B = B; f.zero = zero_; f.precise_1x1 = precise_1x1_; f.full = full();
+  f.s = stream; f.B = B; f.zero = store_.zero(); f.precise_1x1 = precise_1x1_; f.full = full();
   return run_two_pass(f, dry, workspace, ws_bytes, bytes_needed, [&](VFwd& f) -> int {
     const bool d = f.dry;
     Act x; x.p = f.P<float>((size_t)B * H * W * cfg_.ch); x.C = cfg_.ch; x.H = H; x.W = W;

@@ -1,6 +1,5 @@
 // First-stage (AutoencoderKL) executor state (see vae.cpp).
 #pragma once
-#include <map>
 #include <string>
 #include <vector>
 
@@ -11,8 +10,6 @@
 namespace sdmi {
 
 enum VKind { V_RES, V_ATTN, V_UP, V_DOWN };
-// VW_CONV_SPLIT3: the 3x3 conv weights of a full-precision handle, packed [w_hi | w_hi | w_lo] (launch_pack_conv_split3)
-enum VWKind { VW_F32, VW_CONV, VW_SPLIT3, VW_PLAIN16, VW_CONV_OUT, VW_CONV_SPLIT3 };
 
 struct VLayer {
   VKind kind = V_RES;
@@ -25,18 +22,9 @@ struct VLayer {
   float* f32[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
 };
 
-struct VWeightSlot {
-  std::string key;
-  std::vector<int64_t> shape;
-  VWKind kind = VW_F32;
-  void** dst = nullptr;
-  bool set = false;
-};
-
 class Vae {
  public:
   Vae() = default;
-  ~Vae();
   Vae(const Vae&) = delete;
   Vae& operator=(const Vae&) = delete;
 
@@ -51,7 +39,7 @@ class Vae {
   int encode(const float* img, float* moments, int B, int H, int W, void* workspace, int64_t ws_bytes, hipStream_t stream,
              bool dry, int64_t* bytes_needed);
 
-  const std::vector<VWeightSlot>& slots() const { return slots_; }
+  const WeightStore& weights() const { return store_; }
   int factor() const { return 1 << (cfg_.n_levels - 1); }
 
   sdmi_vae_cfg cfg_{};
@@ -59,22 +47,16 @@ class Vae {
   int parts_ = 0;
   int enc_zc() const { return ext_.double_z ? 2 * cfg_.z_channels : cfg_.z_channels; }    // encoder.conv_out channels
   int enc_ed() const { return ext_.double_z ? 2 * cfg_.embed_dim : cfg_.embed_dim; }      // quant_conv output channels
-  f16* zero_ = nullptr;
   bool precise_1x1_ = true;
   // SDMI_PRECISION_FULL: every MFMA operand of the ResBlocks, the resampling convs and the mid-block attention is a split-fp16 pair
-  // (vae.cpp: VFwd::*_full); fixed at creation, the weights are packed for it
+  // (vae.cpp: VFwd); fixed at creation, the weights are packed for it
   int precision_ = SDMI_PRECISION_MIXED;
   bool full() const { return precision_ == SDMI_PRECISION_FULL; }
 
  private:
   friend struct VFwd;
-  void expect(const std::string& key, std::vector<int64_t> shape, VWKind kind, void** dst);
-  int dev_alloc(void** dst, size_t bytes);
-
   std::vector<VLayer> dec_, enc_;
-  std::vector<VWeightSlot> slots_;
-  std::map<std::string, int> slot_index_;
-  std::vector<void*> owned_;
+  WeightStore store_;           // (slots point into the VLayer objects and the members below)
   // decoder ends
   float *pq_w_ = nullptr, *pq_b_ = nullptr;                 // post_quant_conv
   float *dci_w_ = nullptr, *dci_b_ = nullptr;               // decoder.conv_in (raw OIHW fp32)

@@ -680,3 +680,108 @@ def test_prefetch_wave_covers_every_line_of_a_unit_exactly_once():
             assert rows == want and len(seen) == 160 * 4, (M, len(seen))
         else:                                          # tiny grids: a prefix of the slots exists; whatever is touched is a valid line
             assert set(rows) <= set(want)
+
+
+# ---- weight-slot order, packed-blob size and workspace sizes of every committed model configuration ---------------------------------
+def _layout_cases():
+    from oracle.plan import SD_V1, TINY
+    from oracle.vae_ref import TINY_VAE
+    from stable_diffusion_amd import synthetic as S
+    from stable_diffusion_amd.clip import CLIP_VIT_L14_TEXT
+    cases = {}
+    unets = {'sdv1': SD_V1.ref_kwargs(), 'tiny': TINY.ref_kwargs(), 'laion': S.LAION_UNET_KWARGS, 'inpaint': S.INPAINT_UNET_KWARGS,
+             'cin': S.CIN_UNET_KWARGS, 'churches': S.CHURCHES_UNET_KWARGS, 'faces': S.FACES_UNET_KWARGS, 'bsr': S.BSR_UNET_KWARGS}
+    for name, kw in unets.items():
+        for prec in ('mixed', 'full'):
+            cases[f'unet {name} {prec}'] = ('unet', kw, prec)
+    kl = dict(ddconfig=S.SD_V1_VAE_DDCONFIG, embed_dim=4)
+    stages = {'kl_f8': kl, 'kl_tiny': dict(ddconfig=TINY_VAE.ddconfig(), embed_dim=TINY_VAE.embed_dim), 'vq_f4': S.CIN_VQ_KWARGS,
+              'vq_f4_noattn': S.INPAINT_VQ_KWARGS}
+    for name, kw in stages.items():
+        for prec in ('mixed', 'full'):
+            cases[f'first_stage {name} {prec}'] = ('first_stage', kw, prec)
+    tiny_clip = dict(vocab_size=1000, hidden_size=128, intermediate_size=512, num_hidden_layers=2, num_attention_heads=2,
+                     max_position_embeddings=77)
+    cases['clip vit_l14'] = ('clip', CLIP_VIT_L14_TEXT, None)
+    cases['clip tiny'] = ('clip', tiny_clip, None)
+    cases['bert laion'] = ('bert', S.LAION_BERT_KWARGS, None)
+    cases['bert tiny'] = ('bert', dict(n_embed=128, n_layer=2, vocab_size=1000), None)
+    return cases
+
+
+def _layout_of(case):
+    """(number of weights, sha256 of the (key, shape) list in index order, [packed-blob bytes,] workspace bytes per shape): host calls only"""
+    import hashlib
+    kind, kw, prec = _layout_cases()[case]
+    if kind == 'unet':
+        from stable_diffusion_amd import UNetModelHIP
+        h = UNetModelHIP(**kw, hip_precision=prec)._handle
+        L = 77 if kw.get('use_spatial_transformer') else 0
+        sizes = (h.lib.sdmi_unet_packed_bytes(h.h), h.lib.sdmi_unet_workspace_bytes(h.h, 2, 16, 16, L),
+                 h.lib.sdmi_unet_workspace_bytes(h.h, 1, 32, 32, L))
+    elif kind == 'first_stage':
+        from stable_diffusion_amd import AutoencoderKLHIP, VQModelInterfaceHIP
+        h = (VQModelInterfaceHIP(**kw, hip_precision=prec) if 'n_embed' in kw else
+             AutoencoderKLHIP(kw['ddconfig'], None, kw['embed_dim'], hip_precision=prec))._handle
+        sizes = tuple(h.lib.sdmi_vae_decode_workspace_bytes(h.h, *s) for s in ((1, 64, 64), (2, 8, 8), (1, 16, 24))) + \
+            tuple(h.lib.sdmi_vae_encode_workspace_bytes(h.h, *s) for s in ((1, 512, 512), (2, 64, 64)))
+    elif kind == 'clip':
+        from stable_diffusion_amd.clip import _ClipHandle, make_clip_cfg
+        h = _ClipHandle(make_clip_cfg(kw))
+        sizes = tuple(h.lib.sdmi_clip_workspace_bytes(h.h, *s) for s in ((2, 77), (1, 13)))
+    else:
+        from stable_diffusion_amd.bert import _BertHandle, make_bert_cfg
+        h = _BertHandle(make_bert_cfg(**kw))
+        sizes = tuple(h.lib.sdmi_bert_workspace_bytes(h.h, *s) for s in ((2, 77), (1, 13)))
+    specs = h.weight_specs()
+    return (len(specs), hashlib.sha256(repr([(k, tuple(s)) for k, s in specs]).encode()).hexdigest()) + tuple(int(b) for b in sizes)
+
+
+# Recorded at the commit before the shared weight store (csrc/weights.h).  The slot order is the index order the Python modules iterate and
+# the buffer order of the packed-weight blob; a change to this table needs an SDMI_ABI_VERSION bump.
+#   unet:        num_weights, sha256(keys, shapes), packed_bytes, workspace (2,16,16), workspace (1,32,32)   [77 context tokens, 0 without context]
+#   first_stage: num_weights, sha256, decode workspace (1,64,64) (2,8,8) (1,16,24), encode workspace (1,512,512) (2,64,64)
+#   clip / bert: num_weights, sha256, workspace (2,77) (1,13)
+_REFUSED = 'refused'          # the class-conditional UNet's 960-wide heads have no full-precision kernel: creation raises
+_LAYOUT = {
+    'bert laion': (422, 'a270c83f311dcbb4a3eb0ee936e6749fffedc90b8a914162cdf3dd355573fd2e', 44339200, 38342656),
+    'bert tiny': (32, '63b96962f50735727b71e9086ec29a63d88763ec2e270b0b5b714d271ee1b9ca', 39014400, 37892096),
+    'clip tiny': (36, 'a12d67b46afe22cb8a4c2df04f89938ecff73fd513d66625dea3135d6565dc78', 25956352, 25268224),
+    'clip vit_l14': (196, 'c2afee8ef45afe5648df1cb50af97a544cd43c1c46e7be28639ca45cee9fee03', 29708288, 25587712),
+    'first_stage kl_f8 full': (248, '4df0aec1eef61605f6a554bec94bb1ac0adfa9837fb9876f3794db355ef26ef9', 2058461184, 119320576, 241483776, 1160814592, 91267072),
+    'first_stage kl_f8 mixed': (248, '4df0aec1eef61605f6a554bec94bb1ac0adfa9837fb9876f3794db355ef26ef9', 1857134592, 113029120, 222609408, 1026596864, 87072768),
+    'first_stage kl_tiny full': (124, 'c5eca3d875960e3c22979ae352a23bd2e599fcbf5699048167a048d38b7acb72', 108109824, 58372096, 58638336, 540057600, 71868416),
+    'first_stage kl_tiny mixed': (124, 'c5eca3d875960e3c22979ae352a23bd2e599fcbf5699048167a048d38b7acb72', 138518528, 58175488, 58048512, 1227923456, 74489856),
+    'first_stage vq_f4 full': (205, '208d74c7370d26ddd5a7b4fd6378c4aff4d90609945dda0fc649e28672a1f14a', 565321728, 72658944, 101502976, 1211146240, 92839936),
+    'first_stage vq_f4 mixed': (205, '208d74c7370d26ddd5a7b4fd6378c4aff4d90609945dda0fc649e28672a1f14a', 514990080, 71086080, 96784384, 1093705728, 88645632),
+    'first_stage vq_f4_noattn full': (185, 'f17b482c3bd1b3c10eafe6039177cc9322d184f172ba54775dcec478d4f40ae2', 556933120, 72396800, 100716544, 1177591808, 91791360),
+    'first_stage vq_f4_noattn mixed': (185, 'f17b482c3bd1b3c10eafe6039177cc9322d184f172ba54775dcec478d4f40ae2', 506601472, 70823936, 95997952, 1043374080, 87597056),
+    'unet bsr full': (306, 'e363147a6e06b0d1578c553be3f38051499164c534437b9f8b2da8b37d30655f', 669638144, 88813568, 92540416),
+    'unet bsr mixed': (306, 'e363147a6e06b0d1578c553be3f38051499164c534437b9f8b2da8b37d30655f', 245292544, 88537088, 91987456),
+    'unet churches full': (520, 'ef330ec4eb2c820c1685341eecf72048779d8d1020f6be558698a17e1921f785', 1712405504, 93816832, 102211840),
+    'unet churches mixed': (520, 'ef330ec4eb2c820c1685341eecf72048779d8d1020f6be558698a17e1921f785', 666942464, 93423616, 101425408),
+    'unet cin full': _REFUSED,
+    'unet cin mixed': (688, '88ff26be13f96983a172a72376546db3bd006df5fce8adbab90fb889076e3f88', 881172992, 91924992, 98238464),
+    'unet faces full': (368, 'a5083ad2aa6c3ab72ea44b6b41d3985747161f0281d60ebcc1dd3884505923b1', 1618670080, 93461248, 101774592),
+    'unet faces mixed': (368, 'a5083ad2aa6c3ab72ea44b6b41d3985747161f0281d60ebcc1dd3884505923b1', 597889536, 93102848, 101057792),
+    'unet inpaint full': (416, 'e136d7f7e32b0c90fc8cb5c8825dad2f3227cd22fb67a655dd6b2b9b34e89f6d', 2282069504, 95416832, 105613824),
+    'unet inpaint mixed': (416, 'e136d7f7e32b0c90fc8cb5c8825dad2f3227cd22fb67a655dd6b2b9b34e89f6d', 847355392, 94368256, 103516672),
+    'unet laion full': (686, '58453951a69ff90a3fbfe4d6f418c1c1434bc588f5ccd757d18b539ed577cb09', 5177164032, 109198848, 131379200),
+    'unet laion mixed': (686, '58453951a69ff90a3fbfe4d6f418c1c1434bc588f5ccd757d18b539ed577cb09', 1974911232, 102803968, 119180800),
+    'unet sdv1 full': (686, 'e65096cd93ea12e8027610352db5bbd19be41e03aab9c401d717bc8cc066eab8', 5100486912, 108883456, 131221504),
+    'unet sdv1 mixed': (686, 'e65096cd93ea12e8027610352db5bbd19be41e03aab9c401d717bc8cc066eab8', 1898234112, 102488576, 119023104),
+    'unet tiny full': (686, '10d218f406cb92451c6f477c9bfe02d49a4aa4c4adb84ec0e77ae26fe634d49d', 203552000, 87218688, 89177600),
+    'unet tiny mixed': (686, '10d218f406cb92451c6f477c9bfe02d49a4aa4c4adb84ec0e77ae26fe634d49d', 75461888, 85939712, 86737920),
+}
+
+
+@pytest.mark.parametrize('case', sorted(_layout_cases()))
+def test_weight_and_workspace_layout_is_pinned(case):
+    want = _LAYOUT[case]
+    if want == _REFUSED:
+        with pytest.raises(NotImplementedError, match='head dims up to 160'):
+            _layout_of(case)
+        return
+    got = _layout_of(case)
+    assert all(int(v) > 0 for v in got[2:]), got
+    assert got == want
