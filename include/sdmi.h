@@ -141,6 +141,10 @@ int sdmi_unet_hint_timestep(sdmi_unet* h, int64_t t);
  * executor on every would-be replay and fails if the patched tape differs from it.
  * No counterpart in the reference (pure Python, scripts/txt2img.py drives torch ops one by one). */
 int sdmi_unet_tape_stats(sdmi_unet* h, int64_t* replayed, int64_t* recorded);
+/* Which ResBlocks run their skip_connection as the 1x1 tail phase of conv2's launch (SDMI_SKIP_FOLD, default on) at this
+ * shape: a dry pass (host only, like sdmi_unet_workspace_bytes) writes 1 (folded) or 0 per ResBlock with a skip convolution, in execution
+ * order, into folded[0 .. cap) and returns their number, or -1. */
+int sdmi_unet_skip_fold_plan(sdmi_unet* h, int B, int H, int W, int Lctx, int32_t* folded, int cap);
 
 /* UNetModel.forward(x, timesteps, context) openaimodel.py:710-742, reached through
  * LatentDiffusion.apply_model ddpm.py:891-900,986-992 and DiffusionWrapper.forward ddpm.py:1402-1410.
@@ -353,6 +357,16 @@ typedef struct sdmi_igemm_desc {
   void* out_lo;
 } sdmi_igemm_desc;
 int sdmi_k_igemm(const sdmi_igemm_desc* d, void* stream);
+/* ... with a 1x1 tail phase (a ResBlock's skip_connection inside conv2's launch, openaimodel.py:263-276): `d` is a stride-1 3x3 conv on a
+ * halo-staged tile (tile 14..17, or -1 = tuning table; any other tile is an error, never a silent drop of the term), and
+ *   out = conv3x3(a) + cat(t0, t1, t2)[M][tail_kt] tail_w[N][tail_kt]^T + epilogue,
+ * accumulated in the conv's fp32 accumulators behind its chunk loop.  t0 .. t2: fp16 [M][tail_ld] buffers, tail_c (% 64 == 0) channels of each;
+ * tail_kt = tail_c (t0 only, tail_w = fp16 [N][tail_c]) or 3 tail_c (t0 = hi, t1 = lo, t2 = hi against sdmi_k_pack_split3 weights).  Under
+ * split-K the tail's k-tiles are dealt over the conv's splits in contiguous ranges (sdmi_k_tail_split_range: host arithmetic only).
+ * Entry points beside sdmi_k_igemm rather than new sdmi_igemm_desc fields: the struct layout and SDMI_ABI_VERSION stay as they are. */
+int sdmi_k_igemm_tail(const sdmi_igemm_desc* d, const void* t0, const void* t1, const void* t2, int tail_c, int tail_ld, const void* tail_w,
+                      int tail_kt, void* stream);
+int sdmi_k_tail_split_range(int nkt, int nsplit, int split, int* begin, int* end);
 /* GEGLU -> FF-out -> proj_out of a SpatialTransformer as ONE launch (ABI 12; csrc/rowchain.hip; ldm/modules/attention.py:58-64,214,
  * 258-261): out = residual + proj_out(t + FF(norm3(t))) for C = 320 channels, a workgroup per 32 token rows.
  * proj_out: the split-fp16 1x1 descriptor of the last GEMM (split16 = 1, c0 = N = C, w = sdmi_k_pack_split3, bias, residual, out_f32,
@@ -515,6 +529,9 @@ int sdmi_tune_begin(void);
 int sdmi_tune_round(int r);
 int sdmi_tune_end(const char* path, int* n_keys);
 int sdmi_tune_dump(char* buf, int buflen);
+/* (tile, split-K) the loaded table holds for a key (host only); kt = K of a conv's 1x1 tail phase: the key that carries it is tried first,
+ * then the plain conv's entry (kt = 0; table lines without the optional 12th column).  0 = found, 1 = no entry. */
+int sdmi_tune_lookup(int M, int N, int K, int ksize, int stride, int up, int mode, int splitk_req, int kt, int* tile, int* splitk);
 /* per-launch timing of the library's kernels (HIP events on the launch stream): begin, run forwards, then end
  * writes a JSON array [{"name","launches","ms","flops","bytes"}] (algorithmic flops / bytes per kernel class) */
 int sdmi_profile_begin(void);

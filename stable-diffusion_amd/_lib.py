@@ -127,6 +127,10 @@ _SIGS = {
     'sdmi_bert_forward': (C.c_int, [c_ptr, c_ptr, c_ptr, C.c_int, C.c_int, c_ptr, C.c_int64, c_ptr]),
     'sdmi_has_experiments': (C.c_int, []),
     'sdmi_k_igemm': (C.c_int, [C.POINTER(IGemmDesc), c_ptr]),
+    'sdmi_k_igemm_tail': (C.c_int, [C.POINTER(IGemmDesc), c_ptr, c_ptr, c_ptr, C.c_int, C.c_int, c_ptr, C.c_int, c_ptr]),
+    'sdmi_k_tail_split_range': (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    'sdmi_tune_lookup': (C.c_int, [C.c_int] * 9 + [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    'sdmi_unet_skip_fold_plan': (C.c_int, [c_ptr, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int]),
     'sdmi_k_ff_tail': (C.c_int, [C.POINTER(IGemmDesc), c_ptr, c_ptr, C.c_float, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
     'sdmi_k_gn_conv3': (C.c_int, [C.POINTER(IGemmDesc), c_ptr, c_ptr, C.c_int, C.c_int, c_ptr, C.c_int64, c_ptr, c_ptr, C.c_float, c_ptr]),
     'sdmi_k_st_mid_ctx': (C.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, C.c_float, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, C.c_int, C.c_int, C.c_float, c_ptr,

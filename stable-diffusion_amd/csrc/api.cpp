@@ -358,6 +358,33 @@ int sdmi_k_igemm(const sdmi_igemm_desc* d, void* stream) {
   IGemmTune t; t.tile = d->tile; t.dma = d->dma;
   return launch_igemm(p, t, (hipStream_t)stream);
 }
+int sdmi_k_igemm_tail(const sdmi_igemm_desc* d, const void* t0, const void* t1, const void* t2, int tail_c, int tail_ld, const void* tail_w,
+                      int tail_kt, void* stream) {
+  SDMI_CHECK(d, "null descriptor");
+  IGemmParams p = IGemmParams();
+  if (igemm_params_of(d, p)) return -1;
+  p.tail_a0 = (const f16*)t0; p.tail_a1 = (const f16*)t1; p.tail_a2 = (const f16*)t2;
+  p.tail_c = tail_c; p.tail_ld = tail_ld; p.tail_w = (const f16*)tail_w; p.tail_kt = tail_kt;
+  IGemmTune t; t.tile = d->tile; t.dma = d->dma;
+  return launch_igemm(p, t, (hipStream_t)stream);
+}
+int sdmi_k_tail_split_range(int nkt, int nsplit, int split, int* begin, int* end) {
+  SDMI_CHECK(begin && end && nkt >= 0 && nsplit >= 1 && split >= 0 && split < nsplit, "bad arguments");
+  tail_split_range(nkt, nsplit, split, begin, end);
+  return 0;
+}
+int sdmi_tune_lookup(int M, int N, int K, int ksize, int stride, int up, int mode, int splitk_req, int kt, int* tile, int* splitk) {
+  SDMI_CHECK(tile && splitk, "null argument");
+  return tune_lookup(M, N, K, ksize, stride, up, mode, splitk_req, kt, tile, splitk);
+}
+int sdmi_unet_skip_fold_plan(sdmi_unet* h, int B, int H, int W, int Lctx, int32_t* folded, int cap) {
+  SDMI_CHECK(h && (folded || cap == 0), "null argument");
+  int64_t need = 0;
+  if (h->impl.run(nullptr, nullptr, nullptr, nullptr, nullptr, B, H, W, Lctx, nullptr, 0, nullptr, true, false, &need)) return -1;
+  const std::vector<int>& plan = h->impl.skip_fold_plan_;
+  for (int i = 0; i < (int)plan.size() && i < cap; ++i) folded[i] = plan[i];
+  return (int)plan.size();
+}
 int sdmi_k_ff_tail(const sdmi_igemm_desc* proj_out, const void* ln_f16, const float* lnp, float ln_eps, const float* csd,
                    const void* wgg_f16, const void* wff2_f16, const float* bff2, const float* t, void* stream) {
   SDMI_CHECK(proj_out, "null descriptor");

@@ -253,7 +253,22 @@ struct IGemmParams {
   // halo-staged conv geometry (launcher): output rows per image in a tile, images per tile, log2(pixels per image part)
   int halo_thi = 0, halo_ipt = 1, log2_tpi = 30;
   unsigned long long magic_hpi = 0;
+  // ---- 1x1 tail of a halo-staged conv (conv3halo.hip, TAIL instantiations): out += cat(tail_a0, tail_a1, tail_a2)[M][tail_kt] tail_w[N][tail_kt]^T
+  // accumulated into the conv's own accumulators behind its chunk loop -- a ResBlock's skip_connection inside conv2's launch
+  // (openaimodel.py:233-240,263-276: skip_connection(x) + h).  Every source is tail_c channels (a multiple of 64) of an fp16 [M][tail_ld] buffer
+  // whose rows are the conv's output pixels; tail_kt = tail_c (single pass, W_CONV weights) or 3 tail_c ([hi | lo | hi] against W_SPLIT3's
+  // [w_hi | w_hi | w_lo]).  tail_kt = 0: no tail.  The tail's k-tiles are dealt over the conv's splits in contiguous ranges (tail_split_range).
+  const f16* tail_a0 = nullptr; const f16* tail_a1 = nullptr; const f16* tail_a2 = nullptr;
+  int tail_c = 0, tail_ld = 0;
+  const f16* tail_w = nullptr;
+  int tail_kt = 0;
 };
+// k-tiles [begin, end) of a tail of nkt k-tiles that split `split` of nsplit runs: contiguous, every k-tile exactly once, empty ranges allowed
+// (host and device: the kernel and the launcher's checks use this one expression)
+__host__ __device__ static inline void tail_split_range(int nkt, int nsplit, int split, int* begin, int* end) {
+  *begin = (int)(((long long)split * nkt) / nsplit);
+  *end = (int)(((long long)(split + 1) * nkt) / nsplit);
+}
 
 constexpr int SDMI_NUM_TILES = 22;   // tile ids 0 .. 21 (14..17: halo-staged 3x3 conv), see kTiles in igemm.hip and include/sdmi.h
 struct IGemmTune {        // runtime knobs (tests sweep them; the executor takes the tuning table's choice)
@@ -262,6 +277,10 @@ struct IGemmTune {        // runtime knobs (tests sweep them; the executor takes
 };
 
 int launch_igemm(const IGemmParams& p, const IGemmTune& tune, hipStream_t stream);
+// host only: will launch_igemm run this auto-configured 3x3 conv (with the tail fields it carries) on a halo-staged tile?  (igemm.hip)
+bool igemm_plans_halo(const IGemmParams& p);
+// host only: the tuning table's (tile, split-K) of a key; kt = K of a 1x1 tail (tried first, then the plain conv's entry).  0 found, 1 no entry
+int tune_lookup(int M, int N, int K, int ksize, int stride, int up, int mode, int splitk_req, int kt, int* tile, int* splitk);
 // fp16 range guard (range.hip, debug): scan an fp16 activation buffer a launch just wrote; see SDMI_CHECK_RANGE
 bool range_check_enabled();
 uint64_t tune_generation();

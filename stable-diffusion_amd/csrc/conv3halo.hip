@@ -17,7 +17,9 @@ namespace {
 //   LDS: [halo buffer 0 | halo buffer 1 | NS weight stages]; halo rows are pixels (128 B = 64 channels), XOR-swizzled by
 //   the absolute LDS row exactly like the generic tiles, so fragment reads at any row offset stay conflict free.
 //   The nine taps are unrolled: every DMA issue and every counted vmcnt wait is static.
-template <int BM, int BN, int WARPS_M, int WARPS_N, int NS>
+// TAIL: a 1x1 GEMM phase behind the chunk loop, into the same accumulators (IGemmParams::tail_*) -- its own instantiations, so the
+// launches without a tail keep the code the tuner measured.
+template <int BM, int BN, int WARPS_M, int WARPS_N, int NS, bool TAIL = false>
 __global__ void __launch_bounds__(WARPS_M* WARPS_N * 64) conv3halo_kernel(const IGemmParams p, const int tiles_m,
                                                                            const int tiles_n, const int chunks_per_split) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -254,6 +256,106 @@ __global__ void __launch_bounds__(WARPS_M* WARPS_N * 64) conv3halo_kernel(const 
     }
   }
   wait_vmcnt<0>();
+  if constexpr (TAIL) {
+    // ---- 1x1 tail phase (a ResBlock's skip_connection): the k-tiles [t_begin, t_end) of out += A_t W_t^T, A_t = the tile's BM output
+    // pixels as rows of up to three K-concatenated fp16 [M][tail_c] sources, W_t = [N][tail_kt] row-major.  The loop is the DMA main
+    // loop of igemm_kernel<..., KIND_1X1> (stages of (BM + BN) x 128 B, the same swizzle and fragment reads, one raw barrier per k-tile,
+    // counted vmcnt waits: the phase issues nothing but LDS-DMA) over the LDS the drained halo buffers and weight stages leave free.
+    // split / p.splitk / p.tail_kt are scalars: the range and the branch around the phase are the same for every wave of the workgroup,
+    // and a workgroup with an empty range takes no barrier of it.
+    int t_begin, t_end;
+    tail_split_range(p.tail_kt / BK, p.splitk, split, &t_begin, &t_end);
+    if (t_begin < t_end) {
+      constexpr int A_PASSES = BM / RPP;
+      constexpr int STAGE_T = (BM + BN) * 128;
+      constexpr int NS_T = LDS_BYTES / STAGE_T < 4 ? LDS_BYTES / STAGE_T : 4;
+      constexpr int LPT = A_PASSES + PB;               // DMA instructions per thread per k-tile
+      constexpr int PPU = (LPT + U - 2) / (U - 1);     // ... issued in each of the first U - 1 units
+      static_assert(A_PASSES >= 1 && NS_T >= 3 && NS_T * STAGE_T <= LDS_BYTES && LPT * (NS_T - 2) <= 48, "tail ring");
+      // every wave is out of the chunk loop and its surplus DMA has landed: halo buffers and weight stages are free LDS
+      asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+      int ta_off[A_PASSES], tb_off[PB];
+#pragma unroll
+      for (int i = 0; i < A_PASSES; ++i) ta_off[i] = (min(m0 + i * RPP + lrow, p.M - 1) * p.tail_ld + gch * 8) * 2;
+#pragma unroll
+      for (int i = 0; i < PB; ++i) tb_off[i] = (min(n0 + i * RPP + lrow, p.N - 1) * p.tail_kt + gch * 8) * 2;
+      const __amdgpu_buffer_rsrc_t rsrc_tw = __builtin_amdgcn_make_buffer_rsrc((void*)p.tail_w, 0, OOB, 0x00020000);
+      const char* const srcT0 = (const char*)p.tail_a0; const char* const srcT1 = (const char*)p.tail_a1;
+      const char* const srcT2 = (const char*)p.tail_a2;
+      const int tc = p.tail_c;
+      // load cursor (wave-uniform): the next k-tile to issue; it stops on the last k-tile of the range
+      // (the NS_T - 1 surplus issues at the end reload that tile: in bounds, never consumed)
+      int ld_kt = t_begin;
+      const int tc2 = 2 * tc;
+      struct TailCursor { __amdgpu_buffer_rsrc_t rsrc_a; int a_soff, b_soff; unsigned lds; };
+      auto next_tile = [&](int stage) {
+        TailCursor c;
+        const int k0 = ld_kt * BK;                     // first column of the tile in the concatenated K
+        const char* src; int coff;
+        if (k0 < tc) { src = srcT0; coff = k0; }
+        else if (k0 < tc2) { src = srcT1; coff = k0 - tc; }
+        else { src = srcT2; coff = k0 - tc2; }
+        c.rsrc_a = __builtin_amdgcn_make_buffer_rsrc((void*)src, 0, OOB, 0x00020000);
+        c.a_soff = coff * 2; c.b_soff = k0 * 2; c.lds = stage * STAGE_T;
+        if (ld_kt + 1 < t_end) ++ld_kt;
+        return c;
+      };
+      auto issue_piece = [&](const TailCursor& c, int q) {
+        const unsigned row0 = (q < A_PASSES ? q * RPP : BM + (q - A_PASSES) * RPP) + wave_u * 8;
+        auto dst = (__attribute__((address_space(3))) void*)(smem + c.lds + row0 * 128);
+        if (q < A_PASSES) __builtin_amdgcn_raw_ptr_buffer_load_lds(c.rsrc_a, dst, 16, ta_off[q], c.a_soff, 0, 0);
+        else __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_tw, dst, 16, tb_off[q - A_PASSES], c.b_soff, 0, SDMI_W_AUX);
+      };
+      const int ta_lds = (wm * WTM + l31) * 128, tb_lds = BM * 128 + (wn * WTN + l31) * 128;
+      auto read_tail = [&](int stage, int ks, f16x8 (&a)[TM], f16x8 (&b)[TN]) {
+        const unsigned char* st = smem + stage * STAGE_T + (((ks * 2 + lg) ^ rsw) << 4);
+#pragma unroll
+        for (int i = 0; i < TM; ++i) a[i] = *(const f16x8*)(st + ta_lds + i * 32 * 128);
+#pragma unroll
+        for (int j = 0; j < TN; ++j) b[j] = *(const f16x8*)(st + tb_lds + j * 32 * 128);
+      };
+#pragma unroll
+      for (int s2 = 0; s2 < NS_T - 1; ++s2) {
+        const TailCursor c = next_tile(s2);
+#pragma unroll
+        for (int q = 0; q < LPT; ++q) issue_piece(c, q);
+      }
+      wait_vmcnt<LPT*(NS_T - 2)>();
+      asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+#pragma unroll
+      for (int g = 0; g < G; ++g) read_tail(0, g, fa[0][g], fb[0][g]);
+      int tcur = 0, tnxt = NS_T - 1;
+      for (int kt = t_begin; kt < t_end; ++kt) {
+        const TailCursor c = next_tile(tnxt);
+        const int tcur1 = (tcur + 1 == NS_T) ? 0 : tcur + 1;
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          if (u + 1 < U) {
+#pragma unroll
+            for (int g = 0; g < G; ++g) read_tail(tcur, (u + 1) * G + g, fa[(u + 1) & 1][g], fb[(u + 1) & 1][g]);
+#pragma unroll
+            for (int q = u * PPU; q < (u + 1) * PPU && q < LPT; ++q) issue_piece(c, q);
+          } else {
+            wait_vmcnt<LPT*(NS_T - 2)>();               // this wave's share of tile kt + 1 has landed
+            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // ... and everybody's; tile kt is fully read
+#pragma unroll
+            for (int g = 0; g < G; ++g) read_tail(tcur1, g, fa[0][g], fb[0][g]);
+          }
+#pragma unroll
+          for (int g = 0; g < G; ++g) mfma_step(fa[u & 1][g], fb[u & 1][g]);
+          __builtin_amdgcn_sched_group_barrier(0x100, G * (TM + TN), 0);
+#pragma unroll
+          for (int e = 0; e < MPU; ++e) {
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+            if (u + 1 < U && e < PPU && u * PPU + e < LPT) __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);
+          }
+        }
+        tcur = tcur1;
+        tnxt = (tnxt + 1 == NS_T) ? 0 : tnxt + 1;
+      }
+      wait_vmcnt<0>();
+    }
+  }
   SDMI_STAMP(dbg_t2);
   igemm_epilogue<BM, BN, WARPS_M, WARPS_N, LDS_BYTES>(p, acc, m0, n0, split, tile_m, tile_n, smem);
 #ifdef SDMI_IGEMM_TIMING
@@ -284,6 +386,15 @@ bool halo_supported(const IGemmParams& p, int bm) {
 template <int BM, int BN, int WARPS_M, int WARPS_N, int NS>
 int launch_halo_cfg(const IGemmParams& p, int splitk, hipStream_t stream) {
   SDMI_CHECK(halo_supported(p, BM), "halo-staged conv tile requested for an unsupported shape");
+  if (p.tail_kt) {      // the 1x1 tail phase (IGemmParams::tail_*): whole 64-channel k-tiles of one to three equally wide sources
+    const int nsrc = p.tail_c > 0 ? p.tail_kt / p.tail_c : 0;
+    SDMI_CHECK(p.tail_c > 0 && p.tail_c % BK == 0 && nsrc >= 1 && nsrc <= 3 && nsrc * p.tail_c == p.tail_kt && p.tail_w && p.tail_a0 &&
+                   (nsrc < 2 || p.tail_a1) && (nsrc < 3 || p.tail_a2) && p.tail_ld >= p.tail_c && p.tail_ld % 8 == 0,
+               "1x1 tail: one to three sources of tail_c % 64 == 0 channels, tail_kt = sources * tail_c, pitch >= tail_c and % 8 == 0");
+    SDMI_CHECK((int64_t)p.M * p.tail_ld * 2 < ((int64_t)1 << 31) - 65536 && (int64_t)p.N * p.tail_kt * 2 < ((int64_t)1 << 31) - 65536,
+               "1x1 tail: tensor too large for 31-bit byte offsets (buffer addressing)");
+    SDMI_CHECK(p.mode == EPI_PLAIN && p.M % BM == 0, "1x1 tail: plain mode, whole row tiles");
+  }
   const int tiles_m = cdiv(p.M, BM), tiles_n = cdiv(p.N, BN);
   const int nch = (p.c0 + p.c1 + p.c2) / BK;
   const int chunks_per_split = cdiv(nch, splitk);
@@ -317,13 +428,16 @@ int launch_halo_cfg(const IGemmParams& p, int splitk, hipStream_t stream) {
   std::string pname = std::string("conv3halo_") + std::to_string(BM) + "x" + std::to_string(BN) + "w" +
                       std::to_string(WARPS_M * WARPS_N) + "s" + std::to_string(NS);
   if (by_shape && prof_enabled())
-    pname += "_M" + std::to_string(p.M) + "_N" + std::to_string(p.N) + "_K" + std::to_string(p.K) + "_s" + std::to_string(nsplit);
+    pname += "_M" + std::to_string(p.M) + "_N" + std::to_string(p.N) + "_K" + std::to_string(p.K) + "_s" + std::to_string(nsplit) +
+             (p.tail_kt ? "_t" + std::to_string(p.tail_kt) : std::string());
   const double src_pix = (double)p.B * p.Hin * p.Win;
-  ProfScope ps(pname.c_str(), 2.0 * p.M * (double)p.N * p.K,
+  // (the tail counts as the reference 1x1 conv: tail_c channels, whatever the number of passes -- as launch_cfg counts k_alg)
+  ProfScope ps(pname.c_str(), 2.0 * p.M * (double)p.N * (p.K + (p.tail_kt ? p.tail_c : 0)),
                src_pix * (p.c0 + p.c1) * 2.0 + (double)p.N * p.K * 2.0 + (double)p.M * p.N * ((p.out_f32 ? 4.0 : 0.0) + (p.out_f16 ? 2.0 : 0.0)) +
-                   (p.residual ? (double)p.M * p.N * 4.0 : 0.0),
+                   (p.residual ? (double)p.M * p.N * 4.0 : 0.0) + (p.tail_kt ? ((double)p.M + p.N) * p.tail_c * 2.0 : 0.0),
                stream);
-  SDMI_LAUNCH((conv3halo_kernel<BM, BN, WARPS_M, WARPS_N, NS>), grid, block, 0, stream, q, tiles_m, tiles_n, chunks_per_split);
+  if (p.tail_kt) SDMI_LAUNCH((conv3halo_kernel<BM, BN, WARPS_M, WARPS_N, NS, true>), grid, block, 0, stream, q, tiles_m, tiles_n, chunks_per_split);
+  else SDMI_LAUNCH((conv3halo_kernel<BM, BN, WARPS_M, WARPS_N, NS>), grid, block, 0, stream, q, tiles_m, tiles_n, chunks_per_split);
   SDMI_HIP_OK(hipGetLastError());
   ps.end();
   if (nsplit > 1) return launch_splitk_reduce(q, nsplit, stream);

@@ -481,6 +481,8 @@ static inline bool tile_is_halo(int t) { return t >= 14 && t <= 17; }
 static inline bool tile_tn_even(int t) { return (kTiles[t].bn / kTiles[t].wn / 32) % 2 == 0; }
 
 static int launch_tile(int tile, const IGemmParams& p, bool dma, int splitk, hipStream_t stream) {
+  // a 1x1 tail (IGemmParams::tail_kt) exists on the halo-staged conv tiles only: any other kernel would silently drop the term
+  if (p.tail_kt && !tile_is_halo(tile)) return fail("a GEMM with a 1x1 tail phase was routed to tile " + std::to_string(tile) + ": only the halo-staged conv tiles 14..17 run a tail");
   if (p.split16) return launch_split16_tile(tile, p, splitk, stream);
   if (igemm_has_half(p)) {   // a source of 32 (mod 64) channels: the kernels with the half k-tile (igemm_h0 / h1 / h2.hip); the halo tiles refuse
     switch (tile) {
@@ -508,9 +510,10 @@ static int launch_tile(int tile, const IGemmParams& p, bool dma, int splitk, hip
 // to libsdmi.so (stable-diffusion_amd/tune_gfx950.txt, committed): the choice is fixed, so results stay bit-reproducible.
 struct TuneKey {
   int M, N, K, ksize, stride, up, mode, splitk_req;
+  int kt = 0;      // K of the 1x1 tail phase of a halo-staged conv (IGemmParams::tail_kt); 0 = none.  An optional 12th column of a table line.
   bool operator<(const TuneKey& o) const {
-    return std::tie(M, N, K, ksize, stride, up, mode, splitk_req) <
-           std::tie(o.M, o.N, o.K, o.ksize, o.stride, o.up, o.mode, o.splitk_req);
+    return std::tie(M, N, K, ksize, stride, up, mode, splitk_req, kt) <
+           std::tie(o.M, o.N, o.K, o.ksize, o.stride, o.up, o.mode, o.splitk_req, o.kt);
   }
 };
 struct TuneChoice { int tile, splitk; double us; };
@@ -543,9 +546,10 @@ class Tuner {
     while (fgets(line, sizeof line, f)) {
       if (line[0] == '#') continue;
       TuneKey k; TuneChoice c; c.us = 0;
-      if (sscanf(line, "%d %d %d %d %d %d %d %d %d %d %lf", &k.M, &k.N, &k.K, &k.ksize, &k.stride, &k.up, &k.mode,
-                 &k.splitk_req, &c.tile, &c.splitk, &c.us) >= 10 && c.tile >= 0 && c.tile < SDMI_NUM_TILES && c.splitk >= 1 &&
-          c.splitk <= 16)
+      k.kt = 0;      // (lines without the 12th column: a conv without a tail)
+      if (sscanf(line, "%d %d %d %d %d %d %d %d %d %d %lf %d", &k.M, &k.N, &k.K, &k.ksize, &k.stride, &k.up, &k.mode,
+                 &k.splitk_req, &c.tile, &c.splitk, &c.us, &k.kt) >= 10 && c.tile >= 0 && c.tile < SDMI_NUM_TILES && c.splitk >= 1 &&
+          c.splitk <= 16 && k.kt >= 0)
         table[k] = c;
     }
     fclose(f);
@@ -555,6 +559,12 @@ class Tuner {
     loaded = true;
     if (env_int("SDMI_TUNE_DISABLE", 0)) return;
     load_file(default_path());
+  }
+  // the entry of a key: a conv with a 1x1 tail first tries the key that carries the tail's K, then the plain conv's entry
+  std::map<TuneKey, TuneChoice>::const_iterator find_entry(TuneKey k) const {
+    auto it = table.find(k);
+    if (it == table.end() && k.kt) { k.kt = 0; it = table.find(k); }
+    return it;
   }
   hipEvent_t ev() {
     if (!pool.empty()) { hipEvent_t e = pool.back(); pool.pop_back(); return e; }
@@ -573,6 +583,7 @@ static std::vector<TuneChoice> tune_candidates(const IGemmParams& p, bool can_sp
   for (int t = 0; t < SDMI_NUM_TILES; ++t) {
     const TileCfg& c = kTiles[t];
     if (tile_is_halo(t) && !halo_supported(p, c.bm)) continue;
+    if (p.tail_kt && !tile_is_halo(t)) continue;                                    // a 1x1 tail phase: the halo-staged conv tiles only
     if (p.split16 && !split16_tile_supported(t)) continue;                         // split-fp16 GEMM: its own instantiations
     // never chosen by any of the round-2 collection runs (profiles/tune_candidates_r02.txt): the 2-stage twins of the
     // 3-stage tiles, 128x128 / 256x128 with 2 stages, and the 64x256 / 256x64 4-wave tiles -- fewer candidates = more
@@ -657,8 +668,10 @@ int tune_end(const char* path, int* n_keys) {
   fprintf(f, "# libsdmi igemm tuning table (gfx950), measured in situ by tools/tune.py -- M N K ksize stride up mode splitk_req tile splitk us\n");
   for (auto& kv : g_tuner.table) {
     const TuneKey& k = kv.first;
-    fprintf(f, "%d %d %d %d %d %d %d %d %d %d %.2f\n", k.M, k.N, k.K, k.ksize, k.stride, k.up, k.mode, k.splitk_req, kv.second.tile,
+    fprintf(f, "%d %d %d %d %d %d %d %d %d %d %.2f", k.M, k.N, k.K, k.ksize, k.stride, k.up, k.mode, k.splitk_req, kv.second.tile,
             kv.second.splitk, kv.second.us);
+    if (k.kt) fprintf(f, " %d", k.kt);
+    fprintf(f, "\n");
   }
   fclose(f);
   return 0;
@@ -673,12 +686,43 @@ int tune_dump(std::string* out) {
       if (c.second.empty()) continue;
       std::vector<float> v = c.second;
       std::sort(v.begin(), v.end());
-      snprintf(buf, sizeof buf, "%d %d %d %d %d %d %d %d | %d %d %.2f %.2f %d\n", k.M, k.N, k.K, k.ksize, k.stride, k.up, k.mode,
-               k.splitk_req, c.first.tile, c.first.splitk, (double)v[v.size() / 2], (double)v[0], (int)v.size());
+      snprintf(buf, sizeof buf, "%d %d %d %d %d %d %d %d%s | %d %d %.2f %.2f %d\n", k.M, k.N, k.K, k.ksize, k.stride, k.up, k.mode,
+               k.splitk_req, k.kt ? (" t" + std::to_string(k.kt)).c_str() : "", c.first.tile, c.first.splitk, (double)v[v.size() / 2], (double)v[0], (int)v.size());
       *out += buf;
     }
   }
   return 0;
+}
+
+// (tile, split-K) the tuning table holds for a key (host only; tests): 0 = found, 1 = no entry
+int tune_lookup(int M, int N, int K, int ksize, int stride, int up, int mode, int splitk_req, int kt, int* tile, int* splitk) {
+  std::lock_guard<std::mutex> lk(g_tuner.mu);
+  g_tuner.ensure_loaded();
+  auto it = g_tuner.find_entry(TuneKey{M, N, K, ksize, stride, up, mode, splitk_req, kt});
+  if (it == g_tuner.table.end()) return 1;
+  *tile = it->second.tile; *splitk = it->second.splitk;
+  return 0;
+}
+
+// Will launch_igemm run this auto-configured stride-1 3x3 conv on a halo-staged tile?  (Host only: the executor asks before it gives conv2 a 1x1
+// tail, which only those tiles run.)  The same decision launch_igemm takes: a table entry on a halo tile that the shape supports -- the
+// heuristic for unknown shapes never picks one; during a tuning collection, whether a halo candidate exists (tune_candidates then offers
+// a conv with a tail nothing else).  `p` carries the tail fields it would be launched with.
+bool igemm_plans_halo(const IGemmParams& p) {
+  static const int env_tile = env_int("SDMI_IGEMM_TILE", -1);
+  if (p.ksize != 3 || p.split16 || igemm_has_half(p) || p.mode != EPI_PLAIN || p.splitk != 0 || env_tile >= 0 || env_int("SDMI_SPLITK", -1) >= 0) return false;
+  std::lock_guard<std::mutex> lk(g_tuner.mu);
+  g_tuner.ensure_loaded();
+  if (g_tuner.collecting) {
+    for (int t = 14; t <= 17; ++t) if (halo_supported(p, kTiles[t].bm)) return true;
+    return false;
+  }
+  auto it = g_tuner.find_entry(TuneKey{p.M, p.N, igemm_nkt(p) * BK, p.ksize, p.stride, p.up, p.mode, 0, p.tail_kt});
+  if (it == g_tuner.table.end()) return false;
+  const int tt = it->second.tile, sk = it->second.splitk, nkt = igemm_nkt(p);
+  const bool can_split = p.splitk_ws && p.N % 4 == 0 && p.ldo % 4 == 0 && (p.residual == nullptr || p.ldr % 4 == 0);
+  return tile_is_halo(tt) && halo_supported(p, kTiles[tt].bm) &&
+         (sk == 1 || (can_split && splitk_ws_need(p, kTiles[tt].bm, kTiles[tt].bn, sk) <= p.splitk_ws_floats && nkt / sk >= 4 && (nkt / 9) % sk == 0));
 }
 
 int launch_igemm(const IGemmParams& p, const IGemmTune& tune, hipStream_t stream) {
@@ -739,7 +783,7 @@ int launch_igemm(const IGemmParams& p, const IGemmTune& tune, hipStream_t stream
   // (the split-fp16 dense GEMM is its own family of kernels: keyed apart with ksize 11)
   // (the key's K counts whole k-tiles, nkt * 64: = K for sources of whole 64-channel chunks; a source that ends in a half tile is keyed as if
   // padded, so every K of the table stays a multiple of 64)
-  TuneKey tkey{p.M, p.N, nkt * BK, p.split16 ? 11 : p.ksize, p.stride, p.up, p.mode, splitk};
+  TuneKey tkey{p.M, p.N, nkt * BK, p.split16 ? 11 : p.ksize, p.stride, p.up, p.mode, splitk, p.tail_kt};
   int tcand = -1;
   if (tile < 0) {
     std::lock_guard<std::mutex> lk(g_tuner.mu);
@@ -758,7 +802,7 @@ int launch_igemm(const IGemmParams& p, const IGemmTune& tune, hipStream_t stream
     } else {
       // a table entry is taken only if it passes the predicates tune_candidates() generated it under (the key does not carry
       // the whole geometry, and the file may be stale or hand-edited): otherwise the heuristic below decides
-      auto it = g_tuner.table.find(tkey);
+      auto it = g_tuner.find_entry(tkey);
       if (it != g_tuner.table.end()) {
         const int tt = it->second.tile, sk = it->second.splitk;
         const bool halo = tile_is_halo(tt);

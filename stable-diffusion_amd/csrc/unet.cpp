@@ -336,6 +336,18 @@ int UNet::finalize() {
       return 0;
     })) return -1;
     SDMI_HIP_OK(hipDeviceSynchronize());
+    // bias of a conv2 that carries its block's skip convolution as a tail phase (Fwd::res_block): out_layers.3.bias + skip_connection.bias,
+    // one fp32 sum per channel (derived from the set weights: not part of the blob)
+    if (for_each_layer([&](Layer& L) -> int {
+      if (L.kind != L_RES || L.updown || L.cin == L.cout || !L.f32[5] || !L.f32[6]) return 0;
+      std::vector<float> b2((size_t)L.cout), bs((size_t)L.cout);
+      SDMI_HIP_OK(hipMemcpy(b2.data(), L.f32[5], b2.size() * sizeof(float), hipMemcpyDeviceToHost));
+      SDMI_HIP_OK(hipMemcpy(bs.data(), L.f32[6], bs.size() * sizeof(float), hipMemcpyDeviceToHost));
+      for (size_t i = 0; i < b2.size(); ++i) b2[i] += bs[i];
+      if (store_.alloc((void**)&L.bias_fold, b2.size() * sizeof(float))) return -1;
+      SDMI_HIP_OK(hipMemcpy(L.bias_fold, b2.data(), b2.size() * sizeof(float), hipMemcpyHostToDevice));
+      return 0;
+    })) return -1;
   }
   ++weights_gen_;
   finalized_ = true;
@@ -440,6 +452,10 @@ struct Fwd : FwdBase {
   bool st_tail_on = false;      // ... and the out-projection of attn2 in front of the tail's chain launch (SDMI_ST_TAIL)
   bool st_mid_ctx_on = false;   // ... and the cross-attention inside the st_mid launch (SDMI_ST_MID_CTX)
   bool ctx1_on = false;         // a context of ONE token: the cross-attention output is V of the sample, copied from the cached V^T (SDMI_CTX1, read per call)
+  // a ResBlock's skip_connection as the 1x1 tail phase of conv2's halo-staged launch (IGemmParams::tail_*; SDMI_SKIP_FOLD, read per call), on maps
+  // up to skip_fold_max_w wide (SDMI_SKIP_FOLD_MAX_W); skip_fold_plan: one entry per ResBlock with a skip convolution, in execution order
+  bool skip_fold_on = false; int skip_fold_max_w = 64;
+  std::vector<int>* skip_fold_plan = nullptr;
   bool gn_conv_on = false;      // ResBlock GroupNorm + SiLU + conv3x3 as one launch where a workgroup can own all output columns (gnconv.hip; SDMI_GN_CONV)
   float* emb_all = nullptr;     // [B][emb_total] (emb_ld = emb_total), or one row of the timestep table shared by every sample (emb_ld = 0)
   int emb_ld = 0;
@@ -505,11 +521,31 @@ struct Fwd : FwdBase {
       gemm(p);
     }
     const float* residual = x0.p;
-    if (Cin != Cout) {       // skip_connection: needs only the raw fp16 copies (written by GroupNorm 1)
-      IGemmParams p = dense1x1(raw, raw_lo, M, Cin, L.w16[2], Cout, H * W, p1);
-      p.bias = L.f32[6]; p.out_f32 = out.p; p.ldo = Cout;
-      gemm(p);
-      residual = out.p;
+    // skip_connection (needs only the raw fp16 copies, written by GroupNorm 1).  out = conv2(...) + skip(x) is one sum per output element:
+    // where conv2 runs on a halo-staged tile the skip conv is the 1x1 tail phase of that launch -- extra k-tiles of conv2's accumulators,
+    // [raw | raw_lo | raw] against W_SPLIT3's [w_hi | w_hi | w_lo] or raw against W_CONV -- with the bias bias2 + bias_skip (L.bias_fold) and
+    // no residual: no skip GEMM launch, no split-K reduce behind it, no fp32 [M][Cout] round trip.  Everything else takes the two launches:
+    // full precision and the split-fp16 last block (their convs are no halo launches), scale-shift blocks and the opt-in gn_conv path
+    // (not measured with a tail), and whatever conv2 shape the tuning table does not send to a halo tile.
+    IGemmParams tailp = IGemmParams();      // conv2's tail fields when folding (tail_kt = 0: two launches)
+    if (Cin != Cout) {
+      bool fold = skip_fold_on && !u->full() && !p3 && !ss && !gc2 && !gn_conv_on && W <= skip_fold_max_w && Cin % 64 == 0 && (dry || L.bias_fold != nullptr);
+      if (fold) {
+        IGemmParams c2 = conv3(raw, Cout, H, W, H, W, 1, 0, L.w16[1], Cout);       // conv2's shape (its operand pointer is not looked at)
+        c2.tail_a0 = raw; c2.tail_a1 = p1 ? raw_lo : nullptr; c2.tail_a2 = p1 ? raw : nullptr;
+        c2.tail_c = Cin; c2.tail_ld = Cin; c2.tail_w = L.w16[2]; c2.tail_kt = p1 ? 3 * Cin : Cin;
+        c2.out_f32 = out.p; c2.ldo = Cout;
+        c2.splitk_ws = splitk_ws; c2.splitk_ws_floats = splitk_ws_floats;
+        fold = igemm_plans_halo(c2);
+        if (fold) tailp = c2;
+      }
+      if (skip_fold_plan && dry) skip_fold_plan->push_back(fold ? 1 : 0);      // (the dry pass in front of every forward decides the same)
+      if (!fold) {
+        IGemmParams p = dense1x1(raw, raw_lo, M, Cin, L.w16[2], Cout, H * W, p1);
+        p.bias = L.f32[6]; p.out_f32 = out.p; p.ldo = Cout;
+        gemm(p);
+        residual = out.p;
+      }
     }
     if (gc2) {
       IGemmParams p = conv3(nullptr, Cout, H, W, H, W, 1, 0, L.w16[1], Cout);
@@ -530,6 +566,11 @@ struct Fwd : FwdBase {
       IGemmParams p = conv3(a2, Cout, H, W, H, W, 1, 0, L.w16[1], Cout);
       if (p3) split3(p, a2, a2_lo, Cout);
       p.bias = L.f32[5]; p.residual = residual; p.ldr = Cout; p.out_f32 = out.p; p.ldo = Cout;
+      if (tailp.tail_kt) {                 // the skip convolution rides in this launch (see above)
+        p.tail_a0 = tailp.tail_a0; p.tail_a1 = tailp.tail_a1; p.tail_a2 = tailp.tail_a2; p.tail_c = tailp.tail_c; p.tail_ld = tailp.tail_ld;
+        p.tail_w = tailp.tail_w; p.tail_kt = tailp.tail_kt;
+        p.bias = L.bias_fold; p.residual = nullptr; p.ldr = 0;
+      }
       attach_gn_targets(p, out);           // ... and those of the GroupNorm(s) that read this block's output
       attach_f16_copy(p, out);             // ... and the fp16 copy a Downsample / Upsample behind this block wants
       gemm(p);
@@ -1126,6 +1167,12 @@ int UNet::run(const float* x, const int64_t* t_i64, const float* t_f32, const fl
     f.ctx1_on = !(e_c1 && atoi(e_c1) == 0);
     const char* e_gc = getenv("SDMI_GN_CONV");
     f.gn_conv_on = e_gc ? atoi(e_gc) != 0 : false;       // (opt-in: bit-identical, 36 us against 41 us with hot operands, +4 us per launch inside a UNet call -- profiles/gn_conv3_r05.txt)
+    const char* e_sf = getenv("SDMI_SKIP_FOLD");          // (A/B knob, read per call: 0 = the skip convolutions as their own GEMM launches)
+    f.skip_fold_on = e_sf ? atoi(e_sf) != 0 : skip_fold_;
+    const char* e_sfw = getenv("SDMI_SKIP_FOLD_MAX_W");   // (... and the widest map whose ResBlocks fold)
+    f.skip_fold_max_w = e_sfw ? atoi(e_sfw) : skip_fold_max_w_;
+    skip_fold_plan_.clear();
+    f.skip_fold_plan = &skip_fold_plan_;
     if (full()) {
       // every chain and fold rounds some operand to fp16 once: the full-precision mode runs the per-op path whatever the knobs say
       f.ln_fold_on = f.ff_tail_on = f.st_head_on = f.st_mid_on = f.st_tail_on = f.st_mid_ctx_on = f.gn_conv_on = false;

@@ -242,6 +242,7 @@ struct Layer {
   f16* w16[3] = {nullptr, nullptr, nullptr};
   float* w32[1] = {nullptr};
   float* f32[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  float* bias_fold = nullptr;    // L_RES with a skip convolution: out_layers.3.bias + skip_connection.bias (finalize(); Fwd::res_block's folded conv2)
   std::vector<TBlock> tb;
 };
 
@@ -315,6 +316,12 @@ class UNet {
   // ... and SpatialTransformer heads (GroupNorm-apply -> proj_in -> q | k | v of the first transformer block) likewise.  SDMI_ST_HEAD=0
   // restores the three launches (bit-identical outputs; A/B).
   bool st_head_ = true;
+  // ResBlock skip convolutions as the 1x1 tail phase of conv2's halo-staged launch (conv3halo.hip TAIL; Fwd::res_block), on maps up to
+  // skip_fold_max_w_ wide.  SDMI_SKIP_FOLD=0 restores the skip GEMM launches (A/B); SDMI_SKIP_FOLD_MAX_W moves the width rule.
+  bool skip_fold_ = true; int skip_fold_max_w_ = 64;
+ public:
+  std::vector<int> skip_fold_plan_;     // the last forward (or dry pass): 1 = folded, per ResBlock with a skip convolution in execution order
+ private:
 
   // ---- launch tapes (tape.h): the launch list of a (shape, workspace, mode, knobs) recorded once and replayed
   struct TapeKey {
