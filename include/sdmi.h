@@ -256,6 +256,15 @@ typedef struct sdmi_clip_cfg {
   int32_t max_positions;
 } sdmi_clip_cfg;
 int sdmi_clip_create(const sdmi_clip_cfg* cfg, sdmi_clip** out);
+/* The handle's precision, fixed at creation (SDMI_PRECISION_* as for the UNet and the first stage; any other value is refused):
+ *   SDMI_PRECISION_MIXED  what sdmi_clip_create creates: every GEMM and attention operand rounded to fp16 once
+ *   SDMI_PRECISION_FULL   every MFMA operand a split-fp16 pair (three passes): Linear weights packed [hi | hi | lo], LayerNorm, the
+ *                         per-head scatter and quick_gelu write hi / lo, the causal self-attention runs on
+ *                         sdmi_k_attention_split16_causal.  Same state_dict keys and shapes; a larger workspace.  A head dim
+ *                         (hidden_size / num_heads) outside {32, 64, 128} is refused at creation with a message that names it.
+ * sdmi_clip_create(cfg, out) = sdmi_clip_create_precision(cfg, SDMI_PRECISION_MIXED, out). */
+int sdmi_clip_create_precision(const sdmi_clip_cfg* cfg, int precision, sdmi_clip** out);
+int sdmi_clip_precision(const sdmi_clip* h);      /* SDMI_PRECISION_*, or -1 for a null handle */
 int sdmi_clip_destroy(sdmi_clip* h);
 /* state_dict keys of CLIPTextModel as transformers 4.19.2 names them (`text_model.embeddings...`, `text_model.encoder
  * .layers.N...`, `text_model.final_layer_norm...`), i.e. the checkpoint's `cond_stage_model.transformer.` sub-tree */
@@ -286,6 +295,11 @@ typedef struct sdmi_bert_cfg {
   int32_t max_seq_len;
 } sdmi_bert_cfg;
 int sdmi_bert_create(const sdmi_bert_cfg* cfg, sdmi_bert** out);
+/* As sdmi_clip_create_precision: SDMI_PRECISION_FULL runs every MFMA operand as a split-fp16 pair (the non-causal
+ * sdmi_k_attention_split16, which has every dim_head of the list above; the exact-erf GELU writes hi / lo).  Same keys and shapes, a
+ * larger workspace; any other precision value is refused.  sdmi_bert_create(cfg, out) = sdmi_bert_create_precision(cfg, SDMI_PRECISION_MIXED, out). */
+int sdmi_bert_create_precision(const sdmi_bert_cfg* cfg, int precision, sdmi_bert** out);
+int sdmi_bert_precision(const sdmi_bert* h);      /* SDMI_PRECISION_*, or -1 for a null handle */
 int sdmi_bert_destroy(sdmi_bert* h);
 /* state_dict keys of TransformerWrapper (`token_emb.weight`, `pos_emb.emb.weight`, `attn_layers.layers.N...`, `norm...`,
  * `to_logits...`), i.e. the checkpoint's `cond_stage_model.transformer.` sub-tree.  `to_logits.*` is shape-checked and
@@ -433,7 +447,12 @@ int sdmi_k_attention(const void* q, const void* k, const void* vt, void* out, in
  * with a message that names it. */
 int sdmi_k_attention_split16(const void* q, const void* q_lo, const void* k, const void* k_lo, const void* vt, const void* vt_lo, void* out,
                              void* out_lo, int BH, int heads, int nq, int nkv, int nkv_pad, int d, float scale, void* stream);
-/* same with a causal mask (query i attends to keys <= i; nq == nkv): CLIPTextModel's self-attention */
+/* sdmi_k_attention_split16 with a causal mask (query i attends to keys <= i; nq == nkv = n): the self-attention of the full-precision
+ * CLIP text encoder.  d in {32, 64, 128}; any other d fails with a message that names it.  The V^T pad columns n .. n_pad, hi and lo,
+ * must be zero, as above. */
+int sdmi_k_attention_split16_causal(const void* q, const void* q_lo, const void* k, const void* k_lo, const void* vt, const void* vt_lo,
+                                    void* out, void* out_lo, int BH, int heads, int n, int n_pad, int d, float scale, void* stream);
+/* sdmi_k_attention with a causal mask (query i attends to keys <= i; nq == nkv): CLIPTextModel's self-attention */
 int sdmi_k_attention_causal(const void* q, const void* k, const void* vt, void* out, int BH, int heads, int n, int n_pad,
                             int d, float scale, void* stream);
 /* GroupNorm(32) over cat(x0,x1) fp32 NHWC; any of the outputs may be NULL.  out_lo / raw_lo = fp16(v - fp16(v)):
@@ -507,6 +526,14 @@ int sdmi_k_patch_unfold(const float* x, const float* c, float* out, int B, int C
 int sdmi_k_patch_fold(const float* o, const float* w, float* out, int B, int C, int H, int W, int kh, int kw, int sy, int sx, int uf, int df,
                       int norm_only, void* stream);
 int sdmi_k_gelu_erf(const float* x, void* out_f16, int64_t n, void* stream);
+/* CLIP's quick_gelu, x * sigmoid(1.702 x): fp32 [n] -> fp16 [n], n % 4 == 0 (the mixed text encoder's feed-forward activation) */
+int sdmi_k_quick_gelu(const float* x, void* out_f16, int64_t n, void* stream);
+/* The two feed-forward activations as producers of a split-fp16 GEMM operand (the full-precision text encoders): fp32 [n], n % 4 == 0
+ * -> out = fp16(y), bit for bit what sdmi_k_quick_gelu / sdmi_k_gelu_erf store (y is the same fp32 expression), and out_lo = fp16(y_ref - out):
+ * y_ref = y for quick_gelu; for the erf form y_ref = x / 2 erfc(-x / sqrt 2) in fp32, so out + out_lo is the GELU to fp32 accuracy although
+ * out keeps the fp16 kernel's bits (its Abramowitz-Stegun erf is up to 2 fp16 ulps off near x = -4; out_lo is then more than half a step of out) */
+int sdmi_k_quick_gelu_split(const float* x, void* out, void* out_lo, int64_t n, void* stream);
+int sdmi_k_gelu_erf_split(const float* x, void* out, void* out_lo, int64_t n, void* stream);
 int sdmi_k_pack_geglu(const float* w, const float* bias, void* wdst_f16, float* bdst, int N, int K, void* stream);
 /* Host post-processing of scripts/txt2img.py:313-324, on the device: img fp32 [B, C, H, W] (the
  * decode_first_stage output) -> uint8 [B, H, W, C] = astype(uint8)(255 * clamp((img + 1) / 2, 0, 1)), bit-identical to

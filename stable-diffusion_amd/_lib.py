@@ -110,6 +110,8 @@ _SIGS = {
     'sdmi_vae_encode_workspace_bytes': (C.c_int64, [c_ptr, C.c_int, C.c_int, C.c_int]),
     'sdmi_vae_encode': (C.c_int, [c_ptr, c_ptr, c_ptr, C.c_int, C.c_int, C.c_int, c_ptr, C.c_int64, c_ptr]),
     'sdmi_clip_create': (C.c_int, [C.POINTER(ClipCfg), C.POINTER(c_ptr)]),
+    'sdmi_clip_create_precision': (C.c_int, [C.POINTER(ClipCfg), C.c_int, C.POINTER(c_ptr)]),
+    'sdmi_clip_precision': (C.c_int, [c_ptr]),
     'sdmi_clip_destroy': (C.c_int, [c_ptr]),
     'sdmi_clip_num_weights': (C.c_int, [c_ptr]),
     'sdmi_clip_weight_info': (C.c_int, [c_ptr, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int)]),
@@ -118,6 +120,8 @@ _SIGS = {
     'sdmi_clip_workspace_bytes': (C.c_int64, [c_ptr, C.c_int, C.c_int]),
     'sdmi_clip_forward': (C.c_int, [c_ptr, c_ptr, c_ptr, C.c_int, C.c_int, c_ptr, C.c_int64, c_ptr]),
     'sdmi_bert_create': (C.c_int, [C.POINTER(BertCfg), C.POINTER(c_ptr)]),
+    'sdmi_bert_create_precision': (C.c_int, [C.POINTER(BertCfg), C.c_int, C.POINTER(c_ptr)]),
+    'sdmi_bert_precision': (C.c_int, [c_ptr]),
     'sdmi_bert_destroy': (C.c_int, [c_ptr]),
     'sdmi_bert_num_weights': (C.c_int, [c_ptr]),
     'sdmi_bert_weight_info': (C.c_int, [c_ptr, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int)]),
@@ -142,11 +146,16 @@ _SIGS = {
                                  c_ptr, c_ptr, c_ptr, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_ptr]),
     'sdmi_k_attention_split16': (C.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, C.c_int, C.c_int, C.c_int, C.c_int,
                                            C.c_int, C.c_int, C.c_float, c_ptr]),
+    'sdmi_k_attention_split16_causal': (C.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                  C.c_int, C.c_float, c_ptr]),
     'sdmi_k_attention_causal': (C.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
                                           c_ptr]),
     'sdmi_k_pointwise_nchw': (C.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, c_ptr]),
     'sdmi_k_softmax_rows': (C.c_int, [c_ptr, c_ptr, C.c_int, C.c_int, C.c_float, c_ptr]),
     'sdmi_k_gelu_erf': (C.c_int, [c_ptr, c_ptr, C.c_int64, c_ptr]),
+    'sdmi_k_quick_gelu': (C.c_int, [c_ptr, c_ptr, C.c_int64, c_ptr]),
+    'sdmi_k_quick_gelu_split': (C.c_int, [c_ptr, c_ptr, c_ptr, C.c_int64, c_ptr]),
+    'sdmi_k_gelu_erf_split': (C.c_int, [c_ptr, c_ptr, c_ptr, C.c_int64, c_ptr]),
     'sdmi_k_attention': (C.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                    C.c_float, c_ptr]),
     'sdmi_k_groupnorm': (C.c_int, [c_ptr, c_ptr, C.c_int, C.c_int, C.c_int, C.c_int, c_ptr, c_ptr, C.c_float, C.c_int,

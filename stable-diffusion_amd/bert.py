@@ -8,9 +8,10 @@ Plugged in through the reference's plugin mechanism (`instantiate_from_config(co
       params:
         n_embed: 1280
         n_layer: 32
+        hip_precision: full      # optional: 'mixed' (default) or 'full' (split-fp16 on every MFMA operand)
 
 Same constructor as the reference (`n_embed`, `n_layer`, `vocab_size`, `max_seq_len`, `device`, `use_tokenizer`,
-`embedding_dropout`; modules.py:82-83) plus an injectable `tokenizer`; same `forward(text)` / `encode(text)` returning
+`embedding_dropout`; modules.py:82-83) plus an injectable `tokenizer` and `hip_precision`; same `forward(text)` / `encode(text)` returning
 [B, 77, n_embed]; same parameter names (`transformer.*` of x_transformer.TransformerWrapper, so the `cond_stage_model.*` part
 of the checkpoint loads, `to_logits` included -- it is never used).  Tokenization stays on the host (BertTokenizerFast
 "bert-base-uncased", modules.py:53-70); the transformer runs in libsdmi.so.  No CPU / PyTorch fallback.
@@ -21,7 +22,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .unet import _Node
+from .unet import PRECISIONS, _Node
 
 # x_transformer.Attention defaults (DEFAULT_DIM_HEAD = 64, heads = 8) and FeedForward(mult=4)
 BERT_HEADS, BERT_DIM_HEAD, BERT_FF_MULT = 8, 64, 4
@@ -37,10 +38,10 @@ def make_bert_cfg(n_embed, n_layer, vocab_size=30522, max_seq_len=77):
 class _BertHandle:
     """Owns one sdmi_bert*."""
 
-    def __init__(self, cfg):
+    def __init__(self, cfg, precision='mixed'):
         self.lib = _lib.load()
         h = C.c_void_p()
-        _lib.check(self.lib.sdmi_bert_create(C.byref(cfg), C.byref(h)))
+        _lib.check(self.lib.sdmi_bert_create_precision(C.byref(cfg), PRECISIONS[precision], C.byref(h)))
         self.h = h
 
     def weight_specs(self):
@@ -74,8 +75,14 @@ class BERTEmbedderHIP(nn.Module):
     UNUSED = ('to_logits.weight', 'to_logits.bias')      # return_embeddings=True: accepted, never uploaded
 
     def __init__(self, n_embed, n_layer, vocab_size=30522, max_seq_len=77, device='cuda', use_tokenizer=True,
-                 embedding_dropout=0.0, tokenizer=None):
+                 embedding_dropout=0.0, tokenizer=None, hip_precision='mixed'):
+        """`hip_precision` (not a keyword of the reference BERTEmbedder): 'mixed' (default) = fp16 MFMA operands; 'full' = every MFMA
+        operand split-fp16 (~22-bit operands, fp32 accumulation), slower.  Fixed for the module's lifetime; same
+        parameter names and shapes."""
         super().__init__()
+        if hip_precision not in PRECISIONS:
+            raise ValueError(f"hip_precision must be one of {sorted(PRECISIONS)}, got {hip_precision!r}")
+        self.hip_precision = hip_precision
         self.use_tknz_fn = use_tokenizer
         self.max_length = max_seq_len
         self.tokenizer = None
@@ -84,7 +91,7 @@ class BERTEmbedderHIP(nn.Module):
         self.device = device
         self.embedding_dropout = embedding_dropout        # identity at inference (eval mode)
         self._cfg = make_bert_cfg(n_embed, n_layer, vocab_size, max_seq_len)
-        self._handle = _BertHandle(self._cfg)
+        self._handle = _BertHandle(self._cfg, hip_precision)
         self._specs = self._handle.weight_specs()          # keys relative to `transformer.`
         self.add_module('transformer', _Node())
         for key, shape in self._specs:

@@ -5,8 +5,10 @@ ldm/models/diffusion/ddpm.py:509-520):
 
     cond_stage_config:
       target: stable_diffusion_amd.clip.FrozenCLIPEmbedderHIP
+      params:
+        hip_precision: full      # optional: 'mixed' (default) or 'full' (split-fp16 on every MFMA operand)
 
-Same constructor (`version`, `device`, `max_length`; modules.py:139), same `forward(text)` / `encode(text)` returning
+Same constructor (`version`, `device`, `max_length`; modules.py:139) plus `hip_precision`, same `forward(text)` / `encode(text)` returning
 `last_hidden_state` [B, 77, 768], same parameter names (`transformer.text_model.*` as transformers 4.19.2 -- the version
 the reference pins -- names them, so the `cond_stage_model.*` part of an SD checkpoint loads).  Tokenization stays on the
 host (`CLIPTokenizer`, exactly the reference's call); the transformer runs in libsdmi.so.  No CPU / PyTorch fallback.
@@ -17,7 +19,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .unet import _Node
+from .unet import PRECISIONS, _Node
 
 CLIP_VIT_L14_TEXT = dict(vocab_size=49408, hidden_size=768, intermediate_size=3072, num_hidden_layers=12,
                          num_attention_heads=12, max_position_embeddings=77)
@@ -36,10 +38,10 @@ def make_clip_cfg(tc):
 class _ClipHandle:
     """Owns one sdmi_clip*."""
 
-    def __init__(self, cfg):
+    def __init__(self, cfg, precision='mixed'):
         self.lib = _lib.load()
         h = C.c_void_p()
-        _lib.check(self.lib.sdmi_clip_create(C.byref(cfg), C.byref(h)))
+        _lib.check(self.lib.sdmi_clip_create_precision(C.byref(cfg), PRECISIONS[precision], C.byref(h)))
         self.h = h
 
     def weight_specs(self):
@@ -66,8 +68,14 @@ class FrozenCLIPEmbedderHIP(nn.Module):
     MAX_BATCH = 64
 
     def __init__(self, version='openai/clip-vit-large-patch14', device='cuda', max_length=77, text_config=None,
-                 tokenizer=None):
+                 tokenizer=None, hip_precision='mixed'):
+        """`hip_precision` (not a keyword of the reference FrozenCLIPEmbedder): 'mixed' (default) = fp16 MFMA operands; 'full' = every
+        MFMA operand split-fp16 (~22-bit operands, fp32 accumulation; DESIGN.md section 2), slower.  Fixed for the module's lifetime;
+        same parameter names and shapes."""
         super().__init__()
+        if hip_precision not in PRECISIONS:
+            raise ValueError(f"hip_precision must be one of {sorted(PRECISIONS)}, got {hip_precision!r}")
+        self.hip_precision = hip_precision
         if tokenizer is None:
             from transformers import CLIPTokenizer
             tokenizer = CLIPTokenizer.from_pretrained(version)         # modules.py:141
@@ -76,7 +84,7 @@ class FrozenCLIPEmbedderHIP(nn.Module):
         self.max_length = max_length
         self.text_config = dict(CLIP_VIT_L14_TEXT if text_config is None else text_config)
         self._cfg = make_clip_cfg(self.text_config)
-        self._handle = _ClipHandle(self._cfg)
+        self._handle = _ClipHandle(self._cfg, hip_precision)
         self._specs = self._handle.weight_specs()          # keys relative to `transformer.`
         self.add_module('transformer', _Node())
         for key, shape in self._specs:

@@ -237,13 +237,20 @@ int sdmi_k_softmax_rows(const float* S, void* P_f16, int rows, int cols, float s
 
 
 // ---- text encoder -------------------------------------------------------------------------------------
-int sdmi_clip_create(const sdmi_clip_cfg* cfg, sdmi_clip** out) {
+int sdmi_clip_create(const sdmi_clip_cfg* cfg, sdmi_clip** out) { return sdmi_clip_create_precision(cfg, SDMI_PRECISION_MIXED, out); }
+int sdmi_clip_create_precision(const sdmi_clip_cfg* cfg, int precision, sdmi_clip** out) {
   SDMI_CHECK(cfg && out, "null argument");
+  SDMI_CHECK(precision == SDMI_PRECISION_MIXED || precision == SDMI_PRECISION_FULL,
+             "precision must be SDMI_PRECISION_MIXED (0) or SDMI_PRECISION_FULL (1), got " + std::to_string(precision));
   sdmi_clip* h = new (std::nothrow) sdmi_clip();
   SDMI_CHECK(h != nullptr, "out of host memory");
-  if (h->impl.build(*cfg)) { delete h; return -1; }
+  if (h->impl.build(*cfg, precision)) { delete h; return -1; }
   *out = h;
   return 0;
+}
+int sdmi_clip_precision(const sdmi_clip* h) {
+  if (!h) { fail("null handle"); return -1; }
+  return h->impl.precision_;
 }
 int sdmi_clip_destroy(sdmi_clip* h) { delete h; return 0; }
 int sdmi_clip_num_weights(const sdmi_clip* h) { return h ? (int)h->impl.weights().slots().size() : fail("null handle"); }
@@ -269,13 +276,20 @@ int sdmi_clip_forward(sdmi_clip* h, const int64_t* ids, float* out, int B, int L
 }
 
 // ---- text encoder of the LAION-400M model ----------------------------------------------------------------------------
-int sdmi_bert_create(const sdmi_bert_cfg* cfg, sdmi_bert** out) {
+int sdmi_bert_create(const sdmi_bert_cfg* cfg, sdmi_bert** out) { return sdmi_bert_create_precision(cfg, SDMI_PRECISION_MIXED, out); }
+int sdmi_bert_create_precision(const sdmi_bert_cfg* cfg, int precision, sdmi_bert** out) {
   SDMI_CHECK(cfg && out, "null argument");
+  SDMI_CHECK(precision == SDMI_PRECISION_MIXED || precision == SDMI_PRECISION_FULL,
+             "precision must be SDMI_PRECISION_MIXED (0) or SDMI_PRECISION_FULL (1), got " + std::to_string(precision));
   sdmi_bert* h = new (std::nothrow) sdmi_bert();
   SDMI_CHECK(h != nullptr, "out of host memory");
-  if (h->impl.build(*cfg)) { delete h; return -1; }
+  if (h->impl.build(*cfg, precision)) { delete h; return -1; }
   *out = h;
   return 0;
+}
+int sdmi_bert_precision(const sdmi_bert* h) {
+  if (!h) { fail("null handle"); return -1; }
+  return h->impl.precision_;
 }
 int sdmi_bert_destroy(sdmi_bert* h) { delete h; return 0; }
 int sdmi_bert_num_weights(const sdmi_bert* h) { return h ? (int)h->impl.weights().slots().size() : fail("null handle"); }
@@ -317,6 +331,23 @@ int sdmi_k_patch_fold(const float* o, const float* w, float* out, int B, int C, 
 }
 int sdmi_k_gelu_erf(const float* x, void* out_f16, int64_t n, void* stream) {
   return launch_gelu_erf(x, (f16*)out_f16, n, (hipStream_t)stream);
+}
+int sdmi_k_quick_gelu(const float* x, void* out_f16, int64_t n, void* stream) {
+  return launch_quick_gelu(x, (f16*)out_f16, n, (hipStream_t)stream);
+}
+int sdmi_k_quick_gelu_split(const float* x, void* out, void* out_lo, int64_t n, void* stream) {
+  return launch_quick_gelu_split(x, (f16*)out, (f16*)out_lo, n, (hipStream_t)stream);
+}
+int sdmi_k_gelu_erf_split(const float* x, void* out, void* out_lo, int64_t n, void* stream) {
+  return launch_gelu_erf_split(x, (f16*)out, (f16*)out_lo, n, (hipStream_t)stream);
+}
+int sdmi_k_attention_split16_causal(const void* q, const void* q_lo, const void* k, const void* k_lo, const void* vt, const void* vt_lo,
+                                    void* out, void* out_lo, int BH, int heads, int n, int n_pad, int d, float scale, void* stream) {
+  AttnSplitParams p = AttnSplitParams();
+  p.q = (const f16*)q; p.q_lo = (const f16*)q_lo; p.k = (const f16*)k; p.k_lo = (const f16*)k_lo;
+  p.vt = (const f16*)vt; p.vt_lo = (const f16*)vt_lo; p.out = (f16*)out; p.out_lo = (f16*)out_lo;
+  p.BH = BH; p.heads = heads; p.nq = n; p.nkv = n; p.nkv_pad = n_pad; p.d = d; p.scale = scale; p.causal = 1;
+  return launch_attention_split16(p, (hipStream_t)stream);
 }
 int sdmi_k_attention_causal(const void* q, const void* k, const void* vt, void* out, int BH, int heads, int n, int n_pad,
                             int d, float scale, void* stream) {

@@ -19,7 +19,11 @@ constexpr int KVT = 64;
 
 __device__ __forceinline__ f16 lo_of(float v, f16 hi) { return (f16)(v - (float)hi); }   // the low half of a split-fp16 pair
 
-template <int D, int NW>
+// CAUSAL (the text encoder of the full-precision mode, clip.cpp): nq == nkv, query i sees keys <= i.  The mask is applied to the scores
+// beside the key-range mask; every wave, with queries or without, walks every key tile of the workgroup and takes part in both barriers
+// (no tile is skipped: at the text lengths one workgroup holds all queries).  Key 0 is visible to every query, so the running maximum is
+// finite from the first tile on and a masked score of -1e30 exponentiates to exactly 0.
+template <int D, int NW, bool CAUSAL>
 __global__ void __launch_bounds__(NW * 64) attn_split16_kernel(const AttnSplitParams p) {
   constexpr int DKS = (D + 15) / 16;   // k-steps of 16 over the head dim (QK^T)
   constexpr int DVT = (D + 31) / 32;   // 32-row tiles over the head dim (PV)
@@ -114,6 +118,15 @@ __global__ void __launch_bounds__(NW * 64) attn_split16_kernel(const AttnSplitPa
           if (kv >= p.nkv) s[kvb][r] = -1e30f;
         }
     }
+    if (CAUSAL && kv0 + KVT - 1 > q0) {          // (wave-uniform: the tile reaches past the wave's first query)
+#pragma unroll
+      for (int kvb = 0; kvb < KVT / 32; ++kvb)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int kv = kv0 + kvb * 32 + (r & 3) + 8 * (r >> 2) + 4 * lg;
+          if (kv > q0 + l31) s[kvb][r] = -1e30f;
+        }
+    }
     // ---- online softmax in fp32 (per query = per lane column; the halves lg = 0 / 1 hold disjoint keys) ----
     float mx = -1e30f;
 #pragma unroll
@@ -195,11 +208,11 @@ __global__ void __launch_bounds__(NW * 64) attn_split16_kernel(const AttnSplitPa
   }
 }
 
-template <int D>
+template <int D, bool CAUSAL = false>
 int launch_d(const AttnSplitParams& p, hipStream_t stream) {
   constexpr int NW = 4;
   dim3 grid((unsigned)((p.nq + 32 * NW - 1) / (32 * NW)), (unsigned)p.BH);
-  SDMI_LAUNCH(attn_split16_kernel<D, NW>, grid, dim3(NW * 64), 0, stream, p);
+  SDMI_LAUNCH((attn_split16_kernel<D, NW, CAUSAL>), grid, dim3(NW * 64), 0, stream, p);
   SDMI_HIP_OK(hipGetLastError());
   return 0;
 }
@@ -214,7 +227,17 @@ int launch_attention_split16(const AttnSplitParams& p, hipStream_t stream) {
   // 2 x MACs of Q K^T and P V (algorithmic); the kernel executes three MFMA passes of each
   const double flops = 4.0 * p.BH * (double)p.nq * p.nkv * p.d;
   const double bytes = 2.0 * 2.0 * p.BH * ((double)p.nq * p.d * 2 + (double)p.nkv * p.d + (double)p.d * p.nkv_pad);
-  ProfScope ps("attention_split16", flops, bytes, stream, 3.0 * flops);
+  ProfScope ps(p.causal ? "attention_split16_causal" : "attention_split16", flops, bytes, stream, 3.0 * flops);
+  if (p.causal) {
+    SDMI_CHECK(p.nq == p.nkv, "split-fp16 causal attention: nq must equal nkv");
+    switch (p.d) {
+      case 32: return launch_d<32, true>(p, stream);
+      case 64: return launch_d<64, true>(p, stream);
+      case 128: return launch_d<128, true>(p, stream);
+      default:
+        return fail("split-fp16 causal attention: head dim " + std::to_string(p.d) + " has no instantiation (32, 64, 128)");
+    }
+  }
   switch (p.d) {
     case 24: return launch_d<24>(p, stream);       // (the staging writes zeros into the unused half of the second k-step and the V^T rows past d)
     case 32: return launch_d<32>(p, stream);

@@ -9,6 +9,7 @@
 // No causal mask and no padding mask: every token attends to all L.  Same kernels as CLIP (clip.cpp): igemm with the per-head
 // scatter epilogue for q|k|v, the plain epilogue with bias + residual + next-LayerNorm post-op for to_out and net.2, the
 // flash-attention kernel, layernorm; the exact-erf GELU kernel for the feed-forward.
+// A SDMI_PRECISION_FULL handle runs the shared split-fp16 walk instead (TextEncBase::forward_full, clip.cpp).
 #include <algorithm>
 
 #include "clip.h"
@@ -17,13 +18,15 @@
 
 namespace sdmi {
 
-int BertText::build(const sdmi_bert_cfg& c) {
+int BertText::build(const sdmi_bert_cfg& c, int precision) {
   cfg_ = c;
+  precision_ = precision;
   SDMI_CHECK(c.dim >= 64 && c.dim % 64 == 0 && c.dim <= 2560, "dim must be a multiple of 64 (64..2560)");
   SDMI_CHECK(c.ff_inner >= 64 && c.ff_inner % 64 == 0, "ff_inner must be a multiple of 64");
   const int dh = c.dim_head;
   SDMI_CHECK(dh == 32 || dh == 40 || dh == 64 || dh == 80 || dh == 128 || dh == 160,
              "dim_head must be one the attention kernel has (32, 40, 64, 80, 128, 160)");
+  // (the full-precision mode refuses nothing more: the non-causal split-fp16 attention has every head dim of this set)
   SDMI_CHECK(c.heads >= 1 && (c.heads * dh) % 64 == 0, "heads * dim_head must be a multiple of 64");
   SDMI_CHECK(c.depth >= 1 && c.vocab_size >= 1 && c.max_seq_len >= 1, "bad BERT config (depth, vocab_size, max_seq_len >= 1)");
   const int64_t D = c.dim, F = c.ff_inner, I = (int64_t)c.heads * dh;
@@ -37,14 +40,14 @@ int BertText::build(const sdmi_bert_cfg& c) {
     store_.expect(a + "0.weight", {D}, W_F32, &Ly.ln[0]);
     store_.expect(a + "0.bias", {D}, W_F32, &Ly.ln[1]);
     const char* names[3] = {"to_q", "to_k", "to_v"};
-    for (int j = 0; j < 3; ++j) store_.expect(a + "1." + names[j] + ".weight", {I, D}, W_ROWS16, &Ly.wqkv, j * (int)I, 3 * (int)I);
-    store_.expect(a + "1.to_out.weight", {D, I}, W_ROWS16, &Ly.wo);
+    for (int j = 0; j < 3; ++j) store_.expect(a + "1." + names[j] + ".weight", {I, D}, lin_kind(), &Ly.wqkv, j * (int)I, 3 * (int)I);
+    store_.expect(a + "1.to_out.weight", {D, I}, lin_kind(), &Ly.wo);
     store_.expect(a + "1.to_out.bias", {D}, W_F32, &Ly.bo);
     store_.expect(f + "0.weight", {D}, W_F32, &Ly.ln[2]);
     store_.expect(f + "0.bias", {D}, W_F32, &Ly.ln[3]);
-    store_.expect(f + "1.net.0.0.weight", {F, D}, W_ROWS16, &Ly.w1);
+    store_.expect(f + "1.net.0.0.weight", {F, D}, lin_kind(), &Ly.w1);
     store_.expect(f + "1.net.0.0.bias", {F}, W_F32, &Ly.b1);
-    store_.expect(f + "1.net.2.weight", {D, F}, W_ROWS16, &Ly.w2);
+    store_.expect(f + "1.net.2.weight", {D, F}, lin_kind(), &Ly.w2);
     store_.expect(f + "1.net.2.bias", {D}, W_F32, &Ly.b2);
   }
   store_.expect("norm.weight", {D}, W_F32, &fln_g_);
@@ -66,6 +69,14 @@ int BertText::forward(const int64_t* ids, float* out, int B, int L, void* worksp
   // split-K slabs: the auto split of the to_out / net.2 GEMMs at the LAION shape (N = 1280, K = 5120, M = 2 x 77) takes 8
   // splits of 64 x 64 tiles = 2M floats; room for 16 splits of the widest N at up to 256 rows, 4M floats at least (CLIP's size)
   const int64_t slab_floats = std::max<int64_t>((int64_t)4 << 20, (int64_t)16 * 256 * std::max(D, 3 * I));
+  if (full()) {
+    TextFullDesc t;
+    t.dim = D; t.inner = I; t.ff = F; t.heads = H; t.dh = dh; t.vocab = cfg_.vocab_size; t.causal = false; t.erf = true;
+    t.tok = tok_; t.pos = pos_; t.fln_g = fln_g_; t.fln_b = fln_b_; t.slab_floats = slab_floats;
+    for (const BLayer& Ly : layers_)
+      t.layers.push_back({Ly.wqkv, nullptr, Ly.wo, Ly.bo, Ly.w1, Ly.b1, Ly.w2, Ly.b2, {Ly.ln[0], Ly.ln[1], Ly.ln[2], Ly.ln[3]}});
+    return forward_full(t, ids, out, B, L, workspace, ws_bytes, stream, dry, bytes_needed);
+  }
   FwdBase f;
   f.s = stream; f.B = B; f.zero = store_.zero(); f.precise_1x1 = false;
   int64_t persist_bytes = 0;

@@ -7,18 +7,22 @@
 //   last_hidden_state = final_layer_norm(x)
 // Same kernels as the UNet's transformer blocks: igemm (per-head scatter epilogue with bias, plain epilogue with the
 // LayerNorm post-op), the flash-attention kernel with a causal mask, layernorm; the token stream is fp32.
+// SDMI_PRECISION_FULL handles (both encoders) run TextEncBase::forward_full at the end of this file instead: split-fp16 operands on every MFMA.
 #include "clip.h"
 
 #include <math.h>
 
 namespace sdmi {
 
-int ClipText::build(const sdmi_clip_cfg& c) {
+int ClipText::build(const sdmi_clip_cfg& c, int precision) {
   cfg_ = c;
+  precision_ = precision;
   SDMI_CHECK(c.hidden_size % 64 == 0 && c.intermediate_size % 64 == 0, "hidden / intermediate size must be multiples of 64");
   SDMI_CHECK(c.num_heads >= 1 && c.hidden_size % c.num_heads == 0, "hidden_size % num_heads");
   const int dh = c.hidden_size / c.num_heads;
   SDMI_CHECK(dh == 32 || dh == 40 || dh == 64 || dh == 80 || dh == 128 || dh == 160, "head dim must be one the attention kernel has");
+  SDMI_CHECK(!full() || dh == 32 || dh == 64 || dh == 128, "full-precision CLIP text encoder: head dim " + std::to_string(dh) +
+                                                               " has no causal split-fp16 attention kernel (32, 64, 128)");
   SDMI_CHECK(c.num_layers >= 1 && c.vocab_size >= 1 && c.max_positions >= 1 && c.hidden_size <= 2560, "bad text-model config");
   const int64_t C = c.hidden_size, I = c.intermediate_size;
   layers_.resize(c.num_layers);
@@ -30,16 +34,16 @@ int ClipText::build(const sdmi_clip_cfg& c) {
     const std::string p = tm + "encoder.layers." + std::to_string(i) + ".";
     const char* names[3] = {"q_proj", "k_proj", "v_proj"};
     for (int j = 0; j < 3; ++j) {
-      store_.expect(p + "self_attn." + names[j] + ".weight", {C, C}, W_ROWS16, &L.wqkv, j * (int)C, 3 * (int)C);
+      store_.expect(p + "self_attn." + names[j] + ".weight", {C, C}, lin_kind(), &L.wqkv, j * (int)C, 3 * (int)C);
       store_.expect(p + "self_attn." + names[j] + ".bias", {C}, W_F32_ROWS, &L.bqkv, j * (int)C, 3 * (int)C);
     }
-    store_.expect(p + "self_attn.out_proj.weight", {C, C}, W_ROWS16, &L.wo);
+    store_.expect(p + "self_attn.out_proj.weight", {C, C}, lin_kind(), &L.wo);
     store_.expect(p + "self_attn.out_proj.bias", {C}, W_F32, &L.bo);
     store_.expect(p + "layer_norm1.weight", {C}, W_F32, &L.ln[0]);
     store_.expect(p + "layer_norm1.bias", {C}, W_F32, &L.ln[1]);
-    store_.expect(p + "mlp.fc1.weight", {I, C}, W_ROWS16, &L.w1);
+    store_.expect(p + "mlp.fc1.weight", {I, C}, lin_kind(), &L.w1);
     store_.expect(p + "mlp.fc1.bias", {I}, W_F32, &L.b1);
-    store_.expect(p + "mlp.fc2.weight", {C, I}, W_ROWS16, &L.w2);
+    store_.expect(p + "mlp.fc2.weight", {C, I}, lin_kind(), &L.w2);
     store_.expect(p + "mlp.fc2.bias", {C}, W_F32, &L.b2);
     store_.expect(p + "layer_norm2.weight", {C}, W_F32, &L.ln[2]);
     store_.expect(p + "layer_norm2.bias", {C}, W_F32, &L.ln[3]);
@@ -67,6 +71,15 @@ int ClipText::forward(const int64_t* ids, float* out, int B, int L, void* worksp
   SDMI_CHECK(dry || finalized_, "sdmi_clip_finalize() has not succeeded yet");
   SDMI_CHECK(B >= 1 && B <= 64 && L >= 1 && L <= cfg_.max_positions, "batch 1..64, 1 <= L <= max_positions");
   SDMI_CHECK(dry || (ids != nullptr && out != nullptr), "ids / out is NULL");
+  if (full()) {
+    TextFullDesc t;
+    t.dim = t.inner = cfg_.hidden_size; t.ff = cfg_.intermediate_size; t.heads = cfg_.num_heads; t.dh = t.dim / t.heads;
+    t.vocab = cfg_.vocab_size; t.causal = true; t.erf = false;
+    t.tok = tok_; t.pos = pos_; t.fln_g = fln_g_; t.fln_b = fln_b_; t.slab_floats = (int64_t)4 << 20;
+    for (const CLayer& Ly : layers_)
+      t.layers.push_back({Ly.wqkv, Ly.bqkv, Ly.wo, Ly.bo, Ly.w1, Ly.b1, Ly.w2, Ly.b2, {Ly.ln[0], Ly.ln[1], Ly.ln[2], Ly.ln[3]}});
+    return forward_full(t, ids, out, B, L, workspace, ws_bytes, stream, dry, bytes_needed);
+  }
   const int C = cfg_.hidden_size, I = cfg_.intermediate_size, H = cfg_.num_heads, dh = C / H;
   const int M = B * L, Lp = (int)round_up(L, 8);
   const float scale = 1.0f / sqrtf((float)dh);
@@ -136,6 +149,75 @@ int ClipText::forward(const int64_t* ids, float* out, int B, int L, void* worksp
       }
     }
     if (!d && !f.rc) f.ok(launch_layernorm(x, fln_g_, fln_b_, nullptr, M, C, 1e-5f, stream, out));
+    if (f.rc) return f.rc;
+    if (d) {
+      persist_bytes = (int64_t)round_up((int64_t)f.persist.peak, 4096) + 4096;
+      if (bytes_needed) *bytes_needed = persist_bytes;
+    } else {
+      SDMI_CHECK(!f.persist.overflow, "internal: arena overflow");
+    }
+  }
+  return 0;
+}
+
+int TextEncBase::forward_full(const TextFullDesc& t, const int64_t* ids, float* out, int B, int L, void* workspace, int64_t ws_bytes,
+                              hipStream_t stream, bool dry, int64_t* bytes_needed) {
+  const int D = t.dim, I = t.inner, F = t.ff, H = t.heads, dh = t.dh;
+  const int M = B * L, Lp = (int)round_up(L, 8);
+  const float scale = 1.0f / sqrtf((float)dh);
+  FwdBase f;
+  f.s = stream; f.B = B; f.zero = store_.zero(); f.precise_1x1 = true;
+  int64_t persist_bytes = 0;
+  for (int pass = 0; pass < 2; ++pass) {
+    const bool d = pass == 0;
+    if (pass == 1 && dry) break;
+    f.dry = d; f.rc = 0;
+    f.persist = Arena(); f.scratch = Arena();
+    f.persist.dry = f.scratch.dry = d;
+    if (!d) {
+      SDMI_CHECK(persist_bytes <= ws_bytes, "workspace too small: need " + std::to_string(persist_bytes) + " bytes, got " +
+                                                std::to_string(ws_bytes));
+      SDMI_CHECK(workspace != nullptr, "workspace is NULL");
+      f.persist.base = (char*)workspace; f.persist.cap = (size_t)persist_bytes;
+    }
+    if (f.begin_pass(t.slab_floats, /*with_gn=*/false)) return -1;
+    float* x = f.P<float>((size_t)M * D);                                         // the token stream
+    const size_t na = (size_t)M * (D > I ? D : I), ny = (size_t)M * (3 * I > F ? 3 * I : F);
+    f16* a = f.P<f16>(na); f16* a_lo = f.P<f16>(na);                              // the operand of the next linear: LayerNorm / attention output
+    float* y = f.P<float>(ny);                                                    // q | k | v, then fc1 (fp32)
+    f16* q = f.P<f16>((size_t)M * I); f16* q_lo = f.P<f16>((size_t)M * I);
+    f16* k = f.P<f16>((size_t)M * I); f16* k_lo = f.P<f16>((size_t)M * I);
+    f16* vt = f.P<f16>((size_t)B * I * Lp); f16* vt_lo = f.P<f16>((size_t)B * I * Lp);
+    f16* g = f.P<f16>((size_t)M * F); f16* g_lo = f.P<f16>((size_t)M * F);
+    auto linear = [&](const f16* hi, const f16* lo, int K, const f16* w, int n_out, const float* bias, float* dst, bool residual) {
+      IGemmParams p = f.dense1x1(hi, lo, M, K, w, n_out, L, true);
+      p.bias = bias; p.out_f32 = dst; p.ldo = n_out;
+      if (residual) { p.residual = dst; p.ldr = n_out; }       // x = f(x) + x, in place
+      f.gemm(p);
+    };
+    auto launch = [&](auto&& fn) { if (!d && !f.rc) f.ok(fn()); };
+    launch([&] { return launch_embed_tokens(ids, t.tok, t.pos, x, M, L, D, t.vocab, stream); });
+    for (const TextFullLayer& Ly : t.layers) {
+      launch([&] { return launch_layernorm_split(x, Ly.ln[0], Ly.ln[1], a, a_lo, M, D, 1e-5f, stream); });
+      linear(a, a_lo, D, Ly.wqkv, 3 * I, Ly.bqkv, y, false);
+      launch([&] { return launch_split_heads(y, 3 * I, 0, q, q_lo, 0, B, L, Lp, H, dh, stream); });
+      launch([&] { return launch_split_heads(y, 3 * I, I, k, k_lo, 0, B, L, Lp, H, dh, stream); });
+      launch([&] { return launch_split_heads(y, 3 * I, 2 * I, vt, vt_lo, 1, B, L, Lp, H, dh, stream); });   // (pad keys written as zero)
+      launch([&] {
+        AttnSplitParams p = AttnSplitParams();
+        p.q = q; p.q_lo = q_lo; p.k = k; p.k_lo = k_lo; p.vt = vt; p.vt_lo = vt_lo; p.out = a; p.out_lo = a_lo;
+        p.BH = B * H; p.heads = H; p.nq = L; p.nkv = L; p.nkv_pad = Lp; p.d = dh; p.scale = scale; p.causal = t.causal ? 1 : 0;
+        return launch_attention_split16(p, stream);
+      });
+      linear(a, a_lo, I, Ly.wo, D, Ly.bo, x, true);
+      launch([&] { return launch_layernorm_split(x, Ly.ln[2], Ly.ln[3], a, a_lo, M, D, 1e-5f, stream); });
+      linear(a, a_lo, D, Ly.w1, F, Ly.b1, y, false);
+      launch([&] {
+        return t.erf ? launch_gelu_erf_split(y, g, g_lo, (int64_t)M * F, stream) : launch_quick_gelu_split(y, g, g_lo, (int64_t)M * F, stream);
+      });
+      linear(g, g_lo, F, Ly.w2, D, Ly.b2, x, true);
+    }
+    launch([&] { return launch_layernorm(x, t.fln_g, t.fln_b, nullptr, M, D, 1e-5f, stream, out); });
     if (f.rc) return f.rc;
     if (d) {
       persist_bytes = (int64_t)round_up((int64_t)f.persist.peak, 4096) + 4096;

@@ -6,6 +6,7 @@
 
 #include "../../include/sdmi.h"
 #include "common.h"
+#include "split16.h"
 #include "unet.h"
 
 namespace sdmi {
@@ -18,21 +19,47 @@ struct CLayer {   // CLIPEncoderLayer
   float* ln[4] = {nullptr, nullptr, nullptr, nullptr};   // layer_norm1.{weight,bias}, layer_norm2.{weight,bias}
 };
 
-// Host plumbing shared by the text encoders: the weight store and the all-set check.  No device code of its own.
+// One transformer layer as the full-precision walk sees it (both encoders): pre-norm attention and feed-forward, weights packed
+// W_SPLIT3_ROWS ([rows][3K] = [hi | hi | lo])
+struct TextFullLayer {
+  const f16* wqkv; const float* bqkv;      // [3 inner][3 dim]; bias [3 inner] or null (BERT)
+  const f16* wo; const float* bo;
+  const f16* w1; const float* b1;
+  const f16* w2; const float* b2;
+  const float* ln[4];
+};
+struct TextFullDesc {
+  int dim = 0, inner = 0, ff = 0, heads = 0, dh = 0, vocab = 0;
+  bool causal = false, erf = false;        // CLIP: causal mask, quick_gelu; BERT: no mask, exact-erf GELU
+  const float *tok = nullptr, *pos = nullptr, *fln_g = nullptr, *fln_b = nullptr;
+  int64_t slab_floats = 0;                 // split-K slabs (the mixed walk's size)
+  std::vector<TextFullLayer> layers;
+};
+
+// Host plumbing shared by the text encoders: the weight store, the all-set check and the full-precision layer walk.
 class TextEncBase {
  public:
   int set_weight(const char* key, const float* ptr, const int64_t* shape, int ndim, hipStream_t stream);
   int finalize();
   const WeightStore& weights() const { return store_; }
+  int precision_ = SDMI_PRECISION_MIXED;       // fixed at creation
+  bool full() const { return precision_ == SDMI_PRECISION_FULL; }
 
  protected:
+  // SDMI_PRECISION_FULL: every MFMA operand a split-fp16 pair, as attn_block_full (unet.cpp) runs the UNet's transformer blocks:
+  // layernorm_split -> split-fp16 GEMM into fp32 -> split_heads x 3 -> attn_split16 (causal or not) -> out-projection with bias and
+  // in-place residual -> layernorm_split -> fc1 -> activation producer (hi | lo) -> fc2 with bias and residual; the final LayerNorm
+  // writes fp32.  No LayerNorm post-op and no per-head scatter epilogue: both round to fp16.
+  int forward_full(const TextFullDesc& t, const int64_t* ids, float* out, int B, int L, void* workspace, int64_t ws_bytes,
+                   hipStream_t stream, bool dry, int64_t* bytes_needed);
+  WKind lin_kind() const { return full() ? W_SPLIT3_ROWS : W_ROWS16; }
   WeightStore store_;           // (slots point into the layer objects of the derived class)
   bool finalized_ = false;
 };
 
 class ClipText : public TextEncBase {
  public:
-  int build(const sdmi_clip_cfg& cfg);
+  int build(const sdmi_clip_cfg& cfg, int precision = SDMI_PRECISION_MIXED);
   // ids int64 [B][L] (device) -> last_hidden_state fp32 [B][L][hidden] (after final_layer_norm)
   int forward(const int64_t* ids, float* out, int B, int L, void* workspace, int64_t ws_bytes, hipStream_t stream, bool dry,
               int64_t* bytes_needed);
@@ -54,7 +81,7 @@ struct BLayer {   // one ('a', 'f') pair of x_transformer.Encoder
 // BERTEmbedder's TransformerWrapper(return_embeddings=True) (see bert.cpp)
 class BertText : public TextEncBase {
  public:
-  int build(const sdmi_bert_cfg& cfg);
+  int build(const sdmi_bert_cfg& cfg, int precision = SDMI_PRECISION_MIXED);
   // ids int64 [B][L] (device) -> embeddings fp32 [B][L][dim] (after the final LayerNorm)
   int forward(const int64_t* ids, float* out, int B, int L, void* workspace, int64_t ws_bytes, hipStream_t stream, bool dry,
               int64_t* bytes_needed);

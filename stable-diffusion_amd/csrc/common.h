@@ -461,6 +461,10 @@ int launch_embed_tokens(const int64_t* ids, const float* tok_emb, const float* p
                         int vocab, hipStream_t s);
 int launch_quick_gelu(const float* x, f16* out, int64_t n, hipStream_t s);
 int launch_gelu_erf(const float* x, f16* out, int64_t n, hipStream_t s);
+// ... the same activations as split-fp16 operand producers: out = fp16(y), the bits of the kernels above, out_lo = fp16(y_ref - out) with
+// y_ref = y (quick_gelu) or the erfc form of the GELU (erf: out + out_lo is then the function itself, not gelu_erf's approximation of it)
+int launch_quick_gelu_split(const float* x, f16* out, f16* out_lo, int64_t n, hipStream_t s);
+int launch_gelu_erf_split(const float* x, f16* out, f16* out_lo, int64_t n, hipStream_t s);
 
 // first-stage (VAE) helpers
 int launch_pointwise_nchw(const float* x_nchw, const float* w, const float* bias, float* out_nchw, int B, int Cin, int Cout,

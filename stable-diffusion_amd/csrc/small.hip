@@ -473,6 +473,27 @@ __global__ void __launch_bounds__(256) gelu_erf_kernel(const float* x, f16* out,
   *(f16x4*)(out + i * 4) = y;
 }
 
+// The two activations as producers of a split-fp16 GEMM operand (the text encoders' full-precision mode): hi = fp16(y) with y the fp32
+// expression of the kernels above -- the same bits -- and lo = fp16(y_ref - hi).  quick_gelu: y_ref = y.  The erf form: gelu_erf's erf
+// (Abramowitz-Stegun, 1.5e-7 absolute) leaves y up to two fp16 ulps off for x around -4, where 1 + erf cancels; y_ref is the erfc form
+// (as geglu_split_kernel, split_ops.hip), so that hi + lo carries the GELU itself and lo takes up what hi is off by.
+template <bool ERF>
+__global__ void __launch_bounds__(256) gelu_split_kernel(const float* x, f16* out, f16* out_lo, int64_t n4) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n4) return;
+  const f32x4 v = *(const f32x4*)(x + i * 4);
+  f16x4 h, l;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const float y = ERF ? gelu_erf(v[j]) : v[j] / (1.0f + __expf(-1.702f * v[j]));
+    const float y_ref = ERF ? 0.5f * v[j] * erfcf(-v[j] * 0.70710678118654752f) : y;
+    h[j] = (f16)y;
+    l[j] = (f16)(y_ref - (float)h[j]);
+  }
+  *(f16x4*)(out + i * 4) = h;
+  *(f16x4*)(out_lo + i * 4) = l;
+}
+
 // ---- first-stage (VAE) helpers ---------------------------------------------------------------------------------------
 // 1x1 conv on a few channels, NCHW fp32 -> NCHW fp32, input optionally pre-scaled:
 // post_quant_conv / quant_conv (ldm/models/autoencoder.py:302-303) and the 1/scale_factor of decode_first_stage
@@ -640,6 +661,22 @@ int launch_quick_gelu(const float* x, f16* out, int64_t n, hipStream_t s) {
 int launch_gelu_erf(const float* x, f16* out, int64_t n, hipStream_t s) {
   SDMI_CHECK(n % 4 == 0, "gelu_erf: n % 4");
   SDMI_LAUNCH(gelu_erf_kernel, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, s, x, out, n / 4);
+  SDMI_HIP_OK(hipGetLastError());
+  return 0;
+}
+
+int launch_quick_gelu_split(const float* x, f16* out, f16* out_lo, int64_t n, hipStream_t s) {
+  SDMI_CHECK(x && out && out_lo, "quick_gelu_split: null operand");
+  SDMI_CHECK(n >= 4 && n % 4 == 0, "quick_gelu_split: n % 4");
+  SDMI_LAUNCH(gelu_split_kernel<false>, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, s, x, out, out_lo, n / 4);
+  SDMI_HIP_OK(hipGetLastError());
+  return 0;
+}
+
+int launch_gelu_erf_split(const float* x, f16* out, f16* out_lo, int64_t n, hipStream_t s) {
+  SDMI_CHECK(x && out && out_lo, "gelu_erf_split: null operand");
+  SDMI_CHECK(n >= 4 && n % 4 == 0, "gelu_erf_split: n % 4");
+  SDMI_LAUNCH(gelu_split_kernel<true>, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, s, x, out, out_lo, n / 4);
   SDMI_HIP_OK(hipGetLastError());
   return 0;
 }

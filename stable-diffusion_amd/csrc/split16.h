@@ -15,6 +15,7 @@ struct AttnSplitParams {
   f16* out = nullptr; f16* out_lo = nullptr;
   int BH = 0, heads = 0, nq = 0, nkv = 0, nkv_pad = 0, d = 0;
   float scale = 1.f;
+  int causal = 0;      // 1: query i sees keys <= i (nq == nkv; d = 32, 64, 128 -- the text encoders' full-precision mode)
 };
 int launch_attention_split16(const AttnSplitParams& p, hipStream_t stream);
 // ... its wide-head form (attn_wide_split16.hip: d = 192 .. 1024 in steps of 64; the V^T pad columns may hold anything there).
