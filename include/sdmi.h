@@ -313,6 +313,57 @@ int64_t sdmi_bert_workspace_bytes(sdmi_bert* h, int B, int L);
 int sdmi_bert_forward(sdmi_bert* h, const int64_t* ids, float* out, int B, int L, void* workspace, int64_t workspace_bytes,
                       void* stream);
 
+/* ---- CLIP image encoder (vision tower) ------------------------------------------------------------------------------
+ * transformers' CLIPVisionModelWithProjection: the tower of the safety checker that scripts/txt2img.py:check_safety and
+ * scripts/img2img.py run on every decoded image, and of FrozenClipImageEmbedder (ldm/modules/encoders/modules.py:197-228).
+ * Mixed precision only (fp16 MFMA operands, fp32 accumulation and residual stream).  Refused at creation, each with a message
+ * that names it: hidden_size or intermediate_size off the 64 grid, a head dim the attention kernel does not have,
+ * image_size % patch_size != 0, more than 1024 tokens; at run time B > 64. */
+typedef struct sdmi_vit sdmi_vit;
+/* CLIPVisionConfig fields + projection_dim (openai/clip-vit-large-patch14: 224, 14, 1024, 4096, 24, 16, 768); hidden_act = quick_gelu */
+typedef struct sdmi_vit_cfg {
+  int32_t image_size;
+  int32_t patch_size;
+  int32_t hidden_size;
+  int32_t intermediate_size;
+  int32_t num_layers;
+  int32_t num_heads;
+  int32_t projection_dim;
+} sdmi_vit_cfg;
+int sdmi_vit_create(const sdmi_vit_cfg* cfg, sdmi_vit** out);
+int sdmi_vit_destroy(sdmi_vit* h);
+/* state_dict keys of CLIPVisionModelWithProjection: `vision_model.embeddings.{class_embedding, patch_embedding.weight,
+ * position_embedding.weight}`, `vision_model.pre_layrnorm.*` (the reference's spelling), `vision_model.encoder.layers.N.*`,
+ * `vision_model.post_layernorm.*`, `visual_projection.weight` */
+int sdmi_vit_num_weights(const sdmi_vit* h);
+int sdmi_vit_weight_info(const sdmi_vit* h, int idx, char* key_buf, int key_buf_len, int64_t* shape4, int* ndim);
+int sdmi_vit_set_weight(sdmi_vit* h, const char* key, const float* ptr, const int64_t* shape, int ndim, void* stream);
+int sdmi_vit_finalize(sdmi_vit* h);
+int64_t sdmi_vit_workspace_bytes(sdmi_vit* h, int B);
+/* pixel_values: fp32 [B, 3, image_size, image_size] (device), B <= 64.  last_hidden (optional): fp32 [B, T, hidden_size], the encoder
+ * output, T = 1 + (image_size / patch_size)^2; pooled (optional): fp32 [B, hidden_size] = post_layernorm(last_hidden[:, 0]);
+ * image_embeds: fp32 [B, projection_dim] = visual_projection(pooled) */
+int sdmi_vit_forward(sdmi_vit* h, const float* pixel_values, float* last_hidden_or_null, float* pooled_or_null, float* image_embeds, int B,
+                     void* workspace, int64_t workspace_bytes, void* stream);
+/* The tower's streaming kernels.  patchify: fp32 [B, 3, S, S] -> fp16 rows [B (S / p)^2][Kp], column (c, ky, kx) of patch (py, px) in the
+ * order of the conv weight's own [3][p][p] tail, Kp = 3 p^2 rounded up to a multiple of 64 (sdmi_k_vit_kpad), pad columns zero.
+ * embed: out fp32 [B, T, C], row 0 = class_embedding + position_embedding[0], row 1 + i = patch row i + position_embedding[1 + i].
+ * preprocess (FrozenClipImageEmbedder.preprocess): fp32 [B, 3, H, W] in [-1, 1] -> bicubic resize to S x S (align_corners=True,
+ * A = -0.75, border taps clamped, no antialiasing), (x + 1) / 2, then (x - mean) / std with CLIP's constants. */
+int sdmi_k_vit_kpad(int patch_size);
+int sdmi_k_vit_patchify(const float* pixel_values, void* out_f16, int B, int S, int p, void* stream);
+int sdmi_k_vit_embed(const float* patch, const float* class_embedding, const float* position_embedding, float* out, int B, int T, int C,
+                     void* stream);
+int sdmi_k_vit_preprocess(const float* x, float* out, int B, int H, int W, int S, void* stream);
+/* StableDiffusionSafetyChecker.forward behind the tower, all fp32: every vector L2-normalised, all cosines; per image adjustment = 0; for each
+ * special-care concept in index order s = round3(cos - threshold + adjustment) (three decimals, half to even), s > 0 sets adjustment = 0.01;
+ * for each concept s = round3(cos - threshold + adjustment), bad if s > 0; has_nsfw[b] = any bad.  image_embeds [B, E], concept_embeds
+ * [Nc, E], special_care_embeds [Ns, E], thresholds [Nc] / [Ns]; outputs int32 has_nsfw [B] and the rounded scores [B, Nc] / [B, Ns].
+ * 1 <= Nc <= 64, 0 <= Ns <= 64 (the special-care pointers may be NULL when Ns = 0), E % 4 == 0, E <= 8192. */
+int sdmi_k_safety_head(const float* image_embeds, const float* concept_embeds, const float* special_care_embeds,
+                       const float* concept_thresholds, const float* special_care_thresholds, int32_t* has_nsfw, float* concept_scores,
+                       float* special_care_scores, int B, int Nc, int Ns, int E, void* stream);
+
 /* ---- kernel-level entry points (parity tests and micro-benchmarks; same kernels the UNet uses) ---------- */
 typedef struct sdmi_igemm_desc {
   const void* a0; const void* a1; const void* a2;   /* fp16 NHWC sources, channel concat [a0|a1|a2] (a1, a2 optional) */

@@ -13,6 +13,9 @@ this package is the host-side mirror of the reference's interfaces for that path
     BERTEmbedderHIP   <- ldm.modules.encoders.modules.BERTEmbedder (the LAION-400M model's text encoder)
     ClassEmbedderHIP  <- ldm.modules.encoders.modules.ClassEmbedder (the class-conditional ImageNet model's conditioner)
     SuperResolutionHIP <- LatentDiffusion at models/ldm/bsr_sr (tiled x4 super-resolution: split_input_params)
+    CLIPVisionHIP     <- transformers.CLIPVisionModelWithProjection (the tower of the two modules below)
+    StableDiffusionSafetyCheckerHIP <- diffusers' StableDiffusionSafetyChecker (scripts/txt2img.py:check_safety)
+    FrozenClipImageEmbedderHIP <- ldm.modules.encoders.modules.FrozenClipImageEmbedder
 
 Importable as `stable_diffusion_amd` (see stable_diffusion_amd.py at the repo root).
 """
@@ -25,6 +28,7 @@ from .bert import BERTEmbedderHIP  # noqa: F401
 from .class_embedder import ClassEmbedderHIP  # noqa: F401
 from .ldm_shim import LatentDiffusionHIP, DiffusionWrapperHIP  # noqa: F401
 from .superres import SuperResolutionHIP  # noqa: F401
+from .vision import CLIPVisionHIP, StableDiffusionSafetyCheckerHIP, FrozenClipImageEmbedderHIP  # noqa: F401
 from . import debug, postprocess  # noqa: F401
 
-__all__ = ['UNetModelHIP', 'AutoencoderKLHIP', 'VQModelInterfaceHIP', 'FrozenCLIPEmbedderHIP', 'BERTEmbedderHIP', 'ClassEmbedderHIP', 'PLMSSamplerHIP', 'DDIMSamplerHIP', 'DPMSolverSamplerHIP', 'LatentDiffusionHIP', 'DiffusionWrapperHIP', 'SuperResolutionHIP']
+__all__ = ['UNetModelHIP', 'AutoencoderKLHIP', 'VQModelInterfaceHIP', 'FrozenCLIPEmbedderHIP', 'BERTEmbedderHIP', 'ClassEmbedderHIP', 'PLMSSamplerHIP', 'DDIMSamplerHIP', 'DPMSolverSamplerHIP', 'LatentDiffusionHIP', 'DiffusionWrapperHIP', 'SuperResolutionHIP', 'CLIPVisionHIP', 'StableDiffusionSafetyCheckerHIP', 'FrozenClipImageEmbedderHIP']

@@ -40,6 +40,11 @@ class BertCfg(C.Structure):
                 ('dim_head', C.c_int32), ('ff_inner', C.c_int32), ('max_seq_len', C.c_int32)]
 
 
+class VitCfg(C.Structure):
+    _fields_ = [('image_size', C.c_int32), ('patch_size', C.c_int32), ('hidden_size', C.c_int32), ('intermediate_size', C.c_int32),
+                ('num_layers', C.c_int32), ('num_heads', C.c_int32), ('projection_dim', C.c_int32)]
+
+
 class IGemmDesc(C.Structure):
     _fields_ = [('a0', c_ptr), ('a1', c_ptr), ('a2', c_ptr),
                 ('c0', C.c_int32), ('c1', C.c_int32), ('c2', C.c_int32),
@@ -129,6 +134,19 @@ _SIGS = {
     'sdmi_bert_finalize': (C.c_int, [c_ptr]),
     'sdmi_bert_workspace_bytes': (C.c_int64, [c_ptr, C.c_int, C.c_int]),
     'sdmi_bert_forward': (C.c_int, [c_ptr, c_ptr, c_ptr, C.c_int, C.c_int, c_ptr, C.c_int64, c_ptr]),
+    'sdmi_vit_create': (C.c_int, [C.POINTER(VitCfg), C.POINTER(c_ptr)]),
+    'sdmi_vit_destroy': (C.c_int, [c_ptr]),
+    'sdmi_vit_num_weights': (C.c_int, [c_ptr]),
+    'sdmi_vit_weight_info': (C.c_int, [c_ptr, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int)]),
+    'sdmi_vit_set_weight': (C.c_int, [c_ptr, C.c_char_p, c_ptr, C.POINTER(C.c_int64), C.c_int, c_ptr]),
+    'sdmi_vit_finalize': (C.c_int, [c_ptr]),
+    'sdmi_vit_workspace_bytes': (C.c_int64, [c_ptr, C.c_int]),
+    'sdmi_vit_forward': (C.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, C.c_int, c_ptr, C.c_int64, c_ptr]),
+    'sdmi_k_vit_kpad': (C.c_int, [C.c_int]),
+    'sdmi_k_vit_patchify': (C.c_int, [c_ptr, c_ptr, C.c_int, C.c_int, C.c_int, c_ptr]),
+    'sdmi_k_vit_embed': (C.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, C.c_int, C.c_int, C.c_int, c_ptr]),
+    'sdmi_k_vit_preprocess': (C.c_int, [c_ptr, c_ptr, C.c_int, C.c_int, C.c_int, C.c_int, c_ptr]),
+    'sdmi_k_safety_head': (C.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, C.c_int, C.c_int, C.c_int, C.c_int, c_ptr]),
     'sdmi_has_experiments': (C.c_int, []),
     'sdmi_k_igemm': (C.c_int, [C.POINTER(IGemmDesc), c_ptr]),
     'sdmi_k_igemm_tail': (C.c_int, [C.POINTER(IGemmDesc), c_ptr, c_ptr, c_ptr, C.c_int, C.c_int, c_ptr, C.c_int, c_ptr]),

@@ -19,6 +19,7 @@ struct sdmi_unet { sdmi::UNet impl; };
 struct sdmi_vae { sdmi::Vae impl; };
 struct sdmi_clip { sdmi::ClipText impl; };
 struct sdmi_bert { sdmi::BertText impl; };
+struct sdmi_vit { sdmi::ClipVision impl; };
 
 using namespace sdmi;
 
@@ -312,6 +313,59 @@ int sdmi_bert_forward(sdmi_bert* h, const int64_t* ids, float* out, int B, int L
                       void* stream) {
   SDMI_CHECK(h && ids && out, "null argument");
   return h->impl.forward(ids, out, B, L, workspace, workspace_bytes, (hipStream_t)stream, false, nullptr);
+}
+
+// ---- CLIP image encoder ------------------------------------------------------------------------------------------------
+int sdmi_vit_create(const sdmi_vit_cfg* cfg, sdmi_vit** out) {
+  SDMI_CHECK(cfg && out, "null argument");
+  sdmi_vit* h = new (std::nothrow) sdmi_vit();
+  SDMI_CHECK(h != nullptr, "out of host memory");
+  if (h->impl.build(*cfg)) { delete h; return -1; }
+  *out = h;
+  return 0;
+}
+int sdmi_vit_destroy(sdmi_vit* h) { delete h; return 0; }
+int sdmi_vit_num_weights(const sdmi_vit* h) { return h ? (int)h->impl.weights().slots().size() : fail("null handle"); }
+int sdmi_vit_weight_info(const sdmi_vit* h, int idx, char* key_buf, int key_buf_len, int64_t* shape4, int* ndim) {
+  SDMI_CHECK(h, "null argument");
+  return weight_info(h->impl.weights(), idx, key_buf, key_buf_len, shape4, ndim);
+}
+int sdmi_vit_set_weight(sdmi_vit* h, const char* key, const float* ptr, const int64_t* shape, int ndim, void* stream) {
+  SDMI_CHECK(h && key && ptr && shape, "null argument");
+  return h->impl.set_weight(key, ptr, shape, ndim, (hipStream_t)stream);
+}
+int sdmi_vit_finalize(sdmi_vit* h) { SDMI_CHECK(h, "null handle"); return h->impl.finalize(); }
+int64_t sdmi_vit_workspace_bytes(sdmi_vit* h, int B) {
+  if (!h) { fail("null handle"); return 0; }
+  int64_t need = 0;
+  if (h->impl.forward(nullptr, nullptr, nullptr, nullptr, B, nullptr, 0, nullptr, true, &need)) return 0;
+  return need;
+}
+int sdmi_vit_forward(sdmi_vit* h, const float* pixel_values, float* last_hidden_or_null, float* pooled_or_null, float* image_embeds, int B,
+                     void* workspace, int64_t workspace_bytes, void* stream) {
+  SDMI_CHECK(h && pixel_values && image_embeds, "null argument");
+  return h->impl.forward(pixel_values, last_hidden_or_null, pooled_or_null, image_embeds, B, workspace, workspace_bytes, (hipStream_t)stream,
+                         false, nullptr);
+}
+int sdmi_k_vit_kpad(int patch_size) {
+  if (patch_size < 1 || patch_size > 64) { fail("patch_size outside 1..64"); return -1; }
+  return vit_kpad(patch_size);
+}
+int sdmi_k_vit_patchify(const float* pixel_values, void* out_f16, int B, int S, int p, void* stream) {
+  return launch_vit_patchify(pixel_values, (f16*)out_f16, B, S, p, (hipStream_t)stream);
+}
+int sdmi_k_vit_embed(const float* patch, const float* class_embedding, const float* position_embedding, float* out, int B, int T, int C,
+                     void* stream) {
+  return launch_vit_embed(patch, class_embedding, position_embedding, out, B, T, C, (hipStream_t)stream);
+}
+int sdmi_k_vit_preprocess(const float* x, float* out, int B, int H, int W, int S, void* stream) {
+  return launch_vit_preprocess(x, out, B, H, W, S, (hipStream_t)stream);
+}
+int sdmi_k_safety_head(const float* image_embeds, const float* concept_embeds, const float* special_care_embeds,
+                       const float* concept_thresholds, const float* special_care_thresholds, int32_t* has_nsfw, float* concept_scores,
+                       float* special_care_scores, int B, int Nc, int Ns, int E, void* stream) {
+  return launch_safety_head(image_embeds, concept_embeds, special_care_embeds, concept_thresholds, special_care_thresholds, (int*)has_nsfw,
+                            concept_scores, special_care_scores, B, Nc, Ns, E, (hipStream_t)stream);
 }
 int sdmi_k_vq_quantize(const float* z, float z_scale, const float* codebook, float* norms_ws, int n_embed, int D, float* zq, int32_t* idx,
                        int B, int HW, void* stream) {

@@ -8,6 +8,7 @@
 // Same kernels as the UNet's transformer blocks: igemm (per-head scatter epilogue with bias, plain epilogue with the
 // LayerNorm post-op), the flash-attention kernel with a causal mask, layernorm; the token stream is fp32.
 // SDMI_PRECISION_FULL handles (both encoders) run TextEncBase::forward_full at the end of this file instead: split-fp16 operands on every MFMA.
+// The CLIP vision tower (ClipVision, below) walks the same layers through TextEncBase::mixed_layers with the causal mask off.
 #include "clip.h"
 
 #include <math.h>
@@ -29,28 +30,71 @@ int ClipText::build(const sdmi_clip_cfg& c, int precision) {
   const std::string tm = "text_model.";
   store_.expect(tm + "embeddings.token_embedding.weight", {c.vocab_size, C}, W_F32, &tok_);
   store_.expect(tm + "embeddings.position_embedding.weight", {c.max_positions, C}, W_F32, &pos_);
-  for (int i = 0; i < c.num_layers; ++i) {   // NOTE: slots point into layers_, which must not reallocate from here on
-    CLayer& L = layers_[i];
-    const std::string p = tm + "encoder.layers." + std::to_string(i) + ".";
-    const char* names[3] = {"q_proj", "k_proj", "v_proj"};
-    for (int j = 0; j < 3; ++j) {
-      store_.expect(p + "self_attn." + names[j] + ".weight", {C, C}, lin_kind(), &L.wqkv, j * (int)C, 3 * (int)C);
-      store_.expect(p + "self_attn." + names[j] + ".bias", {C}, W_F32_ROWS, &L.bqkv, j * (int)C, 3 * (int)C);
-    }
-    store_.expect(p + "self_attn.out_proj.weight", {C, C}, lin_kind(), &L.wo);
-    store_.expect(p + "self_attn.out_proj.bias", {C}, W_F32, &L.bo);
-    store_.expect(p + "layer_norm1.weight", {C}, W_F32, &L.ln[0]);
-    store_.expect(p + "layer_norm1.bias", {C}, W_F32, &L.ln[1]);
-    store_.expect(p + "mlp.fc1.weight", {I, C}, lin_kind(), &L.w1);
-    store_.expect(p + "mlp.fc1.bias", {I}, W_F32, &L.b1);
-    store_.expect(p + "mlp.fc2.weight", {C, I}, lin_kind(), &L.w2);
-    store_.expect(p + "mlp.fc2.bias", {C}, W_F32, &L.b2);
-    store_.expect(p + "layer_norm2.weight", {C}, W_F32, &L.ln[2]);
-    store_.expect(p + "layer_norm2.bias", {C}, W_F32, &L.ln[3]);
-  }
+  for (int i = 0; i < c.num_layers; ++i)   // NOTE: slots point into layers_, which must not reallocate from here on
+    expect_layer(tm + "encoder.layers." + std::to_string(i) + ".", layers_[i], C, I);
   store_.expect(tm + "final_layer_norm.weight", {C}, W_F32, &fln_g_);
   store_.expect(tm + "final_layer_norm.bias", {C}, W_F32, &fln_b_);
   return 0;
+}
+
+void TextEncBase::expect_layer(const std::string& p, CLayer& L, int64_t C, int64_t I) {
+  const char* names[3] = {"q_proj", "k_proj", "v_proj"};
+  for (int j = 0; j < 3; ++j) {
+    store_.expect(p + "self_attn." + names[j] + ".weight", {C, C}, lin_kind(), &L.wqkv, j * (int)C, 3 * (int)C);
+    store_.expect(p + "self_attn." + names[j] + ".bias", {C}, W_F32_ROWS, &L.bqkv, j * (int)C, 3 * (int)C);
+  }
+  store_.expect(p + "self_attn.out_proj.weight", {C, C}, lin_kind(), &L.wo);
+  store_.expect(p + "self_attn.out_proj.bias", {C}, W_F32, &L.bo);
+  store_.expect(p + "layer_norm1.weight", {C}, W_F32, &L.ln[0]);
+  store_.expect(p + "layer_norm1.bias", {C}, W_F32, &L.ln[1]);
+  store_.expect(p + "mlp.fc1.weight", {I, C}, lin_kind(), &L.w1);
+  store_.expect(p + "mlp.fc1.bias", {I}, W_F32, &L.b1);
+  store_.expect(p + "mlp.fc2.weight", {C, I}, lin_kind(), &L.w2);
+  store_.expect(p + "mlp.fc2.bias", {C}, W_F32, &L.b2);
+  store_.expect(p + "layer_norm2.weight", {C}, W_F32, &L.ln[2]);
+  store_.expect(p + "layer_norm2.bias", {C}, W_F32, &L.ln[3]);
+}
+
+void TextEncBase::mixed_layers(FwdBase& f, const std::vector<CLayer>& layers, const MixedBufs& b, int B, int L, int C, int I, int H, bool causal) {
+  const int M = B * L, Lp = (int)round_up(L, 8), dh = C / H, n_layers = (int)layers.size();
+  const float scale = 1.0f / sqrtf((float)dh);
+  const bool d = f.dry;
+  for (int i = 0; i < n_layers; ++i) {
+    const CLayer& Ly = layers[i];
+    {   // q | k | v = ln Wqkv^T + b, scattered per head (v transposed)
+      IGemmParams p = f.dense(b.ln, M, C, Ly.wqkv, 3 * C, L);
+      p.mode = EPI_HEADS; p.bias = Ly.bqkv; p.seg_dst[0] = b.q; p.seg_dst[1] = b.k; p.seg_dst[2] = b.vt;
+      p.seg_kind[0] = 0; p.seg_kind[1] = 0; p.seg_kind[2] = 1;
+      p.heads = H; p.dh = dh; p.ntok = L; p.ntok_pad = Lp; p.segC = C; p.splitk = 1;
+      f.gemm(p);
+    }
+    if (!d && !f.rc) {
+      AttnParams a = AttnParams();
+      a.q = b.q; a.k = b.k; a.vt = b.vt; a.out = b.ao; a.BH = B * H; a.heads = H; a.nq = L; a.nkv = L; a.nkv_pad = Lp; a.d = dh;
+      a.scale = scale; a.causal = causal ? 1 : 0;
+      f.ok(launch_attention(a, f.s));
+    }
+    {   // x += ao Wo^T + bo ; ln = LayerNorm2(x)
+      IGemmParams p = f.dense(b.ao, M, C, Ly.wo, C, L);
+      p.bias = Ly.bo; p.residual = b.x; p.ldr = C; p.out_f32 = b.x; p.ldo = C;
+      p.ln_gamma = Ly.ln[2]; p.ln_beta = Ly.ln[3]; p.ln_out = b.ln; p.ln_eps = 1e-5f;
+      f.gemm(p);
+    }
+    {   // h1 = ln W1^T + b1 ; g = quick_gelu(h1)
+      IGemmParams p = f.dense(b.ln, M, C, Ly.w1, I, L);
+      p.bias = Ly.b1; p.out_f32 = b.h1; p.ldo = I;
+      f.gemm(p);
+      if (!d && !f.rc) f.ok(launch_quick_gelu(b.h1, b.g, (int64_t)M * I, f.s));
+    }
+    {   // x += g W2^T + b2 ; ln = LayerNorm1 of the next layer
+      IGemmParams p = f.dense(b.g, M, I, Ly.w2, C, L);
+      p.bias = Ly.b2; p.residual = b.x; p.ldr = C; p.out_f32 = b.x; p.ldo = C;
+      if (i + 1 < n_layers) {
+        p.ln_gamma = layers[i + 1].ln[0]; p.ln_beta = layers[i + 1].ln[1]; p.ln_out = b.ln; p.ln_eps = 1e-5f;
+      }
+      f.gemm(p);
+    }
+  }
 }
 
 int TextEncBase::set_weight(const char* key, const float* ptr, const int64_t* shape, int ndim, hipStream_t stream) {
@@ -80,9 +124,8 @@ int ClipText::forward(const int64_t* ids, float* out, int B, int L, void* worksp
       t.layers.push_back({Ly.wqkv, Ly.bqkv, Ly.wo, Ly.bo, Ly.w1, Ly.b1, Ly.w2, Ly.b2, {Ly.ln[0], Ly.ln[1], Ly.ln[2], Ly.ln[3]}});
     return forward_full(t, ids, out, B, L, workspace, ws_bytes, stream, dry, bytes_needed);
   }
-  const int C = cfg_.hidden_size, I = cfg_.intermediate_size, H = cfg_.num_heads, dh = C / H;
+  const int C = cfg_.hidden_size, I = cfg_.intermediate_size, H = cfg_.num_heads;
   const int M = B * L, Lp = (int)round_up(L, 8);
-  const float scale = 1.0f / sqrtf((float)dh);
   FwdBase f;
   f.s = stream; f.B = B; f.zero = store_.zero(); f.precise_1x1 = false;
   int64_t persist_bytes = 0;
@@ -112,43 +155,116 @@ int ClipText::forward(const int64_t* ids, float* out, int B, int L, void* worksp
       if (launch_layernorm(x, layers_[0].ln[0], layers_[0].ln[1], ln, M, C, 1e-5f, stream)) return -1;
       if (Lp != L) SDMI_HIP_OK(hipMemsetAsync(vt, 0, (size_t)B * C * Lp * sizeof(f16), stream));   // pad keys of V^T stay zero
     }
-    for (int i = 0; i < cfg_.num_layers; ++i) {
-      CLayer& Ly = layers_[i];
-      {   // q | k | v = ln Wqkv^T + b, scattered per head (v transposed)
-        IGemmParams p = f.dense(ln, M, C, Ly.wqkv, 3 * C, L);
-        p.mode = EPI_HEADS; p.bias = Ly.bqkv; p.seg_dst[0] = q; p.seg_dst[1] = k; p.seg_dst[2] = vt;
-        p.seg_kind[0] = 0; p.seg_kind[1] = 0; p.seg_kind[2] = 1;
-        p.heads = H; p.dh = dh; p.ntok = L; p.ntok_pad = Lp; p.segC = C; p.splitk = 1;
-        f.gemm(p);
-      }
-      if (!d && !f.rc) {
-        AttnParams a = AttnParams();
-        a.q = q; a.k = k; a.vt = vt; a.out = ao; a.BH = B * H; a.heads = H; a.nq = L; a.nkv = L; a.nkv_pad = Lp; a.d = dh;
-        a.scale = scale; a.causal = 1;
-        f.ok(launch_attention(a, stream));
-      }
-      {   // x += ao Wo^T + bo ; ln = LayerNorm2(x)
-        IGemmParams p = f.dense(ao, M, C, Ly.wo, C, L);
-        p.bias = Ly.bo; p.residual = x; p.ldr = C; p.out_f32 = x; p.ldo = C;
-        p.ln_gamma = Ly.ln[2]; p.ln_beta = Ly.ln[3]; p.ln_out = ln; p.ln_eps = 1e-5f;
-        f.gemm(p);
-      }
-      {   // h1 = ln W1^T + b1 ; g = quick_gelu(h1)
-        IGemmParams p = f.dense(ln, M, C, Ly.w1, I, L);
-        p.bias = Ly.b1; p.out_f32 = h1; p.ldo = I;
-        f.gemm(p);
-        if (!d && !f.rc) f.ok(launch_quick_gelu(h1, g, (int64_t)M * I, stream));
-      }
-      {   // x += g W2^T + b2 ; ln = LayerNorm1 of the next layer
-        IGemmParams p = f.dense(g, M, I, Ly.w2, C, L);
-        p.bias = Ly.b2; p.residual = x; p.ldr = C; p.out_f32 = x; p.ldo = C;
-        if (i + 1 < cfg_.num_layers) {
-          p.ln_gamma = layers_[i + 1].ln[0]; p.ln_beta = layers_[i + 1].ln[1]; p.ln_out = ln; p.ln_eps = 1e-5f;
-        }
-        f.gemm(p);
-      }
-    }
+    mixed_layers(f, layers_, MixedBufs{x, ln, q, k, vt, ao, h1, g}, B, L, C, I, H, /*causal=*/true);
     if (!d && !f.rc) f.ok(launch_layernorm(x, fln_g_, fln_b_, nullptr, M, C, 1e-5f, stream, out));
+    if (f.rc) return f.rc;
+    if (d) {
+      persist_bytes = (int64_t)round_up((int64_t)f.persist.peak, 4096) + 4096;
+      if (bytes_needed) *bytes_needed = persist_bytes;
+    } else {
+      SDMI_CHECK(!f.persist.overflow, "internal: arena overflow");
+    }
+  }
+  return 0;
+}
+
+// ---- CLIP vision tower --------------------------------------------------------------------------------------------------------------
+// CLIPVisionModelWithProjection (modeling_clip.py: CLIPVisionEmbeddings, CLIPVisionTransformer):
+//   x = pre_layrnorm(cat(class_embedding, patch_embedding(pixel_values)) + position_embedding)      (patch_embedding: p x p conv, stride p, no bias)
+//   x = the CLIPEncoderLayers of the text tower, without the causal mask                      -> last_hidden_state
+//   pooled_output = post_layernorm(x[:, 0]);  image_embeds = visual_projection(pooled_output)       (no bias)
+// The patch convolution is vit_patchify (im2col, fp16, K zero-padded to whole 64-wide k-tiles) and ONE dense GEMM of the family; both
+// LayerNorms outside the layers feed fp32 consumers and write fp32.
+int ClipVision::build(const sdmi_vit_cfg& c) {
+  cfg_ = c;
+  precision_ = SDMI_PRECISION_MIXED;
+  SDMI_CHECK(c.hidden_size >= 64 && c.hidden_size % 64 == 0 && c.hidden_size <= 2560,
+             "vision tower: hidden_size " + std::to_string(c.hidden_size) + " must be a multiple of 64 (<= 2560)");
+  SDMI_CHECK(c.intermediate_size >= 64 && c.intermediate_size % 64 == 0,
+             "vision tower: intermediate_size " + std::to_string(c.intermediate_size) + " must be a multiple of 64");
+  SDMI_CHECK(c.num_heads >= 1 && c.hidden_size % c.num_heads == 0, "vision tower: hidden_size % num_heads");
+  const int dh = c.hidden_size / c.num_heads;
+  SDMI_CHECK(dh == 32 || dh == 40 || dh == 64 || dh == 80 || dh == 128 || dh == 160,
+             "vision tower: head dim " + std::to_string(dh) + " is not one the attention kernel has (32, 40, 64, 80, 128, 160)");
+  SDMI_CHECK(c.patch_size >= 1 && c.patch_size <= 64 && c.image_size >= c.patch_size && c.image_size % c.patch_size == 0,
+             "vision tower: image_size % patch_size != 0 (image_size " + std::to_string(c.image_size) + ", patch_size " +
+                 std::to_string(c.patch_size) + ")");
+  SDMI_CHECK(tokens() <= 1024, "vision tower: " + std::to_string(tokens()) + " tokens, more than 1024 tokens are not supported");
+  SDMI_CHECK(c.num_layers >= 1 && c.projection_dim >= 1, "bad vision-model config");
+  const int64_t C = c.hidden_size, I = c.intermediate_size, p = c.patch_size;
+  layers_.resize(c.num_layers);
+  const std::string vm = "vision_model.";
+  store_.expect(vm + "embeddings.class_embedding", {C}, W_F32, &cls_);
+  store_.expect(vm + "embeddings.patch_embedding.weight", {C, 3, p, p}, W_ROWS16_PAD64, &wpatch_);
+  store_.expect(vm + "embeddings.position_embedding.weight", {(int64_t)tokens(), C}, W_F32, &pos_);
+  store_.expect(vm + "pre_layrnorm.weight", {C}, W_F32, &pre_g_);
+  store_.expect(vm + "pre_layrnorm.bias", {C}, W_F32, &pre_b_);
+  for (int i = 0; i < c.num_layers; ++i)   // NOTE: slots point into layers_, which must not reallocate from here on
+    expect_layer(vm + "encoder.layers." + std::to_string(i) + ".", layers_[i], C, I);
+  store_.expect(vm + "post_layernorm.weight", {C}, W_F32, &post_g_);
+  store_.expect(vm + "post_layernorm.bias", {C}, W_F32, &post_b_);
+  store_.expect("visual_projection.weight", {(int64_t)c.projection_dim, C}, W_F32, &wproj_);
+  return 0;
+}
+
+int ClipVision::forward(const float* px, float* last_hidden, float* pooled, float* image_embeds, int B, void* workspace, int64_t ws_bytes,
+                        hipStream_t stream, bool dry, int64_t* bytes_needed) {
+  SDMI_CHECK(dry || finalized_, "sdmi_vit_finalize() has not succeeded yet");
+  SDMI_CHECK(B >= 1 && B <= 64, "vision tower: batch " + std::to_string(B) + " outside 1..64 (B > 64 is not supported)");
+  SDMI_CHECK(dry || (px != nullptr && image_embeds != nullptr), "pixel_values / image_embeds is NULL");
+  const int C = cfg_.hidden_size, I = cfg_.intermediate_size, H = cfg_.num_heads, S = cfg_.image_size, ps = cfg_.patch_size;
+  const int P2 = (S / ps) * (S / ps), T = 1 + P2, M = B * T, Tp = (int)round_up(T, 8), Kp = vit_kpad(ps), Pd = cfg_.projection_dim;
+  FwdBase f;
+  f.s = stream; f.B = B; f.zero = store_.zero(); f.precise_1x1 = false;
+  int64_t persist_bytes = 0;
+  for (int pass = 0; pass < 2; ++pass) {
+    const bool d = pass == 0;
+    if (pass == 1 && dry) break;
+    f.dry = d; f.rc = 0;
+    f.persist = Arena(); f.scratch = Arena();
+    f.persist.dry = f.scratch.dry = d;
+    if (!d) {
+      SDMI_CHECK(persist_bytes <= ws_bytes, "workspace too small: need " + std::to_string(persist_bytes) + " bytes, got " +
+                                                std::to_string(ws_bytes));
+      SDMI_CHECK(workspace != nullptr, "workspace is NULL");
+      f.persist.base = (char*)workspace; f.persist.cap = (size_t)persist_bytes;
+    }
+    if (f.begin_pass((int64_t)4 << 20, /*with_gn=*/false)) return -1;     // split-K slabs only
+    f16* cols = f.P<f16>((size_t)B * P2 * Kp);
+    float* patch = f.P<float>((size_t)B * P2 * C);
+    float* emb = f.P<float>((size_t)M * C);
+    float* x = f.P<float>((size_t)M * C);
+    f16* ln = f.P<f16>((size_t)M * C);
+    f16* q = f.P<f16>((size_t)M * C);
+    f16* k = f.P<f16>((size_t)M * C);
+    f16* vt = f.P<f16>((size_t)B * C * Tp);
+    f16* ao = f.P<f16>((size_t)M * C);
+    float* h1 = f.P<float>((size_t)M * I);
+    f16* g = f.P<f16>((size_t)M * I);
+    float* cls = f.P<float>((size_t)B * C);
+    float* pooled_ws = f.P<float>((size_t)B * C);
+    auto launch = [&](auto&& fn) { if (!d && !f.rc) f.ok(fn()); };
+    launch([&] { return launch_vit_patchify(px, cols, B, S, ps, stream); });
+    {   // the patch embedding: [B P^2][Kp] x [C][Kp]^T, no bias
+      IGemmParams p = f.dense(cols, B * P2, Kp, wpatch_, C, P2);
+      p.out_f32 = patch; p.ldo = C;
+      f.gemm(p);
+    }
+    launch([&] { return launch_vit_embed(patch, cls_, pos_, emb, B, T, C, stream); });
+    launch([&] { return launch_layernorm(emb, pre_g_, pre_b_, nullptr, M, C, 1e-5f, stream, x); });                  // pre_layrnorm, fp32
+    launch([&] { return launch_layernorm(x, layers_[0].ln[0], layers_[0].ln[1], ln, M, C, 1e-5f, stream); });
+    if (!d && !f.rc && Tp != T) SDMI_HIP_OK(hipMemsetAsync(vt, 0, (size_t)B * C * Tp * sizeof(f16), stream));        // pad keys of V^T stay zero
+    mixed_layers(f, layers_, MixedBufs{x, ln, q, k, vt, ao, h1, g}, B, T, C, I, H, /*causal=*/false);
+    if (!d && !f.rc) {
+      if (last_hidden) SDMI_HIP_OK(hipMemcpyAsync(last_hidden, x, (size_t)M * C * sizeof(float), hipMemcpyDeviceToDevice, stream));
+      // post_layernorm reads row 0 of every sample only
+      SDMI_HIP_OK(hipMemcpy2DAsync(cls, (size_t)C * sizeof(float), x, (size_t)T * C * sizeof(float), (size_t)C * sizeof(float), (size_t)B,
+                                   hipMemcpyDeviceToDevice, stream));
+    }
+    float* po = pooled ? pooled : pooled_ws;
+    launch([&] { return launch_layernorm(cls, post_g_, post_b_, nullptr, B, C, 1e-5f, stream, po); });
+    for (int b0 = 0; b0 < B; b0 += 8)       // visual_projection through the fp32 small-batch linear (8 rows per launch)
+      launch([&] { return launch_small_linear(po + (size_t)b0 * C, C, wproj_, nullptr, image_embeds + (size_t)b0 * Pd, Pd, std::min(8, B - b0), Pd, C, 0, stream); });
     if (f.rc) return f.rc;
     if (d) {
       persist_bytes = (int64_t)round_up((int64_t)f.persist.peak, 4096) + 4096;

@@ -1,5 +1,5 @@
 // Text-encoder executor state: HF CLIPTextModel as wrapped by FrozenCLIPEmbedder (clip.cpp) and the LAION-400M model's
-// BERTEmbedder transformer (bert.cpp).
+// BERTEmbedder transformer (bert.cpp); and the CLIP vision tower (ClipVision, clip.cpp) on the same weight store and layer walk.
 #pragma once
 #include <string>
 #include <vector>
@@ -52,6 +52,11 @@ class TextEncBase {
   // writes fp32.  No LayerNorm post-op and no per-head scatter epilogue: both round to fp16.
   int forward_full(const TextFullDesc& t, const int64_t* ids, float* out, int B, int L, void* workspace, int64_t ws_bytes,
                    hipStream_t stream, bool dry, int64_t* bytes_needed);
+  // The mixed-precision walk over CLIPEncoderLayers (fp16 MFMA operands, fp32 residual stream x), shared by the text tower (causal) and the
+  // vision tower (not causal).  On entry ln = fp16(LayerNorm1 of layer 0 (x)) and the pad keys of vt are zero; on exit x is the encoder output.
+  struct MixedBufs { float* x; f16 *ln, *q, *k, *vt, *ao; float* h1; f16* g; };
+  void mixed_layers(FwdBase& f, const std::vector<CLayer>& layers, const MixedBufs& b, int B, int L, int C, int I, int H, bool causal);
+  void expect_layer(const std::string& prefix, CLayer& L, int64_t C, int64_t I);     // the 16 tensors of one CLIPEncoderLayer
   WKind lin_kind() const { return full() ? W_SPLIT3_ROWS : W_ROWS16; }
   WeightStore store_;           // (slots point into the layer objects of the derived class)
   bool finalized_ = false;
@@ -68,6 +73,24 @@ class ClipText : public TextEncBase {
  private:
   std::vector<CLayer> layers_;
   float *tok_ = nullptr, *pos_ = nullptr, *fln_g_ = nullptr, *fln_b_ = nullptr;
+};
+
+// transformers' CLIPVisionModelWithProjection (models/clip/modeling_clip.py: CLIPVisionTransformer + visual_projection): the safety checker's
+// tower and FrozenClipImageEmbedder's.  Mixed precision only.
+class ClipVision : public TextEncBase {
+ public:
+  int build(const sdmi_vit_cfg& cfg);
+  int tokens() const { const int P = cfg_.image_size / cfg_.patch_size; return 1 + P * P; }
+  // pixel_values fp32 [B][3][S][S] (device) -> last_hidden_state [B][T][hidden] (the encoder output; optional), pooled_output [B][hidden]
+  // (post_layernorm of row 0; optional), image_embeds [B][projection_dim]
+  int forward(const float* px, float* last_hidden, float* pooled, float* image_embeds, int B, void* workspace, int64_t ws_bytes,
+              hipStream_t stream, bool dry, int64_t* bytes_needed);
+  sdmi_vit_cfg cfg_{};
+
+ private:
+  std::vector<CLayer> layers_;
+  f16* wpatch_ = nullptr;               // [hidden][vit_kpad(patch)]
+  float *cls_ = nullptr, *pos_ = nullptr, *pre_g_ = nullptr, *pre_b_ = nullptr, *post_g_ = nullptr, *post_b_ = nullptr, *wproj_ = nullptr;
 };
 
 struct BLayer {   // one ('a', 'f') pair of x_transformer.Encoder

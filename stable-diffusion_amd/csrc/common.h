@@ -466,6 +466,20 @@ int launch_gelu_erf(const float* x, f16* out, int64_t n, hipStream_t s);
 int launch_quick_gelu_split(const float* x, f16* out, f16* out_lo, int64_t n, hipStream_t s);
 int launch_gelu_erf_split(const float* x, f16* out, f16* out_lo, int64_t n, hipStream_t s);
 
+// CLIP vision tower helpers (vit.hip)
+int vit_kpad(int patch_size);           // columns of a patchify row: 3 p^2 rounded up to the 64-wide k-tile of the GEMM family
+// pixel_values fp32 NCHW [B][3][S][S] -> fp16 [B (S / p)^2][vit_kpad(p)]: column (c, ky, kx) of patch (py, px); pad columns zero
+int launch_vit_patchify(const float* px, f16* out, int B, int S, int p, hipStream_t s);
+// out [B][T][C] fp32: row 0 = cls + pos[0], row 1 + i = patch[b (T - 1) + i] + pos[1 + i]
+int launch_vit_embed(const float* patch, const float* cls, const float* pos, float* out, int B, int T, int C, hipStream_t s);
+// [B][3][H][W] in [-1, 1] -> bicubic (align_corners, A = -0.75) [B][3][S][S], (x + 1) / 2, CLIP mean / std
+int launch_vit_preprocess(const float* x, float* out, int B, int H, int W, int S, hipStream_t s);
+// StableDiffusionSafetyChecker's head: cosines of image_embeds [B][E] with the special-care [Ns][E] and concept [Nc][E] vectors, the
+// running adjustment, scores rounded to three decimals -> has_nsfw int32 [B], concept_scores [B][Nc], special_scores [B][Ns]
+int launch_safety_head(const float* image_embeds, const float* concept_embeds, const float* special_care_embeds, const float* concept_thr,
+                       const float* special_thr, int* has_nsfw, float* concept_scores, float* special_scores, int B, int Nc, int Ns, int E,
+                       hipStream_t s);
+
 // first-stage (VAE) helpers
 int launch_pointwise_nchw(const float* x_nchw, const float* w, const float* bias, float* out_nchw, int B, int Cin, int Cout,
                           int HW, float in_scale, hipStream_t s);

@@ -54,6 +54,7 @@ size_t WeightStore::bytes(const WeightSlot& s) {
     case W_SPLIT3: case W_CONV_SPLIT3: return 3 * numel * sizeof(f16);
     case W_QKV_LEGACY: return numel * sizeof(f16) * (s.split ? 3 : 1);
     case W_ROWS16: return rows * sizeof(f16);
+    case W_ROWS16_PAD64: return (size_t)s.buf_rows * (size_t)round_up(s.ld, 64) * sizeof(f16);
     case W_SPLIT3_ROWS: return 3 * rows * sizeof(f16);
     case W_DROP: return 0;
   }
@@ -133,6 +134,10 @@ int WeightStore::set(const char* key, const float* ptr, const int64_t* shape, in
       break;
     case W_ROWS16:
       rc = launch_pack_rows(dptr, (f16*)*s.dst, (int)shape[0], (int)shape[1], s.row0, s.ld, stream);
+      break;
+    case W_ROWS16_PAD64:
+      SDMI_HIP_OK(hipMemsetAsync(*s.dst, 0, bytes(s), stream));
+      rc = launch_pack_rows(dptr, (f16*)*s.dst, (int)shape[0], s.ld, 0, (int)round_up(s.ld, 64), stream);
       break;
     case W_QKV_LEGACY:
     case W_QKV_LEGACY_B: {

@@ -20,13 +20,14 @@ struct DevStage {
 // W_F32 / W_F32_ROWS    fp32 as it is / rows [row0, ..) of a concatenated fp32 matrix (the emb_layers, a q | k | v bias)
 // W_CONV / W_CONV_OUT   conv weight OIHW -> fp16 [O][ky,kx,I] / the fp32 OHWI layout of the output convolution
 // W_ROWS16              rows [row0, ..) of an fp16 [buf_rows][ld] matrix (a linear, a 1x1 conv, q | k | v concatenations)
+// W_ROWS16_PAD64        an fp16 [rows][round_up(ld, 64)] matrix, the columns behind ld zero (the ViT patch embedding: K = 588 -> 640)
 // W_SPLIT3 / W_SPLIT3_ROWS / W_CONV_SPLIT3   the split-fp16 forms [w_hi | w_hi | w_lo] of a matrix, of rows of one, of a conv weight
 // W_GEGLU_W / W_GEGLU_B the GEGLU projection and its bias, rows interleaved (value32 | gate32)
 // W_QKV_LEGACY / W_QKV_LEGACY_B   the AttentionBlock's conv1d qkv weight / bias, its head-interleaved rows (head, q | k | v, channel)
 //                       permuted to the [q | k | v] head-major rows launch_split_heads reads
 // W_DROP                accepted (shape-checked) and never uploaded -- a checkpoint tensor the forward does not use
 enum WKind { W_F32, W_F32_ROWS, W_CONV, W_CONV_OUT, W_ROWS16, W_GEGLU_W, W_GEGLU_B, W_SPLIT3, W_SPLIT3_ROWS, W_CONV_SPLIT3, W_QKV_LEGACY,
-             W_QKV_LEGACY_B, W_DROP };
+             W_QKV_LEGACY_B, W_DROP, W_ROWS16_PAD64 };
 
 struct WeightSlot {
   std::string key;

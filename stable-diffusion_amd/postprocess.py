@@ -6,7 +6,8 @@
     Image.fromarray(x).save(path)                       -> `save_png`
     put_watermark(img, wm_encoder)                      -> `put_watermark` (needs the optional `imwatermark` package)
 
-The safety checker stays the reference's (a second CLIP model, out of scope: SURVEY.md 2 / DESIGN.md 7).
+The safety checker is built as well: `stable_diffusion_amd.vision.StableDiffusionSafetyCheckerHIP` (its CLIP ViT-L/14 vision tower and the
+concept head in libsdmi).  Its feature extractor (PIL resize and crop) stays the reference's host call.
 """
 import numpy as np
 import torch

@@ -83,6 +83,40 @@ def synthetic_clip_state_dict(text_config=None, seed=0):
 
 
 
+# ---- the CLIP vision tower (safety checker, image embedder) ------------------------------------------------------------------------------
+# the smallest geometry with every tail: 5 tokens (padded to 8), d = 32, GEMM rows 15 (B = 3), K = 588 zero-padded to 640
+VIT_TINY = dict(image_size=28, patch_size=14, hidden_size=64, num_attention_heads=2, num_hidden_layers=2, intermediate_size=128,
+                projection_dim=32)
+# ViT-L/14's widths and its 257 tokens (nkv_pad 264, eight 32-query slices plus one row, d = 64) with 2 of the 24 layers
+VIT_L14_THIN = dict(image_size=224, patch_size=14, hidden_size=1024, num_attention_heads=16, num_hidden_layers=2, intermediate_size=4096,
+                    projection_dim=768)
+
+
+@torch.no_grad()
+def synthetic_vision_state_dict(cfg=None, seed=0):
+    """CPU state_dict (CLIPVisionModelWithProjection key names) of a seeded random CLIP vision tower, one generator per key.  Scaled so that
+    every LayerNorm input has rms of order 1: class / position embeddings 0.5 N, the patch convolution 1 / sqrt(3 p^2) N (unit gain on
+    N(0, 1) pixel values), linear weights 1 / sqrt(fan_in) N, norm gammas 1 + 0.1 N, biases / betas 0.02 N."""
+    from .vision import CLIPVisionHIP
+    specs = CLIPVisionHIP(cfg)._specs
+    sd = {}
+    for name, shape in specs:
+        g = _key_generator(name, seed)
+        if name.endswith(('class_embedding', 'position_embedding.weight')):
+            t = 0.5 * torch.randn(shape, generator=g)
+        elif name.endswith('.weight') and len(shape) >= 2:
+            fan_in = 1
+            for s in shape[1:]:
+                fan_in *= s
+            t = torch.randn(shape, generator=g) / math.sqrt(fan_in)
+        elif name.endswith('.weight'):
+            t = 1.0 + 0.1 * torch.randn(shape, generator=g)
+        else:
+            t = 0.02 * torch.randn(shape, generator=g)
+        sd[name] = t
+    return sd
+
+
 @torch.no_grad()
 def synthetic_bert_state_dict(n_embed=1280, n_layer=32, vocab_size=30522, max_seq_len=77, seed=0):
     """CPU state_dict (keys `transformer.*`, as under `cond_stage_model.` in the LAION-400M checkpoint) of a seeded random

@@ -91,7 +91,7 @@ def _warn(msg):
     print('\n' + '!' * 100 + f'\n!! run_reference_script: {msg}\n' + '!' * 100 + '\n', file=sys.stderr, flush=True)
 
 
-def install_stubs(have_gpu, offline_stubs=False, real_ckpt=False):
+def install_stubs(have_gpu, offline_stubs=False, real_ckpt=False, hip_safety=None):
     import yaml
     import transformers          # before the stand-ins: it probes optional packages (torchvision, ...) via find_spec
 
@@ -177,22 +177,45 @@ def install_stubs(have_gpu, offline_stubs=False, real_ckpt=False):
         @classmethod
         def from_pretrained(cls, *a, **k): return cls()
         def __call__(self, images, clip_input): return images, [False] * len(images)
-    try:
-        import diffusers.pipelines.stable_diffusion.safety_checker as _sc   # noqa: F401
-        _real_sc = _sc.StableDiffusionSafetyChecker.from_pretrained.__func__
+    if hip_safety:
+        # --hip-safety: StableDiffusionSafetyCheckerHIP where the reference builds diffusers' checker (scripts/txt2img.py:26-29)
+        def _hip_safety_from_pretrained(cls, *a, **k):
+            from stable_diffusion_amd import synthetic
+            from stable_diffusion_amd.vision import StableDiffusionSafetyCheckerHIP
+            if hip_safety != 'synthetic':
+                print(f'run_reference_script: safety checker = StableDiffusionSafetyCheckerHIP.from_pretrained({hip_safety!r})', flush=True)
+                return StableDiffusionSafetyCheckerHIP.from_pretrained(hip_safety).cuda()
+            _stand_in_allowed('the NSFW safety checker weights (--hip-safety synthetic)')
+            _warn('SAFETY CHECKER = StableDiffusionSafetyCheckerHIP WITH SEEDED RANDOM WEIGHTS and thresholds no cosine reaches: the tower and '
+                  'the concept head run, every image is reported as safe')
+            m = StableDiffusionSafetyCheckerHIP()
+            sd = synthetic.synthetic_vision_state_dict(None, 1234)
+            sd = {('vision_model.' + key if key.startswith('vision_model.') else key): v for key, v in sd.items()}
+            g = torch.Generator().manual_seed(1234)
+            sd.update(concept_embeds=torch.randn(m.concept_embeds.shape, generator=g), concept_embeds_weights=torch.full(m.concept_embeds_weights.shape, 2.0),
+                      special_care_embeds=torch.randn(m.special_care_embeds.shape, generator=g),
+                      special_care_embeds_weights=torch.full(m.special_care_embeds_weights.shape, 2.0))
+            m.load_state_dict(sd, strict=True)
+            return m.cuda()
+        _module('diffusers.pipelines.stable_diffusion.safety_checker',
+                StableDiffusionSafetyChecker=type('StableDiffusionSafetyChecker', (), {'from_pretrained': classmethod(_hip_safety_from_pretrained)}))
+    else:
+        try:
+            import diffusers.pipelines.stable_diffusion.safety_checker as _sc   # noqa: F401
+            _real_sc = _sc.StableDiffusionSafetyChecker.from_pretrained.__func__
 
-        def _safety_from_pretrained(cls, *a, **k):
-            try:
-                return _real_sc(cls, *a, **k)
-            except Exception as e:      # no network / no cache
-                _stand_in_allowed(f'the NSFW safety checker weights ({type(e).__name__})')
-                _warn('SAFETY CHECKER STUBBED: every image is reported as safe (has_nsfw = False)')
-                return _Safety()
-        _sc.StableDiffusionSafetyChecker.from_pretrained = classmethod(_safety_from_pretrained)
-    except ImportError:
-        _stand_in_allowed('the `diffusers` package (NSFW safety checker)')
-        _warn('SAFETY CHECKER STUBBED (diffusers is not installed): every image is reported as safe')
-        _module('diffusers.pipelines.stable_diffusion.safety_checker', StableDiffusionSafetyChecker=_Safety)
+            def _safety_from_pretrained(cls, *a, **k):
+                try:
+                    return _real_sc(cls, *a, **k)
+                except Exception as e:      # no network / no cache
+                    _stand_in_allowed(f'the NSFW safety checker weights ({type(e).__name__})')
+                    _warn('SAFETY CHECKER STUBBED: every image is reported as safe (has_nsfw = False)')
+                    return _Safety()
+            _sc.StableDiffusionSafetyChecker.from_pretrained = classmethod(_safety_from_pretrained)
+        except ImportError:
+            _stand_in_allowed('the `diffusers` package (NSFW safety checker)')
+            _warn('SAFETY CHECKER STUBBED (diffusers is not installed): every image is reported as safe')
+            _module('diffusers.pipelines.stable_diffusion.safety_checker', StableDiffusionSafetyChecker=_Safety)
 
     for name in ('clip', 'kornia', 'taming', 'taming.modules', 'taming.modules.vqvae'):
         if name not in sys.modules:
@@ -428,6 +451,12 @@ def main():
     ap.add_argument('--offline-stubs', action='store_true',
                     help='allow seeded stand-ins for the CLIP tokenizer / text model / safety checker when the HF hub is '
                          'unreachable (synthetic checkpoints only; each substitution prints a warning)')
+    ap.add_argument('--hip-safety', action='store_true',
+                    help='StableDiffusionSafetyCheckerHIP in place of the safety checker (needs the MI355X).  With --hip-safety-dir its weights '
+                         'come from that directory; otherwise seeded random weights with thresholds no image reaches (needs --offline-stubs).  '
+                         'Off by default.')
+    ap.add_argument('--hip-safety-dir', default=None, metavar='DIR',
+                    help='a local copy of the shipped checker (config.json + model.safetensors / pytorch_model.bin); implies --hip-safety')
     ap.add_argument('script', choices=['txt2img', 'img2img'])
     ap.add_argument('rest', nargs=argparse.REMAINDER)
     args = ap.parse_args()
@@ -460,7 +489,10 @@ def main():
     global SYNTHETIC_SEED
     if not real_ckpt:
         SYNTHETIC_SEED = int(ckpt.split(':')[1]) if ':' in ckpt else 0
-    install_stubs(have_gpu, offline_stubs=args.offline_stubs, real_ckpt=real_ckpt)
+    hip_safety = args.hip_safety_dir or ('synthetic' if args.hip_safety else None)
+    if hip_safety and not have_gpu:
+        raise SystemExit('--hip-safety needs the MI355X (the HIP path has no CPU fallback)')
+    install_stubs(have_gpu, offline_stubs=args.offline_stubs, real_ckpt=real_ckpt, hip_safety=hip_safety)
     patch_torch_load()
 
     import ldm.models.diffusion.ddim as ddim
