@@ -276,6 +276,18 @@ int64_t sdmi_clip_workspace_bytes(sdmi_clip* h, int B, int L);
 /* ids: int64 [B, L] token ids (device); out: fp32 [B, L, hidden_size] = last_hidden_state */
 int sdmi_clip_forward(sdmi_clip* h, const int64_t* ids, float* out, int B, int L, void* workspace, int64_t workspace_bytes,
                       void* stream);
+/* OpenAI CLIP's encode_text (clip/model.py), what FrozenCLIPTextEmbedder runs (ldm/modules/encoders/modules.py:165-194).  A handle
+ * created here declares one more weight behind the tower's, `text_projection.weight` [projection_dim, hidden_size] (the key and
+ * orientation of transformers' CLIPTextModelWithProjection; no bias); sdmi_clip_create / sdmi_clip_create_precision handles keep their
+ * weight lists and refuse sdmi_clip_text_embeds by name.  sdmi_clip_forward works on both. */
+int sdmi_clip_create_projection(const sdmi_clip_cfg* cfg, int projection_dim, int precision, sdmi_clip** out);
+int sdmi_clip_projection_dim(const sdmi_clip* h);  /* 0 for a handle without a projection, -1 for a null handle */
+int64_t sdmi_clip_text_embeds_workspace_bytes(sdmi_clip* h, int B, int L);
+/* ids: int64 [B, L] (device); out: fp32 [B, projection_dim] = last_hidden_state[b, argmax(ids[b, :])] @ text_projection.weight^T, the FIRST
+ * maximum as clip/model.py takes it (no fixed eos id), divided by its L2 norm when normalize != 0.  Two launches behind the tower (gather + projection, normalisation); the
+ * projection's operands are those of the handle's precision (fp16 once, or split-fp16 pairs with the three products of that mode). */
+int sdmi_clip_text_embeds(sdmi_clip* h, const int64_t* ids, float* out, int B, int L, int normalize, void* workspace,
+                          int64_t workspace_bytes, void* stream);
 
 /* ---- text encoder of the LAION-400M model (BERTEmbedder) -------------------------------------------------------
  * Replaces `self.transformer(tokens, return_embeddings=True)` of BERTEmbedder.forward (ldm/modules/encoders/modules.py:
@@ -363,6 +375,47 @@ int sdmi_k_vit_preprocess(const float* x, float* out, int B, int H, int W, int S
 int sdmi_k_safety_head(const float* image_embeds, const float* concept_embeds, const float* special_care_embeds,
                        const float* concept_thresholds, const float* special_care_thresholds, int32_t* has_nsfw, float* concept_scores,
                        float* special_care_scores, int B, int Nc, int Ns, int E, void* stream);
+
+/* ---- exact k-nearest-neighbour search (retrieval conditioning) -------------------------------------------------------
+ * Replaces `Searcher.search` of scripts/knn2img.py (scann's score_brute_force with dot_product between L2-normalised vectors): an exact
+ * maximum-cosine search over a database of raw fp32 embeddings kept on the device, one copy of the rows plus one inverse norm per row.
+ * Results are ordered by descending score, ties go to the LOWER row index (a stable argsort of -score).  Exact arithmetic in fp32 with
+ * one fixed summation order: a (query, row) score has the same bits wherever the row sits.  Limits, each refused with a message that
+ * names it: D % 4 == 0, D <= 1024, 1 <= B <= 64, 1 <= k <= 64, k <= rows, rows < 2^31 (row offsets are 64-bit).
+ * Additive entry points: no existing struct or call changes, SDMI_ABI_VERSION stays as it is. */
+typedef struct sdmi_knn sdmi_knn;
+/* allocates capacity * (D + 1) floats; refused when that exceeds the free device memory (the message names both sizes) */
+int sdmi_knn_create(int D, int64_t capacity_rows, sdmi_knn** out);
+int sdmi_knn_destroy(sdmi_knn* h);
+/* raw (unnormalised) rows [n][D], host or device memory, copied to rows first_row .. first_row + n; chunks arrive in order
+ * (first_row <= rows set so far), so a multi-file database needs no second host copy */
+int sdmi_knn_set_rows(sdmi_knn* h, int64_t first_row, int64_t n, const float* rows, void* stream);
+/* inverse norms on the device; synchronises the stream.  A row with a zero or non-finite norm is an error that names the first such row */
+int sdmi_knn_finalize(sdmi_knn* h, void* stream);
+int64_t sdmi_knn_rows(const sdmi_knn* h);         /* rows set so far, or -1 for a null handle */
+int sdmi_knn_dim(const sdmi_knn* h);
+int64_t sdmi_knn_workspace_bytes(sdmi_knn* h, int B, int k);
+/* queries: fp32 [B, D] (device), normalised on the device.  idx_out int32 [B, k], score_out fp32 [B, k] = (q / |q|) . x / |x|;
+ * nn_out (optional) fp32 [B, k, D] = x[idx] / |x[idx]|.  Launches: scan, merge (two stages above 64 slabs), gather. */
+int sdmi_knn_search(sdmi_knn* h, const float* queries, int B, int k, int32_t* idx_out, float* score_out, float* nn_out_or_null,
+                    void* workspace, int64_t workspace_bytes, void* stream);
+/* the sampler's context: c fp32 [B, 1, D] (device) is the query AND slot 0 of c_out fp32 [B, 1 + k, D] (copied bit for bit); slots 1 .. k
+ * are the normalised neighbours: `torch.cat([c, nn_embeddings], dim=1)` with no host round trip.  idx_out / score_out as above. */
+int sdmi_knn_condition(sdmi_knn* h, const float* c, int B, int k, float* c_out, int32_t* idx_out, float* score_out, void* workspace,
+                       int64_t workspace_bytes, void* stream);
+/* The kernels, with the slab size explicit.  inv_norm: fp32 [N].  scan: candidates [B][ceil(N / slab_rows)][k] (score, row index), unsorted,
+ * lists of slabs with fewer than k rows padded with (-inf, INT32_MAX).  merge: candidates [B][n_lists][k] -> idx / score [B][k] in the
+ * order above.  gather: out row b * (k + (c0 != NULL)) + slot at pitch ldo floats (ldo >= D, ldo % 4 == 0); c0 [B][D] or NULL. */
+int sdmi_k_knn_inv_norm(const float* db, int64_t N, int D, float* inv_norm, void* stream);
+int sdmi_k_knn_scan(const float* db, const float* inv_norm, int64_t N, int D, const float* queries, int B, int k, int64_t slab_rows,
+                    float* cand_score, int32_t* cand_idx, void* stream);
+int sdmi_k_knn_merge(const float* cand_score, const int32_t* cand_idx, int B, int n_lists, int k, int32_t* idx_out, float* score_out,
+                     void* stream);
+/* a plain read-only sweep of n_floats (a multiple of 4) with 16-byte loads: the bandwidth ceiling tools/bench_knn.py measures the scan
+ * against.  sink: one float on the device, practically never written. */
+int sdmi_k_knn_stream_read(const float* p, int64_t n_floats, float* sink, void* stream);
+int sdmi_k_knn_gather(const float* db, const float* inv_norm, int64_t N, int D, const int32_t* idx, int B, int k, const float* c0_or_null,
+                      float* out, int64_t ldo, void* stream);
 
 /* ---- kernel-level entry points (parity tests and micro-benchmarks; same kernels the UNet uses) ---------- */
 typedef struct sdmi_igemm_desc {

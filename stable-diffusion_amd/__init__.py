@@ -16,6 +16,8 @@ this package is the host-side mirror of the reference's interfaces for that path
     CLIPVisionHIP     <- transformers.CLIPVisionModelWithProjection (the tower of the two modules below)
     StableDiffusionSafetyCheckerHIP <- diffusers' StableDiffusionSafetyChecker (scripts/txt2img.py:check_safety)
     FrozenClipImageEmbedderHIP <- ldm.modules.encoders.modules.FrozenClipImageEmbedder
+    FrozenCLIPTextEmbedderHIP <- ldm.modules.encoders.modules.FrozenCLIPTextEmbedder (OpenAI CLIP encode_text: pooled, projected)
+    SearcherHIP       <- scripts/knn2img.py: Searcher (exact k-NN over the retrieval database, on the device)
 
 Importable as `stable_diffusion_amd` (see stable_diffusion_amd.py at the repo root).
 """
@@ -23,12 +25,13 @@ from . import _lib  # noqa: F401
 from .unet import UNetModelHIP  # noqa: F401
 from .samplers import PLMSSamplerHIP, DDIMSamplerHIP, DPMSolverSamplerHIP  # noqa: F401
 from .vae import AutoencoderKLHIP, VQModelInterfaceHIP  # noqa: F401
-from .clip import FrozenCLIPEmbedderHIP  # noqa: F401
+from .clip import FrozenCLIPEmbedderHIP, FrozenCLIPTextEmbedderHIP  # noqa: F401
 from .bert import BERTEmbedderHIP  # noqa: F401
 from .class_embedder import ClassEmbedderHIP  # noqa: F401
 from .ldm_shim import LatentDiffusionHIP, DiffusionWrapperHIP  # noqa: F401
 from .superres import SuperResolutionHIP  # noqa: F401
 from .vision import CLIPVisionHIP, StableDiffusionSafetyCheckerHIP, FrozenClipImageEmbedderHIP  # noqa: F401
+from .retrieval import SearcherHIP  # noqa: F401
 from . import debug, postprocess  # noqa: F401
 
-__all__ = ['UNetModelHIP', 'AutoencoderKLHIP', 'VQModelInterfaceHIP', 'FrozenCLIPEmbedderHIP', 'BERTEmbedderHIP', 'ClassEmbedderHIP', 'PLMSSamplerHIP', 'DDIMSamplerHIP', 'DPMSolverSamplerHIP', 'LatentDiffusionHIP', 'DiffusionWrapperHIP', 'SuperResolutionHIP', 'CLIPVisionHIP', 'StableDiffusionSafetyCheckerHIP', 'FrozenClipImageEmbedderHIP']
+__all__ = ['UNetModelHIP', 'AutoencoderKLHIP', 'VQModelInterfaceHIP', 'FrozenCLIPEmbedderHIP', 'BERTEmbedderHIP', 'ClassEmbedderHIP', 'PLMSSamplerHIP', 'DDIMSamplerHIP', 'DPMSolverSamplerHIP', 'LatentDiffusionHIP', 'DiffusionWrapperHIP', 'SuperResolutionHIP', 'CLIPVisionHIP', 'StableDiffusionSafetyCheckerHIP', 'FrozenClipImageEmbedderHIP', 'FrozenCLIPTextEmbedderHIP', 'SearcherHIP']

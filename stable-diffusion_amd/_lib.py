@@ -124,6 +124,10 @@ _SIGS = {
     'sdmi_clip_finalize': (C.c_int, [c_ptr]),
     'sdmi_clip_workspace_bytes': (C.c_int64, [c_ptr, C.c_int, C.c_int]),
     'sdmi_clip_forward': (C.c_int, [c_ptr, c_ptr, c_ptr, C.c_int, C.c_int, c_ptr, C.c_int64, c_ptr]),
+    'sdmi_clip_create_projection': (C.c_int, [C.POINTER(ClipCfg), C.c_int, C.c_int, C.POINTER(c_ptr)]),
+    'sdmi_clip_projection_dim': (C.c_int, [c_ptr]),
+    'sdmi_clip_text_embeds_workspace_bytes': (C.c_int64, [c_ptr, C.c_int, C.c_int]),
+    'sdmi_clip_text_embeds': (C.c_int, [c_ptr, c_ptr, c_ptr, C.c_int, C.c_int, C.c_int, c_ptr, C.c_int64, c_ptr]),
     'sdmi_bert_create': (C.c_int, [C.POINTER(BertCfg), C.POINTER(c_ptr)]),
     'sdmi_bert_create_precision': (C.c_int, [C.POINTER(BertCfg), C.c_int, C.POINTER(c_ptr)]),
     'sdmi_bert_precision': (C.c_int, [c_ptr]),
@@ -147,6 +151,20 @@ _SIGS = {
     'sdmi_k_vit_embed': (C.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, C.c_int, C.c_int, C.c_int, c_ptr]),
     'sdmi_k_vit_preprocess': (C.c_int, [c_ptr, c_ptr, C.c_int, C.c_int, C.c_int, C.c_int, c_ptr]),
     'sdmi_k_safety_head': (C.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, C.c_int, C.c_int, C.c_int, C.c_int, c_ptr]),
+    'sdmi_knn_create': (C.c_int, [C.c_int, C.c_int64, C.POINTER(c_ptr)]),
+    'sdmi_knn_destroy': (C.c_int, [c_ptr]),
+    'sdmi_knn_set_rows': (C.c_int, [c_ptr, C.c_int64, C.c_int64, c_ptr, c_ptr]),
+    'sdmi_knn_finalize': (C.c_int, [c_ptr, c_ptr]),
+    'sdmi_knn_rows': (C.c_int64, [c_ptr]),
+    'sdmi_knn_dim': (C.c_int, [c_ptr]),
+    'sdmi_knn_workspace_bytes': (C.c_int64, [c_ptr, C.c_int, C.c_int]),
+    'sdmi_knn_search': (C.c_int, [c_ptr, c_ptr, C.c_int, C.c_int, c_ptr, c_ptr, c_ptr, c_ptr, C.c_int64, c_ptr]),
+    'sdmi_knn_condition': (C.c_int, [c_ptr, c_ptr, C.c_int, C.c_int, c_ptr, c_ptr, c_ptr, c_ptr, C.c_int64, c_ptr]),
+    'sdmi_k_knn_inv_norm': (C.c_int, [c_ptr, C.c_int64, C.c_int, c_ptr, c_ptr]),
+    'sdmi_k_knn_scan': (C.c_int, [c_ptr, c_ptr, C.c_int64, C.c_int, c_ptr, C.c_int, C.c_int, C.c_int64, c_ptr, c_ptr, c_ptr]),
+    'sdmi_k_knn_merge': (C.c_int, [c_ptr, c_ptr, C.c_int, C.c_int, C.c_int, c_ptr, c_ptr, c_ptr]),
+    'sdmi_k_knn_stream_read': (C.c_int, [c_ptr, C.c_int64, c_ptr, c_ptr]),
+    'sdmi_k_knn_gather': (C.c_int, [c_ptr, c_ptr, C.c_int64, C.c_int, c_ptr, C.c_int, C.c_int, c_ptr, c_ptr, C.c_int64, c_ptr]),
     'sdmi_has_experiments': (C.c_int, []),
     'sdmi_k_igemm': (C.c_int, [C.POINTER(IGemmDesc), c_ptr]),
     'sdmi_k_igemm_tail': (C.c_int, [C.POINTER(IGemmDesc), c_ptr, c_ptr, c_ptr, C.c_int, C.c_int, c_ptr, C.c_int, c_ptr]),

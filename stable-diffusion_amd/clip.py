@@ -38,10 +38,13 @@ def make_clip_cfg(tc):
 class _ClipHandle:
     """Owns one sdmi_clip*."""
 
-    def __init__(self, cfg, precision='mixed'):
+    def __init__(self, cfg, precision='mixed', projection_dim=0):
         self.lib = _lib.load()
         h = C.c_void_p()
-        _lib.check(self.lib.sdmi_clip_create_precision(C.byref(cfg), PRECISIONS[precision], C.byref(h)))
+        if projection_dim:      # one more weight behind the tower's: text_projection.weight
+            _lib.check(self.lib.sdmi_clip_create_projection(C.byref(cfg), int(projection_dim), PRECISIONS[precision], C.byref(h)))
+        else:
+            _lib.check(self.lib.sdmi_clip_create_precision(C.byref(cfg), PRECISIONS[precision], C.byref(h)))
         self.h = h
 
     def weight_specs(self):
@@ -84,7 +87,7 @@ class FrozenCLIPEmbedderHIP(nn.Module):
         self.max_length = max_length
         self.text_config = dict(CLIP_VIT_L14_TEXT if text_config is None else text_config)
         self._cfg = make_clip_cfg(self.text_config)
-        self._handle = _ClipHandle(self._cfg, hip_precision)
+        self._handle = self._make_handle()
         self._specs = self._handle.weight_specs()          # keys relative to `transformer.`
         self.add_module('transformer', _Node())
         for key, shape in self._specs:
@@ -102,6 +105,9 @@ class FrozenCLIPEmbedderHIP(nn.Module):
         self._sentinels = None
         self._ws = None
         self.freeze()
+
+    def _make_handle(self):
+        return _ClipHandle(self._cfg, self.hip_precision)
 
     def freeze(self):
         """modules.py:146-149"""
@@ -146,10 +152,9 @@ class FrozenCLIPEmbedderHIP(nn.Module):
         self._packed_sig = self._signature()
 
     # ---- CLIPTextModel(input_ids).last_hidden_state ----------------------------------------------------------------------
-    @torch.no_grad()
-    def encode_ids(self, ids):
+    def _checked_ids(self, ids):
         if not ids.is_cuda:
-            raise RuntimeError('FrozenCLIPEmbedderHIP runs on an MI355X device tensor only (no CPU fallback)')
+            raise RuntimeError(f'{type(self).__name__} runs on an MI355X device tensor only (no CPU fallback)')
         if ids.dim() != 2 or ids.shape[1] > self._cfg.max_positions:
             raise ValueError(f'input_ids must be [B, L <= {self._cfg.max_positions}]')
         if self._packed_sig is None or self._packed_sig != self._signature():
@@ -157,6 +162,11 @@ class FrozenCLIPEmbedderHIP(nn.Module):
         ids = ids.detach().to(torch.int64).contiguous()
         if int(ids.min()) < 0 or int(ids.max()) >= self._cfg.vocab_size:
             raise IndexError('token id out of range')           # what nn.Embedding raises in the reference
+        return ids
+
+    @torch.no_grad()
+    def encode_ids(self, ids):
+        ids = self._checked_ids(ids)
         B, L = ids.shape
         out = torch.empty((B, L, self._cfg.hidden_size), dtype=torch.float32, device=ids.device)
         for b0 in range(0, B, self.MAX_BATCH):
@@ -181,3 +191,72 @@ class FrozenCLIPEmbedderHIP(nn.Module):
 
     def encode(self, text):
         return self(text)
+
+
+OPENAI_CLIP_VERSIONS = {'ViT-L/14': 'openai/clip-vit-large-patch14', 'ViT-B/32': 'openai/clip-vit-base-patch32',
+                        'ViT-B/16': 'openai/clip-vit-base-patch16'}
+
+
+class FrozenCLIPTextEmbedderHIP(FrozenCLIPEmbedderHIP):
+    """Drop-in for `ldm.modules.encoders.modules.FrozenCLIPTextEmbedder` (modules.py:165-194), the text conditioner of the
+    retrieval-augmented model (scripts/knn2img.py): OpenAI CLIP's `encode_text` -- the text tower, the row at the EOT token (the first
+    maximum of the ids, as clip/model.py takes it), `text_projection`, optionally the L2 normalisation.  `forward(text)` returns [B, E],
+    `encode(text)` [B, n_repeat, E], `encode_ids(ids)` [B, E] for callers with their own tokenizer.
+
+    Parameters carry transformers' CLIPTextModelWithProjection names (`transformer.text_model.*`, `transformer.text_projection.weight`);
+    `vision.openai_clip_text_to_transformers` converts the text half of an OpenAI-CLIP state dict.  `text_config` is a CLIPTextConfig dict with
+    `projection_dim` (default: ViT-L/14's, 768).  The tokenizer is host Python: `tokenizer=` as given, else transformers' CLIPTokenizer with
+    padding='max_length'.  `clip.tokenize` pads with 0 where CLIPTokenizer pads with its own pad id; under the causal mask the EOT row never
+    sees a position behind it and the pooled row is the EOT row, so the pad id cannot change the output (tests/test_clip_text_embeds_gpu.py
+    checks it bit for bit)."""
+
+    def __init__(self, version='ViT-L/14', device='cuda', max_length=77, n_repeat=1, normalize=True, text_config=None, tokenizer=None,
+                 hip_precision='mixed'):
+        tc = dict(CLIP_VIT_L14_TEXT, projection_dim=768) if text_config is None else dict(text_config)
+        if int(tc.get('projection_dim', 0)) < 1:
+            raise ValueError('FrozenCLIPTextEmbedderHIP needs text_config["projection_dim"] (the width of text_projection)')
+        super().__init__(version=OPENAI_CLIP_VERSIONS.get(version, version), device=device, max_length=max_length, text_config=tc,
+                         tokenizer=tokenizer, hip_precision=hip_precision)
+        self.n_repeat = n_repeat
+        self.normalize = normalize
+        self._ews = None
+
+    def _make_handle(self):
+        return _ClipHandle(self._cfg, self.hip_precision, int(self.text_config['projection_dim']))
+
+    @torch.no_grad()
+    def hidden_states(self, ids):
+        """the tower's final-LayerNorm output [B, L, W] of the same handle (what FrozenCLIPEmbedderHIP.encode_ids returns)"""
+        return super().encode_ids(ids)
+
+    @torch.no_grad()
+    def encode_ids(self, ids, normalize=None):
+        ids = self._checked_ids(ids)
+        B, L = ids.shape
+        E = int(self.text_config['projection_dim'])
+        lib = self._handle.lib
+        out = torch.empty((B, E), dtype=torch.float32, device=ids.device)
+        for b0 in range(0, B, self.MAX_BATCH):
+            nb = min(self.MAX_BATCH, B - b0)
+            key = (nb, L, str(ids.device))
+            if self._ews is None or self._ews[0] != key:
+                need = lib.sdmi_clip_text_embeds_workspace_bytes(self._handle.h, nb, L)
+                if need <= 0:
+                    _lib.check(-1)
+                self._ews = (key, torch.empty(int(need), dtype=torch.uint8, device=ids.device))
+            ws = self._ews[1]
+            _lib.check(lib.sdmi_clip_text_embeds(self._handle.h, ids[b0:b0 + nb].data_ptr(), out[b0:b0 + nb].data_ptr(), nb, L,
+                                                 int(self.normalize if normalize is None else normalize), ws.data_ptr(), ws.numel(),
+                                                 _lib.stream_ptr()))
+        return out
+
+    def forward(self, text):
+        """modules.py:182-187"""
+        return super().forward(text)            # (tokenize, then this class's encode_ids)
+
+    def encode(self, text):
+        """modules.py:189-194: [B, n_repeat, E]"""
+        z = self(text)
+        if z.ndim == 2:
+            z = z[:, None, :]
+        return z.expand(-1, self.n_repeat, -1).contiguous()

@@ -8,6 +8,7 @@
 #include "unet.h"
 #include "vae.h"
 #include "clip.h"
+#include "knn.h"
 
 namespace sdmi {
 static thread_local std::string g_err;
@@ -20,6 +21,7 @@ struct sdmi_vae { sdmi::Vae impl; };
 struct sdmi_clip { sdmi::ClipText impl; };
 struct sdmi_bert { sdmi::BertText impl; };
 struct sdmi_vit { sdmi::ClipVision impl; };
+struct sdmi_knn { sdmi::Knn impl; };
 
 using namespace sdmi;
 
@@ -270,6 +272,32 @@ int64_t sdmi_clip_workspace_bytes(sdmi_clip* h, int B, int L) {
   if (h->impl.forward(nullptr, nullptr, B, L, nullptr, 0, nullptr, true, &need)) return 0;
   return need;
 }
+int sdmi_clip_create_projection(const sdmi_clip_cfg* cfg, int projection_dim, int precision, sdmi_clip** out) {
+  SDMI_CHECK(cfg && out, "null argument");
+  SDMI_CHECK(precision == SDMI_PRECISION_MIXED || precision == SDMI_PRECISION_FULL,
+             "precision must be SDMI_PRECISION_MIXED (0) or SDMI_PRECISION_FULL (1), got " + std::to_string(precision));
+  SDMI_CHECK(projection_dim >= 1, "projection_dim must be positive, got " + std::to_string(projection_dim));
+  sdmi_clip* h = new (std::nothrow) sdmi_clip();
+  SDMI_CHECK(h != nullptr, "out of host memory");
+  if (h->impl.build(*cfg, precision, projection_dim)) { delete h; return -1; }
+  *out = h;
+  return 0;
+}
+int sdmi_clip_projection_dim(const sdmi_clip* h) {
+  if (!h) { fail("null handle"); return -1; }
+  return h->impl.proj_dim_;
+}
+int64_t sdmi_clip_text_embeds_workspace_bytes(sdmi_clip* h, int B, int L) {
+  if (!h) { fail("null handle"); return 0; }
+  int64_t need = 0;
+  if (h->impl.text_embeds(nullptr, nullptr, B, L, 0, nullptr, 0, nullptr, true, &need)) return 0;
+  return need;
+}
+int sdmi_clip_text_embeds(sdmi_clip* h, const int64_t* ids, float* out, int B, int L, int normalize, void* workspace,
+                          int64_t workspace_bytes, void* stream) {
+  SDMI_CHECK(h && ids && out, "null argument");
+  return h->impl.text_embeds(ids, out, B, L, normalize, workspace, workspace_bytes, (hipStream_t)stream, false, nullptr);
+}
 int sdmi_clip_forward(sdmi_clip* h, const int64_t* ids, float* out, int B, int L, void* workspace, int64_t workspace_bytes,
                       void* stream) {
   SDMI_CHECK(h && ids && out, "null argument");
@@ -366,6 +394,59 @@ int sdmi_k_safety_head(const float* image_embeds, const float* concept_embeds, c
                        float* special_care_scores, int B, int Nc, int Ns, int E, void* stream) {
   return launch_safety_head(image_embeds, concept_embeds, special_care_embeds, concept_thresholds, special_care_thresholds, (int*)has_nsfw,
                             concept_scores, special_care_scores, B, Nc, Ns, E, (hipStream_t)stream);
+}
+// ---- exact k-NN search -----------------------------------------------------------------------------------------------
+int sdmi_knn_create(int D, int64_t capacity_rows, sdmi_knn** out) {
+  SDMI_CHECK(out, "null argument");
+  sdmi_knn* h = new (std::nothrow) sdmi_knn();
+  SDMI_CHECK(h != nullptr, "out of host memory");
+  if (h->impl.build(D, capacity_rows)) { delete h; return -1; }
+  *out = h;
+  return 0;
+}
+int sdmi_knn_destroy(sdmi_knn* h) { delete h; return 0; }
+int sdmi_knn_set_rows(sdmi_knn* h, int64_t first_row, int64_t n, const float* rows, void* stream) {
+  SDMI_CHECK(h && rows, "null argument");
+  return h->impl.set_rows(first_row, n, rows, (hipStream_t)stream);
+}
+int sdmi_knn_finalize(sdmi_knn* h, void* stream) { SDMI_CHECK(h, "null handle"); return h->impl.finalize((hipStream_t)stream); }
+int64_t sdmi_knn_rows(const sdmi_knn* h) {
+  if (!h) { fail("null handle"); return -1; }
+  return h->impl.n_;
+}
+int sdmi_knn_dim(const sdmi_knn* h) { return h ? h->impl.D_ : fail("null handle"); }
+int64_t sdmi_knn_workspace_bytes(sdmi_knn* h, int B, int k) {
+  if (!h) { fail("null handle"); return 0; }
+  if (knn_check_args(h->impl.n_, h->impl.D_, B, k)) return 0;
+  return h->impl.workspace_bytes(B, k);
+}
+int sdmi_knn_search(sdmi_knn* h, const float* queries, int B, int k, int32_t* idx_out, float* score_out, float* nn_out_or_null,
+                    void* workspace, int64_t workspace_bytes, void* stream) {
+  SDMI_CHECK(h, "null handle");
+  return h->impl.search(queries, B, k, (int*)idx_out, score_out, nn_out_or_null, nullptr, workspace, workspace_bytes, (hipStream_t)stream);
+}
+int sdmi_knn_condition(sdmi_knn* h, const float* c, int B, int k, float* c_out, int32_t* idx_out, float* score_out, void* workspace,
+                       int64_t workspace_bytes, void* stream) {
+  SDMI_CHECK(h && c && c_out, "null argument");
+  return h->impl.search(c, B, k, (int*)idx_out, score_out, c_out, c, workspace, workspace_bytes, (hipStream_t)stream);
+}
+int sdmi_k_knn_inv_norm(const float* db, int64_t N, int D, float* inv_norm, void* stream) {
+  return launch_knn_inv_norm(db, N, D, inv_norm, (hipStream_t)stream);
+}
+int sdmi_k_knn_scan(const float* db, const float* inv_norm, int64_t N, int D, const float* queries, int B, int k, int64_t slab_rows,
+                    float* cand_score, int32_t* cand_idx, void* stream) {
+  return launch_knn_scan(db, inv_norm, N, D, queries, B, k, slab_rows, cand_score, (int*)cand_idx, (hipStream_t)stream);
+}
+int sdmi_k_knn_merge(const float* cand_score, const int32_t* cand_idx, int B, int n_lists, int k, int32_t* idx_out, float* score_out,
+                     void* stream) {
+  return launch_knn_merge(cand_score, (const int*)cand_idx, B, n_lists, k, (int*)idx_out, score_out, (hipStream_t)stream);
+}
+int sdmi_k_knn_stream_read(const float* p, int64_t n_floats, float* sink, void* stream) {
+  return launch_knn_stream_read(p, n_floats, sink, (hipStream_t)stream);
+}
+int sdmi_k_knn_gather(const float* db, const float* inv_norm, int64_t N, int D, const int32_t* idx, int B, int k, const float* c0_or_null,
+                      float* out, int64_t ldo, void* stream) {
+  return launch_knn_gather(db, inv_norm, N, D, (const int*)idx, B, k, c0_or_null, out, ldo, (hipStream_t)stream);
 }
 int sdmi_k_vq_quantize(const float* z, float z_scale, const float* codebook, float* norms_ws, int n_embed, int D, float* zq, int32_t* idx,
                        int B, int HW, void* stream) {

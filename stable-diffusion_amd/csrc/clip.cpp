@@ -15,9 +15,11 @@
 
 namespace sdmi {
 
-int ClipText::build(const sdmi_clip_cfg& c, int precision) {
+int ClipText::build(const sdmi_clip_cfg& c, int precision, int projection_dim) {
   cfg_ = c;
   precision_ = precision;
+  proj_dim_ = projection_dim;
+  SDMI_CHECK(projection_dim >= 0 && projection_dim <= 4096, "projection_dim " + std::to_string(projection_dim) + " outside 0 .. 4096");
   SDMI_CHECK(c.hidden_size % 64 == 0 && c.intermediate_size % 64 == 0, "hidden / intermediate size must be multiples of 64");
   SDMI_CHECK(c.num_heads >= 1 && c.hidden_size % c.num_heads == 0, "hidden_size % num_heads");
   const int dh = c.hidden_size / c.num_heads;
@@ -34,7 +36,24 @@ int ClipText::build(const sdmi_clip_cfg& c, int precision) {
     expect_layer(tm + "encoder.layers." + std::to_string(i) + ".", layers_[i], C, I);
   store_.expect(tm + "final_layer_norm.weight", {C}, W_F32, &fln_g_);
   store_.expect(tm + "final_layer_norm.bias", {C}, W_F32, &fln_b_);
+  if (projection_dim > 0) store_.expect("text_projection.weight", {(int64_t)projection_dim, C}, lin_kind(), &wproj_);
   return 0;
+}
+
+int ClipText::text_embeds(const int64_t* ids, float* out, int B, int L, int normalize, void* workspace, int64_t ws_bytes, hipStream_t stream,
+                          bool dry, int64_t* bytes_needed) {
+  SDMI_CHECK(proj_dim_ > 0, "sdmi_clip_text_embeds: this handle was created without a text projection (sdmi_clip_create_projection)");
+  int64_t need_fwd = 0;
+  if (forward(nullptr, nullptr, B, L, nullptr, 0, nullptr, true, &need_fwd)) return -1;
+  const int64_t hid_bytes = round_up((int64_t)B * L * cfg_.hidden_size * (int64_t)sizeof(float), 4096);
+  if (bytes_needed) *bytes_needed = need_fwd + hid_bytes;
+  if (dry) return 0;
+  SDMI_CHECK(ids != nullptr && out != nullptr, "ids / out is NULL");
+  SDMI_CHECK(workspace != nullptr && ws_bytes >= need_fwd + hid_bytes, "workspace too small: need " + std::to_string(need_fwd + hid_bytes) +
+                                                                           " bytes, got " + std::to_string(ws_bytes));
+  float* hidden = (float*)workspace;
+  if (forward(ids, hidden, B, L, (char*)workspace + hid_bytes, ws_bytes - hid_bytes, stream, false, nullptr)) return -1;
+  return launch_clip_pool_project(ids, hidden, wproj_, full(), out, B, L, cfg_.hidden_size, proj_dim_, normalize, stream);
 }
 
 void TextEncBase::expect_layer(const std::string& p, CLayer& L, int64_t C, int64_t I) {

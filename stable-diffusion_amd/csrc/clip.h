@@ -64,16 +64,27 @@ class TextEncBase {
 
 class ClipText : public TextEncBase {
  public:
-  int build(const sdmi_clip_cfg& cfg, int precision = SDMI_PRECISION_MIXED);
+  // projection_dim > 0 declares `text_projection.weight` [projection_dim][hidden] behind the tower's weights (CLIPTextModelWithProjection)
+  int build(const sdmi_clip_cfg& cfg, int precision = SDMI_PRECISION_MIXED, int projection_dim = 0);
   // ids int64 [B][L] (device) -> last_hidden_state fp32 [B][L][hidden] (after final_layer_norm)
   int forward(const int64_t* ids, float* out, int B, int L, void* workspace, int64_t ws_bytes, hipStream_t stream, bool dry,
               int64_t* bytes_needed);
+  // OpenAI CLIP's encode_text: the tower, then the row at the first maximum of ids[b, :] times text_projection^T, optionally L2-normalised
+  // -> out fp32 [B][projection_dim].  The hidden state lives at the head of the workspace; two launches behind the tower (textpool.hip).
+  int text_embeds(const int64_t* ids, float* out, int B, int L, int normalize, void* workspace, int64_t ws_bytes, hipStream_t stream, bool dry,
+                  int64_t* bytes_needed);
   sdmi_clip_cfg cfg_{};
+  int proj_dim_ = 0;
 
  private:
   std::vector<CLayer> layers_;
   float *tok_ = nullptr, *pos_ = nullptr, *fln_g_ = nullptr, *fln_b_ = nullptr;
+  f16* wproj_ = nullptr;                // text_projection.weight: fp16 rows (mixed) or split-fp16 rows [hi | hi | lo] (full)
 };
+
+// hidden fp32 [B][L][W] (the final-LayerNorm output), w [E][W] fp16 or [E][3 W] split-fp16 -> out fp32 [B][E] (textpool.hip)
+int launch_clip_pool_project(const int64_t* ids, const float* hidden, const f16* w, bool full, float* out, int B, int L, int W, int E,
+                             int normalize, hipStream_t s);
 
 // transformers' CLIPVisionModelWithProjection (models/clip/modeling_clip.py: CLIPVisionTransformer + visual_projection): the safety checker's
 // tower and FrozenClipImageEmbedder's.  Mixed precision only.

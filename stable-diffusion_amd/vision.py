@@ -329,6 +329,67 @@ def transformers_to_openai_clip(sd):
     return out
 
 
+_OPENAI_TEXT_TOP = {'token_embedding.weight': 'text_model.embeddings.token_embedding.weight',
+                    'positional_embedding': 'text_model.embeddings.position_embedding.weight',
+                    'ln_final.weight': 'text_model.final_layer_norm.weight', 'ln_final.bias': 'text_model.final_layer_norm.bias'}
+_OPENAI_NOT_TEXT = ('visual.', 'logit_scale', 'input_resolution', 'context_length', 'vocab_size')
+
+
+def openai_clip_text_to_transformers(sd):
+    """The text half of an OpenAI `clip` state dict (`visual.*`, `logit_scale` and the jit archive's scalars are ignored) ->
+    CLIPTextModelWithProjection naming: `transformer.resblocks.N.attn.in_proj_{weight, bias}` split into q | k | v, `text_projection`
+    ([width, embed]) transposed into `text_projection.weight`."""
+    out = {}
+    for k, v in sd.items():
+        if k.startswith(_OPENAI_NOT_TEXT):
+            continue
+        if k in _OPENAI_TEXT_TOP:
+            out[_OPENAI_TEXT_TOP[k]] = v
+        elif k == 'text_projection':
+            out['text_projection.weight'] = v.t().contiguous()
+        elif k.startswith('transformer.resblocks.'):
+            n, rest = k[len('transformer.resblocks.'):].split('.', 1)
+            p = f'text_model.encoder.layers.{n}.'
+            if rest in ('attn.in_proj_weight', 'attn.in_proj_bias'):
+                leaf = rest.rsplit('_', 1)[1]
+                for name, part in zip(('q_proj', 'k_proj', 'v_proj'), v.chunk(3, dim=0)):
+                    out[p + f'self_attn.{name}.{leaf}'] = part.contiguous()
+            elif rest in _OPENAI_LAYER:
+                out[p + _OPENAI_LAYER[rest]] = v
+            else:
+                raise KeyError(f'unexpected OpenAI-clip key {k!r}')
+        else:
+            raise KeyError(f'unexpected OpenAI-clip key {k!r}')
+    return out
+
+
+def transformers_to_openai_clip_text(sd):
+    """The inverse of `openai_clip_text_to_transformers` (`text_model.embeddings.position_ids` has no OpenAI counterpart and is dropped)."""
+    inv_top = {v: k for k, v in _OPENAI_TEXT_TOP.items()}
+    inv_layer = {v: k for k, v in _OPENAI_LAYER.items()}
+    out, qkv = {}, {}
+    for k, v in sd.items():
+        if k in inv_top:
+            out[inv_top[k]] = v
+        elif k == 'text_projection.weight':
+            out['text_projection'] = v.t().contiguous()
+        elif k == 'text_model.embeddings.position_ids':
+            continue
+        elif k.startswith('text_model.encoder.layers.'):
+            n, rest = k[len('text_model.encoder.layers.'):].split('.', 1)
+            p = f'transformer.resblocks.{n}.'
+            if rest in inv_layer:
+                out[p + inv_layer[rest]] = v
+            else:
+                _, name, leaf = rest.split('.')
+                qkv.setdefault((p, leaf), {})[name] = v
+        else:
+            raise KeyError(f'unexpected CLIPTextModelWithProjection key {k!r}')
+    for (p, leaf), parts in qkv.items():
+        out[p + f'attn.in_proj_{leaf}'] = torch.cat([parts['q_proj'], parts['k_proj'], parts['v_proj']], 0)
+    return out
+
+
 class FrozenClipImageEmbedderHIP(nn.Module):
     """modules.py:197-228: `preprocess` = bicubic resize to the tower's image size (align_corners=True), (x + 1) / 2, CLIP mean / std -- one launch
     of sdmi_k_vit_preprocess; `forward(x)` = image_embeds of the preprocessed images (`self.model.encode_image`).  Parameters live under

@@ -1,0 +1,95 @@
+"""The front half of the reference's `scripts/knn2img.py --use_neighbors`: prompts (or token ids) -> CLIP text embeds -> exact k-NN in a
+retrieval database -> the conditioning tensor c [B, 1 + k, D] the sampler takes.
+
+    python tools/knn_cond.py --database DIR --knn 10 --prompt "a painting of a virus monster playing guitar" [--text-weights CKPT]
+    python tools/knn_cond.py --database DIR --knn 10 --ids-file ids.txt --text-weights CKPT --out cond.pt
+
+--database       a directory of `.npz` files in the reference's layout (embedding, img_id, patch_coords)
+--prompt / --from-file   prompts; they need a tokenizer (`--tokenizer`, a local transformers CLIPTokenizer directory)
+--ids-file       one line of whitespace-separated token ids per sample instead (no tokenizer needed)
+--text-weights   a torch checkpoint of the text encoder: an OpenAI-CLIP state dict or transformers' CLIPTextModelWithProjection one
+--queries        skip the text encoder: a `.npy` / `.pt` of query vectors [B, D] (e.g. image embeds)
+Prints the neighbour row ids, image ids and cosines per sample; --out saves {'c', 'nns', 'scores', 'img_ids', 'patch_coords'}.
+Runs on the GPU only: there is no CPU path."""
+import argparse
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from stable_diffusion_amd import FrozenCLIPTextEmbedderHIP, SearcherHIP, vision  # noqa: E402
+
+
+def load_text_encoder(a):
+    sd = torch.load(a.text_weights, map_location='cpu')
+    sd = sd.get('state_dict', sd)
+    if 'text_projection' in sd or 'token_embedding.weight' in sd:
+        sd = vision.openai_clip_text_to_transformers(sd)
+    sd = {k[len('transformer.'):] if k.startswith('transformer.') else k: v for k, v in sd.items()}
+    W = sd['text_model.embeddings.token_embedding.weight'].shape[1]
+    layers = 1 + max(int(k.split('.')[3]) for k in sd if k.startswith('text_model.encoder.layers.'))
+    tc = dict(vocab_size=sd['text_model.embeddings.token_embedding.weight'].shape[0], hidden_size=W,
+              intermediate_size=sd['text_model.encoder.layers.0.mlp.fc1.weight'].shape[0], num_hidden_layers=layers,
+              num_attention_heads=max(1, W // 64), max_position_embeddings=sd['text_model.embeddings.position_embedding.weight'].shape[0],
+              projection_dim=sd['text_projection.weight'].shape[0])
+    tok = object()
+    if a.tokenizer:
+        from transformers import CLIPTokenizer
+        tok = CLIPTokenizer.from_pretrained(a.tokenizer)
+    m = FrozenCLIPTextEmbedderHIP(text_config=tc, tokenizer=tok, hip_precision=a.hip_precision)
+    m.load_state_dict({'transformer.' + k: v.float() for k, v in sd.items() if not k.endswith('position_ids')}, strict=False)
+    return m.cuda()
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument('--database', required=True)
+    ap.add_argument('--knn', type=int, default=10)
+    ap.add_argument('--prompt', action='append')
+    ap.add_argument('--from-file')
+    ap.add_argument('--ids-file')
+    ap.add_argument('--queries')
+    ap.add_argument('--text-weights')
+    ap.add_argument('--tokenizer')
+    ap.add_argument('--hip-precision', default='mixed', choices=['mixed', 'full'])
+    ap.add_argument('--out')
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit('knn_cond.py needs the GPU: the text encoder and the search have no CPU path')
+    if a.queries:
+        q = np.load(a.queries) if a.queries.endswith('.npy') else torch.load(a.queries, map_location='cpu')
+        c = torch.as_tensor(q, dtype=torch.float32).reshape(len(q), 1, -1).cuda()
+    else:
+        if not a.text_weights:
+            raise SystemExit('give --text-weights (the text encoder checkpoint) or --queries (ready query vectors)')
+        enc = load_text_encoder(a)
+        if a.ids_file:
+            ids = torch.tensor([[int(t) for t in line.split()] for line in open(a.ids_file) if line.strip()], dtype=torch.int64)
+            c = enc.encode_ids(ids.cuda())[:, None]
+        else:
+            prompts = list(a.prompt or [])
+            if a.from_file:
+                prompts += [line.rstrip('\n') for line in open(a.from_file) if line.strip()]
+            if not prompts:
+                raise SystemExit('give --prompt, --from-file or --ids-file')
+            if not a.tokenizer:
+                raise SystemExit('prompts need --tokenizer (a local CLIPTokenizer directory); --ids-file takes token ids instead')
+            c = enc.encode(prompts)                        # knn2img.py: c = clip_text_encoder.encode(prompts)
+    searcher = SearcherHIP(a.database)
+    cond, idx, score = searcher.condition(c, a.knn, return_neighbours=True)      # knn2img.py: searcher(c, opt.knn) + torch.cat([c, nn], dim=1)
+    idx, score = idx.cpu().numpy(), score.cpu().numpy()
+    for b in range(idx.shape[0]):
+        print(f'sample {b}:')
+        for j in range(idx.shape[1]):
+            print(f'  {j:2d}  row {idx[b, j]:9d}  img_id {searcher.img_id[idx[b, j]]}  cosine {score[b, j]:.6f}')
+    print(f'c: {tuple(cond.shape)} {cond.dtype} on {cond.device}')
+    if a.out:
+        torch.save({'c': cond.cpu(), 'nns': torch.from_numpy(idx.astype(np.int64)), 'scores': torch.from_numpy(score),
+                    'img_ids': torch.from_numpy(np.asarray(searcher.img_id[idx]).astype(np.int64)),
+                    'patch_coords': torch.from_numpy(np.asarray(searcher.patch_coords[idx]))}, a.out)
+
+
+if __name__ == '__main__':
+    main()
