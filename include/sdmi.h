@@ -485,6 +485,16 @@ int sdmi_k_igemm(const sdmi_igemm_desc* d, void* stream);
 int sdmi_k_igemm_tail(const sdmi_igemm_desc* d, const void* t0, const void* t1, const void* t2, int tail_c, int tail_ld, const void* tail_w,
                       int tail_kt, void* stream);
 int sdmi_k_tail_split_range(int nkt, int nsplit, int split, int* begin, int* end);
+/* conv3x3(nearest x2 (a)) as the four 2x2 "phase" convs of ONE launch (csrc/igemm_kernel.h KIND_2X2): output pixel
+ * (2i + a, 2j + c) of the upsampled map sees only source rows {i - 1 + a, i + a} and columns {j - 1 + c, j + c}, so each parity class is a 2x2
+ * conv on the source map with summed taps -- 4 / 9 of the MACs.  `d` describes the reference op exactly as for sdmi_k_igemm (ksize 3, stride 1,
+ * up 1, Hout = 2 Hin, Wout = 2 Win, one source of c0 % 64 == 0 channels, mode 0, no residual, splitk 0 or 1, tile -1 or a generic tile) except that
+ * d->w = the weights sdmi_k_up_phase_weights derived: fp16 [4 phases = 2 a + c][N][4 c0], k' = ((ch / 64) * 4 + 2 dy + dx) * 64 + ch % 64.
+ * sdmi_k_up_phase_weights(w_packed = sdmi_k_pack_conv_weight's fp16 [N][9 Cin], dst, N, Cin): the 1, 2 or 4 taps of the 3x3 window that fall on
+ * one source pixel are added in fp32 in (ky, kx) order and rounded once to fp16.
+ * Entry points beside sdmi_k_igemm rather than new sdmi_igemm_desc fields: the struct layout and SDMI_ABI_VERSION stay as they are. */
+int sdmi_k_igemm_up_phase(const sdmi_igemm_desc* d, void* stream);
+int sdmi_k_up_phase_weights(const void* w_packed_f16, void* dst_f16, int N, int Cin, void* stream);
 /* GEGLU -> FF-out -> proj_out of a SpatialTransformer as ONE launch (ABI 12; csrc/rowchain.hip; ldm/modules/attention.py:58-64,214,
  * 258-261): out = residual + proj_out(t + FF(norm3(t))) for C = 320 channels, a workgroup per 32 token rows.
  * proj_out: the split-fp16 1x1 descriptor of the last GEMM (split16 = 1, c0 = N = C, w = sdmi_k_pack_split3, bias, residual, out_f32,

@@ -169,6 +169,8 @@ _SIGS = {
     'sdmi_k_igemm': (C.c_int, [C.POINTER(IGemmDesc), c_ptr]),
     'sdmi_k_igemm_tail': (C.c_int, [C.POINTER(IGemmDesc), c_ptr, c_ptr, c_ptr, C.c_int, C.c_int, c_ptr, C.c_int, c_ptr]),
     'sdmi_k_tail_split_range': (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    'sdmi_k_igemm_up_phase': (C.c_int, [C.POINTER(IGemmDesc), c_ptr]),
+    'sdmi_k_up_phase_weights': (C.c_int, [c_ptr, c_ptr, C.c_int, C.c_int, c_ptr]),
     'sdmi_tune_lookup': (C.c_int, [C.c_int] * 9 + [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     'sdmi_unet_skip_fold_plan': (C.c_int, [c_ptr, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int]),
     'sdmi_k_ff_tail': (C.c_int, [C.POINTER(IGemmDesc), c_ptr, c_ptr, C.c_float, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),

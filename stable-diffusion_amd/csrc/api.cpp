@@ -534,6 +534,20 @@ int sdmi_k_igemm_tail(const sdmi_igemm_desc* d, const void* t0, const void* t1, 
   IGemmTune t; t.tile = d->tile; t.dma = d->dma;
   return launch_igemm(p, t, (hipStream_t)stream);
 }
+int sdmi_k_igemm_up_phase(const sdmi_igemm_desc* d, void* stream) {
+  SDMI_CHECK(d, "null descriptor");
+  IGemmParams p = IGemmParams();
+  if (igemm_params_of(d, p)) return -1;
+  SDMI_CHECK(p.ksize == 3 && p.up == 1 && p.stride == 1 && p.Hout == 2 * p.Hin && p.Wout == 2 * p.Win && p.c1 == 0 && p.c2 == 0 && !p.split16,
+             "up_phase: the descriptor is the reference op, a 3x3 stride-1 conv of one nearest-x2 upsampled source (Hout = 2 Hin, Wout = 2 Win)");
+  IGemmParams q = up_phase_of(p, p.w);
+  q.splitk = d->splitk;
+  IGemmTune t; t.tile = d->tile; t.dma = d->dma;
+  return launch_igemm(q, t, (hipStream_t)stream);
+}
+int sdmi_k_up_phase_weights(const void* w_packed, void* dst, int N, int Cin, void* stream) {
+  return launch_up_phase_weights((const f16*)w_packed, (f16*)dst, N, Cin, (hipStream_t)stream);
+}
 int sdmi_k_tail_split_range(int nkt, int nsplit, int split, int* begin, int* end) {
   SDMI_CHECK(begin && end && nkt >= 0 && nsplit >= 1 && split >= 0 && split < nsplit, "bad arguments");
   tail_split_range(nkt, nsplit, split, begin, end);

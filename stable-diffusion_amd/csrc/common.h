@@ -279,6 +279,15 @@ struct IGemmTune {        // runtime knobs (tests sweep them; the executor takes
 int launch_igemm(const IGemmParams& p, const IGemmTune& tune, hipStream_t stream);
 // host only: will launch_igemm run this auto-configured 3x3 conv (with the tail fields it carries) on a halo-staged tile?  (igemm.hip)
 bool igemm_plans_halo(const IGemmParams& p);
+// host only: will the executor run this Upsample conv (`p` = its KIND_3X3_UP launch) as the four 2x2 phase convs of one ksize = 2 launch?  (igemm.hip)
+bool igemm_plans_up_phase(const IGemmParams& p);
+// ... and the IGemmParams of that launch: rows = the SOURCE pixels of one phase (Hout x Wout = Hin x Win, M = B Hin Win), K = 4 Cin, w = the
+// derived [4][N][4 Cin] weights (launch_up_phase_weights); bias, outputs (4 M rows of pitch ldo) and statistics targets as they were
+static inline IGemmParams up_phase_of(const IGemmParams& p, const f16* w_phase) {
+  IGemmParams q = p;
+  q.ksize = 2; q.Hout = p.Hin; q.Wout = p.Win; q.M = p.B * p.Hin * p.Win; q.K = 4 * p.c0; q.w = w_phase; q.splitk = 0;      // (splitk 0: the table's tile; the launcher runs it unsplit)
+  return q;
+}
 // host only: the tuning table's (tile, split-K) of a key; kt = K of a 1x1 tail (tried first, then the plain conv's entry).  0 found, 1 no entry
 int tune_lookup(int M, int N, int K, int ksize, int stride, int up, int mode, int splitk_req, int kt, int* tile, int* splitk);
 // fp16 range guard (range.hip, debug): scan an fp16 activation buffer a launch just wrote; see SDMI_CHECK_RANGE
@@ -519,6 +528,8 @@ int launch_pack_split3(const float* w, f16* dst, int N, int K, hipStream_t s);
 // 32 (mod 64) channels 32 wide.  The same bytes as launch_pack_conv_weight when every source is a multiple of 64.
 int launch_pack_conv_weight_src(const float* w_oihw, f16* dst, int O, int I, int KH, int KW, int c0, int c1, int c2, hipStream_t s);
 int launch_pack_conv_split3(const float* w, f16* dst, int O, int I, int KH, int KW, hipStream_t s);
+// packed 3x3 weights [N][9 Cin] -> the weights [4][N][4 Cin] of the four 2x2 phase convs of conv3x3(nearest x2 (x)) (small.hip; Cin % 64 == 0)
+int launch_up_phase_weights(const f16* wp, f16* dst, int N, int Cin, hipStream_t s);
 int launch_pack_geglu(const float* w, const float* bias, f16* wdst, float* bdst, int N, int K, hipStream_t s);
 int launch_pack_conv_out(const float* w_oihw, float* dst, int O, int I, hipStream_t s);   // -> [O][3][3][I] fp32
 

@@ -539,6 +539,14 @@ class Tuner {
     }
     return "tune_gfx950.txt";
   }
+  // The rows of the 2x2 phase kind (key ksize 2) live in a file of their own beside the table -- tune_up_phase_gfx950.txt next to tune_gfx950.txt,
+  // <path>.up_phase for any other table path: the main table keeps exactly the key codes it had (1, 3, 11, 13).
+  static std::string phase_path_of(const std::string& table_path) {
+    static const std::string base = "tune_gfx950.txt";
+    if (table_path.size() >= base.size() && table_path.compare(table_path.size() - base.size(), base.size(), base) == 0)
+      return table_path.substr(0, table_path.size() - base.size()) + "tune_up_phase_gfx950.txt";
+    return table_path + ".up_phase";
+  }
   void load_file(const std::string& path) {
     FILE* f = fopen(path.c_str(), "r");
     if (!f) return;
@@ -559,6 +567,7 @@ class Tuner {
     loaded = true;
     if (env_int("SDMI_TUNE_DISABLE", 0)) return;
     load_file(default_path());
+    load_file(phase_path_of(default_path()));
   }
   // the entry of a key: a conv with a 1x1 tail first tries the key that carries the tail's K, then the plain conv's entry
   std::map<TuneKey, TuneChoice>::const_iterator find_entry(TuneKey k) const {
@@ -597,13 +606,13 @@ static std::vector<TuneChoice> tune_candidates(const IGemmParams& p, bool can_sp
     for (int sk : splits) {
       if ((sk == 5 || sk == 10) && !tile_is_halo(t)) continue;
       if (sk > 1) {
-        if (p.splitk != 0 || !can_split) break;                        // caller pinned the split
+        if (p.splitk != 0 || !can_split || p.ksize == 2) break;        // caller pinned the split (the 2x2 phase convs run unsplit)
         if (nkt / sk < 4) break;                                       // >= 4 k-tiles per split
         if (tile_is_halo(t) && (nkt / 9) % sk != 0) continue;          // halo tiles split at 64-channel chunk granularity
         if (blocks * (sk / 2 + 1) > 1536) break;                       // already plenty of blocks one step earlier
         if (splitk_ws_need(p, c.bm, c.bn, sk) > p.splitk_ws_floats) break;
       }
-      if (blocks * sk < 48 && sk < 16 && nkt / (sk * 2) >= 4 && can_split && p.splitk == 0) continue;   // hopelessly few blocks
+      if (blocks * sk < 48 && sk < 16 && nkt / (sk * 2) >= 4 && can_split && p.splitk == 0 && p.ksize != 2) continue;   // hopelessly few blocks
       out.push_back({t, p.splitk > 1 ? p.splitk : sk, 0.0});
       if (p.splitk != 0) break;
     }
@@ -663,17 +672,26 @@ int tune_end(const char* path, int* n_keys) {
   if (n_keys) *n_keys = (int)g_tuner.stats.size();
   ++g_tune_generation;
   const std::string out = (path && *path) ? std::string(path) : Tuner::default_path();
-  FILE* f = fopen(out.c_str(), "w");
-  if (!f) return fail("cannot write the tuning table to " + out);
-  fprintf(f, "# libsdmi igemm tuning table (gfx950), measured in situ by tools/tune.py -- M N K ksize stride up mode splitk_req tile splitk us\n");
-  for (auto& kv : g_tuner.table) {
-    const TuneKey& k = kv.first;
-    fprintf(f, "%d %d %d %d %d %d %d %d %d %d %.2f", k.M, k.N, k.K, k.ksize, k.stride, k.up, k.mode, k.splitk_req, kv.second.tile,
-            kv.second.splitk, kv.second.us);
-    if (k.kt) fprintf(f, " %d", k.kt);
-    fprintf(f, "\n");
+  // two files: the table, and the rows of the 2x2 phase kind (ksize 2) beside it (Tuner::phase_path_of; written only when there are any)
+  bool any_phase = false;
+  for (auto& kv : g_tuner.table) any_phase = any_phase || kv.first.ksize == 2;
+  for (int which = 0; which < (any_phase ? 2 : 1); ++which) {
+    const std::string path_w = which ? Tuner::phase_path_of(out) : out;
+    FILE* f = fopen(path_w.c_str(), "w");
+    if (!f) return fail("cannot write the tuning table to " + path_w);
+    fputs(which ? "# libsdmi igemm tuning table (gfx950), the 2x2 phase convs of the Upsample convs (ksize 2: M = rows of one phase, K = 4 Cin; compared with "
+                       "the site's up = 1 row of the main table), measured in situ by tools/tune.py -- M N K ksize stride up mode splitk_req tile splitk us\n"
+                     : "# libsdmi igemm tuning table (gfx950), measured in situ by tools/tune.py -- M N K ksize stride up mode splitk_req tile splitk us\n", f);
+    for (auto& kv : g_tuner.table) {
+      const TuneKey& k = kv.first;
+      if ((k.ksize == 2) != (which == 1)) continue;
+      fprintf(f, "%d %d %d %d %d %d %d %d %d %d %.2f", k.M, k.N, k.K, k.ksize, k.stride, k.up, k.mode, k.splitk_req, kv.second.tile,
+              kv.second.splitk, kv.second.us);
+      if (k.kt) fprintf(f, " %d", k.kt);
+      fprintf(f, "\n");
+    }
+    fclose(f);
   }
-  fclose(f);
   return 0;
 }
 // per-candidate timings of the last collection as text lines (for profiles/): key | tile splitk us n
@@ -725,9 +743,39 @@ bool igemm_plans_halo(const IGemmParams& p) {
          (sk == 1 || (can_split && splitk_ws_need(p, kTiles[tt].bm, kTiles[tt].bn, sk) <= p.splitk_ws_floats && nkt / sk >= 4 && (nkt / 9) % sk == 0));
 }
 
+// Will the executor run this Upsample conv as the four 2x2 phase convs (KIND_2X2, one launch)?  `p` = the KIND_3X3_UP launch it issues otherwise.
+// (Host only.)  Yes where the tuning table has a phase row (ksize 2, M = the rows of one phase, K = 4 Cin, unsplit) that beats the up = 1 row
+// of the same site -- the sites that need split-K to win (weight streaming: the phase weights are 16 / 9 of the bytes) keep today's kernel.
+// SDMI_UP_PHASE (read per call: the tests and the A/B flip it): 0 = never, 1 = by the table (default), 2 = wherever the kernel can run (tests).
+// During a tuning collection: only in a run restricted to the phase family (SDMI_TUNE_ONLY_KSIZE=2), so that its rows get measured in situ.
+bool igemm_plans_up_phase(const IGemmParams& p) {
+  static const int env_tile = env_int("SDMI_IGEMM_TILE", -1);
+  static const int only_ksize = env_int("SDMI_TUNE_ONLY_KSIZE", -1);
+  const int knob = env_int("SDMI_UP_PHASE", 1);
+  if (!knob || p.ksize != 3 || !p.up || p.stride != 1 || p.split16 || p.c1 || p.c2 || p.c0 % BK || p.mode != EPI_PLAIN || p.residual ||
+      p.splitk > 1 || (env_tile >= 0 && tile_is_halo(env_tile)) || (int64_t)32 * p.N * p.c0 >= ((int64_t)1 << 31))
+    return false;
+  std::lock_guard<std::mutex> lk(g_tuner.mu);
+  g_tuner.ensure_loaded();
+  if (g_tuner.collecting) return only_ksize == 2;
+  if (knob == 2) return true;
+  const auto ph = g_tuner.find_entry(TuneKey{p.B * p.Hin * p.Win, p.N, 4 * p.c0, 2, 1, 1, p.mode, 0, 0});
+  const auto old = g_tuner.find_entry(TuneKey{p.M, p.N, 9 * p.c0, 3, 1, 1, p.mode, 0, 0});
+  // (a tie is not a win: the in-situ medians of one shape move by a percent or so between collection runs, so the phase row has to be 3 % ahead)
+  return ph != g_tuner.table.end() && old != g_tuner.table.end() && ph->second.splitk == 1 && !tile_is_halo(ph->second.tile) && ph->second.us > 0.0 &&
+         ph->second.us < 0.97 * old->second.us;
+}
+
 int launch_igemm(const IGemmParams& p, const IGemmTune& tune, hipStream_t stream) {
   SDMI_CHECK(p.M > 0 && p.N > 0 && p.K > 0, "empty GEMM");
-  SDMI_CHECK(p.ksize == 1 || p.ksize == 3, "ksize must be 1 or 3");
+  SDMI_CHECK(p.ksize == 1 || p.ksize == 3 || p.ksize == 2, "ksize must be 1 or 3 (or 2: the four 2x2 phase convs of an upsample conv)");
+  const bool phase = p.ksize == 2;
+  if (phase)      // KIND_2X2 (igemm_dev.h): rows = source pixels, w = the derived [4][N][4 Cin] weights (launch_up_phase_weights), outputs = 4 M rows
+    SDMI_CHECK(p.up == 1 && p.stride == 1 && p.Hout == p.Hin && p.Wout == p.Win && p.mode == EPI_PLAIN && p.c1 == 0 && p.c2 == 0 && p.c0 % BK == 0 &&
+                   !p.split16 && !p.residual && !p.ln_out && !p.lnp_out && !p.f16_scale && !p.lnf_part && !p.pgn_out && !p.tail_kt && p.splitk <= 1 &&
+                   (int64_t)4 * p.N * p.K * 2 < ((int64_t)1 << 31),
+               "upsample phase convs: nearest x2 of one source of whole 64-channel chunks (Hout x Wout = the SOURCE map), plain epilogue without residual / "
+               "LayerNorm / tail, unsplit");
   const int Cin = p.c0 + p.c1 + p.c2;
   SDMI_CHECK(p.K == p.ksize * p.ksize * Cin, "K != ksize^2 * (c0 + c1 + c2)");
   // (a source of 32 (mod 64) channels ends in a half k-tile; the split-fp16 dense family checks its own K)
@@ -739,7 +787,7 @@ int launch_igemm(const IGemmParams& p, const IGemmTune& tune, hipStream_t stream
   SDMI_CHECK(p.c1 == 0 || p.a1 != nullptr, "second A source missing");
   SDMI_CHECK(p.c2 == 0 || (p.a2 != nullptr && p.lda2 % 8 == 0), "third A source missing");
   SDMI_CHECK((p.c1 == 0 || p.lda1 == p.lda0) && (p.c2 == 0 || p.lda2 == p.lda0), "all A sources must share one row pitch");
-  SDMI_CHECK(!p.up || (p.ksize == 3 && p.stride == 1), "upsample folding needs a 3x3 stride-1 conv");
+  SDMI_CHECK(!p.up || ((p.ksize == 3 || phase) && p.stride == 1), "upsample folding needs a 3x3 stride-1 conv");
   if (p.mode == EPI_GEGLU) SDMI_CHECK(p.N % 64 == 0 && p.out_f16 != nullptr, "GEGLU needs N % 64 == 0 and an fp16 output");
   if (p.ln_out)
     SDMI_CHECK(p.mode == EPI_PLAIN && p.out_f32 && p.ldo == p.N && p.N % 4 == 0 && p.N <= 2560 && p.ln_gamma && p.ln_beta,
@@ -776,7 +824,7 @@ int launch_igemm(const IGemmParams& p, const IGemmTune& tune, hipStream_t stream
                                (p.residual == nullptr || p.ldr % 4 == 0);
   const bool can_split_heads = p.mode == EPI_HEADS && p.splitk_ws && p.dh % 4 == 0 && p.segC % 4 == 0;
   const bool can_split = can_split_plain || can_split_heads;
-  if (env_split >= 0 && splitk == 0) splitk = env_split;
+  if (env_split >= 0 && splitk == 0 && !phase) splitk = env_split;
 
   // ---- (tile, split-K): explicit request > tuning table / collection run > heuristic ------------------------------
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -811,7 +859,7 @@ int launch_igemm(const IGemmParams& p, const IGemmTune& tune, hipStream_t stream
                                           : (sk == 1 || (ws_ok && nkt / sk >= 4 && (halo || (sk != 5 && sk != 10)) &&
                                                          (!halo || (nkt / 9) % sk == 0)));
         if (split_ok && (p.mode != EPI_GEGLU || tile_tn_even(tt)) && (!halo || halo_supported(p, kTiles[tt].bm)) &&
-            (!p.split16 || split16_tile_supported(tt))) {
+            (!p.split16 || split16_tile_supported(tt)) && (!phase || sk == 1)) {
           tile = tt; splitk = sk;
         }
       }
@@ -834,6 +882,10 @@ int launch_igemm(const IGemmParams& p, const IGemmTune& tune, hipStream_t stream
     // does not divide this shape gives way to the 64 x 64 one (3 stages), which does (checked above)
     const int hw = p.Hout * p.Wout;
     if (p.M % kTiles[tile].bm || p.N % kTiles[tile].bn || hw % kTiles[tile].bm || (p.split16 && !split16_tile_supported(tile))) tile = 5;
+  }
+  if (phase) {        // the phase index takes the split's place in the tile numbering: unsplit, generic tiles only
+    SDMI_CHECK(!tile_is_halo(tile) && splitk <= 1, "upsample phase convs run unsplit on the generic tiles");
+    splitk = 1;
   }
   if (splitk <= 0) {  // auto: enough blocks to keep bytes in flight on all 256 CUs, >= 8 k-tiles per split
     splitk = 1;
@@ -901,7 +953,7 @@ int launch_igemm(const IGemmParams& p, const IGemmTune& tune, hipStream_t stream
       for (int sg = 0; sg < p.N / p.segC; ++sg)
         if (range_scan(what, p.seg_dst[sg], p.seg_kind[sg] == 0 ? (int64_t)p.M * p.segC : (int64_t)p.B * p.segC * p.ntok_pad, stream)) return -1;
     } else if (p.out_f16) {
-      if (range_scan(what, p.out_f16, (int64_t)(p.M - 1) * p.ldo + (p.mode == EPI_GEGLU ? p.N / 2 : p.N), stream)) return -1;
+      if (range_scan(what, p.out_f16, (int64_t)((phase ? 4 : 1) * (int64_t)p.M - 1) * p.ldo + (p.mode == EPI_GEGLU ? p.N / 2 : p.N), stream)) return -1;
     }
     if (p.ln_out && range_scan("LayerNorm output", p.ln_out, (int64_t)p.M * p.N, stream)) return -1;
   }

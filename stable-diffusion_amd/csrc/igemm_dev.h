@@ -87,7 +87,9 @@ __device__ __forceinline__ void wait_vmcnt() {
 
 // Kernel kinds: the gather of the implicit A matrix differs, so each is its own instantiation (no runtime branches and no
 // dead per-row state in the k-loop).
-enum : int { KIND_1X1 = 0, KIND_3X3 = 1, KIND_3X3_UP = 2 };
+// KIND_2X2: the four parity classes ("phases") of conv3x3(nearest x2 (x)) as 2x2 convolutions on the SOURCE map, all four in one launch
+// (output pixel (2i + a, 2j + c) sees source rows {i - 1 + a, i + a} and columns {j - 1 + c, j + c}: 4 / 9 of the MACs); IGemmParams::ksize == 2.
+enum : int { KIND_1X1 = 0, KIND_3X3 = 1, KIND_3X3_UP = 2, KIND_2X2 = 3 };
 
 // floor(m / d) for 0 <= m, m * d < 2^40, with magic = ceil(2^40 / d) (host computed): the per-row (batch, y, x) split of
 // the prologue without the ~40-instruction integer division sequences
@@ -180,11 +182,13 @@ __device__ __forceinline__ float sum8_dpp(float v) {
 // wave's TM x TN MFMA tiles -> bias / time-embedding row vector / residual / fp32 + fp16 (+ split-fp16 low half) stores,
 // GEGLU, per-head q / k / v^T scatter, split-K slabs, GroupNorm statistics.  `smem` = the block's LDS (free at this point:
 // every LDS-DMA of the block has landed and is no longer read), LDS_BYTES its size.
-template <int BM, int BN, int WARPS_M, int WARPS_N, int LDS_BYTES>
+// PHASE (KIND_2X2 launches, plain mode, unsplit): row m of the launch is SOURCE pixel (b, i, j) (Hout x Wout = the source map) and `phase` =
+// 2 a + c its parity class: the output row is pixel (b, 2i + a, 2j + c) of the 2 Hout x 2 Wout map.  Only the output addresses change.
+template <int BM, int BN, int WARPS_M, int WARPS_N, int LDS_BYTES, bool PHASE = false>
 __device__ __forceinline__ void igemm_epilogue(const IGemmParams& p_arg, f32x16 (&acc)[BM / WARPS_M / 32][BN / WARPS_N / 32],
                                                const int m0, const int n0, const int split, const int tile_m,
                                                const int tile_n, unsigned char* smem, const float lnf_mean = 0.f,
-                                               const float lnf_rstd = 1.f) {
+                                               const float lnf_rstd = 1.f, const int phase = 0) {
 #ifdef SDMI_IGEMM_TIMING
   IGemmParams p = p_arg;                                  // timing build: epilogue ablations (wrong results, time only)
   if (p.dbg_abl & 1) p.residual = nullptr;
@@ -202,6 +206,16 @@ __device__ __forceinline__ void igemm_epilogue(const IGemmParams& p_arg, f32x16 
   const int wm = wave / WARPS_N, wn = wave - wm * WARPS_N;
   const int l31 = lane & 31, lg = lane >> 5;
   const int HWout = p.Hout * p.Wout;
+  auto orow = [&](int m) -> size_t {                     // output row of launch row m < M (the identity but for PHASE)
+    if constexpr (PHASE) {
+      const int b = fast_div_hw(m, p.magic_hw);
+      const int rem = m - b * HWout;
+      const int i = fast_div(rem, p.magic_w), j = rem - i * p.Wout;
+      return ((size_t)(b * 2 * p.Hout + 2 * i + (phase >> 1)) * (size_t)(2 * p.Wout) + (size_t)(2 * j + (phase & 1)));
+    } else {
+      return (size_t)m;
+    }
+  };
   // C/D layout of 32x32 MFMA: col = lane & 31, row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)
   const int mw = m0 + wm * WTM, nw = n0 + wn * WTN;
   // Full interior tiles take a branch-free path: all residual loads of a 32-row slab are issued back to back
@@ -355,7 +369,7 @@ __device__ __forceinline__ void igemm_epilogue(const IGemmParams& p_arg, f32x16 
           const int row = q * RPI + rl;
           float* const lp = wl + row * LSTR + c4;
           const f32x4 v = *(const f32x4*)lp + colv + resv[q];
-          const size_t ro = (size_t)(mw + i * 32 + row) * p.ldo + nw + c4;
+          const size_t ro = orow(mw + i * 32 + row) * p.ldo + nw + c4;
           if (p.out_f32) SDMI_ST_F32X4(p.out_f32, ro, v);
           const f32x4 vs = v * g4;                         // (g4 = 1 without a scale: exact)
           const f16x4 h = {(f16)vs[0], (f16)vs[1], (f16)vs[2], (f16)vs[3]};
@@ -413,7 +427,7 @@ __device__ __forceinline__ void igemm_epilogue(const IGemmParams& p_arg, f32x16 
           }
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
-            const size_t ro = (size_t)(mw + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lg) * p.ldo + nw + l31;
+            const size_t ro = orow(mw + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lg) * p.ldo + nw + l31;
 #pragma unroll
             for (int j = 0; j < TN; ++j) {
               const float v = acc[i][j][r] + colv[j] + resv[r][j];
@@ -439,6 +453,7 @@ __device__ __forceinline__ void igemm_epilogue(const IGemmParams& p_arg, f32x16 
           const int m = mw + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lg;
           if (m >= p.M) continue;
           const float* rv = (!atomic && p.rowvec) ? (p.rowvec + (size_t)(m / HWout) * p.ld_rowvec) : nullptr;
+          const size_t om = orow(m) * p.ldo;
 #pragma unroll
           for (int j = 0; j < TN; ++j) {
             const int n = nw + j * 32 + l31;
@@ -451,9 +466,9 @@ __device__ __forceinline__ void igemm_epilogue(const IGemmParams& p_arg, f32x16 
               if (rv) v += rv[n];
               if (p.residual) v += p.residual[(size_t)m * p.ldr + n];
               acc[i][j][r] = v;
-              if (p.out_f32) p.out_f32[(size_t)m * p.ldo + n] = v;
-              if (p.out_f16) p.out_f16[(size_t)m * p.ldo + n] = (f16)v;
-              if (p.out_lo) p.out_lo[(size_t)m * p.ldo + n] = (f16)(v - (float)(f16)v);
+              if (p.out_f32) p.out_f32[om + n] = v;
+              if (p.out_f16) p.out_f16[om + n] = (f16)v;
+              if (p.out_lo) p.out_lo[om + n] = (f16)(v - (float)(f16)v);
             }
           }
         }

@@ -23,7 +23,10 @@ __global__ void __launch_bounds__(WARPS_M* WARPS_N * 64) igemm_kernel(const IGem
   // stub, and silently drops the stub of an instantiation whose body it cannot type-check -- so the body is device-only.
 #if defined(__HIP_DEVICE_COMPILE__)
   constexpr bool UP = KIND == KIND_3X3_UP;
-  constexpr bool K3 = KIND != KIND_1X1;
+  constexpr bool K2 = KIND == KIND_2X2;          // the four 2x2 phase convs of an upsample conv: 4x the tiles, the phase from the tile index
+  constexpr bool K3 = KIND != KIND_1X1;          // a conv with taps (3x3, or the 2x2 of a phase)
+  constexpr int TW = K2 ? 2 : 3;                 // taps per window row
+  static_assert(!K2 || (DMA && !HALF), "the 2x2 phase kind: LDS-DMA, whole 64-channel chunks");
   constexpr int NT = WARPS_M * WARPS_N * 64;
   constexpr int RPP = NT / 8;  // rows per load pass (8 chunks of 16 B per 128-B row)
   constexpr int A_PASSES = BM / RPP;
@@ -52,7 +55,8 @@ __global__ void __launch_bounds__(WARPS_M* WARPS_N * 64) igemm_kernel(const IGem
   else { tile_n = tmn / tiles_m; tile_m = tmn - tile_n * tiles_m; }
   const int m0 = tile_m * BM, n0 = tile_n * BN;
   const int nkt = HALF ? p.nkt : p.K / BK;       // (HALF: tiles, not K / 64 -- a source of 32 (mod 64) channels ends in a half tile)
-  const int kt_begin = split * kt_per_split;
+  // (K2: launches are unsplit, and `split` numbers the parity class instead -- phase = 2 a + c for output pixels (2i + a, 2j + c))
+  const int kt_begin = K2 ? 0 : split * kt_per_split;
   const int kt_end = min(nkt, kt_begin + kt_per_split);
   if (kt_begin >= kt_end) return;
 
@@ -81,7 +85,10 @@ __global__ void __launch_bounds__(WARPS_M* WARPS_N * 64) igemm_kernel(const IGem
   // compute a copy of it that the epilogue never stores, which keeps every load unconditional and in bounds.
   const int HWout = p.Hout * p.Wout;
   const int pad = K3 ? p.pad : 0;                   // 1, or 0 for the VAE encoder's (0,1,0,1)-padded stride-2 conv
-  constexpr int ntap = K3 ? 9 : 1;
+  // K2: row m is SOURCE pixel (i, j) (Hout x Wout = Hin x Win); phase (a, c) reads source rows {i - 1 + a, i + a} and columns {j - 1 + c, j + c}:
+  // a 2x2 conv with zero pad top / left = 1 - a / 1 - c (bottom / right = a / c), affine in the tap like the plain 3x3
+  const int pad_y = K2 ? 1 - (split >> 1) : pad, pad_x = K2 ? 1 - (split & 1) : pad;
+  constexpr int ntap = K3 ? TW * TW : 1;
   const int ld = p.lda0;                            // all sources share the row pitch (checked by the launcher)
   int a_off[A_PASSES];                              // byte offsets (< 2^31, checked by the launcher)
   unsigned a_mask[K3 ? A_PASSES : 1];
@@ -115,8 +122,8 @@ __global__ void __launch_bounds__(WARPS_M* WARPS_N * 64) igemm_kernel(const IGem
       if constexpr (K3) {
         unsigned mk = 0;
 #pragma unroll
-        for (int t = 0; t < 9; ++t) {
-          const int iy = cy + t / 3 - pad, ix = cx + t % 3 - pad;
+        for (int t = 0; t < ntap; ++t) {
+          const int iy = cy + t / TW - pad_y, ix = cx + t % TW - pad_x;
           if (iy >= 0 && iy < p.Hin && ix >= 0 && ix < p.Win) mk |= 1u << t;
         }
         a_mask[i] = mk | ((HALF && gch < 4) ? mk << 9 : 0u);       // bits 9..17: the taps of a half k-tile (none for chunk lanes 4..7)
@@ -141,7 +148,7 @@ __global__ void __launch_bounds__(WARPS_M* WARPS_N * 64) igemm_kernel(const IGem
   // where the second / third source begins in them), ld_boff the dense weight columns (bytes): b_soff accumulates the real widths.
   int ld_tap = K3 ? kt_begin % ntap : 0;
   int ld_cin0 = (kt_begin / ntap) * BK;
-  int ld_ky = K3 ? ld_tap / 3 : 0, ld_kx = K3 ? ld_tap - 3 * (ld_tap / 3) : 0;
+  int ld_ky = K3 ? ld_tap / TW : 0, ld_kx = K3 ? ld_tap - TW * (ld_tap / TW) : 0;
   const int pc0 = p.c0, pc1 = p.c1, pc2 = p.c2;
   const int pp0 = (pc0 + BK - 1) & ~(BK - 1), pp01 = pp0 + ((pc1 + BK - 1) & ~(BK - 1));      // (= c0, c0 + c1 without HALF)
   int ld_boff = 0;
@@ -158,10 +165,11 @@ __global__ void __launch_bounds__(WARPS_M* WARPS_N * 64) igemm_kernel(const IGem
   // The A base is moved back by the offset of tap (0, 0) relative to tap (pad, pad), so every tap's soffset is >= 0.
   // Everything the k-loop touches lives in registers (no IGemmParams re-reads: those are scalar memory loads).
   constexpr int OOB = (int)0x80000000;              // >= num_records of every descriptor below
-  const long long a_shift = (K3 && !UP) ? (long long)(pad * p.Win + pad) * ld * 2 : 0;
+  const long long a_shift = (K3 && !UP) ? (long long)(pad_y * p.Win + pad_x) * ld * 2 : 0;
   const char* const srcA0 = (const char*)p.a0 - a_shift; const char* const srcA1 = (const char*)p.a1 - a_shift;
   const char* const srcA2 = (const char*)p.a2 - a_shift;
-  const __amdgpu_buffer_rsrc_t rsrc_w = __builtin_amdgcn_make_buffer_rsrc((void*)p.w, 0, OOB, 0x00020000);
+  const f16* const w_base = K2 ? p.w + (size_t)split * (size_t)p.N * (size_t)p.K : p.w;      // (K2: [4 phases][N][K])
+  const __amdgpu_buffer_rsrc_t rsrc_w = __builtin_amdgcn_make_buffer_rsrc((void*)w_base, 0, OOB, 0x00020000);
   const int pWin = p.Win;
 
   // the scalar part of one k-tile's addresses, captured when the tile is scheduled; the per-pass issues may come later
@@ -184,7 +192,7 @@ __global__ void __launch_bounds__(WARPS_M* WARPS_N * 64) igemm_kernel(const IGem
       if constexpr (HALF) ld_boff += half ? BKH * 2 : BK * 2;
       if constexpr (K3) {
         ++ld_tap;
-        if (++ld_kx == 3) { ld_kx = 0; ++ld_ky; }
+        if (++ld_kx == TW) { ld_kx = 0; ++ld_ky; }
         if (ld_tap == ntap) { ld_tap = 0; ld_ky = 0; ld_kx = 0; ld_cin0 += BK; }
       } else {
         ld_cin0 += BK;
@@ -346,7 +354,8 @@ __global__ void __launch_bounds__(WARPS_M* WARPS_N * 64) igemm_kernel(const IGem
 
   // ---- epilogue ------------------------------------------------------------------------------------
   SDMI_STAMP(dbg_t2);
-  igemm_epilogue<BM, BN, WARPS_M, WARPS_N, NS * STAGE_BYTES>(p, acc, m0, n0, split, tile_m, tile_n, smem, lnf_mean, lnf_rstd);
+  igemm_epilogue<BM, BN, WARPS_M, WARPS_N, NS * STAGE_BYTES, K2>(p, acc, m0, n0, K2 ? 0 : split, tile_m, tile_n, smem, lnf_mean, lnf_rstd,
+                                                                 K2 ? split : 0);
 #ifdef SDMI_IGEMM_TIMING
   if (p.dbg_times && tid == 0) {        // (where a workgroup's time goes; blocks that return early in the epilogue are not stamped)
     long long* d = p.dbg_times + 6 * (size_t)blockIdx.x;      // d[3] = after the output stores (written inside the epilogue)
@@ -375,10 +384,12 @@ int launch_cfg(const IGemmParams& p, bool dma, int splitk, hipStream_t stream) {
   q.magic_hw = div_magic_hw(p.Hout * p.Wout);
   q.magic_w = div_magic(p.Wout);
   for (int t = 0; t < p.gn_n; ++t) q.gn_magic[t] = div_magic(p.gn_cpg[t]);
-  dim3 grid(tiles_m * tiles_n * nsplit), block(WARPS_M * WARPS_N * 64);
+  const bool phase = p.ksize == 2;       // KIND_2X2: M = the rows of ONE phase (B * Hin * Win), four phases in the grid, 4 M output rows
+  if (phase) SDMI_CHECK(!HALF && dma && nsplit == 1, "the 2x2 phase convs run unsplit on the LDS-DMA kernels, whole 64-channel chunks only");
+  dim3 grid(tiles_m * tiles_n * (phase ? 4 : nsplit)), block(WARPS_M * WARPS_N * 64);
   static const int by_shape = env_int("SDMI_PROF_SHAPES", 0);
   std::string pname = std::string("igemm_") + std::to_string(BM) + "x" + std::to_string(BN) + "w" +
-                      std::to_string(WARPS_M * WARPS_N) + "s" + std::to_string(NS) + (HALF ? "h" : "");
+                      std::to_string(WARPS_M * WARPS_N) + "s" + std::to_string(NS) + (HALF ? "h" : "") + (phase ? "_up2x2" : "");
   if (by_shape && prof_enabled())
     pname += "_M" + std::to_string(p.M) + "_N" + std::to_string(p.N) + "_K" + std::to_string(p.K) + "_k" +
              std::to_string(p.ksize) + "_m" + std::to_string(p.mode) + "_s" + std::to_string(nsplit);
@@ -389,11 +400,14 @@ int launch_cfg(const IGemmParams& p, bool dma, int splitk, hipStream_t stream) {
   // run three passes); bytes likewise count the reference op's operands once (one fp16 activation read, one weight read)
   const int k_alg = p.k_alg > 0 ? p.k_alg : p.K;
   const double cin_alg = p.k_alg > 0 ? (double)p.k_alg : (double)(p.c0 + p.c1 + p.c2);
-  ProfScope ps(pname.c_str(), 2.0 * p.M * (double)p.N * k_alg,
-               src_pix * cin_alg * 2.0 + (double)p.N * k_alg * 2.0 + (double)p.M * n_out * out_b +
+  // (phase convs: the reference op is the 3x3 conv on the upsampled map -- 4 M output rows of 9 Cin MACs; executed: 4 M rows of K = 4 Cin)
+  const double m_out = phase ? 4.0 * p.M : (double)p.M;
+  const double k_ref = phase ? 9.0 * cin_alg : (double)k_alg;
+  ProfScope ps(pname.c_str(), 2.0 * m_out * (double)p.N * k_ref,
+               src_pix * cin_alg * 2.0 + (double)p.N * k_ref * 2.0 + m_out * n_out * out_b +
                    (p.residual ? (double)p.M * p.N * 4.0 : 0.0),
-               stream, 2.0 * p.M * (double)p.N * p.K);
-  const int kind = p.ksize == 1 ? KIND_1X1 : (p.up ? KIND_3X3_UP : KIND_3X3);
+               stream, 2.0 * m_out * (double)p.N * p.K);
+  const int kind = p.ksize == 1 ? KIND_1X1 : (phase ? KIND_2X2 : (p.up ? KIND_3X3_UP : KIND_3X3));
 #define SDMI_LAUNCH_KIND(K_)                                                                                        \
   do {                                                                                                              \
     if (dma) SDMI_LAUNCH((igemm_kernel<BM, BN, WARPS_M, WARPS_N, true, NS, K_, HALF>), grid, block, 0, stream, q,   \
@@ -403,7 +417,9 @@ int launch_cfg(const IGemmParams& p, bool dma, int splitk, hipStream_t stream) {
   } while (0)
   if (kind == KIND_1X1) SDMI_LAUNCH_KIND(KIND_1X1);
   else if (kind == KIND_3X3) SDMI_LAUNCH_KIND(KIND_3X3);
-  else SDMI_LAUNCH_KIND(KIND_3X3_UP);
+  else if (kind == KIND_3X3_UP) SDMI_LAUNCH_KIND(KIND_3X3_UP);
+  else if constexpr (!HALF) SDMI_LAUNCH((igemm_kernel<BM, BN, WARPS_M, WARPS_N, true, NS, KIND_2X2, false>), grid, block, 0, stream, q, tiles_m, tiles_n,
+                                        kt_per_split);
 #undef SDMI_LAUNCH_KIND
   SDMI_HIP_OK(hipGetLastError());
   ps.end();

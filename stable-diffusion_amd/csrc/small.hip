@@ -714,6 +714,39 @@ int launch_pack_conv_weight(const float* w, f16* dst, int O, int I, int KH, int 
   SDMI_HIP_OK(hipGetLastError());
   return 0;
 }
+// Weights of the four 2x2 phase convs of conv3x3(nearest x2 (x)) (igemm KIND_2X2), derived from the PACKED fp16 3x3 weights wp[N][9 Cin]:
+// dst[phase = 2 a + c][n][k'], k' = ((i / 64) * 4 + 2 dy + dx) * 64 + i % 64 (the kernel's K order: 64-channel chunk major, tap fastest).  Output pixel
+// (2i + a, 2j + c) reads source row i - 1 + a + dy through the 3x3 rows ky in [dy ? 1 + a : 0, dy ? 2 : a] (columns alike with c, dx): the 1, 2
+// or 4 contributing taps are added in fp32 in (ky, kx) order and rounded once to fp16 (nearest-even).
+__global__ void up_phase_weights_kernel(const f16* wp, f16* dst, int N, int Cin) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int K4 = 4 * Cin;
+  if (idx >= (int64_t)4 * N * K4) return;
+  const int phase = (int)(idx / ((int64_t)N * K4));
+  const int64_t rem = idx - (int64_t)phase * N * K4;
+  const int n = (int)(rem / K4), k = (int)(rem - (int64_t)n * K4);
+  const int chunk = k / 256, tap = (k % 256) / 64, ch = k % 64;
+  const int a = phase >> 1, c = phase & 1, dy = tap >> 1, dx = tap & 1;
+  const int ky0 = dy ? 1 + a : 0, ky1 = dy ? 2 : a, kx0 = dx ? 1 + c : 0, kx1 = dx ? 2 : c;
+  const f16* src = wp + (size_t)n * 9 * Cin + (size_t)chunk * 9 * 64 + ch;
+  float s = 0.f;
+  bool first = true;
+  for (int ky = ky0; ky <= ky1; ++ky)
+    for (int kx = kx0; kx <= kx1; ++kx) {
+      const float v = (float)src[(ky * 3 + kx) * 64];
+      s = first ? v : s + v;
+      first = false;
+    }
+  dst[idx] = (f16)s;
+}
+int launch_up_phase_weights(const f16* wp, f16* dst, int N, int Cin, hipStream_t s) {
+  SDMI_CHECK(wp && dst && N > 0 && Cin > 0 && Cin % 64 == 0, "upsample phase weights: whole 64-channel chunks of packed 3x3 weights");
+  const int64_t total = (int64_t)16 * N * Cin;
+  SDMI_CHECK(total < ((int64_t)1 << 31), "upsample phase weights: too large");
+  SDMI_LAUNCH(up_phase_weights_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, wp, dst, N, Cin);
+  SDMI_HIP_OK(hipGetLastError());
+  return 0;
+}
 // Touch one dword of every 128-byte line of [ptr, ptr + bytes): pulls the range through this XCD's L2 into the Infinity Cache.
 // The loaded values are only kept alive (never stored).  A cache hint: no correctness role.
 __global__ void __launch_bounds__(256) prefetch_lines_kernel(const unsigned* p, long long nlines) {

@@ -335,6 +335,13 @@ int UNet::finalize() {
       }
       return 0;
     })) return -1;
+    // weights of the four 2x2 phase convs of every Upsample conv that may run as them (Fwd::resample; derived from the packed fp16 weights: not
+    // part of the blob, re-derived whenever the weights were set again).  Mixed precision only: the full mode's weights are split-fp16.
+    if (for_each_layer([&](Layer& L) -> int {
+      if (L.kind != L_UP || full() || L.cin % 64 != 0) return 0;
+      if (store_.alloc((void**)&L.w_up_phase, (size_t)16 * L.cout * L.cin * sizeof(f16))) return -1;
+      return launch_up_phase_weights(L.w16[0], L.w_up_phase, L.cout, L.cin, nullptr);
+    })) return -1;
     SDMI_HIP_OK(hipDeviceSynchronize());
     // bias of a conv2 that carries its block's skip convolution as a tail phase (Fwd::res_block): out_layers.3.bias + skip_connection.bias,
     // one fp32 sum per channel (derived from the set weights: not part of the blob)
@@ -872,6 +879,9 @@ struct Fwd : FwdBase {
     IGemmParams p = conv3(x16, C, Hin, Win, Hout, Wout, up ? 1 : 2, up ? 1 : 0, L.w16[0], L.cout);
     p.bias = L.f32[0]; p.out_f32 = out.p; p.ldo = L.cout;
     attach_gn_targets(p, out);
+    // nearest x2 + 3x3 as the four 2x2 phase convs of one launch (igemm KIND_2X2: 4 / 9 of the MACs) where the tuning table says that wins;
+    // its statistics rows are the source pixels of a phase, so a sample must hold a multiple of 32 of those
+    if (up && L.w_up_phase && (p.gn_n == 0 || (Hin * Win) % 32 == 0) && igemm_plans_up_phase(p)) p = up_phase_of(p, L.w_up_phase);
     gemm(p);
     scratch.off = mark;
     return out;

@@ -243,6 +243,7 @@ struct Layer {
   float* w32[1] = {nullptr};
   float* f32[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   float* bias_fold = nullptr;    // L_RES with a skip convolution: out_layers.3.bias + skip_connection.bias (finalize(); Fwd::res_block's folded conv2)
+  f16* w_up_phase = nullptr;     // L_UP, mixed precision, cin % 64 == 0: [4][cout][4 cin] weights of the conv's four 2x2 phase convs (finalize(); Fwd::resample)
   std::vector<TBlock> tb;
 };
 

@@ -160,6 +160,17 @@ int Vae::finalize() {
     if (launch_vq_norms(cb_, cb_norm_, ext_.n_embed, cfg_.embed_dim, nullptr)) return -1;
     SDMI_HIP_OK(hipDeviceSynchronize());
   }
+  // weights of the four 2x2 phase convs of every Upsample conv that may run as them (resample(); derived from the packed fp16 weights: not part
+  // of the blob, re-derived whenever the weights were set again).  Mixed precision only: the full mode's weights are split-fp16.
+  if (!full()) {
+    SDMI_HIP_OK(hipDeviceSynchronize());           // (set_weight packed on the caller's stream)
+    for (auto& L : dec_) {
+      if (L.kind != V_UP || L.cin % 64 != 0) continue;
+      if (store_.alloc((void**)&L.w_up_phase, (size_t)16 * L.cout * L.cin * sizeof(f16))) return -1;
+      if (launch_up_phase_weights(L.w16[0], L.w_up_phase, L.cout, L.cin, nullptr)) return -1;
+    }
+    SDMI_HIP_OK(hipDeviceSynchronize());
+  }
   finalized_ = true;
   return 0;
 }
@@ -315,6 +326,8 @@ struct VFwd : FwdBase {
     if (full) split3(p, x16, x16_lo, C);
     if (!up) p.pad = 0;                   // F.pad(x, (0,1,0,1)) + conv(stride 2, padding 0)
     p.bias = L.f32[0]; p.out_f32 = out.p; p.ldo = C;
+    // nearest x2 + 3x3 as the four 2x2 phase convs of one launch (igemm KIND_2X2: 4 / 9 of the MACs) where the tuning table says that wins
+    if (up && !full && L.w_up_phase && igemm_plans_up_phase(p)) p = up_phase_of(p, L.w_up_phase);
     gemm(p);
     scratch.off = mark;
     return out;

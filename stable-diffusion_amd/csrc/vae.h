@@ -20,6 +20,7 @@ struct VLayer {
   // V_UP / V_DOWN: w16 = {conv},                         f32 = {conv.b}
   f16* w16[4] = {nullptr, nullptr, nullptr, nullptr};
   float* f32[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  f16* w_up_phase = nullptr;     // V_UP, mixed precision, cin % 64 == 0: [4][cout][4 cin] weights of the conv's four 2x2 phase convs (finalize())
 };
 
 class Vae {

@@ -13,6 +13,11 @@ split-K summation order, i.e. the exact output bits) is fixed.
 later brings its own shapes and changes no other model's tiles): `--workloads churches32b8,churches32b2 --append-new`,
 `--workloads faces64b8,faces64b2,bsr64b8,bsr64b2 --append-new`, `--workloads bsr128b8,bsr128b1 --append-new` (bsr_sr's 128 x 128
 windows, nine of them as 8 + 1 rows; profiles/tune_candidates_bsr128.txt).
+
+The 2x2 phase convs of the Upsample convs (key ksize 2) are a family of their own, measured in a run restricted to it -- the executors take
+the phase form during a collection only then -- and kept in tune_up_phase_gfx950.txt beside the table:
+`SDMI_TUNE_ONLY_KSIZE=2 python tools/tune.py --workloads unet64,unet96,vaedec64,vaedec96 --append-new` (the shapes of the three bench
+workloads and the first stage; profiles/tune_candidates_up_phase.txt).
 """
 import argparse
 import ctypes as C
@@ -129,12 +134,19 @@ def main():
     if args.append_new:
         key = lambda ln: tuple(ln.split()[:8])
         rows = lambda path: [ln for ln in open(path).read().splitlines() if ln and not ln.startswith('#')]
-        have = {key(ln) for ln in rows(args.out)} if os.path.exists(args.out) else set()
-        fresh = [ln for ln in rows(out) if key(ln) not in have]
-        with open(args.out, 'a') as f:
-            f.write(''.join(ln + '\n' for ln in fresh))
-        os.remove(out)
-        print(f'[tune] --append-new: {len(fresh)} new rows appended, {len(have)} kept as they were', flush=True)
+
+        def phase_path(p):      # the rows of the 2x2 phase kind (ksize 2) live beside the table (csrc/igemm.hip Tuner::phase_path_of)
+            return p[:-len('tune_gfx950.txt')] + 'tune_up_phase_gfx950.txt' if p.endswith('tune_gfx950.txt') else p + '.up_phase'
+        for dst, new in ((args.out, out), (phase_path(args.out), phase_path(out))):
+            if not os.path.exists(new):
+                continue
+            have = {key(ln) for ln in rows(dst)} if os.path.exists(dst) else set()
+            fresh = [ln for ln in rows(new) if key(ln) not in have]
+            head = '' if os.path.exists(dst) else open(new).read().splitlines()[0] + '\n'
+            with open(dst, 'a') as f:
+                f.write(head + ''.join(ln + '\n' for ln in fresh))
+            os.remove(new)
+            print(f'[tune] --append-new: {len(fresh)} new rows appended to {os.path.basename(dst)}, {len(have)} kept as they were', flush=True)
     print(f'[tune] {n.value} shapes tuned over {args.reps} x {args.rounds} rounds of {[w for w, _ in fns]} in '
           f'{time.time() - t0:.1f} s -> {args.out}', flush=True)
     if args.dump:
