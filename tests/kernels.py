@@ -212,6 +212,28 @@ def gn_acc_sums(acc):
     return s, ss
 
 
+def gn_stats_ratio(out, B, HW, acc, cpg, cbase=0):
+    """worst |accumulated - fp64 sum over the STORED output| / bound over the 32 groups of one statistics target, for the sum and for the sum
+    of squares.  out [B HW, N] fp32 is channels [cbase, cbase + N) of a GroupNorm input with cpg channels per group.  The bound is the one
+    tests/test_skip_fold_gpu.py and tests/test_up_phase_gpu.py apply at (N / 32, 0), with the group's own element count: fp32 partial sums of
+    n = HW * (channels of `out` in the group) stored values, then exact fixed-point adds of 2^-40 resolution:
+        (n + 4) 2^-24 sum|v| + n 2^-40        and        2 (n + 4) 2^-24 sum v^2 + n 2^-40.
+    A group this output has no channel in must hold exactly zero (its bound is 0: any word there gives inf)."""
+    N = out.shape[1]
+    v = out.double().reshape(B, HW, N)
+    gi = ((cbase + torch.arange(N, device=out.device)) // cpg).clamp_max(32)       # (33 bins: an out-of-range channel would show in bin 32)
+    def per_group(t):
+        return torch.zeros((B, 33), dtype=torch.float64, device=out.device).index_add_(1, gi, t)[:, :32].cpu()
+    n = HW * per_group(torch.ones((B, N), dtype=torch.float64, device=out.device))
+    rs, ra, rss = per_group(v.sum(1)), per_group(v.abs().sum(1)), per_group((v * v).sum(1))
+    s, ss = gn_acc_sums(acc)
+    eps = 2.0 ** -24
+    def worst(err, bound):
+        r = torch.where(bound > 0, err / bound.clamp_min(1e-300), torch.where(err > 0, torch.full_like(err, float('inf')), torch.zeros_like(err)))
+        return float(r.max())
+    return (worst((s - rs).abs(), (n + 4) * eps * ra + n * 2.0 ** -40), worst((ss - rss).abs(), (n + 4) * eps * rss * 2 + n * 2.0 ** -40))
+
+
 def ln_fold_prep(w16, K, gamma, beta, bias=None, out=None):
     """column terms of a LayerNorm-folding GEMM from the packed fp16 weights w16 [N, ldw >= K]: (cs, d) fp32 [N]; `out` = the caller's
     (cs, d), e.g. in guarded buffers (tests/guard.py)"""

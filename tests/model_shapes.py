@@ -4,6 +4,9 @@ It yields (1) every state_dict key with its shape and (2) every kernel launch si
 GroupNorms, 3x3 convs, 1x1 skip convs, resample2, the transformer / legacy-attention GEMMs with their epilogue mode, attention, the
 context K / V projection.  Launches whose output feeds GroupNorms carry the (cpg, cbase) statistics targets of their real consumers --
 the next block's norm and, through the skip stack, the concat norm of an output block -- i.e. what FwdBase::attach_gn_targets attaches.
+A ResBlock with a skip convolution also yields a 'conv2_tail' entry: conv2 as the executor launches it where it folds the skip convolution
+into conv2's halo-staged launch (tail channels, passes, what excludes the block); folds() is the executor's decision restated over the
+committed tuning table, and tests/test_model_shapes_host.py pins it against sdmi_unet_skip_fold_plan.
 tests/test_model_shapes_host.py pins (1) against the recorded state_dict keys of the reference models, which makes (2) a derived fact
 and not a hand-typed table; tests/test_model_shapes_gpu.py runs (2)."""
 import json
@@ -16,11 +19,21 @@ MODELS = {
     'cin': ('cin256_v2_config.json', 'cin_unet_state_dict_keys.json', 64, 1),
     'inpaint': ('inpainting_big_config.json', 'inpaint_unet_state_dict_keys.json', 128, 0),
     'laion': ('txt2img_1p4B_eval.json', None, 32, 77),
+    # SD v1 and the tiny plan: the params are the oracle's own configs (oracle/plan.py, the ones tests/test_unet_gpu.py builds its models
+    # from), not a file under golden/
+    'sdv1': ('oracle.plan:SD_V1', None, 64, 77),
+    'tiny': ('oracle.plan:TINY', None, 64, 77),
 }
+HALO_TILES = (14, 15, 16, 17)      # include/sdmi.h: the halo-staged 3x3 conv tiles, the only ones that run a 1x1 tail
+PRECISE_1X1_MAX_DS = 4             # csrc/unet.h precise_1x1_max_ds_: stream 1x1 convs are three-pass split-fp16 below this downsample factor
 
 
 def unet_params(name):
-    with open(os.path.join(GOLDEN, MODELS[name][0])) as f:
+    cfg = MODELS[name][0]
+    if cfg.startswith('oracle.plan:'):
+        import oracle.plan
+        return getattr(oracle.plan, cfg.split(':')[1]).ref_kwargs()
+    with open(os.path.join(GOLDEN, cfg)) as f:
         return json.load(f)['model']['params']['unet_config']['params']
 
 
@@ -37,6 +50,7 @@ def walk(p, latent, nctx):
     mc, mult, nrb, ar = p['model_channels'], p['channel_mult'], p['num_res_blocks'], p['attention_resolutions']
     st, heads, updown = p.get('use_spatial_transformer', False), p.get('num_heads', -1), p.get('resblock_updown', False)
     ctx, te = p.get('context_dim'), 4 * mc
+    scale_shift = p.get('use_scale_shift_norm', False)
     W, L = {}, []
 
     def lin(k, o, i, b=True):
@@ -85,6 +99,14 @@ def walk(p, latent, nctx):
             conv(k + '.skip_connection', cout, cin, 1)
             launch('conv1x1', role='skip', K=cin, N=cout, hw=hw2)
         l2 = launch('conv3', role='conv2', c0=cout, c1=0, N=cout, hin=hw2, hout=hw2, stride=1, up=0, gn=[], **extra)
+        if cin != cout:
+            # conv2 with the skip convolution as its 1x1 tail (csrc/unet.cpp res_block): tail_c = cin channels, three passes where the layer's
+            # p1x1 rule makes the 1x1 split-fp16 (ds < PRECISE_1X1_MAX_DS), the statistics targets of conv2 (the same list: filled later).
+            # `excluded`: what keeps the executor from folding whatever the tuning table says -- the split-fp16 last block, scale-shift
+            # blocks, a source that is no multiple of 64 channels, a map wider than skip_fold_max_w = 64.  Whether an admitted block folds is
+            # the table's decision (folds()).
+            why = [w for w, on in (('p3', p3), ('scale_shift', scale_shift), ('tail_c % 64', cin % 64 != 0), ('width > 64', hw2 > 64)) if on]
+            launch('conv2_tail', N=cout, hw=hw2, tail_c=cin, passes=3 if ds < PRECISE_1X1_MAX_DS else 1, excluded='+'.join(why), gn=l2['gn'])
         return Act(cout, hw2, l2)
 
     def attn(k, x):
@@ -163,9 +185,28 @@ def walk(p, latent, nctx):
     return W, L
 
 
-def model_walk(name):
-    _, _, latent, nctx = MODELS[name]
-    return walk(unet_params(name), latent, nctx)
+def model_walk(name, latent=None):
+    _, _, lat, nctx = MODELS[name]
+    return walk(unet_params(name), lat if latent is None else latent, nctx)
+
+
+def tune_lookup(M, N, Kd, ksize, up, kt=0):
+    """the committed tuning table's (tile, split-K) for the executor's request (stride 1, plain mode, split-K 0) of a conv, or None
+    (sdmi_tune_lookup: host arithmetic, no GPU)"""
+    import ctypes as C
+    from stable_diffusion_amd import _lib
+    t, s = C.c_int(-1), C.c_int(-1)
+    rc = _lib.load().sdmi_tune_lookup(M, N, Kd, ksize, 1, up, 0, 0, kt, C.byref(t), C.byref(s))
+    return (t.value, s.value) if rc == 0 else None
+
+
+def folds(d, B):
+    """the walk's fold decision for a 'conv2_tail' entry at batch B: not excluded, and the table's row for conv2 with that tail (the row keyed
+    with the tail's K where there is one, else the plain conv's) is a halo-staged tile"""
+    if d['excluded']:
+        return False
+    row = tune_lookup(B * d['hw'] ** 2, d['N'], 9 * d['N'], 3, 0, d['passes'] * d['tail_c'])
+    return row is not None and row[0] in HALO_TILES
 
 
 def _freeze(d):
@@ -173,10 +214,11 @@ def _freeze(d):
 
 
 def distinct(name, kinds=None):
-    """the distinct launch geometries of a model at its product size, in first-appearance order: [(kind, dict)]"""
+    """the distinct launch geometries of a model at its product size, in first-appearance order: [(kind, dict)].  ('conv2_tail' is another
+    form of a conv2 + skip pair already listed, not one more launch: it is returned only when asked for by kind.)"""
     seen, out = set(), []
     for kind, d in model_walk(name)[1]:
-        if kinds is not None and kind not in kinds:
+        if (kinds is not None and kind not in kinds) or (kinds is None and kind == 'conv2_tail'):
             continue
         key = (kind, _freeze(d))
         if key not in seen:

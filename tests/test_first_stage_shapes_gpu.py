@@ -17,6 +17,10 @@ workspace, the role's epilogue, batch 1 where a map side is 256 or more and batc
 for those levels are keyed by the batch-1 M), so that the (M, N, K) keys of the tuning table are the product's -- and again at a 32-pixel map side (1024 tokens for the attention GEMMs), batch 2, on the forced axis of test_model_shapes_gpu.py
 (tiles 3 and 5, split-K 1 and 2) with output rows at a pitch of N + 8.  The split-fp16 nin_shortcut runs as launched only (its kernel family
 has its own tiles; test_model_shapes_gpu.py does the same).
+The Upsample convs run here as the 3x3 conv with the nearest x2 folded into its gather (up = 1), which is what the executor launches under
+SDMI_UP_PHASE=0; by default it launches them as the four 2x2 phase convs of one launch wherever the committed phase table has the winning
+row (csrc/vae.cpp decode).  That form of every Upsample site of this walk is run by test_model_shapes_gpu.py::test_upsample_conv_in_both_forms
+and, for every row of tune_up_phase_gfx950.txt, by tests/test_up_phase_tiles_gpu.py.
 After every launch every buffer's guards are checked, inputs must be unchanged bits and the split-K tile counters zero again.
 
 (b) The chain runs each chunk of first_stage_shapes.CHAIN_SHAPES at its row offset r0, at C = 512 and C = 128, under the six score regimes

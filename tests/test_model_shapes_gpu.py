@@ -17,6 +17,16 @@ for the roles that have them (the 1x1 convs and projections on the stream; the t
 three-source product); and on a thin forced axis that pins what the heuristic of launch_igemm can choose (tiles 3 and 5, split-K 1 and 2;
 there the concat is launched as two sources a0 | a1, the skip conv also carries a residual and a statistics target, and output rows are
 at a pitch of N + 8, so that a store past the N tail of a row lands in a gap).
+Two roles are launched by the executor in another form than that request since the skip fold and the phase convs, and run here in that form
+too, for these models and for SD v1 (model_shapes 'sdv1': oracle.plan.SD_V1 at a 64 x 64 latent, 77 tokens):
+  conv2 + skip   where the committed table sends conv2 to a halo-staged tile the skip convolution is the 1x1 tail of conv2's launch
+                 (sdmi_k_igemm_tail; bias2 + bias_skip, no residual): test_conv2_with_the_skip_tail_as_launched runs every distinct folding
+                 site (model_shapes.folds, pinned against sdmi_unet_skip_fold_plan on the CPU) at the bars of test_skip_fold_shapes_gpu.py.
+                 test_plain_gemm_and_conv above runs the same sites as the two launches of SDMI_SKIP_FOLD=0 (and of every block that does
+                 not fold)
+  up             the Upsample conv is the four 2x2 phase convs of one launch where the table's phase row beats the up = 1 row by 3 %
+                 (SDMI_UP_PHASE=1, the default), the 3x3 conv with the folded upsampling otherwise: test_upsample_conv_in_both_forms runs
+                 every distinct site, the first stages' included, in both forms, which is each setting of the knob without restating the rule
 NOT run here -- these launch variants of the executor stay covered by the whole-UNet goldens (and, at SD's shapes only, by their own
 kernel tests): GroupNorm + SiLU applied inside the split-K reduction of a ResBlock's conv1 (pgn_*; test_igemm_splitk_reduce_groupnorm_
 behind_a_grid_barrier runs 40 / 20 / 16 channels per group, the new models have 18 .. 32); out_lo of the last FF-out; the one-token context
@@ -961,6 +971,79 @@ ENTRY_POINTS = {
     'st_tail': lambda P: _ep_ff_tail(P, True), 'st_head': _ep_st_head, 'st_mid': lambda P: _ep_st_mid(P, False),
     'st_mid_ctx': lambda P: _ep_st_mid(P, True), 'gn_conv3': _ep_gn_conv3,
 }
+
+
+# ---- conv2 + skip and the Upsample convs as the executor launches them since the skip fold and the phase convs --------------------------
+FOLD_MODELS = ('sdv1', 'cin', 'inpaint', 'laion')
+REDUCE_ABOVE = 16384          # source rows of an Upsample conv above which the site runs on a 32 x 32 source with the table's tile forced
+
+
+def _fold_cases():
+    """every distinct ResBlock of the four UNets whose skip convolution the executor folds at batch 2 (model_shapes.folds: not excluded,
+    and the committed table sends conv2 to a halo-staged tile)"""
+    seen, out = set(), []
+    for model in FOLD_MODELS:
+        for _, d in MS.distinct(model, ('conv2_tail',)):
+            key = (d['hw'], d['N'], d['tail_c'], d['passes'], tuple(d['gn']))
+            if MS.folds(d, B) and key not in seen:
+                seen.add(key)
+                out.append(pytest.param(model, d, id=f'{model}-{MS.case_id("conv2_tail", d)}'))
+    return out
+
+
+@pytest.mark.parametrize('model,d', _fold_cases())
+def test_conv2_with_the_skip_tail_as_launched(model, d):
+    """conv2 + skip_connection of a folding ResBlock as ONE launch (sdmi_k_igemm_tail, tile -1, split-K 0: the table's halo-staged tile and
+    split), with the statistics targets of conv2's real consumers, at the bars of tests/test_skip_fold_shapes_gpu.py"""
+    import test_skip_fold_gpu as SF
+    import test_skip_fold_shapes_gpu as SFS
+    shape = (f'{model}_{d["hw"]}x{d["hw"]}_b{B}', B, d['hw'], d['hw'])
+    c = SF._operands(shape, d['N'], d['tail_c'], d['passes'], ca=d['N'])
+    SFS.check_case(f'{model} {MS.case_id("conv2_tail", d)}', c, -1, 0, d['gn'], two_launches=False)
+    SF._REFS.pop((shape, d['N'], d['tail_c'], d['passes'], d['N']))       # (one site per case: nothing to share, the largest is 100 MB)
+
+
+def _up_cases():
+    """every distinct Upsample conv of the four UNets and of the three first stages: (source side, C, N, statistics targets)"""
+    import first_stage_shapes as FS
+    seen, out = set(), []
+    for model in FOLD_MODELS:
+        for _, d in MS.distinct(model, ('conv3',)):
+            key = (d['hin'], d['c0'], d['N'], tuple(d['gn']))
+            if d['role'] == 'up' and key not in seen:
+                seen.add(key)
+                out.append(pytest.param(*key, id=f'{model}-{MS.case_id("conv3", d)}'))
+    for _, d in FS.distinct(kinds=('conv3',)):
+        key = (d['hin'], d['C'], d['N'], ())
+        if d['role'] == 'up' and key not in seen:
+            seen.add(key)
+            out.append(pytest.param(*key, id=f'first_stage-{FS.case_id("conv3", d)}'))
+    return out
+
+
+@pytest.mark.parametrize('hin,C,N,targets', _up_cases())
+def test_upsample_conv_in_both_forms(hin, C, N, targets):
+    """an Upsample conv as the executor launches it under either setting of SDMI_UP_PHASE: the 3x3 conv with the nearest x2 folded into its
+    gather (sdmi_k_igemm, up = 1) and the four 2x2 phase convs on derived weights (sdmi_k_igemm_up_phase), each with tile -1 and split-K 0 and
+    the statistics targets of the real consumers, at batch 2.  A site of more than REDUCE_ABOVE source rows runs its (N, C) on a 32 x 32 source with the
+    table's tile for the site forced (the tile index depends on the tile count, not on which rows a tile holds)."""
+    import test_up_phase_gpu as UP
+    import test_up_phase_tiles_gpu as UPT
+    targets = list(targets)
+    tag = f'up {C}->{N} {hin}x{hin} b{B}'
+    rows = B * hin * hin
+    old_req, ph_req, src = (-1, 0), (-1, 0), hin
+    if rows > REDUCE_ABOVE:
+        src = 32
+        # (the table's rows for the first stages' levels are keyed by the batch-1 M: the site's row at this batch, else at batch 1, else none)
+        old_req = MS.tune_lookup(4 * rows, N, 9 * C, 3, 1) or MS.tune_lookup(4 * rows // B, N, 9 * C, 3, 1) or (-1, 0)
+        ph_req = MS.tune_lookup(rows, N, 4 * C, 2, 1) or MS.tune_lookup(rows // B, N, 4 * C, 2, 1) or (-1, 0)
+        tag += f' reduced to 32x32 (3x3-up {old_req}, phase {ph_req})'
+    old = _Case(tag + ' 3x3-up', c0=C, c1=0, N=N, Hin=src, Win=src, Hout=2 * src, Wout=2 * src, ksize=3, up=1, gn=targets)
+    _assert_case(*old.run(*old_req, as_executor=True))
+    c = UP._operands(B, src, src, C, N)
+    UPT.check_launch(tag + ' phase', c, ph_req[0], splitk=0 if ph_req[0] < 0 else 1, targets=targets)
+    UP._REFS.pop((c['B'], src, src, C, N), None)
 
 
 @pytest.mark.parametrize('entry', list(ENTRY_POINTS))

@@ -61,6 +61,45 @@ def test_walk_statistics_targets():
                 assert len(d['gn']) <= 2 and cpg >= 2 and (cbase + d['N'] + cpg - 1) // cpg <= 32
 
 
+@pytest.mark.parametrize('name', ['sdv1', 'tiny'])
+def test_walk_fold_sites_match_the_executors_plan(name, monkeypatch):
+    """the walk's ResBlocks with a skip convolution are the executor's (sdmi_unet_skip_fold_plan: a dry pass, no GPU) in number and order,
+    and the walk's fold decision -- not excluded, and the committed table's row is a halo-staged tile -- is the plan's entry for every one of
+    them, at batch 2 and 64 x 64 latents, where 13 of SD v1's 14 fold"""
+    import ctypes as C
+    import oracle.plan
+    from stable_diffusion_amd import UNetModelHIP
+    for k in ('SDMI_SKIP_FOLD', 'SDMI_SKIP_FOLD_MAX_W', 'SDMI_IGEMM_TILE', 'SDMI_SPLITK', 'SDMI_TUNE_FILE'):
+        monkeypatch.delenv(k, raising=False)
+    h = UNetModelHIP(**getattr(oracle.plan, MS.MODELS[name][0].split(':')[1]).ref_kwargs())._handle
+    buf = (C.c_int32 * 64)()
+    n = h.lib.sdmi_unet_skip_fold_plan(h.h, 2, 64, 64, 77, buf, 64)
+    assert n >= 0, h.lib.sdmi_last_error()
+    plan = list(buf[:n])
+    sites = [d for k, d in MS.model_walk(name, latent=64)[1] if k == 'conv2_tail']
+    assert len(sites) == len(plan) == 14
+    mine = [int(MS.folds(d, 2)) for d in sites]
+    print(f'[walk vs plan {name}] plan {plan}, walk {mine}; sites ' + ', '.join(f'{d["hw"]}x{d["hw"]} {d["tail_c"]}x{d["passes"]}->{d["N"]}' for d in sites))
+    assert mine == plan
+    assert sites[-1]['excluded'] == 'p3' and all(not d['excluded'] for d in sites[:-1])
+    if name == 'sdv1':
+        assert plan == [1] * 13 + [0]
+        # the three sites tests/test_skip_fold_shapes_gpu.py runs are sites of this walk
+        assert {(d['hw'], d['N'], d['tail_c'], d['passes']) for d in sites} >= {(8, 1280, 2560, 1), (16, 1280, 2560, 1), (32, 640, 1920, 3)}
+        # the pass count per site, in execution order (the table has no rows keyed by the tail's K, so the plan above cannot see it): the
+        # stream 1x1 convs are three-pass split-fp16 on the two upper levels (ds 1, 2: 64 x 64, 32 x 32) and single-pass below (README.md,
+        # DESIGN.md section 2 "Precision design"; csrc/unet.cpp Layer::p1x1) -- input_blocks.4 (32 x 32), .7 (16 x 16), output_blocks.0-2
+        # (8 x 8), .3-5 (16 x 16), .6-8 (32 x 32), .9-11 (64 x 64)
+        assert [(d['hw'], d['passes']) for d in sites] == [(32, 3), (16, 1)] + [(8, 1)] * 3 + [(16, 1)] * 3 + [(32, 3)] * 3 + [(64, 3)] * 3
+
+
+def test_walk_up_sites_of_sdv1():
+    """the Upsample convs of SD v1 and the concat norms they feed as the first source: what tests/test_up_phase_tiles_gpu.py takes its second
+    statistics target from"""
+    ups = [(d['c0'], d['hin'], d['gn']) for k, d in MS.distinct('sdv1', ('conv3',)) if d['role'] == 'up']
+    assert ups == [(1280, 8, [(80, 0)]), (1280, 16, [(60, 0)]), (640, 32, [(30, 0)])]
+
+
 @pytest.mark.parametrize('shape,dtype,ld', [((5, 24), torch.float16, 32), ((3, 7, 10), torch.float32, None), ((33,), torch.int64, None),
                                             ((300, 200), torch.float32, 264), ((2, 32, 8, 16), torch.int64, None)])
 def test_guard_selfcheck(shape, dtype, ld):

@@ -16,7 +16,6 @@ launch tapes' verify mode, and the launch count of an SD-v1 call at 64 x 64.
 Measured on an MI355X: see profiles/skip_fold_ab.txt."""
 import ctypes as C
 import json
-import math
 import os
 
 import numpy as np
@@ -28,12 +27,13 @@ pytestmark = pytest.mark.gpu
 
 import guard  # noqa: E402  (tests/ is on sys.path via conftest's rootdir insertion)
 import kernels as K  # noqa: E402
+import skip_fold_cases as SC  # noqa: E402
 
 DEV = 'cuda'
 EPS32 = 2.0 ** -24
 CA = 384            # conv2's input channels: 6 chunks of 64, so the halo tiles split 1, 2, 3 and 6 ways on chunk boundaries
 SPLITS = (1, 2, 3, 6)
-HALO_BM = {14: 256, 15: 256, 16: 128, 17: 128}
+HALO_BM = SC.HALO_BM
 
 # name, B, H, W, tiles: 8 x 8 maps are whole images per tile (two in BM = 128, four in BM = 256), 16 x 16 maps image rows (BM = 128: 8 rows, two
 # tiles per image; BM = 256: the image)
@@ -47,23 +47,19 @@ _SHAPE = {s[0]: s for s in SHAPES}
 _REFS = {}
 
 
-def _g(seed):
-    return torch.Generator().manual_seed(seed)
-
-
-def _operands(shape, Cout, Cin, passes):
-    """device operands and the fp64 references of one geometry, built once and left unchanged"""
-    key = (shape, Cout, Cin, passes)
+def _operands(shape, Cout, Cin, passes, ca=CA):
+    """device operands and the fp64 references of one geometry, built once and left unchanged.  shape: a name of SHAPES, or (name, B, H, W);
+    ca: conv2's input channels (the draws: tests/skip_fold_cases.py, on the CPU, so that the CPU control sees the same numbers)"""
+    if isinstance(shape, str):
+        shape = _SHAPE[shape][:4]
+    key = (shape, Cout, Cin, passes, ca)
     if key in _REFS:
         return _REFS[key]
-    _, B, H, W, _ = _SHAPE[shape]
+    name, B, H, W = shape
     M = B * H * W
-    g = _g(1000 * Cout + 10 * Cin + passes + sum(map(ord, shape)))
-    a = torch.randn((M, CA), generator=g).to(DEV).half()
-    w = (torch.randn((Cout, CA, 3, 3), generator=g) / math.sqrt(9 * CA)).to(DEV)
-    x = (2.0 * torch.randn((M, Cin), generator=g)).to(DEV)
-    ws = (torch.randn((Cout, Cin), generator=g) / math.sqrt(Cin)).to(DEV)
-    b2, bs = torch.randn(Cout, generator=g).to(DEV), torch.randn(Cout, generator=g).to(DEV)
+    CA = ca
+    a, w, x, ws, b2, bs = (t.to(DEV) for t in SC.draw(name, B, H, W, ca, Cout, Cin, passes))
+    a = a.half()
     bias = b2 + bs                                       # fp32, as finalize() folds the two biases
     wp = K.pack_conv_weight(w)
     x_hi, x_lo = K.cast_f16(x, want_lo=True)
@@ -85,8 +81,8 @@ def _operands(shape, Cout, Cin, passes):
     ref = conv + skip + bias.double()[None]
     mag = mag + bias.double().abs()[None]
     torch.cuda.synchronize()
-    c = dict(B=B, H=H, W=W, M=M, Cout=Cout, Cin=Cin, passes=passes, Kt=passes * Cin, a=a, wp=wp, x_hi=x_hi, x_lo=x_lo, wt=wt, b2=b2, bs=bs,
-             bias=bias, ref=ref, mag=mag)
+    c = dict(B=B, H=H, W=W, M=M, CA=CA, Cout=Cout, Cin=Cin, passes=passes, Kt=passes * Cin, a=a, wp=wp, x_hi=x_hi, x_lo=x_lo, wt=wt, b2=b2,
+             bs=bs, bias=bias, ref=ref, mag=mag)
     _REFS[key] = c
     return c
 
@@ -94,7 +90,7 @@ def _operands(shape, Cout, Cin, passes):
 def _desc(c, a, wp, bias, out, tile, splitk, ws, cnt, residual=None, out_f16=None, gn=None):
     from stable_diffusion_amd import _lib
     d = _lib.IGemmDesc()
-    d.a0 = a.data_ptr(); d.c0 = CA; d.lda0 = a.stride(0)
+    d.a0 = a.data_ptr(); d.c0 = c['CA']; d.lda0 = a.stride(0)
     d.B, d.Hin, d.Win, d.Hout, d.Wout, d.ksize, d.stride, d.up = c['B'], c['H'], c['W'], c['H'], c['W'], 3, 1, 0
     d.w = wp.data_ptr(); d.N = c['Cout']; d.mode = 0
     d.bias = bias.data_ptr()
@@ -104,14 +100,19 @@ def _desc(c, a, wp, bias, out, tile, splitk, ws, cnt, residual=None, out_f16=Non
     d.splitk, d.tile, d.dma = splitk, tile, -1
     d.splitk_ws = ws.data_ptr(); d.splitk_ws_floats = ws.numel()
     d.splitk_cnt = cnt.data_ptr(); d.splitk_cnt_ints = cnt.numel()
-    if gn is not None:
-        acc, cpg = gn
-        d.gn_n = 1; d.gn_acc[0] = acc.data_ptr(); d.gn_cpg[0] = cpg; d.gn_cbase[0] = 0
+    if gn is not None:          # (acc, cpg) at cbase 0, or a list of up to two (acc, cpg, cbase)
+        gn = [gn + (0,)] if isinstance(gn, tuple) else gn
+        d.gn_n = len(gn)
+        for i, (acc, cpg, cbase) in enumerate(gn):
+            d.gn_acc[i] = acc.data_ptr(); d.gn_cpg[i] = cpg; d.gn_cbase[i] = cbase
     return d
 
 
-def _run(c, tile, splitk, extras, folded):
-    """one launch configuration in guarded buffers -> (out fp32, out fp16 | None, statistics accumulators | None)"""
+def _run(c, tile, splitk, extras, folded, targets=None):
+    """one launch configuration in guarded buffers -> (out fp32, out fp16 | None, statistics accumulators | None).  splitk 0: the launcher
+    chooses (slabs for 16 splits are given).  targets: the (cpg, cbase) statistics targets of a run with extras, [(N / 32, 0)] by default;
+    when given, the accumulators come back as a list in that order.  After the launch: every guard intact, the split-K tile counters zero
+    again, every operand bit-unchanged."""
     from stable_diffusion_amd import _lib
     lib = _lib.load()
     P = guard.Pool(DEV)
@@ -121,11 +122,13 @@ def _run(c, tile, splitk, extras, folded):
     x_lo = P.put('x_lo', c['x_lo']) if c['passes'] == 3 else None
     out = P.new('out', (M, N), torch.float32)
     o16 = P.new('out_f16', (M, N), torch.float16) if extras else None
-    acc = P.new('gn_acc', (c['B'], 32, 8, 16), torch.int64, fill=0) if extras else None
+    tg = ([(N // 32, 0)] if targets is None else list(targets)) if extras else []
+    accs = [P.new(f'gn_acc{i}', (c['B'], 32, 8, 16), torch.int64, fill=0) for i in range(len(tg))]
+    acc = (accs[0] if targets is None else accs) if extras else None
     rM, rN = (M + 255) // 256 * 256, (N + 127) // 128 * 128
-    ws = P.new('splitk_ws', (max(splitk, 1) * rM * rN,), torch.float32, row_bytes=4 * rN)
+    ws = P.new('splitk_ws', ((splitk if splitk > 0 else 16) * rM * rN,), torch.float32, row_bytes=4 * rN)
     cnt = P.new('splitk_cnt', (8192,), torch.int32, fill=0)
-    gn = (acc, N // 32) if extras else None
+    gn = [(ac, cpg, cbase) for ac, (cpg, cbase) in zip(accs, tg)] or None
     if folded:
         bias = P.put('bias', c['bias'])
         d = _desc(c, a, wp, bias, out, tile, splitk, ws, cnt, out_f16=o16, gn=gn)
@@ -138,7 +141,13 @@ def _run(c, tile, splitk, extras, folded):
         d = _desc(c, a, wp, b2, out, tile, splitk, ws, cnt, residual=skip, out_f16=o16, gn=gn)
         _lib.check(lib.sdmi_k_igemm(C.byref(d), _lib.stream_ptr()))
     torch.cuda.synchronize()
-    P.check(f'{"folded" if folded else "two launches"} tile {tile} split {splitk}')
+    tag = f'{"folded" if folded else "two launches"} tile {tile} split {splitk}'
+    P.check(tag)
+    assert int(cnt.abs().max()) == 0, f'{tag}: split-K tile counters not left zero'
+    for v, k in ((a, 'a'), (wp, 'wp'), (wt, 'wt'), (x_hi, 'x_hi'), (x_lo, 'x_lo')):
+        assert v is None or torch.equal(v.view(torch.int16), c[k].view(torch.int16)), f'{tag}: operand {k} was modified'
+    for v, k in ((bias, 'bias'),) if folded else ((b2, 'b2'), (bs, 'bs')):
+        assert torch.equal(v.view(torch.int32), c[k].view(torch.int32)), f'{tag}: operand {k} was modified'
     return out, o16, acc
 
 
@@ -146,7 +155,7 @@ def _ratio(c, out, splitk):
     """worst |got - ref| / bound over the elements (inf if anything is not finite)"""
     if not bool(torch.isfinite(out).all()):
         return float('inf')
-    bound = (9 * CA + c['Kt'] + splitk + 4) * EPS32 * c['mag']
+    bound = (9 * c['CA'] + c['Kt'] + splitk + 4) * EPS32 * c['mag']
     return float(((out.double() - c['ref']).abs() / bound).max())
 
 

@@ -67,7 +67,7 @@ def _operands(B, H, W, Cin, N):
     return c
 
 
-def _desc(c, a, w, bias, out, tile, out_f16=None, gn=None, up=1):
+def _desc(c, a, w, bias, out, tile, out_f16=None, gn=None, up=1, splitk=1):
     from stable_diffusion_amd import _lib
     d = _lib.IGemmDesc()
     d.a0 = a.data_ptr(); d.c0 = c['Cin']; d.lda0 = a.stride(0)
@@ -75,15 +75,19 @@ def _desc(c, a, w, bias, out, tile, out_f16=None, gn=None, up=1):
     d.w = w.data_ptr(); d.N = c['N']; d.mode = 0
     d.bias = bias.data_ptr()
     d.out_f32 = out.data_ptr(); d.ldo = out.stride(0); d.out_f16 = _lib.ptr(out_f16)
-    d.splitk, d.tile, d.dma = 1, tile, -1
-    if gn is not None:
-        acc, cpg = gn
-        d.gn_n = 1; d.gn_acc[0] = acc.data_ptr(); d.gn_cpg[0] = cpg; d.gn_cbase[0] = 0
+    d.splitk, d.tile, d.dma = splitk, tile, -1          # (splitk 0 is the executor's request: the tuning table's key)
+    if gn is not None:          # (acc, cpg) at cbase 0, or a list of up to two (acc, cpg, cbase)
+        gn = [gn + (0,)] if isinstance(gn, tuple) else gn
+        d.gn_n = len(gn)
+        for i, (acc, cpg, cbase) in enumerate(gn):
+            d.gn_acc[i] = acc.data_ptr(); d.gn_cpg[i] = cpg; d.gn_cbase[i] = cbase
     return d
 
 
-def _run(c, tile, extras, phase):
-    """one launch in guarded buffers -> (out fp32 [4 M, N], out fp16 | None, statistics accumulators | None, derived weights as the device made them)"""
+def _run(c, tile, extras, phase, targets=None, splitk=1):
+    """one launch in guarded buffers -> (out fp32 [4 M, N], out fp16 | None, statistics accumulators | None, derived weights as the device made
+    them).  targets: the (cpg, cbase) statistics targets of a run with extras, [(N / 32, 0)] by default; when given, the accumulators come back
+    as a list in that order.  After the launch: every guard intact, every operand bit-unchanged."""
     from stable_diffusion_amd import _lib
     lib = _lib.load()
     Pl = guard.Pool(DEV)
@@ -91,19 +95,24 @@ def _run(c, tile, extras, phase):
     a, wp, bias = Pl.put('a', c['a']), Pl.put('w', c['wp']), Pl.put('bias', c['bias'])
     out = Pl.new('out', (4 * M, N), torch.float32)
     o16 = Pl.new('out_f16', (4 * M, N), torch.float16) if extras else None
-    acc = Pl.new('gn_acc', (c['B'], 32, 8, 16), torch.int64, fill=0) if extras else None
-    gn = (acc, N // 32) if extras else None
+    tg = ([(N // 32, 0)] if targets is None else list(targets)) if extras else []
+    accs = [Pl.new(f'gn_acc{i}', (c['B'], 32, 8, 16), torch.int64, fill=0) for i in range(len(tg))]
+    acc = (accs[0] if targets is None else accs) if extras else None
+    gn = [(ac, cpg, cbase) for ac, (cpg, cbase) in zip(accs, tg)] or None
     wph = None
     if phase:
         wph = Pl.new('w_phase', (4, N, 4 * Cin), torch.float16)
         _lib.check(lib.sdmi_k_up_phase_weights(wp.data_ptr(), wph.data_ptr(), N, Cin, _lib.stream_ptr()))
-        d = _desc(c, a, wph, bias, out, tile, out_f16=o16, gn=gn)
+        d = _desc(c, a, wph, bias, out, tile, out_f16=o16, gn=gn, splitk=splitk)
         _lib.check(lib.sdmi_k_igemm_up_phase(C.byref(d), _lib.stream_ptr()))
     else:
         d = _desc(c, a, wp, bias, out, tile, out_f16=o16, gn=gn)
         _lib.check(lib.sdmi_k_igemm(C.byref(d), _lib.stream_ptr()))
     torch.cuda.synchronize()
-    Pl.check(f'{"phase" if phase else "3x3 up"} tile {tile}')
+    tag = f'{"phase" if phase else "3x3 up"} tile {tile}'
+    Pl.check(tag)
+    assert torch.equal(a.view(torch.int16), c['a'].view(torch.int16)) and torch.equal(wp.view(torch.int16), c['wp'].view(torch.int16)) and \
+        torch.equal(bias.view(torch.int32), c['bias'].view(torch.int32)), f'{tag}: an input operand was modified'
     return out, o16, acc, wph
 
 
