@@ -88,7 +88,14 @@ int sdmi_unet_create_ext(const sdmi_unet_cfg* cfg, const sdmi_unet_ext* ext, int
  *                               bedroom LDMs (models/ldm/celeba256, ffhq256, lsun_beds256: model_channels 224, n = 32 -> 14 / 21 / 28 heads) and
  *                               bsr_sr (160, n = 32 -> 20 heads).  A handle with attention_block = 1 takes model_channels % 32 == 0 (GEMM sources
  *                               of 32 (mod 64) channels end in a half k-tile); SpatialTransformer handles keep model_channels % 64 == 0.
- *                               A packed blob records n and is imported only by a handle created with the same n. */
+ *                               A packed blob records n and is imported only by a handle created with the same n.
+ *                               Also with attention_block = 0 (additive: a flag value that was refused before, no struct or call changes,
+ *                               SDMI_ABI_VERSION stays as it is): every SpatialTransformer runs ch / n heads of n channels
+ *                               (openaimodel.py:542-549; legacy True or False give the same heads wherever n divides ch).  Only n = 32 is admitted
+ *                               there (the head dim this family is tested at; any other value is refused by name), cfg.num_heads must be -1 and
+ *                               n must divide every attention level.  The retrieval-augmented model
+ *                               (configs/retrieval-augmented-diffusion/768x768.yaml: model_channels 448, n = 32 -> 14 / 28 / 42 / 56 heads, 16
+ *                               latent channels in and out) and layout-to-image (models/ldm/layout2img-openimages256: 128, n = 32). */
 #define SDMI_UNET_NUM_HEAD_CHANNELS_SHIFT 16
 #define SDMI_UNET_NUM_HEAD_CHANNELS_MASK 0x0fff0000u
 #define SDMI_UNET_NUM_HEAD_CHANNELS(n) (((unsigned)(n) << SDMI_UNET_NUM_HEAD_CHANNELS_SHIFT) & SDMI_UNET_NUM_HEAD_CHANNELS_MASK)

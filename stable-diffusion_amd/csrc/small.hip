@@ -312,6 +312,124 @@ __global__ void __launch_bounds__(256) conv_out4_kernel(const float* h, const fl
   }
 }
 
+// Output heads of 9 .. 16 channels (the retrieval-augmented UNet writes 16 latent channels).  Sixteen outputs on the 4-pixel form would be
+// 64 accumulators and 32 live weight quads per lane; instead blockIdx.y picks one half of the outputs -- n0 = 0 or 8 -- and a wave runs
+// conv_out4_kernel<8>'s loop for that half: the same register budget (no scratch: profiles/kernel_resources_conv_out16.txt), every weight
+// quad still loaded once per wave and tap; the input rows are read by both halves (the second read hits L2).  An accumulator sees exactly
+// the terms conv_out_kernel gives it, in its order: taps ascending, channel quads ascending inside a tap, out-of-image taps skipped.
+// Cin <= 512, W % COP == 0, Cout <= 2 * CO_MAXN; outputs n >= Cout of the upper half read weight row 0 and are not stored.
+__global__ void __launch_bounds__(256) conv_out4_halves_kernel(const float* h, const float* w, const float* bias, float* out, int B,
+                                                               int H, int W, int Cin, int Cout) {
+  constexpr int NOUT = CO_MAXN;
+  const int lane = threadIdx.x & 63;
+  const int g = blockIdx.x * 4 + (threadIdx.x >> 6);       // pixel group
+  const int n0 = blockIdx.y * NOUT;                        // first output channel of this half
+  const int wq = W / COP;
+  if (g >= B * H * wq) return;
+  const int b = g / (H * wq), rem = g - b * H * wq, y = rem / wq, x0 = (rem - y * wq) * COP;
+  const int K = 9 * Cin;
+  const int c0 = lane * 4, c1 = lane * 4 + 256;
+  const bool v0 = c0 < Cin, v1 = c1 < Cin;
+  float acc[COP][NOUT];
+#pragma unroll
+  for (int p = 0; p < COP; ++p)
+#pragma unroll
+    for (int n = 0; n < NOUT; ++n) acc[p][n] = 0.f;
+  const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int ky = 0; ky < 3; ++ky) {
+    const int iy = y + ky - 1;
+    if (iy < 0 || iy >= H) continue;                       // (wave-uniform)
+    f32x4 xa[COP + 2], xb[COP + 2];                        // input columns x0 - 1 .. x0 + COP of this row, both channel passes
+#pragma unroll
+    for (int j = 0; j < COP + 2; ++j) {
+      const int ix = x0 - 1 + j;
+      const bool in = ix >= 0 && ix < W;
+      const float* src = h + ((size_t)(b * H + iy) * W + (in ? ix : 0)) * Cin;
+      xa[j] = (in && v0) ? *(const f32x4*)(src + c0) : zero;
+      xb[j] = (in && v1) ? *(const f32x4*)(src + c1) : zero;
+    }
+#pragma unroll
+    for (int kx = 0; kx < 3; ++kx) {
+      const int tap = ky * 3 + kx;
+      f32x4 wa[NOUT], wb[NOUT];
+#pragma unroll
+      for (int n = 0; n < NOUT; ++n) {
+        const float* wp = w + (size_t)(n0 + n < Cout ? n0 + n : 0) * K + tap * Cin;
+        wa[n] = v0 ? *(const f32x4*)(wp + c0) : zero;
+        wb[n] = v1 ? *(const f32x4*)(wp + c1) : zero;
+      }
+#pragma unroll
+      for (int p = 0; p < COP; ++p) {
+        const int ix = x0 + p + kx - 1;
+        if (ix < 0 || ix >= W) continue;                   // (wave-uniform) out-of-image tap: skipped, as in conv_out_kernel
+        const f32x4 xv = xa[p + kx], xw = xb[p + kx];
+        if (v0) {
+#pragma unroll
+          for (int n = 0; n < NOUT; ++n) acc[p][n] += wa[n][0] * xv[0] + wa[n][1] * xv[1] + wa[n][2] * xv[2] + wa[n][3] * xv[3];
+        }
+        if (v1) {
+#pragma unroll
+          for (int n = 0; n < NOUT; ++n) acc[p][n] += wb[n][0] * xw[0] + wb[n][1] * xw[1] + wb[n][2] * xw[2] + wb[n][3] * xw[3];
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int n = 0; n < NOUT; ++n) {
+    const bool live = n0 + n < Cout;
+    f32x4 r;
+#pragma unroll
+    for (int p = 0; p < COP; ++p) {
+      float v = acc[p][n];
+#pragma unroll
+      for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
+      r[p] = v + ((bias && live) ? bias[n0 + n] : 0.f);
+    }
+    if (lane == 0 && live) *(f32x4*)(out + (((size_t)b * Cout + n0 + n) * H + y) * W + x0) = r;
+  }
+}
+
+// ... and the fallback (any W, any Cin % 4 == 0): conv_out_kernel's loop, one wave per output pixel and half of the outputs
+__global__ void __launch_bounds__(256) conv_out_halves_kernel(const float* h, const float* w, const float* bias, float* out, int B,
+                                                              int H, int W, int Cin, int Cout) {
+  const int lane = threadIdx.x & 63;
+  const int m = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int n0 = blockIdx.y * CO_MAXN;
+  const int M = B * H * W;
+  if (m >= M) return;
+  const int b = m / (H * W), rem = m - b * H * W, y = rem / W, x = rem - y * W;
+  float acc[CO_MAXN];
+#pragma unroll
+  for (int n = 0; n < CO_MAXN; ++n) acc[n] = 0.f;
+  const int K = 9 * Cin;
+  for (int tap = 0; tap < 9; ++tap) {
+    const int ky = tap / 3, kx = tap - ky * 3;
+    const int iy = y + ky - 1, ix = x + kx - 1;
+    if (iy < 0 || iy >= H || ix < 0 || ix >= W) continue;
+    const float* src = h + ((size_t)(b * H + iy) * W + ix) * Cin;
+    for (int c = lane * 4; c < Cin; c += 256) {
+      const f32x4 xv = *(const f32x4*)(src + c);
+#pragma unroll
+      for (int n = 0; n < CO_MAXN; ++n) {
+        if (n0 + n < Cout) {
+          const f32x4 wv = *(const f32x4*)(w + (size_t)(n0 + n) * K + tap * Cin + c);
+          acc[n] += wv[0] * xv[0] + wv[1] * xv[1] + wv[2] * xv[2] + wv[3] * xv[3];
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int n = 0; n < CO_MAXN; ++n) {
+    if (n0 + n < Cout) {
+      float v = acc[n];
+#pragma unroll
+      for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
+      if (lane == 0) out[(((size_t)b * Cout + n0 + n) * H + y) * W + x] = v + (bias ? bias[n0 + n] : 0.f);
+    }
+  }
+}
+
 // ---- packing -------------------------------------------------------------------------------------------
 __global__ void pack_conv_kernel(const float* w, f16* dst, int O, int I, int KH, int KW) {
   const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -622,8 +740,17 @@ int launch_conv_in(const float* x, const float* w, const float* bias, float* out
 
 int launch_conv_out(const float* h, const float* w, const float* bias, float* out, int B, int H, int W, int Cin, int Cout,
                     hipStream_t s) {
-  SDMI_CHECK(Cout <= CO_MAXN && Cin % 4 == 0, "conv_out: out_channels <= 8, Cin % 4 == 0");
+  SDMI_CHECK(Cout >= 1 && Cout <= 2 * CO_MAXN && Cin % 4 == 0, "conv_out: out_channels <= 16, Cin % 4 == 0");
   ProfScope ps("conv_out_f32", 2.0 * B * H * W * (double)Cout * Cin * 9, (double)B * H * W * (Cin + Cout) * 4.0, s);
+  if (Cout > CO_MAXN) {        // 9 .. 16 outputs: two halves of 8 in one launch (grid.y); Cout <= 8 launches what it always did, below
+    const bool al = ((((uintptr_t)h | (uintptr_t)w | (uintptr_t)out) & 15) == 0);
+    if (W % COP == 0 && Cin <= 512 && al)
+      SDMI_LAUNCH(conv_out4_halves_kernel, dim3(cdiv(B * H * (W / COP), 4), 2), dim3(256), 0, s, h, w, bias, out, B, H, W, Cin, Cout);
+    else
+      SDMI_LAUNCH(conv_out_halves_kernel, dim3(cdiv(B * H * W, 4), 2), dim3(256), 0, s, h, w, bias, out, B, H, W, Cin, Cout);
+    SDMI_HIP_OK(hipGetLastError());
+    return 0;
+  }
   // (an LDS-resident-weights variant, 32 pixels per block, was measured at 169 us vs 64 us: one wave per pixel keeps 1024
   // independent waves in flight, which this latency-bound fp32 kernel needs more than it needs fewer weight re-reads)
   const char* e_co4 = getenv("SDMI_CONV_OUT4");                  // A/B knob, read per launch (1 per UNet call)

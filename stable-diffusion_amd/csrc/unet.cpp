@@ -66,8 +66,13 @@ int UNet::build(const sdmi_unet_cfg& c, int precision, const sdmi_unet_ext* ext,
   SDMI_CHECK(ext_.resblock_updown == 0 || ext_.resblock_updown == 1, "resblock_updown must be 0 or 1");
   SDMI_CHECK(c.n_levels >= 1 && c.n_levels <= 8 && c.n_attention_resolutions >= 0 && c.n_attention_resolutions <= 8,
              "bad level / attention_resolutions count");
-  SDMI_CHECK(num_head_channels_ == 0 || ext_.attention_block == 1,
-             "num_head_channels is expressed for the AttentionBlock family only (attention_block = 1); a SpatialTransformer takes num_heads");
+  // (with attention_block = 0 the SpatialTransformers take heads = ch / num_head_channels, dim_head = num_head_channels: openaimodel.py:542-549,
+  // the retrieval-augmented and layout-to-image UNets), at the one head dim that family is tested at
+  SDMI_CHECK(num_head_channels_ == 0 || ext_.attention_block == 1 || num_head_channels_ == 32,
+             "num_head_channels " + std::to_string(num_head_channels_) + " on a SpatialTransformer handle (attention_block = 0): only 32 is admitted "
+             "(the head dim this family is tested at)");
+  SDMI_CHECK(num_head_channels_ == 0 || ext_.attention_block == 1 || c.num_heads < 1,
+             "num_head_channels together with num_heads on a SpatialTransformer handle: one of the two (pass num_heads = -1 with num_head_channels)");
   // AttentionBlock UNets: every GEMM source is a multiple of 32 channels (a source of 32 (mod 64) ends in a half k-tile, igemm_kernel.h);
   // the SpatialTransformer's row-strip chains and LayerNorm fold keep whole 64-channel chunks
   if (ext_.attention_block == 1) SDMI_CHECK(c.model_channels > 0 && c.model_channels % 32 == 0, "model_channels must be a multiple of 32 on this path");
@@ -164,6 +169,9 @@ int UNet::build(const sdmi_unet_cfg& c, int precision, const sdmi_unet_ext* ext,
       if (L.kind == L_ATTN) {
         SDMI_CHECK(!(full() && L.dh > 160), L.prefix + ": attention head dim " + std::to_string(L.dh) +
                    " has no full-precision kernel (split-fp16 attention is instantiated up to head dim 160)");
+        if (num_head_channels_ > 0)
+          SDMI_CHECK(L.cin % num_head_channels_ == 0, L.prefix + ": " + std::to_string(L.cin) + " channels not divisible by num_head_channels " +
+                     std::to_string(num_head_channels_));
         return 0;
       }
       if (L.kind != L_ATTN_LEGACY) return 0;

@@ -255,3 +255,30 @@ def synthetic_faces_vq_state_dict(seed=0, vq_kwargs=None):
     from .vae import VQModelInterfaceHIP
     m = VQModelInterfaceHIP(**(vq_kwargs or FACES_VQ_KWARGS))
     return synthetic_named_state_dict([(k, tuple(v.shape)) for k, v in m.state_dict().items()], seed)
+
+
+# ---- the retrieval-augmented model (configs/retrieval-augmented-diffusion/768x768.yaml) and layout-to-image -------------------
+# SD v1's SpatialTransformer blocks with num_head_channels = 32 (14 / 28 / 42 / 56 heads at 448 .. 1792 channels), 16 latent channels
+RDM_UNET_KWARGS = dict(image_size=48, in_channels=16, out_channels=16, model_channels=448, attention_resolutions=[4, 2, 1],
+                       num_res_blocks=2, channel_mult=[1, 2, 3, 4], use_scale_shift_norm=False, resblock_updown=False,
+                       num_head_channels=32, use_spatial_transformer=True, transformer_depth=1, context_dim=768,
+                       use_checkpoint=True)                                                                # yaml:19-42
+RDM_SCHEDULE = dict(timesteps=1000, linear_start=0.0015, linear_end=0.015, conditioning_key='crossattn')   # yaml:5-6,9,15
+LAYOUT_UNET_KWARGS = dict(image_size=64, in_channels=3, out_channels=3, model_channels=128, attention_resolutions=[8, 4, 2],
+                          num_res_blocks=2, channel_mult=[1, 2, 3, 4], num_head_channels=32, use_spatial_transformer=True,
+                          transformer_depth=3, context_dim=512)              # models/ldm/layout2img-openimages256/config.yaml:16-36
+# stand-ins of the retrieval-augmented UNet for the tests.  RDM64: the yaml at model_channels 64 (2 / 4 / 6 / 8 heads, 30.2 M parameters).
+# RDM448X2: the real width over two levels -- the real head counts 14 / 28 and the real 14 / 28 / 42 channels per GroupNorm group.
+RDM64_UNET_KWARGS = dict(RDM_UNET_KWARGS, model_channels=64)
+RDM448X2_UNET_KWARGS = dict(RDM_UNET_KWARGS, channel_mult=[1, 2], attention_resolutions=[1, 2], num_res_blocks=1)
+# RDM320X1: one level of 320 channels -- 10 heads of 32: the one width at which this family runs the row-strip chain launches (C == 320)
+RDM320X1_UNET_KWARGS = dict(RDM_UNET_KWARGS, model_channels=320, channel_mult=[1], attention_resolutions=[1], num_res_blocks=1)
+RDM_STANDINS = {'rdm64': RDM64_UNET_KWARGS, 'rdm448x2': RDM448X2_UNET_KWARGS, 'rdm320x1': RDM320X1_UNET_KWARGS, 'layout': LAYOUT_UNET_KWARGS,
+                'rdm': RDM_UNET_KWARGS}
+
+
+def synthetic_rdm_unet_state_dict(seed=0, unet_kwargs=None):
+    """CPU state_dict (reference UNetModel key names) of a seeded random retrieval-augmented UNet (or a stand-in / layout-to-image)."""
+    from .unet import UNetModelHIP
+    m = UNetModelHIP(**(unet_kwargs or RDM_UNET_KWARGS))
+    return synthetic_named_state_dict([(k, tuple(v.shape)) for k, v in m.state_dict().items()], seed)

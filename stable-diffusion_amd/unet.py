@@ -120,28 +120,33 @@ class UNetModelHIP(nn.Module):
         #   faces / bedrooms / super-resolution (models/ldm/celeba256, ffhq256, lsun_beds256: one unet_config, model_channels 224;
         #   models/ldm/bsr_sr: 160): legacy AttentionBlocks with num_head_channels=32 and num_heads left at -1 (openaimodel.py:561-563:
         #   heads = ch // 32 -> 14 / 21 / 28, 20), plain Downsample / Upsample convolutions, no scale-shift norm; widths that are
-        #   multiples of 32, not of 64 (the GEMM kernels' half k-tile).  num_head_channels with a spatial transformer stays refused.
+        #   multiples of 32, not of 64 (the GEMM kernels' half k-tile).
+        #   retrieval-augmented diffusion / layout-to-image (configs/retrieval-augmented-diffusion/768x768.yaml:19-42,
+        #   models/ldm/layout2img-openimages256/config.yaml:16-36): SD v1's SpatialTransformer blocks with num_head_channels=32 and
+        #   num_heads left at -1, legacy at its default True.  openaimodel.py:542-549 gives num_heads = ch // num_head_channels and
+        #   dim_head = num_head_channels with legacy False, and with legacy True recomputes dim_head = ch // num_heads -- the same
+        #   number wherever num_head_channels divides ch (checked against the reference module: tools/make_golden_rdm.py builds it
+        #   with either flag and gets one key list and one output).  Admitted for the head dims the tests run (ST_HEAD_CHANNELS).
         self.use_spatial_transformer = bool(use_spatial_transformer)
         unsupported = []
         if use_spatial_transformer:
             if context_dim is None: unsupported.append('use_spatial_transformer=True with context_dim')
-            if legacy and num_head_channels != -1:
-                unsupported.append('a spatial transformer with num_heads, not num_head_channels (legacy=True recomputes dim_head from it)')
             if resblock_updown: unsupported.append('resblock_updown=False with a spatial transformer')
         else:
             if context_dim is not None: unsupported.append('context_dim=None without a spatial transformer')
             if not legacy: unsupported.append('legacy=True without a spatial transformer')
             if use_new_attention_order: unsupported.append('use_new_attention_order=False (QKVAttentionLegacy)')
         nhc = num_head_channels != -1
-        if use_spatial_transformer:
-            if num_heads == -1 or nhc: unsupported.append('num_heads (not num_head_channels) with a spatial transformer')
-        elif nhc:
+        if nhc:
             # the reference asserts exactly one of the two is set (openaimodel.py:489-493) and lets num_head_channels win where both are
             if num_heads != -1: unsupported.append('num_head_channels with num_heads == -1 (one of the two, as the shipped configs)')
             chans = [model_channels * m for i, m in enumerate(channel_mult) if 2 ** i in list(attention_resolutions)]
             chans.append(model_channels * list(channel_mult)[-1])       # (the middle block)
             if num_head_channels < 1 or any(c % num_head_channels for c in chans):
                 unsupported.append(f'num_head_channels={num_head_channels} dividing every attention level ({sorted(set(chans))})')
+            elif use_spatial_transformer and num_head_channels not in self.ST_HEAD_CHANNELS:
+                unsupported.append(f'num_head_channels in {sorted(self.ST_HEAD_CHANNELS)} with a spatial transformer (the head dims this '
+                                   f'family is tested at), got num_head_channels={num_head_channels}')
         elif num_heads == -1:
             unsupported.append('num_heads or num_head_channels')
         if model_channels % 32 or (use_spatial_transformer and model_channels % 64):
@@ -161,17 +166,19 @@ class UNetModelHIP(nn.Module):
                                    'lacks: ' + ', '.join(rule))
         if num_classes is not None or n_embed is not None: unsupported.append('no class conditioning / codebook head')
         if dropout != 0: unsupported.append('dropout=0')
-        if unsupported:
-            raise NotImplementedError('UNetModelHIP supports the SD-v1, latent-inpainting, unconditional and num_head_channels AttentionBlock '
-                                      'UNet families only; needs: ' +
-                                      '; '.join(unsupported))
-        if use_spatial_transformer and hip_precision == 'full':
-            # heads wider than 160 run on the wide-head kernel (csrc/attn_wide.hip), which has no split-fp16 form
+        if use_spatial_transformer and hip_precision == 'full' and (nhc or num_heads > 0):
+            # heads wider than 160 run on the wide-head kernel (csrc/attn_wide.hip), which has no split-fp16 form.  (In front of the other
+            # refusals: with num_head_channels set the head dim is that number, and one above the limit is named as such.)
             levels = [model_channels * m for i, m in enumerate(channel_mult) if 2 ** i in list(attention_resolutions)]
-            d_max = max(levels + [model_channels * list(channel_mult)[-1]]) // num_heads
+            d_max = num_head_channels if nhc else max(levels + [model_channels * list(channel_mult)[-1]]) // num_heads
             if d_max > self.FULL_MAX_HEAD_DIM:
+                how = f'num_head_channels={num_head_channels}' if nhc else f'num_heads={num_heads}'
                 raise NotImplementedError(f"hip_precision='full' supports attention head dims up to {self.FULL_MAX_HEAD_DIM}; this "
-                                          f'configuration has d_head = {d_max} (num_heads={num_heads}): use hip_precision=\'mixed\'')
+                                          f'configuration has d_head = {d_max} ({how}): use hip_precision=\'mixed\'')
+        if unsupported:
+            raise NotImplementedError('UNetModelHIP supports the SD-v1, latent-inpainting, unconditional and num_head_channels AttentionBlock / '
+                                      'SpatialTransformer UNet families only; needs: ' +
+                                      '; '.join(unsupported))
         if isinstance(context_dim, (list, tuple)) or type(context_dim).__name__ == 'ListConfig':
             context_dim = list(context_dim)[0]
         context_dim = 0 if context_dim is None else context_dim
@@ -188,7 +195,7 @@ class UNetModelHIP(nn.Module):
         self._cfg = make_cfg(in_channels, out_channels, model_channels, num_res_blocks, self.channel_mult,
                              self.attention_resolutions, num_heads, transformer_depth, self.context_dim)
         ext = None
-        if not use_spatial_transformer or resblock_updown:
+        if not use_spatial_transformer or resblock_updown or nhc:      # (the creation flag word travels with an ext struct)
             ext = _lib.UNetExt()
             ext.attention_block, ext.resblock_updown = int(not use_spatial_transformer), int(bool(resblock_updown))
         self.num_head_channels = num_head_channels
@@ -386,6 +393,7 @@ class UNetModelHIP(nn.Module):
 
     # ---- UNetModel.forward (openaimodel.py:710-742) ----------------------------------------------------------
     FULL_MAX_HEAD_DIM = 160       # widest head of the split-fp16 attention kernel (csrc/attn_split16.hip)
+    ST_HEAD_CHANNELS = (32,)      # num_head_channels admitted with a spatial transformer: the head dims tests/test_rdm_gpu.py runs
     MAX_ROWS = 8      # rows per library call (sdmi_unet_forward); larger batches are split, rows are independent
 
     @torch.no_grad()

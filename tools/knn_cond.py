@@ -1,5 +1,5 @@
-"""The front half of the reference's `scripts/knn2img.py --use_neighbors`: prompts (or token ids) -> CLIP text embeds -> exact k-NN in a
-retrieval database -> the conditioning tensor c [B, 1 + k, D] the sampler takes.
+"""The reference's `scripts/knn2img.py --use_neighbors` up to the sampled latent: prompts (or token ids) -> CLIP text embeds -> exact k-NN in a
+retrieval database -> the conditioning tensor c [B, 1 + k, D] -> (with --unet-weights) DDIM sampling with the retrieval-augmented UNet.
 
     python tools/knn_cond.py --database DIR --knn 10 --prompt "a painting of a virus monster playing guitar" [--text-weights CKPT]
     python tools/knn_cond.py --database DIR --knn 10 --ids-file ids.txt --text-weights CKPT --out cond.pt
@@ -9,6 +9,10 @@ retrieval database -> the conditioning tensor c [B, 1 + k, D] the sampler takes.
 --ids-file       one line of whitespace-separated token ids per sample instead (no tokenizer needed)
 --text-weights   a torch checkpoint of the text encoder: an OpenAI-CLIP state dict or transformers' CLIPTextModelWithProjection one
 --queries        skip the text encoder: a `.npy` / `.pt` of query vectors [B, D] (e.g. image embeds)
+--unet-weights   also sample (knn2img.py:362-375): a torch checkpoint of the UNet (`model.diffusion_model.*` keys of the model checkpoint, or bare
+                 UNetModel keys), or `synthetic` for seeded random weights; --unet picks the configuration (rdm = the yaml; rdm64 = the
+                 64-wide stand-in), --steps / --scale / --ddim-eta / --H / --W are the script's options (uc = zeros_like(c) unless --scale 1.0),
+                 --out-latents saves samples_ddim [B, 16, H / 16, W / 16].  The KL-f16 first stage is not built yet: the latent is not decoded.
 Prints the neighbour row ids, image ids and cosines per sample; --out saves {'c', 'nns', 'scores', 'img_ids', 'patch_coords'}.
 Runs on the GPU only: there is no CPU path."""
 import argparse
@@ -43,6 +47,30 @@ def load_text_encoder(a):
     return m.cuda()
 
 
+def sample_latents(cond, a):
+    """knn2img.py:362-375 on HIP classes: uc = zeros_like(c), DDIM on a [16, H / 16, W / 16] latent"""
+    from stable_diffusion_amd import DDIMSamplerHIP, LatentDiffusionHIP, UNetModelHIP, synthetic
+    kw = synthetic.RDM_STANDINS[a.unet]
+    unet = UNetModelHIP(**kw, hip_precision=a.hip_precision)
+    if a.unet_weights == 'synthetic':
+        sd = synthetic.synthetic_named_state_dict([(k, tuple(v.shape)) for k, v in unet.state_dict().items()], 0)
+    else:
+        sd = torch.load(a.unet_weights, map_location='cpu')
+        sd = sd.get('state_dict', sd)
+        pre = 'model.diffusion_model.'
+        if any(k.startswith(pre) for k in sd):
+            sd = {k[len(pre):]: v for k, v in sd.items() if k.startswith(pre)}
+    unet.load_state_dict(sd, strict=True)
+    if cond.shape[2] != kw['context_dim']:
+        raise SystemExit(f'the conditioning has {cond.shape[2]} channels, this UNet takes context_dim = {kw["context_dim"]}')
+    ld = LatentDiffusionHIP(unet.cuda(), **synthetic.RDM_SCHEDULE).cuda()
+    uc = torch.zeros_like(cond) if a.scale != 1.0 else None
+    shape = [kw['in_channels'], a.H // 16, a.W // 16]                # (knn2img.py:366: hardcoded for the f16 model)
+    samples, _ = DDIMSamplerHIP(ld).sample(S=a.steps, conditioning=cond, batch_size=cond.shape[0], shape=shape, verbose=False,
+                                           unconditional_guidance_scale=a.scale, unconditional_conditioning=uc, eta=a.ddim_eta)
+    return samples
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument('--database', required=True)
@@ -55,7 +83,17 @@ def main():
     ap.add_argument('--tokenizer')
     ap.add_argument('--hip-precision', default='mixed', choices=['mixed', 'full'])
     ap.add_argument('--out')
+    ap.add_argument('--unet-weights')
+    ap.add_argument('--unet', default='rdm', choices=['rdm', 'rdm64'])
+    ap.add_argument('--steps', type=int, default=50)
+    ap.add_argument('--scale', type=float, default=5.0)
+    ap.add_argument('--ddim-eta', type=float, default=0.0)
+    ap.add_argument('--H', type=int, default=768)
+    ap.add_argument('--W', type=int, default=768)
+    ap.add_argument('--out-latents')
     a = ap.parse_args()
+    if a.unet_weights and (a.H % 128 or a.W % 128):
+        raise SystemExit('--H and --W must be multiples of 128 (a 16x smaller latent, halved three times by the UNet)')
     if not torch.cuda.is_available():
         raise SystemExit('knn_cond.py needs the GPU: the text encoder and the search have no CPU path')
     if a.queries:
@@ -89,6 +127,12 @@ def main():
         torch.save({'c': cond.cpu(), 'nns': torch.from_numpy(idx.astype(np.int64)), 'scores': torch.from_numpy(score),
                     'img_ids': torch.from_numpy(np.asarray(searcher.img_id[idx]).astype(np.int64)),
                     'patch_coords': torch.from_numpy(np.asarray(searcher.patch_coords[idx]))}, a.out)
+    if a.unet_weights:
+        samples = sample_latents(cond, a)
+        print(f'samples_ddim: {tuple(samples.shape)} finite {bool(torch.isfinite(samples).all())} |x| max {float(samples.abs().max()):.3f}; '
+              'not decoded: the KL-f16 first stage of this model is not built yet')
+        if a.out_latents:
+            torch.save(samples.cpu(), a.out_latents)
 
 
 if __name__ == '__main__':
