@@ -190,7 +190,8 @@ int sdmi_dpm_solver_step(const float* eps_model, int cfg, float scale, const flo
  * (ldm/modules/diffusionmodules/model.py:528-568), and `encode_first_stage` (ddpm.py:825-863) ->
  * AutoencoderKL.encode (autoencoder.py:324-328) -> Encoder.forward (model.py:427-460). */
 typedef struct sdmi_vae sdmi_vae;
-/* ddconfig of configs/stable-diffusion/v1-inference.yaml:51-65 (attn_resolutions = [], dropout 0, double_z) + embed_dim */
+/* ddconfig of configs/stable-diffusion/v1-inference.yaml:51-65 (attn_resolutions = [], dropout 0, double_z) + embed_dim
+ * (attn_resolutions != []: sdmi_vae_create_attn, below; z_channels <= 16, embed_dim <= 16, in_channels <= 16, out_ch <= 8) */
 typedef struct sdmi_vae_cfg {
   int32_t ch;
   int32_t out_ch;
@@ -225,6 +226,21 @@ int sdmi_vae_create_ext(const sdmi_vae_cfg* cfg, const sdmi_vae_ext* ext, int pa
  * ext = NULL is {1, 1, 0}.  sdmi_vae_create_ext(cfg, ext, parts, out) = sdmi_vae_create_precision(cfg, ext, parts, SDMI_PRECISION_MIXED, out). */
 int sdmi_vae_create_precision(const sdmi_vae_cfg* cfg, const sdmi_vae_ext* ext, int parts, int precision, sdmi_vae** out);
 int sdmi_vae_precision(const sdmi_vae* h);        /* SDMI_PRECISION_*, or -1 for a null handle */
+/* First stages with attention at resolution levels: `attn_resolutions` of the ddconfig (additive; sdmi_vae_cfg and sdmi_vae_ext are
+ * unchanged).  KL-f16 of the retrieval-augmented model (models/first_stage_models/kl-f16: ch 128, ch_mult [1,1,2,2,4], z_channels 16,
+ * embed_dim 16, attn_resolutions [16]) is attn_level_mask = 1 << 4.
+ *   attn_level_mask   bit l set: an AttnBlock (one head of d = ch * ch_mult[l]) follows EVERY ResBlock of level l -- encoder.down.l.attn.i
+ *                     for i < num_res_blocks, decoder.up.l.attn.i for i <= num_res_blocks (model.py:404-405, 442-444, 517-518, 553-555).
+ *                     The caller resolves attn_resolutions to levels: level l runs at resolution >> l.  Bits at or past n_levels are refused.
+ * A handle with a non-zero mask runs every attention block in mixed precision, the mid block's included, as GroupNorm -> q / k / v GEMMs ->
+ * ONE flash launch (sdmi_k_attention's kernels, d = 512 on KL-f16) -> proj_out + residual: no N x N score buffer, any latent size.  In
+ * SDMI_PRECISION_FULL the blocks are the split-fp16 ones of sdmi_vae_create_precision.  Every attention width of the handle that its mode has
+ * no kernel for (mixed: sdmi_k_attention's head dims; full: sdmi_k_attention_split16's) is refused here, by level.
+ * z_channels and embed_dim may be up to 16 (double_z: a 32-channel encoder.conv_out and a 32 -> 32 quant_conv).
+ * sdmi_vae_create_precision(cfg, ext, parts, precision, out) = sdmi_vae_create_attn(cfg, ext, parts, precision, 0, out): mask 0 launches
+ * exactly what that entry always launched. */
+int sdmi_vae_create_attn(const sdmi_vae_cfg* cfg, const sdmi_vae_ext* ext, int parts, int precision, uint32_t attn_level_mask,
+                         sdmi_vae** out);
 /* VQModelInterface.decode(h, force_not_quantize) (autoencoder.py:274-283): quantize = 1 replaces z_scale * z by its nearest
  * codebook entry first (sdmi_k_vq_quantize's arithmetic), then post_quant_conv -> decoder; quantize = 0 is sdmi_vae_decode.
  * The workspace is sdmi_vae_decode_workspace_bytes. */
@@ -606,6 +622,11 @@ int sdmi_k_conv_in(const float* x_nchw, const float* w_oihw, const float* bias, 
                    int W, int Cout, void* stream);
 int sdmi_k_conv_out(const float* h_nhwc, const float* w_ohwi, const float* bias, float* out_nchw, int B, int H, int W,
                     int Cin, int Cout, void* stream);
+/* the same 3x3 output convolution for up to 32 outputs (the KL-f16 encoder's conv_out: 2 x 16 moment channels): one launch of
+ * ceil(Cout / 8) slices of eight outputs for Cout > 8; up to 16 outputs it launches what sdmi_k_conv_out launches, which keeps refusing
+ * more than 16 */
+int sdmi_k_conv_out32(const float* h_nhwc, const float* w_ohwi, const float* bias, float* out_nchw, int B, int H, int W,
+                      int Cin, int Cout, void* stream);
 int sdmi_k_pack_conv_weight(const float* w_oihw, void* dst_f16, int O, int I, int KH, int KW, void* stream);
 /* ... for A sources that are multiples of 32 channels (c0 + c1 + c2 == I, each % 32 == 0): the 64-channel chunks are numbered per source,
  * and the last chunk of a source of 32 (mod 64) channels is 32 wide (the kernels' half k-tile).  K = KH*KW*I stays dense.  With every source
@@ -617,7 +638,8 @@ int sdmi_k_pack_split3(const float* w, void* dst_f16, int N, int K, void* stream
 /* [O][I][KH][KW] fp32 -> fp16 [O][3 KH KW I]: the 3-pass split-fp16 3x3 conv weights [w_hi | w_hi | w_lo], i.e. sdmi_k_pack_conv_weight
  * of the virtual [O][3 I][KH][KW] tensor, met by the K-concatenated operand a0 = hi, a1 = lo, a2 = hi (c0 = c1 = c2 = I); I % 32 == 0 */
 int sdmi_k_pack_conv_split3(const float* w_oihw, void* dst_f16, int O, int I, int KH, int KW, void* stream);
-/* first-stage helpers: 1x1 conv NCHW->NCHW on <= 16 channels (input pre-scaled); row softmax fp32 -> fp16 */
+/* first-stage helpers: 1x1 conv NCHW->NCHW on <= 32 input channels (input pre-scaled; Cin <= 16 and 17 .. 32 are two instantiations of
+ * one kernel, per output: bias, then the input channels ascending); row softmax fp32 -> fp16 */
 int sdmi_k_pointwise_nchw(const float* x, const float* w, const float* bias, float* out, int B, int Cin, int Cout, int HW,
                           float in_scale, void* stream);
 int sdmi_k_softmax_rows(const float* S, void* P_f16, int rows, int cols, float scale, void* stream);

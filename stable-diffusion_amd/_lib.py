@@ -100,6 +100,7 @@ _SIGS = {
     'sdmi_vae_destroy': (C.c_int, [c_ptr]),
     'sdmi_vae_create_ext': (C.c_int, [C.POINTER(VaeCfg), C.POINTER(VaeExt), C.c_int, C.POINTER(c_ptr)]),
     'sdmi_vae_create_precision': (C.c_int, [C.POINTER(VaeCfg), C.POINTER(VaeExt), C.c_int, C.c_int, C.POINTER(c_ptr)]),
+    'sdmi_vae_create_attn': (C.c_int, [C.POINTER(VaeCfg), C.POINTER(VaeExt), C.c_int, C.c_int, C.c_uint32, C.POINTER(c_ptr)]),
     'sdmi_vae_precision': (C.c_int, [c_ptr]),
     'sdmi_vae_decode_vq': (C.c_int, [c_ptr, c_ptr, C.c_float, C.c_int, c_ptr, C.c_int, C.c_int, C.c_int, c_ptr, C.c_int64, c_ptr]),
     'sdmi_k_vq_quantize': (C.c_int, [c_ptr, C.c_float, c_ptr, c_ptr, C.c_int, C.c_int, c_ptr, c_ptr, C.c_int, C.c_int, c_ptr]),
@@ -214,6 +215,7 @@ _SIGS = {
     'sdmi_k_conv_out': (C.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_ptr]),
     'sdmi_k_pack_conv_weight': (C.c_int, [c_ptr, c_ptr, C.c_int, C.c_int, C.c_int, C.c_int, c_ptr]),
     'sdmi_k_pack_conv_weight_src': (C.c_int, [c_ptr, c_ptr, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_ptr]),
+    'sdmi_k_conv_out32': (C.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_ptr]),
     'sdmi_k_pack_conv_out': (C.c_int, [c_ptr, c_ptr, C.c_int, C.c_int, c_ptr]),
     'sdmi_k_pack_split3': (C.c_int, [c_ptr, c_ptr, C.c_int, C.c_int, c_ptr]),
     'sdmi_k_pack_conv_split3': (C.c_int, [c_ptr, c_ptr, C.c_int, C.c_int, C.c_int, C.c_int, c_ptr]),

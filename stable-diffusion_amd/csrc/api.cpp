@@ -179,12 +179,16 @@ int sdmi_vae_create_ext(const sdmi_vae_cfg* cfg, const sdmi_vae_ext* ext, int pa
   return sdmi_vae_create_precision(cfg, ext, parts, SDMI_PRECISION_MIXED, out);
 }
 int sdmi_vae_create_precision(const sdmi_vae_cfg* cfg, const sdmi_vae_ext* ext, int parts, int precision, sdmi_vae** out) {
+  return sdmi_vae_create_attn(cfg, ext, parts, precision, 0u, out);
+}
+int sdmi_vae_create_attn(const sdmi_vae_cfg* cfg, const sdmi_vae_ext* ext, int parts, int precision, uint32_t attn_level_mask,
+                         sdmi_vae** out) {
   SDMI_CHECK(cfg && out, "null argument");
   SDMI_CHECK(precision == SDMI_PRECISION_MIXED || precision == SDMI_PRECISION_FULL,
              "precision must be SDMI_PRECISION_MIXED (0) or SDMI_PRECISION_FULL (1), got " + std::to_string(precision));
   sdmi_vae* h = new (std::nothrow) sdmi_vae();
   SDMI_CHECK(h != nullptr, "out of host memory");
-  if (h->impl.build(*cfg, parts, ext, precision)) { delete h; return -1; }
+  if (h->impl.build(*cfg, parts, ext, precision, attn_level_mask)) { delete h; return -1; }
   *out = h;
   return 0;
 }
@@ -712,6 +716,12 @@ int sdmi_k_conv_in(const float* x, const float* w, const float* bias, float* out
 }
 int sdmi_k_conv_out(const float* h, const float* w, const float* bias, float* out, int B, int H, int W, int Cin, int Cout,
                     void* stream) {
+  // (this entry keeps the contract it was published with, the UNet output heads': up to 16 outputs; sdmi_k_conv_out32 is the wider one)
+  SDMI_CHECK(Cout <= 16, "conv_out: out_channels <= 16 on this entry (sdmi_k_conv_out32 takes up to 32)");
+  return launch_conv_out(h, w, bias, out, B, H, W, Cin, Cout, (hipStream_t)stream);
+}
+int sdmi_k_conv_out32(const float* h, const float* w, const float* bias, float* out, int B, int H, int W, int Cin, int Cout,
+                      void* stream) {
   return launch_conv_out(h, w, bias, out, B, H, W, Cin, Cout, (hipStream_t)stream);
 }
 int sdmi_k_pack_conv_weight(const float* w, void* dst, int O, int I, int KH, int KW, void* stream) {

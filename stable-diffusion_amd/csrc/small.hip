@@ -312,18 +312,20 @@ __global__ void __launch_bounds__(256) conv_out4_kernel(const float* h, const fl
   }
 }
 
-// Output heads of 9 .. 16 channels (the retrieval-augmented UNet writes 16 latent channels).  Sixteen outputs on the 4-pixel form would be
-// 64 accumulators and 32 live weight quads per lane; instead blockIdx.y picks one half of the outputs -- n0 = 0 or 8 -- and a wave runs
-// conv_out4_kernel<8>'s loop for that half: the same register budget (no scratch: profiles/kernel_resources_conv_out16.txt), every weight
-// quad still loaded once per wave and tap; the input rows are read by both halves (the second read hits L2).  An accumulator sees exactly
-// the terms conv_out_kernel gives it, in its order: taps ascending, channel quads ascending inside a tap, out-of-image taps skipped.
-// Cin <= 512, W % COP == 0, Cout <= 2 * CO_MAXN; outputs n >= Cout of the upper half read weight row 0 and are not stored.
+// Output heads of 9 .. 32 channels (the retrieval-augmented UNet writes 16 latent channels; the KL-f16 encoder's conv_out writes the 32
+// moment channels of a 16-channel latent).  Sixteen outputs on the 4-pixel form would be 64 accumulators and 32 live weight quads per
+// lane; instead blockIdx.y picks one slice of eight outputs -- n0 = 0, 8, 16 or 24; two slices ("halves") up to 16 outputs, up to four
+// above -- and a wave runs conv_out4_kernel<8>'s loop for that slice: the same register budget (no scratch:
+// profiles/kernel_resources_conv_out16.txt, kernel_resources_conv_out32.txt), every weight quad still loaded once per wave and tap; the
+// input rows are read by every slice (the later reads hit L2).  An accumulator sees exactly the terms conv_out_kernel gives it, in its
+// order: taps ascending, channel quads ascending inside a tap, out-of-image taps skipped.
+// Cin <= 512, W % COP == 0, Cout <= 8 * gridDim.y <= 4 * CO_MAXN; outputs n >= Cout of the last slice read weight row 0 and are not stored.
 __global__ void __launch_bounds__(256) conv_out4_halves_kernel(const float* h, const float* w, const float* bias, float* out, int B,
                                                                int H, int W, int Cin, int Cout) {
   constexpr int NOUT = CO_MAXN;
   const int lane = threadIdx.x & 63;
   const int g = blockIdx.x * 4 + (threadIdx.x >> 6);       // pixel group
-  const int n0 = blockIdx.y * NOUT;                        // first output channel of this half
+  const int n0 = blockIdx.y * NOUT;                        // first output channel of this slice
   const int wq = W / COP;
   if (g >= B * H * wq) return;
   const int b = g / (H * wq), rem = g - b * H * wq, y = rem / wq, x0 = (rem - y * wq) * COP;
@@ -390,7 +392,7 @@ __global__ void __launch_bounds__(256) conv_out4_halves_kernel(const float* h, c
   }
 }
 
-// ... and the fallback (any W, any Cin % 4 == 0): conv_out_kernel's loop, one wave per output pixel and half of the outputs
+// ... and the fallback (any W, any Cin % 4 == 0): conv_out_kernel's loop, one wave per output pixel and slice of eight outputs
 __global__ void __launch_bounds__(256) conv_out_halves_kernel(const float* h, const float* w, const float* bias, float* out, int B,
                                                               int H, int W, int Cin, int Cout) {
   const int lane = threadIdx.x & 63;
@@ -615,7 +617,10 @@ __global__ void __launch_bounds__(256) gelu_split_kernel(const float* x, f16* ou
 // ---- first-stage (VAE) helpers ---------------------------------------------------------------------------------------
 // 1x1 conv on a few channels, NCHW fp32 -> NCHW fp32, input optionally pre-scaled:
 // post_quant_conv / quant_conv (ldm/models/autoencoder.py:302-303) and the 1/scale_factor of decode_first_stage
-constexpr int PW_MAXC = 16;
+// PW_MAXC: the input channels a thread keeps in registers -- 16 (every first stage with up to 8 latent channels; Cin <= 16 runs this
+// instantiation, the kernel as it always was) or 32 (the 32 -> 32 quant_conv of the KL-f16 first stage).  Per output: the bias, then the
+// input channels ascending, each input multiplied by in_scale when it is loaded.
+template <int PW_MAXC>
 __global__ void __launch_bounds__(256) pointwise_nchw_kernel(const float* x, const float* w, const float* bias, float* out,
                                                              int B, int Cin, int Cout, int HW, float in_scale) {
   const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -740,14 +745,15 @@ int launch_conv_in(const float* x, const float* w, const float* bias, float* out
 
 int launch_conv_out(const float* h, const float* w, const float* bias, float* out, int B, int H, int W, int Cin, int Cout,
                     hipStream_t s) {
-  SDMI_CHECK(Cout >= 1 && Cout <= 2 * CO_MAXN && Cin % 4 == 0, "conv_out: out_channels <= 16, Cin % 4 == 0");
+  SDMI_CHECK(Cout >= 1 && Cout <= 4 * CO_MAXN && Cin % 4 == 0, "conv_out: out_channels <= 32, Cin % 4 == 0");
   ProfScope ps("conv_out_f32", 2.0 * B * H * W * (double)Cout * Cin * 9, (double)B * H * W * (Cin + Cout) * 4.0, s);
-  if (Cout > CO_MAXN) {        // 9 .. 16 outputs: two halves of 8 in one launch (grid.y); Cout <= 8 launches what it always did, below
+  if (Cout > CO_MAXN) {        // 9 .. 32 outputs: slices of 8 in one launch (grid.y = 2, 3 or 4); Cout <= 8 launches what it always did, below
     const bool al = ((((uintptr_t)h | (uintptr_t)w | (uintptr_t)out) & 15) == 0);
+    const int slices = cdiv(Cout, CO_MAXN);      // (9 .. 16 outputs: 2, the launch they always had)
     if (W % COP == 0 && Cin <= 512 && al)
-      SDMI_LAUNCH(conv_out4_halves_kernel, dim3(cdiv(B * H * (W / COP), 4), 2), dim3(256), 0, s, h, w, bias, out, B, H, W, Cin, Cout);
+      SDMI_LAUNCH(conv_out4_halves_kernel, dim3(cdiv(B * H * (W / COP), 4), slices), dim3(256), 0, s, h, w, bias, out, B, H, W, Cin, Cout);
     else
-      SDMI_LAUNCH(conv_out_halves_kernel, dim3(cdiv(B * H * W, 4), 2), dim3(256), 0, s, h, w, bias, out, B, H, W, Cin, Cout);
+      SDMI_LAUNCH(conv_out_halves_kernel, dim3(cdiv(B * H * W, 4), slices), dim3(256), 0, s, h, w, bias, out, B, H, W, Cin, Cout);
     SDMI_HIP_OK(hipGetLastError());
     return 0;
   }
@@ -810,10 +816,11 @@ int launch_gelu_erf_split(const float* x, f16* out, f16* out_lo, int64_t n, hipS
 
 int launch_pointwise_nchw(const float* x, const float* w, const float* bias, float* out, int B, int Cin, int Cout, int HW,
                           float in_scale, hipStream_t s) {
-  SDMI_CHECK(Cin >= 1 && Cin <= PW_MAXC && Cout >= 1, "pointwise conv: 1 <= Cin <= 16");
+  SDMI_CHECK(Cin >= 1 && Cin <= 32 && Cout >= 1, "pointwise conv: 1 <= Cin <= 32");
   const int64_t total = (int64_t)B * HW;
-  SDMI_LAUNCH(pointwise_nchw_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, x, w, bias, out, B, Cin,
-                     Cout, HW, in_scale);
+  const dim3 grid((unsigned)((total + 255) / 256));
+  if (Cin <= 16) SDMI_LAUNCH(pointwise_nchw_kernel<16>, grid, dim3(256), 0, s, x, w, bias, out, B, Cin, Cout, HW, in_scale);
+  else SDMI_LAUNCH(pointwise_nchw_kernel<32>, grid, dim3(256), 0, s, x, w, bias, out, B, Cin, Cout, HW, in_scale);
   SDMI_HIP_OK(hipGetLastError());
   return 0;
 }

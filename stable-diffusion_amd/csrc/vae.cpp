@@ -10,6 +10,9 @@
 // the following implicit-GEMM conv; nin_shortcut (1x1 on the raw stream) runs as a 3-pass split-fp16 GEMM; the first
 // (z -> 512) and last (128 -> 3) convs and the two 1x1 "quant" convs are fp32.  Attention over N = H*W tokens with
 // d = C = 512 is three GEMMs (q k^T, softmax rows, P v) on the igemm kernel, in query chunks so S stays cache-sized.
+// A handle created with attention at resolution levels (sdmi_vae_create_attn, attn_level_mask != 0: KL-f16 of the retrieval-augmented model,
+// AttnBlocks after every ResBlock of the 16 x 16 level) runs every attention block, level and mid, as one flash launch instead
+// (VFwd::attn_block_flash): no S / P buffers, any token count.
 //
 // A handle created with SDMI_PRECISION_FULL (sdmi_vae_create_precision) runs the same layers with every MFMA operand as a split-fp16
 // pair, as the UNet's full-precision mode does (unet.cpp: Fwd::res_block / resample / attn_block_full): GroupNorm writes hi | lo, the
@@ -26,8 +29,14 @@
 
 namespace sdmi {
 
-int Vae::build(const sdmi_vae_cfg& c, int parts, const sdmi_vae_ext* ext, int precision) {
-  cfg_ = c; parts_ = parts; precision_ = precision;
+// head dims launch_attention instantiates (attn.hip / attn_wide.hip) among the widths a first stage can have (ch % 64 == 0 does not hold for
+// the narrow ones, which are listed for the message's sake) ...
+static bool mixed_attn_width(int d) { return d == 32 || d == 40 || d == 64 || d == 80 || d == 96 || d == 128 || d == 160 || (d > 160 && d <= 1024 && d % 64 == 0); }
+// ... and launch_attention_split16's (attn_split16.hip / attn_wide_split16.hip)
+static bool full_attn_width(int d) { return d == 64 || d == 128 || (d > 160 && d <= 1024 && d % 64 == 0); }
+
+int Vae::build(const sdmi_vae_cfg& c, int parts, const sdmi_vae_ext* ext, int precision, uint32_t attn_level_mask) {
+  cfg_ = c; parts_ = parts; precision_ = precision; attn_level_mask_ = attn_level_mask;
   if (ext) ext_ = *ext;
   SDMI_CHECK((ext_.double_z == 0 || ext_.double_z == 1) && (ext_.mid_attn == 0 || ext_.mid_attn == 1) && ext_.n_embed >= 0,
              "first-stage extension: double_z and mid_attn are 0 or 1, n_embed >= 0");
@@ -36,16 +45,37 @@ int Vae::build(const sdmi_vae_cfg& c, int parts, const sdmi_vae_ext* ext, int pr
   SDMI_CHECK(parts >= 1 && parts <= 3, "parts: 1 decoder, 2 encoder, 3 both");
   SDMI_CHECK(c.n_levels >= 1 && c.n_levels <= 8 && c.num_res_blocks >= 1, "bad level / res block count");
   SDMI_CHECK(c.ch % 64 == 0, "ch must be a multiple of 64 on this path");
-  SDMI_CHECK(c.in_channels >= 1 && c.in_channels <= 16 && c.z_channels >= 1 && c.z_channels <= 4 && c.embed_dim >= 1 &&
-                 c.embed_dim <= 8 && c.out_ch >= 1 && c.out_ch <= 8,
-             "in_channels <= 16, z_channels <= 4, embed_dim <= 8, out_ch <= 8 on this path");
+  // (z_channels 16 / embed_dim 16 with double_z: encoder.conv_out writes 32 channels, quant_conv reads 32 -- launch_conv_out's and
+  // launch_pointwise_nchw's limits; decoder.conv_in reads 16 -- launch_conv_in's)
+  SDMI_CHECK(c.in_channels >= 1 && c.in_channels <= 16 && c.z_channels >= 1 && c.z_channels <= 16 && c.embed_dim >= 1 &&
+                 c.embed_dim <= 16 && c.out_ch >= 1 && c.out_ch <= 8,
+             "in_channels <= 16, z_channels <= 16, embed_dim <= 16, out_ch <= 8 on this path");
   const int n = c.n_levels;
+  SDMI_CHECK((attn_level_mask >> n) == 0, "attn_level_mask " + std::to_string(attn_level_mask) + " names a level past the last one (" +
+             std::to_string(n) + " levels)");
   if (full() && ext_.mid_attn) {       // the mid-block attention is single-headed at d = the mid width
     const int d = c.ch * c.ch_mult[n - 1];
-    const bool narrow = d == 64 || d == 128, wide = d > 160 && d <= 1024 && d % 64 == 0;
-    SDMI_CHECK(narrow || wide, "full-precision first stage: mid-block attention width " + std::to_string(d) +
+    SDMI_CHECK(full_attn_width(d), "full-precision first stage: mid-block attention width " + std::to_string(d) +
                " has no split-fp16 attention kernel (64, 128, and 192 .. 1024 in steps of 64)");
   }
+  // a handle with level attention runs every mixed-precision attention block, the mid block's too, as one flash launch at d = its width
+  // (a handle without keeps the GEMM / softmax / GEMM form, which takes any width)
+  if (!full() && attn_level_mask && ext_.mid_attn) {
+    const int d = c.ch * c.ch_mult[n - 1];
+    SDMI_CHECK(mixed_attn_width(d), "first stage with level attention: mid-block attention width " + std::to_string(d) +
+               " has no attention kernel (32 / 40 / 64 / 80 / 96 / 128 / 160, and 192 .. 1024 in steps of 64)");
+  }
+  for (int lvl = 0; lvl < n; ++lvl) {
+    if (!((attn_level_mask >> lvl) & 1)) continue;
+    const int d = c.ch * c.ch_mult[lvl];
+    if (full())
+      SDMI_CHECK(full_attn_width(d), "full-precision first stage: level " + std::to_string(lvl) + " attention width " + std::to_string(d) +
+                 " has no split-fp16 attention kernel (64, 128, and 192 .. 1024 in steps of 64)");
+    else
+      SDMI_CHECK(mixed_attn_width(d), "first stage: level " + std::to_string(lvl) + " attention width " + std::to_string(d) +
+                 " has no attention kernel (32 / 40 / 64 / 80 / 96 / 128 / 160, and 192 .. 1024 in steps of 64)");
+  }
+  auto level_attn = [&](int lvl) { return ((attn_level_mask >> lvl) & 1) != 0; };
   const WKind conv_kind = full() ? W_CONV_SPLIT3 : W_CONV;
   const WKind lin_kind = full() ? W_SPLIT3 : W_ROWS16;
   auto res = [&](const std::string& p, int ci, int co) { VLayer L; L.kind = V_RES; L.prefix = p; L.cin = ci; L.cout = co; return L; };
@@ -61,6 +91,7 @@ int Vae::build(const sdmi_vae_cfg& c, int parts, const sdmi_vae_ext* ext, int pr
       for (int i = 0; i <= c.num_res_blocks; ++i) {
         dec_.push_back(res("decoder.up." + std::to_string(lvl) + ".block." + std::to_string(i), bi, bo));
         bi = bo;
+        if (level_attn(lvl)) dec_.push_back(one(V_ATTN, "decoder.up." + std::to_string(lvl) + ".attn." + std::to_string(i), bi));   // model.py:553-555
       }
       if (lvl != 0) dec_.push_back(one(V_UP, "decoder.up." + std::to_string(lvl) + ".upsample", bi));
     }
@@ -73,6 +104,7 @@ int Vae::build(const sdmi_vae_cfg& c, int parts, const sdmi_vae_ext* ext, int pr
       for (int i = 0; i < c.num_res_blocks; ++i) {
         enc_.push_back(res("encoder.down." + std::to_string(lvl) + ".block." + std::to_string(i), bi, bo));
         bi = bo;
+        if (level_attn(lvl)) enc_.push_back(one(V_ATTN, "encoder.down." + std::to_string(lvl) + ".attn." + std::to_string(i), bi));   // model.py:442-444
       }
       if (lvl != n - 1) enc_.push_back(one(V_DOWN, "encoder.down." + std::to_string(lvl) + ".downsample", bi));
     }
@@ -181,6 +213,7 @@ int Vae::finalize() {
 struct VFwd : FwdBase {
   static constexpr float EPS = 1e-6f;        // Normalize(): GroupNorm(32, eps=1e-6)   model.py:37-38
   bool full = false;                         // the handle's precision (Vae::full())
+  bool flash = false;                        // the handle has level attention (Vae::attn_level_mask_ != 0): attn_block_flash, not attn_block
 
   // SDMI_PRECISION_FULL: the 3x3 convs take split-fp16 operands (FwdBase::split3 against weights packed W_CONV_SPLIT3; the `_lo` buffers
   // below are null in the mixed mode), and no GEMM is split along K: every output element is then summed over K in one fixed order
@@ -312,6 +345,45 @@ struct VFwd : FwdBase {
     return out;
   }
 
+  // AttnBlock on a handle with level attention (Vae::attn_level_mask_ != 0), mixed precision, level and mid block alike: GroupNorm, the
+  // q / k / v GEMMs scattering their fp16 outputs straight into the flash kernels' layouts (EPI_HEADS with one head of d = C: q, k as
+  // [B][N][C], v as V^T [B][C][Np]), ONE flash launch (attn.hip up to d = 160, attn_wide.hip for 192 .. 1024: d = 512 on KL-f16),
+  // proj_out with the residual.  No S / P buffers (attn_block's are QC x N: 2304 x 2304 at the native 48 x 48 latent, per image and block)
+  // and no N % 64 rule: the flash kernels mask the keys past nkv, so any H x W runs.
+  // The v bias is added INSIDE the v GEMM (its epilogue, before the fp16 rounding of V^T), where attn_block adds it after P V; the pad
+  // columns N .. Np - 1 of V^T are zeroed first, as the kernels' contract asks (AttnParams::vt).
+  Act attn_block_flash(VLayer& L, const Act& x) {
+    const int H = x.H, W = x.W, N = H * W, M = B * N, C = L.cin;
+    const int Np = (int)round_up(N, 8);
+    const size_t mark = scratch.off;
+    f16* xn = S<f16>((size_t)M * C);
+    groupnorm(x, nullptr, L.f32[0], L.f32[1], EPS, 0, xn, nullptr, nullptr);
+    f16* qkv[3] = {S<f16>((size_t)M * C), S<f16>((size_t)M * C), S<f16>((size_t)B * C * Np)};
+    f16* ao = S<f16>((size_t)M * C);
+    if (!dry && !rc && Np != N) {
+      hipError_t e = memset_async(qkv[2], 0, (size_t)B * C * Np * sizeof(f16), s);
+      if (e != hipSuccess) ok(fail(std::string("hipMemsetAsync: ") + hipGetErrorString(e)));
+    }
+    for (int i = 0; i < 3; ++i) {
+      IGemmParams p = dense(xn, M, C, L.w16[i], C, N);
+      p.mode = EPI_HEADS; p.bias = L.f32[2 + i]; p.seg_dst[0] = qkv[i]; p.seg_kind[0] = i == 2 ? 1 : 0;
+      p.heads = 1; p.dh = C; p.ntok = N; p.ntok_pad = Np; p.segC = C; p.splitk = 1;
+      gemm(p);
+    }
+    AttnParams a = AttnParams();
+    a.q = qkv[0]; a.k = qkv[1]; a.vt = qkv[2]; a.out = ao; a.BH = B; a.heads = 1; a.nq = N; a.nkv = N; a.nkv_pad = Np; a.d = C;
+    a.scale = 1.0f / sqrtf((float)C);
+    if (!dry && !rc) ok(launch_attention(a, s));
+    Act out; out.p = P<float>((size_t)M * C); out.C = C; out.H = H; out.W = W;
+    {
+      IGemmParams p = dense(ao, M, C, L.w16[3], C, N);
+      p.bias = L.f32[5]; p.residual = x.p; p.ldr = C; p.out_f32 = out.p; p.ldo = C;
+      gemm(p);
+    }
+    scratch.off = mark;
+    return out;
+  }
+
   Act resample(VLayer& L, const Act& x, bool up) {   // model.py:41-79
     const int Hin = x.H, Win = x.W, C = x.C;
     if (!up && ((Hin | Win) & 1)) ok(fail("first-stage Downsample needs even H and W"));
@@ -336,7 +408,7 @@ struct VFwd : FwdBase {
   Act run_layer(VLayer& L, const Act& x) {
     switch (L.kind) {
       case V_RES: return res_block(L, x);
-      case V_ATTN: return full ? attn_block_full(L, x) : attn_block(L, x);
+      case V_ATTN: return full ? attn_block_full(L, x) : (flash ? attn_block_flash(L, x) : attn_block(L, x));
       case V_UP: return resample(L, x, true);
       case V_DOWN: return resample(L, x, false);
     }
@@ -384,7 +456,7 @@ int Vae::decode(const float* z, float z_scale, float* img, int B, int H, int W, 
   SDMI_CHECK(H >= 1 && W >= 1, "bad shape");
   SDMI_CHECK(dry || (z != nullptr && img != nullptr), "z / img is NULL");
   VFwd f;
-  f.s = stream; f.B = B; f.zero = store_.zero(); f.precise_1x1 = precise_1x1_; f.full = full();
+  f.s = stream; f.B = B; f.zero = store_.zero(); f.precise_1x1 = precise_1x1_; f.full = full(); f.flash = attn_level_mask_ != 0;
   const int n = cfg_.n_levels, c_in = cfg_.ch * cfg_.ch_mult[n - 1];
   return run_two_pass(f, dry, workspace, ws_bytes, bytes_needed, [&](VFwd& f) -> int {
     const bool d = f.dry;
@@ -415,7 +487,7 @@ int Vae::encode(const float* img, float* moments, int B, int H, int W, void* wor
   SDMI_CHECK(H >= fct && W >= fct && H % fct == 0 && W % fct == 0, "H and W must be multiples of 2^(levels-1)");
   SDMI_CHECK(dry || (img != nullptr && moments != nullptr), "img / moments is NULL");
   VFwd f;
-  f.s = stream; f.B = B; f.zero = store_.zero(); f.precise_1x1 = precise_1x1_; f.full = full();
+  f.s = stream; f.B = B; f.zero = store_.zero(); f.precise_1x1 = precise_1x1_; f.full = full(); f.flash = attn_level_mask_ != 0;
   return run_two_pass(f, dry, workspace, ws_bytes, bytes_needed, [&](VFwd& f) -> int {
     const bool d = f.dry;
     Act x; x.p = f.P<float>((size_t)B * H * W * cfg_.ch); x.C = cfg_.ch; x.H = H; x.W = W;

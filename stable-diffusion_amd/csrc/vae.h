@@ -29,7 +29,10 @@ class Vae {
   Vae(const Vae&) = delete;
   Vae& operator=(const Vae&) = delete;
 
-  int build(const sdmi_vae_cfg& cfg, int parts, const sdmi_vae_ext* ext = nullptr, int precision = SDMI_PRECISION_MIXED);
+  // attn_level_mask: bit l set = an AttnBlock follows every ResBlock of level l, in the encoder (down.l.attn.i) and in the decoder
+  // (up.l.attn.i): the reference's attn_resolutions, resolved to levels by the caller (sdmi_vae_create_attn)
+  int build(const sdmi_vae_cfg& cfg, int parts, const sdmi_vae_ext* ext = nullptr, int precision = SDMI_PRECISION_MIXED,
+            uint32_t attn_level_mask = 0);
   int set_weight(const char* key, const float* ptr, const int64_t* shape, int ndim, hipStream_t stream);
   int finalize();
   // z [B, embed_dim, H, W] fp32 NCHW -> img [B, out_ch, H*f, W*f] fp32 NCHW; z is multiplied by z_scale first
@@ -53,6 +56,9 @@ class Vae {
   // (vae.cpp: VFwd); fixed at creation, the weights are packed for it
   int precision_ = SDMI_PRECISION_MIXED;
   bool full() const { return precision_ == SDMI_PRECISION_FULL; }
+  // levels with attention after every ResBlock; non-zero also moves every mixed-precision attention block of the handle, the mid block's
+  // included, to the flash form (vae.cpp: VFwd::attn_block_flash).  0: the handle launches what it launched before the mask existed
+  uint32_t attn_level_mask_ = 0;
 
  private:
   friend struct VFwd;

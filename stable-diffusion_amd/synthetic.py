@@ -282,3 +282,28 @@ def synthetic_rdm_unet_state_dict(seed=0, unet_kwargs=None):
     from .unet import UNetModelHIP
     m = UNetModelHIP(**(unet_kwargs or RDM_UNET_KWARGS))
     return synthetic_named_state_dict([(k, tuple(v.shape)) for k, v in m.state_dict().items()], seed)
+
+
+# ---- KL-f16, the first stage of the retrieval-augmented model (models/first_stage_models/kl-f16) ------------------------------------------
+# AttnBlocks after every ResBlock of the 16 x 16 level (level 4: d = 512), 16 latent channels: a 32-channel encoder.conv_out and quant_conv
+KL_F16_DDCONFIG = dict(double_z=True, z_channels=16, resolution=256, in_channels=3, out_ch=3, ch=128, ch_mult=[1, 1, 2, 2, 4],
+                       num_res_blocks=2, attn_resolutions=[16], dropout=0.0)                                   # 768x768.yaml:48-64
+KL_F16_KWARGS = dict(embed_dim=16, ddconfig=KL_F16_DDCONFIG)                                                   # yaml:47
+KL_F16_SCALE_FACTOR = 0.22765929                                                                               # yaml:13
+# stand-ins for the tests.  kl_f16_thin: the yaml at ch 64 -- level attention at d = 256 (the wide flash kernel), z = 16.  kl_narrow: two levels
+# with attention on the lower one at d = 128 (attn.hip), z = 4.  kl_two_levels: the same with attention on both levels (two mask bits), d = 64
+# at the full image resolution.
+KL_F16_THIN_DDCONFIG = dict(KL_F16_DDCONFIG, ch=64)
+KL_NARROW_DDCONFIG = dict(double_z=True, z_channels=4, resolution=32, in_channels=3, out_ch=3, ch=64, ch_mult=[1, 2], num_res_blocks=2,
+                          attn_resolutions=[16], dropout=0.0)
+KL_TWO_LEVELS_DDCONFIG = dict(KL_NARROW_DDCONFIG, attn_resolutions=[32, 16])
+KL_F16_STANDINS = {'kl_f16': KL_F16_KWARGS, 'kl_f16_thin': dict(embed_dim=16, ddconfig=KL_F16_THIN_DDCONFIG),
+                   'kl_narrow': dict(embed_dim=4, ddconfig=KL_NARROW_DDCONFIG), 'kl_two_levels': dict(embed_dim=4, ddconfig=KL_TWO_LEVELS_DDCONFIG)}
+
+
+def synthetic_kl_f16_state_dict(seed=0, kwargs=None):
+    """CPU state_dict (reference AutoencoderKL key names) of a seeded random KL-f16 first stage (or a stand-in)."""
+    from .vae import AutoencoderKLHIP
+    kw = kwargs or KL_F16_KWARGS
+    m = AutoencoderKLHIP(kw['ddconfig'], None, kw['embed_dim'])
+    return synthetic_named_state_dict([(k, tuple(v.shape)) for k, v in m.state_dict().items()], seed)

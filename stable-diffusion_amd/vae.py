@@ -57,11 +57,35 @@ def _check_precision(hip_precision):
     return hip_precision
 
 
+def attn_level_mask(ddconfig):
+    """`attn_resolutions` resolved to levels the way Encoder.__init__ / Decoder.__init__ do (model.py:389-411, 481-524): level l runs at
+    curr_res = resolution // 2**l and gets an AttnBlock after every ResBlock when that value is in attn_resolutions.  Returns the bit mask
+    (bit l = level l) sdmi_vae_create_attn takes.  An entry that names no level is refused, by name: the reference would silently build a
+    model without that attention, and a config that means something else than it says is not run."""
+    dd = dict(ddconfig)
+    wanted = [int(r) for r in dd.get('attn_resolutions', [])]
+    if not wanted:
+        return 0
+    n = len(list(dd.get('ch_mult', (1, 2, 4, 8))))
+    res = int(dd['resolution'])
+    enc = [res // 2 ** l for l in range(n)]                              # Encoder: curr_res //= 2 after every level but the last
+    dec = [(res // 2 ** (n - 1)) * 2 ** (n - 1 - l) for l in range(n)]   # Decoder: from the lowest level up, curr_res *= 2
+    missing = [r for r in wanted if r not in enc]
+    if missing or enc != dec:
+        raise NotImplementedError(
+            f'attn_resolutions entry {missing[0] if missing else wanted[0]} names no level of this first stage: the levels run at '
+            f'resolutions {enc}' + ('' if enc == dec else f' in the encoder and {dec} in the decoder') +
+            ' (resolution // 2**level); AutoencoderKLHIP does not drop an attention the config asks for')
+    return sum(1 << l for l in range(n) if enc[l] in wanted)
+
+
 def make_vae_cfg(ddconfig, embed_dim, vq=False):
-    """vq: the VQModelInterface family (double_z False, attn_type 'vanilla' or 'none'); else the SD-v1 AutoencoderKL one."""
+    """vq: the VQModelInterface family (double_z False, attn_type 'vanilla' or 'none', no attn_resolutions); else the AutoencoderKL one
+    (SD-v1's KL-f8, and KL-f16 with attention at resolution levels: attn_level_mask)."""
     dd = dict(ddconfig)
     unsupported = []
-    if list(dd.get('attn_resolutions', [])): unsupported.append('attn_resolutions=[] (mid-block attention only)')
+    if vq and list(dd.get('attn_resolutions', [])): unsupported.append('attn_resolutions=[] (mid-block attention only)')
+    if not vq: attn_level_mask(dd)           # (refuses an entry that names no level)
     if dd.get('dropout', 0.0) != 0: unsupported.append('dropout=0')
     if vq:
         if dd.get('double_z', True): unsupported.append('double_z=False')
@@ -90,12 +114,15 @@ def make_vae_cfg(ddconfig, embed_dim, vq=False):
 class _VaeHandle:
     """Owns one sdmi_vae*."""
 
-    def __init__(self, cfg, parts, ext=None, precision='mixed'):
+    def __init__(self, cfg, parts, ext=None, precision='mixed', attn_mask=0):
         self.lib = _lib.load()
         self.h = None
         h = C.c_void_p()
-        _lib.check(self.lib.sdmi_vae_create_precision(C.byref(cfg), None if ext is None else C.byref(ext), parts,
-                                                      PRECISIONS[precision], C.byref(h)))
+        e = None if ext is None else C.byref(ext)
+        if attn_mask:       # (a handle without level attention is created by the entry it always was)
+            _lib.check(self.lib.sdmi_vae_create_attn(C.byref(cfg), e, parts, PRECISIONS[precision], attn_mask, C.byref(h)))
+        else:
+            _lib.check(self.lib.sdmi_vae_create_precision(C.byref(cfg), e, parts, PRECISIONS[precision], C.byref(h)))
         self.h = h
 
     def weight_specs(self):
@@ -124,8 +151,9 @@ class AutoencoderKLHIP(nn.Module):
     def __init__(self, ddconfig, lossconfig=None, embed_dim=4, ckpt_path=None, ignore_keys=[], image_key='image',
                  colorize_nlabels=None, monitor=None, parts=3, hip_precision='mixed'):
         """`hip_precision` (not a keyword of the reference AutoencoderKL): 'mixed' (default) = fp16 MFMA operands; 'full' = every MFMA
-        operand of the ResBlocks, the resampling convs and the mid-block attention is a split-fp16 pair (three MFMA passes), as in
-        UNetModelHIP's full mode.  Fixed for the module's lifetime; the state_dict keys are the same in both modes."""
+        operand of the ResBlocks, the resampling convs and the attention blocks is a split-fp16 pair (three MFMA passes), as in
+        UNetModelHIP's full mode.  Fixed for the module's lifetime; the state_dict keys are the same in both modes.
+        `ddconfig['attn_resolutions']` (KL-f16: [16]) puts an AttnBlock behind every ResBlock of the levels it names (attn_level_mask)."""
         super().__init__()
         self.hip_precision = _check_precision(hip_precision)
         self.image_key = image_key
@@ -133,7 +161,8 @@ class AutoencoderKLHIP(nn.Module):
         self.ddconfig = dict(ddconfig)
         self._cfg = make_vae_cfg(ddconfig, embed_dim)
         self._parts = parts
-        self._handle = _VaeHandle(self._cfg, parts, None, hip_precision)
+        self.attn_level_mask = attn_level_mask(ddconfig)      # attn_resolutions as levels (0: mid-block attention only)
+        self._handle = _VaeHandle(self._cfg, parts, None, hip_precision, self.attn_level_mask)
         self._specs = self._handle.weight_specs()
         for key, shape in self._specs:
             *path, leaf = key.split('.')

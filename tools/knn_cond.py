@@ -1,5 +1,6 @@
-"""The reference's `scripts/knn2img.py --use_neighbors` up to the sampled latent: prompts (or token ids) -> CLIP text embeds -> exact k-NN in a
-retrieval database -> the conditioning tensor c [B, 1 + k, D] -> (with --unet-weights) DDIM sampling with the retrieval-augmented UNet.
+"""The reference's `scripts/knn2img.py --use_neighbors`: prompts (or token ids) -> CLIP text embeds -> exact k-NN in a retrieval database ->
+the conditioning tensor c [B, 1 + k, D] -> (with --unet-weights) DDIM sampling with the retrieval-augmented UNet -> decode_first_stage with
+the KL-f16 first stage -> PNGs.
 
     python tools/knn_cond.py --database DIR --knn 10 --prompt "a painting of a virus monster playing guitar" [--text-weights CKPT]
     python tools/knn_cond.py --database DIR --knn 10 --ids-file ids.txt --text-weights CKPT --out cond.pt
@@ -12,7 +13,10 @@ retrieval database -> the conditioning tensor c [B, 1 + k, D] -> (with --unet-we
 --unet-weights   also sample (knn2img.py:362-375): a torch checkpoint of the UNet (`model.diffusion_model.*` keys of the model checkpoint, or bare
                  UNetModel keys), or `synthetic` for seeded random weights; --unet picks the configuration (rdm = the yaml; rdm64 = the
                  64-wide stand-in), --steps / --scale / --ddim-eta / --H / --W are the script's options (uc = zeros_like(c) unless --scale 1.0),
-                 --out-latents saves samples_ddim [B, 16, H / 16, W / 16].  The KL-f16 first stage is not built yet: the latent is not decoded.
+                 --out-latents saves samples_ddim [B, 16, H / 16, W / 16].
+--vae-weights    the KL-f16 first stage that decodes samples_ddim (knn2img.py:377-378: decode_first_stage, clamp((x + 1) / 2, 0, 1)): a torch
+                 checkpoint (`first_stage_model.*` keys of the model checkpoint, or bare AutoencoderKL keys), or `synthetic`; default: whatever
+                 --unet-weights is (the model checkpoint holds both).  --outdir (default .) receives one PNG per sample, knn_00000.png ...
 Prints the neighbour row ids, image ids and cosines per sample; --out saves {'c', 'nns', 'scores', 'img_ids', 'patch_coords'}.
 Runs on the GPU only: there is no CPU path."""
 import argparse
@@ -71,6 +75,33 @@ def sample_latents(cond, a):
     return samples
 
 
+def decode_latents(samples, a):
+    """knn2img.py:377-386: x = decode_first_stage(samples_ddim) with the yaml's scale_factor, clamp((x + 1) / 2, 0, 1), one PNG per sample"""
+    from PIL import Image
+    from stable_diffusion_amd import AutoencoderKLHIP, synthetic
+    kw = synthetic.KL_F16_KWARGS
+    vae = AutoencoderKLHIP(kw['ddconfig'], None, kw['embed_dim'], parts=1, hip_precision=a.hip_precision)
+    src = a.vae_weights or a.unet_weights
+    if src == 'synthetic':
+        sd = synthetic.synthetic_named_state_dict([(k, tuple(v.shape)) for k, v in vae.state_dict().items()], 0)
+    else:
+        sd = torch.load(src, map_location='cpu')
+        sd = sd.get('state_dict', sd)
+        pre = 'first_stage_model.'
+        if any(k.startswith(pre) for k in sd):
+            sd = {k[len(pre):]: v for k, v in sd.items() if k.startswith(pre)}
+        sd = {k: v for k, v in sd.items() if k in vae.state_dict()}          # (a decoder-only handle: encoder.* / loss.* are not its keys)
+    vae.load_state_dict(sd, strict=True)
+    x = vae.cuda().decode_first_stage(samples, scale_factor=synthetic.KL_F16_SCALE_FACTOR)
+    x = torch.clamp((x + 1.0) / 2.0, min=0.0, max=1.0)
+    os.makedirs(a.outdir, exist_ok=True)
+    paths = []
+    for i, img in enumerate((255.0 * x).permute(0, 2, 3, 1).cpu().numpy()):
+        paths.append(os.path.join(a.outdir, f'knn_{i:05d}.png'))
+        Image.fromarray(img.astype(np.uint8)).save(paths[-1])
+    return x, paths
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument('--database', required=True)
@@ -91,6 +122,8 @@ def main():
     ap.add_argument('--H', type=int, default=768)
     ap.add_argument('--W', type=int, default=768)
     ap.add_argument('--out-latents')
+    ap.add_argument('--vae-weights')
+    ap.add_argument('--outdir', default='.')
     a = ap.parse_args()
     if a.unet_weights and (a.H % 128 or a.W % 128):
         raise SystemExit('--H and --W must be multiples of 128 (a 16x smaller latent, halved three times by the UNet)')
@@ -129,10 +162,11 @@ def main():
                     'patch_coords': torch.from_numpy(np.asarray(searcher.patch_coords[idx]))}, a.out)
     if a.unet_weights:
         samples = sample_latents(cond, a)
-        print(f'samples_ddim: {tuple(samples.shape)} finite {bool(torch.isfinite(samples).all())} |x| max {float(samples.abs().max()):.3f}; '
-              'not decoded: the KL-f16 first stage of this model is not built yet')
+        print(f'samples_ddim: {tuple(samples.shape)} finite {bool(torch.isfinite(samples).all())} |x| max {float(samples.abs().max()):.3f}')
         if a.out_latents:
             torch.save(samples.cpu(), a.out_latents)
+        x, paths = decode_latents(samples, a)
+        print(f'x_samples_ddim: {tuple(x.shape)} finite {bool(torch.isfinite(x).all())} mean {float(x.mean()):.3f}; wrote {", ".join(paths)}')
 
 
 if __name__ == '__main__':
