@@ -668,6 +668,27 @@ int sdmi_k_patch_unfold(const float* x, const float* c, float* out, int B, int C
                         int l0, int nl, void* stream);
 int sdmi_k_patch_fold(const float* o, const float* w, float* out, int B, int C, int H, int W, int kh, int kw, int sy, int sx, int uf, int df,
                       int norm_only, void* stream);
+/* SpatialRescaler.forward (modules.py:125-132), method 'bilinear', multiplier 0.5: x fp32 NCHW [B, Cin, H, W] -> out fp32 NCHW
+ * [B, Cout, H >> n, W >> n] (w [Cout, Cin], bias [Cout] or NULL), or [B, Cin, H >> n, W >> n] with w == NULL (no channel_mapper).
+ * Additive entry points, ABI 17.  The arithmetic is this library's definition:
+ *   - one stage: out[i][j] = ((a + b) + (c + d)) * 0.25f with a b at row 2i, cols 2j, 2j+1 and c d at row 2i+1; every stage is rounded
+ *     to fp32, no FP contraction.  bilinear at scale 0.5 with align_corners=False samples exactly between two pixels, so an odd last row
+ *     or column is never read and the output is H >> n by W >> n.  (torch's CPU kernel sums the four taps in an order that varies with
+ *     the shape; the scalings are exact, so the orders differ only in how the sum is rounded.)
+ *   - channel map: out[o] = bias[o] + sum_c w[o][c] p[c] in fp32 (fused multiply-add).  Channels go in chunks of 8 round-robin to 8 waves;
+ *     a wave sums its channels in ascending order and the 8 wave sums are added to the bias in ascending wave order.  The summation tree
+ *     is a function of Cin alone -- never of B, H, W, the load path or the launch geometry; no atomics: two runs give the same bits.
+ *   - sdmi_k_spatial_rescale_labels: labels int32 [B, H, W], class c of a pixel = channel c of its one-hot row; x is never built.
+ *     p[c] = count_c * 2^(-2n) over the pixel's block for every class in ascending order through the same accumulation code: the output is
+ *     bit-identical to sdmi_k_spatial_rescale on one_hot(labels).  A label outside [0, Cin) matches no class (the caller checks the range).
+ * 16-byte loads when W % 4 == 0 (n = 2), 8-byte loads when W % 2 == 0 (n = 1), and the pointer is 16-byte aligned; element loads that give
+ * the same bits otherwise.  Offsets are 64-bit.
+ * Refused (-1, nothing launched): n_stages outside 0 .. 2; Cout outside 1 .. 8 with w set; Cin < 1; B < 1; H or W below 2^n; null x /
+ * labels / out; bias without w; the label entry without w. */
+int sdmi_k_spatial_rescale(const float* x, const float* w, const float* bias, float* out, int B, int Cin, int H, int W, int n_stages,
+                           int Cout, void* stream);
+int sdmi_k_spatial_rescale_labels(const int32_t* labels, const float* w, const float* bias, float* out, int B, int Cin, int H, int W,
+                                  int n_stages, int Cout, void* stream);
 int sdmi_k_gelu_erf(const float* x, void* out_f16, int64_t n, void* stream);
 /* CLIP's quick_gelu, x * sigmoid(1.702 x): fp32 [n] -> fp16 [n], n % 4 == 0 (the mixed text encoder's feed-forward activation) */
 int sdmi_k_quick_gelu(const float* x, void* out_f16, int64_t n, void* stream);

@@ -13,6 +13,8 @@ this package is the host-side mirror of the reference's interfaces for that path
     BERTEmbedderHIP   <- ldm.modules.encoders.modules.BERTEmbedder (the LAION-400M model's text encoder)
     ClassEmbedderHIP  <- ldm.modules.encoders.modules.ClassEmbedder (the class-conditional ImageNet model's conditioner)
     SuperResolutionHIP <- LatentDiffusion at models/ldm/bsr_sr (tiled x4 super-resolution: split_input_params)
+    SpatialRescalerHIP <- ldm.modules.encoders.modules.SpatialRescaler (the semantic-synthesis models' cond stage)
+    SemanticSynthesisHIP <- LatentDiffusion at models/ldm/semantic_synthesis256 / 512 (an image from a segmentation map)
     CLIPVisionHIP     <- transformers.CLIPVisionModelWithProjection (the tower of the two modules below)
     StableDiffusionSafetyCheckerHIP <- diffusers' StableDiffusionSafetyChecker (scripts/txt2img.py:check_safety)
     FrozenClipImageEmbedderHIP <- ldm.modules.encoders.modules.FrozenClipImageEmbedder
@@ -30,8 +32,10 @@ from .bert import BERTEmbedderHIP  # noqa: F401
 from .class_embedder import ClassEmbedderHIP  # noqa: F401
 from .ldm_shim import LatentDiffusionHIP, DiffusionWrapperHIP  # noqa: F401
 from .superres import SuperResolutionHIP  # noqa: F401
+from .rescaler import SpatialRescalerHIP  # noqa: F401
+from .semantic import SemanticSynthesisHIP  # noqa: F401
 from .vision import CLIPVisionHIP, StableDiffusionSafetyCheckerHIP, FrozenClipImageEmbedderHIP  # noqa: F401
 from .retrieval import SearcherHIP  # noqa: F401
 from . import debug, postprocess  # noqa: F401
 
-__all__ = ['UNetModelHIP', 'AutoencoderKLHIP', 'VQModelInterfaceHIP', 'FrozenCLIPEmbedderHIP', 'BERTEmbedderHIP', 'ClassEmbedderHIP', 'PLMSSamplerHIP', 'DDIMSamplerHIP', 'DPMSolverSamplerHIP', 'LatentDiffusionHIP', 'DiffusionWrapperHIP', 'SuperResolutionHIP', 'CLIPVisionHIP', 'StableDiffusionSafetyCheckerHIP', 'FrozenClipImageEmbedderHIP', 'FrozenCLIPTextEmbedderHIP', 'SearcherHIP']
+__all__ = ['UNetModelHIP', 'AutoencoderKLHIP', 'VQModelInterfaceHIP', 'FrozenCLIPEmbedderHIP', 'BERTEmbedderHIP', 'ClassEmbedderHIP', 'PLMSSamplerHIP', 'DDIMSamplerHIP', 'DPMSolverSamplerHIP', 'LatentDiffusionHIP', 'DiffusionWrapperHIP', 'SuperResolutionHIP', 'SpatialRescalerHIP', 'SemanticSynthesisHIP', 'CLIPVisionHIP', 'StableDiffusionSafetyCheckerHIP', 'FrozenClipImageEmbedderHIP', 'FrozenCLIPTextEmbedderHIP', 'SearcherHIP']

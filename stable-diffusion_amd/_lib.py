@@ -107,6 +107,8 @@ _SIGS = {
     'sdmi_k_patch_unfold': (C.c_int, [c_ptr, c_ptr, c_ptr] + [C.c_int] * 11 + [c_ptr]),
     'sdmi_k_patch_fold': (C.c_int, [c_ptr, c_ptr, c_ptr] + [C.c_int] * 11 + [c_ptr]),
     'sdmi_k_resample2': (C.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_ptr]),
+    'sdmi_k_spatial_rescale': (C.c_int, [c_ptr, c_ptr, c_ptr, c_ptr] + [C.c_int] * 6 + [c_ptr]),
+    'sdmi_k_spatial_rescale_labels': (C.c_int, [c_ptr, c_ptr, c_ptr, c_ptr] + [C.c_int] * 6 + [c_ptr]),
     'sdmi_vae_num_weights': (C.c_int, [c_ptr]),
     'sdmi_vae_weight_info': (C.c_int, [c_ptr, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int)]),
     'sdmi_vae_set_weight': (C.c_int, [c_ptr, C.c_char_p, c_ptr, C.POINTER(C.c_int64), C.c_int, c_ptr]),

@@ -9,6 +9,7 @@
 #include "vae.h"
 #include "clip.h"
 #include "knn.h"
+#include "rescale.h"
 
 namespace sdmi {
 static thread_local std::string g_err;
@@ -467,6 +468,14 @@ int sdmi_k_patch_unfold(const float* x, const float* c, float* out, int B, int C
 int sdmi_k_patch_fold(const float* o, const float* w, float* out, int B, int C, int H, int W, int kh, int kw, int sy, int sx, int uf, int df,
                       int norm_only, void* stream) {
   return launch_patch_fold(o, w, out, B, C, H, W, kh, kw, sy, sx, uf, df, norm_only, (hipStream_t)stream);
+}
+int sdmi_k_spatial_rescale(const float* x, const float* w, const float* bias, float* out, int B, int Cin, int H, int W, int n_stages,
+                           int Cout, void* stream) {
+  return launch_spatial_rescale(x, w, bias, out, B, Cin, H, W, n_stages, Cout, (hipStream_t)stream);
+}
+int sdmi_k_spatial_rescale_labels(const int32_t* labels, const float* w, const float* bias, float* out, int B, int Cin, int H, int W,
+                                  int n_stages, int Cout, void* stream) {
+  return launch_spatial_rescale_labels((const int*)labels, w, bias, out, B, Cin, H, W, n_stages, Cout, (hipStream_t)stream);
 }
 int sdmi_k_gelu_erf(const float* x, void* out_f16, int64_t n, void* stream) {
   return launch_gelu_erf(x, (f16*)out_f16, n, (hipStream_t)stream);

@@ -243,6 +243,13 @@ BSR_UNET_KWARGS = dict(image_size=64, in_channels=6, out_channels=3, model_chann
 BSR_SCHEDULE = dict(timesteps=1000, linear_start=0.0015, linear_end=0.0155, conditioning_key='concat')    # yaml:5-6,8,14 (concat_mode)
 
 
+# ---- the semantic-synthesis models (models/ldm/semantic_synthesis256, semantic_synthesis512: one unet_config but image_size) ----------
+SEMANTIC_UNET_KWARGS = dict(image_size=128, in_channels=6, out_channels=3, model_channels=128, attention_resolutions=[32, 16, 8],
+                            num_res_blocks=2, channel_mult=[1, 4, 8], num_heads=8)                         # semantic_synthesis512 yaml:16-32
+SEMANTIC_RESCALER_KWARGS = dict(n_stages=2, in_channels=182, out_channels=3)                               # yaml:55-60 (the VQ-f4 stage: FACES_VQ_KWARGS)
+SEMANTIC_SCHEDULE = dict(timesteps=1000, linear_start=0.0015, linear_end=0.0205, conditioning_key='concat')   # yaml:5-6,8,14 (concat_mode)
+
+
 def synthetic_faces_unet_state_dict(seed=0, unet_kwargs=None):
     """CPU state_dict (reference UNetModel key names) of a seeded random face / bedroom UNet (or, with BSR_UNET_KWARGS, bsr_sr's)."""
     from .unet import UNetModelHIP

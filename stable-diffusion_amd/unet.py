@@ -127,6 +127,10 @@ class UNetModelHIP(nn.Module):
         #   dim_head = num_head_channels with legacy False, and with legacy True recomputes dim_head = ch // num_heads -- the same
         #   number wherever num_head_channels divides ch (checked against the reference module: tools/make_golden_rdm.py builds it
         #   with either flag and gets one key list and one output).  Admitted for the head dims the tests run (ST_HEAD_CHANNELS).
+        #   semantic synthesis (models/ldm/semantic_synthesis256 / 512 config.yaml:16-32): the inpainting family's legacy AttentionBlocks
+        #   (num_heads=8) with the face family's plain Downsample / Upsample convolutions (resblock_updown=False), model_channels 128,
+        #   channel_mult [1, 4, 8] (a 128 -> 512 ResBlock), six input channels.  attention_resolutions [32, 16, 8] names none of the
+        #   three levels (ds 1 / 2 / 4), so the only attention is the middle block's: 8 heads of 128 at width 1024.
         self.use_spatial_transformer = bool(use_spatial_transformer)
         unsupported = []
         if use_spatial_transformer:
@@ -176,7 +180,7 @@ class UNetModelHIP(nn.Module):
                 raise NotImplementedError(f"hip_precision='full' supports attention head dims up to {self.FULL_MAX_HEAD_DIM}; this "
                                           f'configuration has d_head = {d_max} ({how}): use hip_precision=\'mixed\'')
         if unsupported:
-            raise NotImplementedError('UNetModelHIP supports the SD-v1, latent-inpainting, unconditional and num_head_channels AttentionBlock / '
+            raise NotImplementedError('UNetModelHIP supports the SD-v1, latent-inpainting, unconditional, semantic-synthesis and num_head_channels AttentionBlock / '
                                       'SpatialTransformer UNet families only; needs: ' +
                                       '; '.join(unsupported))
         if isinstance(context_dim, (list, tuple)) or type(context_dim).__name__ == 'ListConfig':
