@@ -175,6 +175,32 @@ int sdmi_sampler_step(const float* eps_model, int cfg, float scale, const float*
                       const float* old1, const float* old2, float a_t, float a_prev, float sigma, float sqrt_1m_at,
                       const float* noise, float* e_t_out, float* x_prev, float* pred_x0, int64_t n, void* stream);
 
+/* The same step split at pred_x0, for quantize_x0 (ddim.py:195-197, plms.py:207-209: first_stage_model.quantize(pred_x0) sits between
+ * pred_x0 and x_prev).  sdmi_sampler_step_x0 is the first half: the CFG combine, the multistep e' and pred_x0 = (x - sqrt_1m_at e') /
+ * sqrt(a_t), the bits sdmi_sampler_step writes; ep_out (required) receives e', e_t_out is optional.  sdmi_sampler_step_from_x0 is the
+ * second half from a given pred_x0: x_prev = sqrt(a_prev) pred_x0 + sqrt(1 - a_prev - sigma^2) ep + sigma noise (noise optional, sigma > 0).
+ * The two chained with nothing in between write the x_prev of sdmi_sampler_step. */
+int sdmi_sampler_step_x0(const float* eps_model, int cfg, float scale, const float* x, int mode, const float* old0, const float* old1,
+                         const float* old2, float a_t, float sqrt_1m_at, float* e_t_out, float* ep_out, float* pred_x0, int64_t n,
+                         void* stream);
+int sdmi_sampler_step_from_x0(const float* pred_x0, const float* ep, float a_prev, float sigma, const float* noise, float* x_prev,
+                              int64_t n, void* stream);
+
+/* ---- ancestral DDPM step: LatentDiffusion.p_mean_variance + p_sample (ddpm.py:1047-1107) and the mask blend of p_sample_loop /
+ * progressive_denoising (:1203-1205, :1154-1157) in one launch; fp32, each op rounded on its own in the reference's order:
+ *   x0 = c_recip x - c_recipm1 eps;  clip != 0: x0 = clamp(x0, -1, 1) (a NaN stays NaN);  mean = coef1 x0 + coef2 x;
+ *   x_prev = mean + s noise;  with mask: x_prev = (sa x0_orig + s1ma q_noise) mask + (1 - mask) x_prev
+ *   c_recip, c_recipm1, coef1, coef2, sa, s1ma: sqrt_recip_alphas_cumprod[t], sqrt_recipm1_alphas_cumprod[t], posterior_mean_coef1[t],
+ *     posterior_mean_coef2[t], sqrt_alphas_cumprod[t], sqrt_one_minus_alphas_cumprod[t] of DDPM.register_schedule
+ *   s = (t != 0) * exp(0.5 * posterior_log_variance_clipped[t]);  noise: required with x_prev, already times the temperature
+ *   mask (optional; of the latent's full shape), x0_orig, q_noise: the inpainting blend
+ *   x0_out (optional) receives x0; x_prev may be x (in place)
+ * Two partial forms, for quantize_denoised (the codebook quantizer sits between x0 and the posterior mean):
+ *   x_prev NULL: up to x0_out only;   eps NULL and x0_in set: from the given x0 (no clamp). */
+int sdmi_ddpm_step(const float* eps, const float* x0_in, const float* x, float c_recip, float c_recipm1, int clip, float coef1,
+                   float coef2, float s, const float* noise, const float* mask, const float* x0_orig, const float* q_noise, float sa,
+                   float s1ma, float* x0_out, float* x_prev, int64_t n, void* stream);
+
 
 /* DPM-Solver++ (2M) step as `scripts/txt2img.py --dpm_solver` runs it: classifier-free combine
  * (dpm_solver.py:340-346), data prediction m0 = (x - sigma_s e) / alpha_s (:386-399) and the multistep update

@@ -94,6 +94,11 @@ _SIGS = {
                                     c_ptr, C.c_int64, c_ptr]),
     'sdmi_sampler_step': (C.c_int, [c_ptr, C.c_int, C.c_float, c_ptr, C.c_int, c_ptr, c_ptr, c_ptr, C.c_float,
                                     C.c_float, C.c_float, C.c_float, c_ptr, c_ptr, c_ptr, c_ptr, C.c_int64, c_ptr]),
+    'sdmi_sampler_step_x0': (C.c_int, [c_ptr, C.c_int, C.c_float, c_ptr, C.c_int, c_ptr, c_ptr, c_ptr, C.c_float, C.c_float, c_ptr,
+                                       c_ptr, c_ptr, C.c_int64, c_ptr]),
+    'sdmi_sampler_step_from_x0': (C.c_int, [c_ptr, c_ptr, C.c_float, C.c_float, c_ptr, c_ptr, C.c_int64, c_ptr]),
+    'sdmi_ddpm_step': (C.c_int, [c_ptr, c_ptr, c_ptr, C.c_float, C.c_float, C.c_int, C.c_float, C.c_float, C.c_float, c_ptr, c_ptr,
+                                 c_ptr, c_ptr, C.c_float, C.c_float, c_ptr, c_ptr, C.c_int64, c_ptr]),
     'sdmi_dpm_solver_step': (C.c_int, [c_ptr, C.c_int, C.c_float, c_ptr, c_ptr, C.c_float, C.c_float, C.c_float, C.c_float,
                                        C.c_float, C.c_int, c_ptr, c_ptr, C.c_int64, c_ptr]),
     'sdmi_vae_create': (C.c_int, [C.POINTER(VaeCfg), C.c_int, C.POINTER(c_ptr)]),

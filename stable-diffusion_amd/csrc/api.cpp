@@ -159,7 +159,35 @@ int sdmi_sampler_step(const float* eps_model, int cfg, float scale, const float*
   p.old0 = old0; p.old1 = old1; p.old2 = old2;
   p.a_t = a_t; p.a_prev = a_prev; p.sigma = sigma; p.sqrt_1m_at = sqrt_1m_at;
   p.noise = noise; p.e_t_out = e_t_out; p.x_prev = x_prev; p.pred_x0 = pred_x0; p.n = n;
+  SDMI_CHECK(x_prev, "sampler_step: missing pointer");
   return launch_sampler_step(p, (hipStream_t)stream);
+}
+
+int sdmi_sampler_step_x0(const float* eps_model, int cfg, float scale, const float* x, int mode, const float* old0, const float* old1,
+                         const float* old2, float a_t, float sqrt_1m_at, float* e_t_out, float* ep_out, float* pred_x0, int64_t n,
+                         void* stream) {
+  SamplerStepParams p = SamplerStepParams();
+  p.eps_model = eps_model; p.cfg = cfg; p.scale = scale; p.x = x; p.mode = mode;
+  p.old0 = old0; p.old1 = old1; p.old2 = old2;
+  p.a_t = a_t; p.sqrt_1m_at = sqrt_1m_at;
+  p.e_t_out = e_t_out; p.ep_out = ep_out; p.pred_x0 = pred_x0; p.n = n;
+  return launch_sampler_step(p, (hipStream_t)stream);
+}
+
+int sdmi_sampler_step_from_x0(const float* pred_x0, const float* ep, float a_prev, float sigma, const float* noise, float* x_prev,
+                              int64_t n, void* stream) {
+  return launch_sampler_step_from_x0(pred_x0, ep, a_prev, sigma, noise, x_prev, n, (hipStream_t)stream);
+}
+
+int sdmi_ddpm_step(const float* eps, const float* x0_in, const float* x, float c_recip, float c_recipm1, int clip, float coef1,
+                   float coef2, float s, const float* noise, const float* mask, const float* x0_orig, const float* q_noise, float sa,
+                   float s1ma, float* x0_out, float* x_prev, int64_t n, void* stream) {
+  DdpmStepParams p = DdpmStepParams();
+  p.eps = eps; p.x0_in = x0_in; p.x = x; p.c_recip = c_recip; p.c_recipm1 = c_recipm1; p.clip = clip;
+  p.coef1 = coef1; p.coef2 = coef2; p.s = s; p.noise = noise;
+  p.mask = mask; p.x0_orig = x0_orig; p.q_noise = q_noise; p.sa = sa; p.s1ma = s1ma;
+  p.x0_out = x0_out; p.x_prev = x_prev; p.n = n;
+  return launch_ddpm_step(p, (hipStream_t)stream);
 }
 
 

@@ -550,8 +550,31 @@ struct SamplerStepParams {
   float* e_t_out = nullptr;          // optional: combined (post-CFG) eps, kept for the history
   float* x_prev = nullptr; float* pred_x0 = nullptr;   // pred_x0 optional
   int64_t n = 0;                     // elements per output (B*4*H*W)
+  // the step split at pred_x0 (quantize_x0): x_prev null -> stop after pred_x0, with the combined e' in ep_out for the second half
+  float* ep_out = nullptr;
 };
 int launch_sampler_step(const SamplerStepParams& p, hipStream_t s);
+// ... its second half: x_prev from a given pred_x0 and e' (a_prev, sigma: the table entries; noise optional as above)
+int launch_sampler_step_from_x0(const float* pred_x0, const float* ep, float a_prev, float sigma, const float* noise, float* x_prev,
+                                int64_t n, hipStream_t s);
+// ancestral DDPM step (fp32): see sampler.hip
+struct DdpmStepParams {
+  const float* eps = nullptr;        // model output; null: x0 comes from x0_in (the second half, after the codebook quantizer)
+  const float* x0_in = nullptr;
+  const float* x = nullptr;          // current latent
+  float c_recip = 1.f, c_recipm1 = 0.f;     // sqrt_recip_alphas_cumprod[t], sqrt_recipm1_alphas_cumprod[t]
+  int clip = 0;                      // clip_denoised
+  float coef1 = 0.f, coef2 = 1.f;    // posterior_mean_coef1[t], posterior_mean_coef2[t]
+  float s = 0.f;                     // (t != 0) * exp(0.5 * posterior_log_variance_clipped[t])
+  const float* noise = nullptr;      // already scaled by temperature
+  const float* mask = nullptr;       // optional blend: all of mask (expanded to the latent's shape), x0_orig, q_noise
+  const float* x0_orig = nullptr; const float* q_noise = nullptr;
+  float sa = 1.f, s1ma = 0.f;        // sqrt_alphas_cumprod[t], sqrt_one_minus_alphas_cumprod[t]
+  float* x0_out = nullptr;           // optional (return_x0)
+  float* x_prev = nullptr;           // may be x; null: stop after x0_out (the first half)
+  int64_t n = 0;
+};
+int launch_ddpm_step(const DdpmStepParams& p, hipStream_t s);
 // decode output fp32 NCHW -> uint8 NHWC exactly as scripts/txt2img.py:313-324 does on the host (sampler.hip)
 int launch_image_u8(const float* img_nchw, unsigned char* out_nhwc, int B, int C, int H, int W, hipStream_t s);
 

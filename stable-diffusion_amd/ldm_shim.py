@@ -153,29 +153,35 @@ class LatentDiffusionHIP(nn.Module):
     """What the samplers touch on `model`: num_timesteps, betas, alphas_cumprod(_prev), device, apply_model."""
 
     def __init__(self, unet, timesteps=1000, linear_start=0.00085, linear_end=0.0120, conditioning_key='crossattn',
-                 first_stage_model=None, scale_factor=1.0, cond_stage_key=None):
+                 first_stage_model=None, scale_factor=1.0, cond_stage_key=None, clip_denoised=True, log_every_t=100, channels=None,
+                 image_size=None):
         """The latent-inpainting model: linear_start=0.0015, linear_end=0.0205, conditioning_key='concat'
         (models/ldm/inpainting_big/config.yaml:5-14).  The unconditional LSUN-Churches model: linear_start=0.0015,
         linear_end=0.0155, conditioning_key=None (models/ldm/lsun_churches256/config.yaml:5-6, cond_stage_config
         '__is_unconditional__': ddpm.py:455-456 leaves the key at None); apply_model(x, t, None).
         `first_stage_model` (an AutoencoderKLHIP / VQModelInterfaceHIP), `scale_factor` and `cond_stage_key` serve decode_first_stage /
         encode_first_stage and the tiled apply_model; set the attribute `split_input_params` (ddpm.py's keys: ks, stride, vqf,
-        patch_distributed_vq, tie_braker, clip_min_weight, clip_max_weight, clip_min_tie_weight, clip_max_tie_weight) to switch tiling on."""
+        patch_distributed_vq, tie_braker, clip_min_weight, clip_max_weight, clip_min_tie_weight, clip_max_tie_weight) to switch tiling on.
+        `clip_denoised` / `log_every_t` are the DDPM constructor's (ddpm.py:53-54; its defaults, which the yaml files inherit -- the
+        LSUN-Churches one sets log_every_t: 200) and serve the ancestral sampler; `channels` / `image_size` only give sample() /
+        sample_log() their default shape (ddpm.py:1221, :1239)."""
         super().__init__()
         self.model = DiffusionWrapperHIP(unet, conditioning_key)
         self.first_stage_model = first_stage_model
         self.scale_factor = float(scale_factor)
         self.cond_stage_key = cond_stage_key
+        self.clip_denoised = bool(clip_denoised)
+        self.log_every_t = int(log_every_t)
+        self.channels, self.image_size = channels, image_size
+        self.shorten_cond_schedule = False
+        from .samplers import ddpm_tables
         betas = make_beta_schedule_linear(timesteps, linear_start, linear_end)
-        alphas_cumprod = np.cumprod(1. - betas, axis=0)
         self.num_timesteps = int(timesteps)
         self.parameterization = 'eps'
-        f32 = lambda a: torch.tensor(a, dtype=torch.float32)
-        self.register_buffer('betas', f32(betas))
-        self.register_buffer('alphas_cumprod', f32(alphas_cumprod))
-        self.register_buffer('alphas_cumprod_prev', f32(np.append(1., alphas_cumprod[:-1])))
-        self.register_buffer('sqrt_alphas_cumprod', f32(np.sqrt(alphas_cumprod)))
-        self.register_buffer('sqrt_one_minus_alphas_cumprod', f32(np.sqrt(1. - alphas_cumprod)))
+        persistent = ('betas', 'alphas_cumprod', 'alphas_cumprod_prev', 'sqrt_alphas_cumprod', 'sqrt_one_minus_alphas_cumprod')
+        for name, tab in ddpm_tables(betas).items():      # every buffer of DDPM.register_schedule but lvlb_weights (a training loss weight)
+            # (the posterior tables stay out of state_dict(): its keys are what they were before the ancestral sampler came)
+            self.register_buffer(name, torch.from_numpy(tab), persistent=name in persistent)
 
     @property
     def device(self):
@@ -298,3 +304,44 @@ class LatentDiffusionHIP(nn.Module):
         sh = (t.shape[0],) + (1,) * (x_start.dim() - 1)
         return self.sqrt_alphas_cumprod.gather(-1, t).reshape(sh) * x_start + \
             self.sqrt_one_minus_alphas_cumprod.gather(-1, t).reshape(sh) * noise
+
+    # ---- ancestral sampling (ddpm.py:1109-1247): DDPMSamplerHIP does the work ------------------------------------------------------
+    @torch.no_grad()
+    def p_sample_loop(self, cond, shape, **kwargs):
+        """ddpm.py:1165-1214"""
+        from .samplers import DDPMSamplerHIP
+        return DDPMSamplerHIP(self).p_sample_loop(cond, shape, **kwargs)
+
+    @torch.no_grad()
+    def progressive_denoising(self, cond, shape, **kwargs):
+        """ddpm.py:1109-1163"""
+        from .samplers import DDPMSamplerHIP
+        return DDPMSamplerHIP(self).progressive_denoising(cond, shape, **kwargs)
+
+    def _default_shape(self):
+        if self.channels is None or self.image_size is None:
+            raise ValueError('no shape given and the model was built without channels / image_size')
+        return (int(self.channels), int(self.image_size), int(self.image_size))
+
+    @torch.no_grad()
+    def sample(self, cond, batch_size=16, return_intermediates=False, x_T=None, verbose=True, timesteps=None, quantize_denoised=False,
+               mask=None, x0=None, shape=None, **kwargs):
+        """ddpm.py:1216-1232 (as there, further keywords are accepted and dropped)"""
+        if shape is None:
+            shape = (batch_size,) + self._default_shape()
+        if cond is not None and not isinstance(cond, dict):
+            cond = [c[:batch_size] for c in cond] if isinstance(cond, list) else cond[:batch_size]
+        return self.p_sample_loop(cond, shape, return_intermediates=return_intermediates, x_T=x_T, verbose=verbose, timesteps=timesteps,
+                                  quantize_denoised=quantize_denoised, mask=mask, x0=x0)
+
+    @torch.no_grad()
+    def sample_log(self, cond, batch_size, ddim, ddim_steps, **kwargs):
+        """ddpm.py:1234-1247.  One keyword beyond the reference's: `shape=(C, H, W)`, for a model built without channels / image_size."""
+        if ddim:
+            from .samplers import DDIMSamplerHIP
+            shape = kwargs.pop('shape', None) or self._default_shape()
+            return DDIMSamplerHIP(self).sample(ddim_steps, batch_size, tuple(shape)[-3:], cond, verbose=False, **kwargs)
+        shape = kwargs.pop('shape', None)
+        if shape is not None and len(shape) == 3:
+            shape = (batch_size,) + tuple(shape)
+        return self.sample(cond=cond, batch_size=batch_size, return_intermediates=True, shape=shape, **kwargs)

@@ -7,7 +7,10 @@ Per step the reference issues ~15 elementwise launches plus four `torch.full` fr
 (plms.py:178-236); here the classifier-free-guidance combine and the PLMS/DDIM latent update are one fused
 gfx950 kernel (`sdmi_sampler_step`, csrc/sampler.hip) evaluated in the reference's fp32 operation order,
 the duplicated `x_in`/`t_in`/`c_in` are built once, and the context tensor is kept identical across steps so
-the UNet reuses its cross-attention K/V.
+the UNet reuses its cross-attention K/V.  With `quantize_x0` the step is split at pred_x0 around `first_stage_model.quantize`.
+
+`DDPMSamplerHIP` is the ancestral sampler of `LatentDiffusion` itself (ddpm.py `p_sample_loop` / `progressive_denoising`, what
+`scripts/sample_diffusion.py --vanilla_sample` runs): one fused launch per step as well (`sdmi_ddpm_step`).
 """
 import numpy as np
 import torch
@@ -38,7 +41,12 @@ def make_tables(alphas_cumprod, ddim_timesteps, eta):
     ac = np.asarray(alphas_cumprod, dtype=np.float32)
     alphas = ac[ddim_timesteps]
     alphas_prev = np.asarray([ac[0]] + ac[ddim_timesteps[:-1]].tolist(), dtype=np.float32)
-    sigmas = (eta * np.sqrt((1 - alphas_prev) / (1 - alphas) * (1 - alphas / alphas_prev))).astype(np.float32)
+    # util.py:65-69 as the reference's types make it come out: alphas is an fp32 tensor there and alphas_prev a float64 array of the same
+    # values, so (1 - alphas_prev) / (1 - alphas) is the tensor's __rtruediv__ -- the fp32 reciprocal of the fp32 difference, times the
+    # float64 numerator -- and every other operation runs in float64; the step then rounds sigma to fp32
+    ap64, a64 = alphas_prev.astype(np.float64), alphas.astype(np.float64)
+    recip = (np.float32(1.0) / (1 - alphas)).astype(np.float64)
+    sigmas = (eta * np.sqrt(recip * (1 - ap64) * (1 - a64 / ap64))).astype(np.float32)
     return dict(alphas=alphas, alphas_prev=alphas_prev, sigmas=sigmas,
                 sqrt_one_minus_alphas=np.sqrt(1.0 - alphas).astype(np.float32))
 
@@ -85,19 +93,39 @@ class _SamplerBase(object):
         self.ddim_sqrt_one_minus_alphas = to_t(t['sqrt_one_minus_alphas'])
 
     # ---- one fused CFG + update launch ------------------------------------------------------------------
-    def _step(self, eps_model, cfg, scale, x, mode, old, index, e_t_out, x_prev, pred_x0=None, noise=None):
+    def _step(self, eps_model, cfg, scale, x, mode, old, index, e_t_out, x_prev, pred_x0=None, noise=None, quantize=False):
+        """Returns pred_x0 (with `quantize` the codebook rows first_stage_model.quantize put in its place: ddim.py:196-197, plms.py:208-209)."""
         if not x.is_cuda:
             raise RuntimeError('the HIP sampler step runs on MI355X device tensors only (no CPU fallback)')
         if self._lib is None:
             self._lib = _lib.load()
         t = self._tab
         o = list(old) + [None, None, None]
+        if quantize:        # the step split at pred_x0: first half, the quantizer (sdmi_k_vq_quantize), second half
+            pred_x0 = torch.empty_like(x) if pred_x0 is None else pred_x0
+            ep = torch.empty_like(x)
+            _lib.check(self._lib.sdmi_sampler_step_x0(
+                eps_model.data_ptr(), int(cfg), float(scale), x.data_ptr(), int(mode), _lib.ptr(o[0]), _lib.ptr(o[1]), _lib.ptr(o[2]),
+                float(t['alphas'][index]), float(t['sqrt_one_minus_alphas'][index]), _lib.ptr(e_t_out), ep.data_ptr(),
+                pred_x0.data_ptr(), x.numel(), _lib.stream_ptr()))
+            pred_x0 = self.model.first_stage_model.quantize(pred_x0)[0].float().contiguous()
+            _lib.check(self._lib.sdmi_sampler_step_from_x0(
+                pred_x0.data_ptr(), ep.data_ptr(), float(t['alphas_prev'][index]), float(t['sigmas'][index]), _lib.ptr(noise),
+                x_prev.data_ptr(), x.numel(), _lib.stream_ptr()))
+            return pred_x0
         _lib.check(self._lib.sdmi_sampler_step(
             eps_model.data_ptr(), int(cfg), float(scale), x.data_ptr(), int(mode),
             _lib.ptr(o[0]), _lib.ptr(o[1]), _lib.ptr(o[2]),
             float(t['alphas'][index]), float(t['alphas_prev'][index]), float(t['sigmas'][index]),
             float(t['sqrt_one_minus_alphas'][index]),
             _lib.ptr(noise), _lib.ptr(e_t_out), x_prev.data_ptr(), _lib.ptr(pred_x0), x.numel(), _lib.stream_ptr()))
+        return pred_x0
+
+    def _check_options(self, score_corrector, quantize_x0):
+        if score_corrector is not None:
+            raise NotImplementedError('score_corrector is not implemented here (the reference ships no corrector)')
+        if quantize_x0 and not hasattr(getattr(self.model, 'first_stage_model', None), 'quantize'):
+            raise NotImplementedError('quantize_x0 needs a first stage with a codebook: model.first_stage_model.quantize (VQModelInterfaceHIP)')
 
     def _hip_unet(self):
         """The UNetModelHIP behind model.apply_model, if any (LatentDiffusion.model.diffusion_model, ddpm.py:1398)."""
@@ -150,8 +178,7 @@ class PLMSSamplerHIP(_SamplerBase):
             print(f'Warning: Got {conditioning.shape[0]} conditionings but batch-size is {batch_size}')
         if isinstance(conditioning, dict):
             raise NotImplementedError('dict conditioning (hybrid models) is outside the SD-v1 txt2img path')
-        if score_corrector is not None or quantize_x0:
-            raise NotImplementedError('score_corrector / quantize_x0 are not used by SD v1 and not implemented here')
+        self._check_options(score_corrector, quantize_x0)
         self.make_schedule(ddim_num_steps=S, ddim_eta=eta, verbose=verbose)
         C, H, W = shape
         size = (batch_size, C, H, W)
@@ -159,11 +186,11 @@ class PLMSSamplerHIP(_SamplerBase):
         return self.plms_sampling(conditioning, size, callback=callback, img_callback=img_callback, mask=mask, x0=x0,
                                   x_T=x_T, log_every_t=log_every_t,
                                   unconditional_guidance_scale=unconditional_guidance_scale,
-                                  unconditional_conditioning=unconditional_conditioning)
+                                  unconditional_conditioning=unconditional_conditioning, quantize_denoised=quantize_x0)
 
     @torch.no_grad()
     def plms_sampling(self, cond, shape, x_T=None, callback=None, img_callback=None, mask=None, x0=None,
-                      log_every_t=100, unconditional_guidance_scale=1., unconditional_conditioning=None):
+                      log_every_t=100, unconditional_guidance_scale=1., unconditional_conditioning=None, quantize_denoised=False):
         scale, uc = unconditional_guidance_scale, unconditional_conditioning
         device, b, img, cfg, c_in, x_in = self._prepare(cond, shape, x_T, uc, scale)
         plan = plms_plan(self.ddim_timesteps)
@@ -177,14 +204,14 @@ class PLMSSamplerHIP(_SamplerBase):
             unet.cache_timesteps([t for p in plan for t in (p[2], p[3]) if t is not None])
         try:
             img = self._plms_loop(plan, total_steps, device, b, img, cfg, c_in, x_in, scale, mask, x0, callback,
-                                  img_callback, log_every_t, intermediates, old_eps)
+                                  img_callback, log_every_t, intermediates, old_eps, quantize_denoised)
         finally:
             if unet is not None:
                 unet.unpin_context()
         return img, intermediates
 
     def _plms_loop(self, plan, total_steps, device, b, img, cfg, c_in, x_in, scale, mask, x0, callback, img_callback,
-                   log_every_t, intermediates, old_eps):
+                   log_every_t, intermediates, old_eps, quantize=False):
         for (i, index, t, t_next, mode) in tqdm(plan, desc='PLMS Sampler', total=total_steps):
             if mask is not None:
                 assert x0 is not None
@@ -196,13 +223,13 @@ class PLMSSamplerHIP(_SamplerBase):
             pred_x0 = torch.empty_like(img)
             if mode == 4:
                 # Pseudo Improved Euler: predictor with e_t, second evaluation at t_next, then (e_t + e_t_next)/2
-                self._step(eps, cfg, scale, img, 0, [], index, e_t, x_prev)
+                self._step(eps, cfg, scale, img, 0, [], index, e_t, x_prev, quantize=quantize)
                 eps_next = self._model_eps(x_in, x_prev, t_next, c_in, cfg, b)
                 x_prev2 = torch.empty_like(img)
-                self._step(eps_next, cfg, scale, img, 4, [e_t], index, None, x_prev2, pred_x0)
+                pred_x0 = self._step(eps_next, cfg, scale, img, 4, [e_t], index, None, x_prev2, pred_x0, quantize=quantize)
                 x_prev = x_prev2
             else:
-                self._step(eps, cfg, scale, img, mode, old_eps, index, e_t, x_prev, pred_x0)
+                pred_x0 = self._step(eps, cfg, scale, img, mode, old_eps, index, e_t, x_prev, pred_x0, quantize=quantize)
             img = x_prev
             old_eps.insert(0, e_t)
             if len(old_eps) >= 4:
@@ -228,8 +255,7 @@ class DDIMSamplerHIP(_SamplerBase):
             print(f'Warning: Got {conditioning.shape[0]} conditionings but batch-size is {batch_size}')
         if isinstance(conditioning, dict):
             raise NotImplementedError('dict conditioning (hybrid models) is outside the SD-v1 txt2img path')
-        if score_corrector is not None or quantize_x0:
-            raise NotImplementedError('score_corrector / quantize_x0 are not used by SD v1 and not implemented here')
+        self._check_options(score_corrector, quantize_x0)
         self.make_schedule(ddim_num_steps=S, ddim_eta=eta, verbose=verbose)
         C, H, W = shape
         size = (batch_size, C, H, W)
@@ -237,11 +263,12 @@ class DDIMSamplerHIP(_SamplerBase):
         return self._loop(conditioning, size, self.ddim_timesteps, x_T=x_T, callback=callback,
                           img_callback=img_callback, mask=mask, x0=x0, log_every_t=log_every_t,
                           temperature=temperature, noise_dropout=noise_dropout,
-                          scale=unconditional_guidance_scale, uc=unconditional_conditioning, desc='DDIM Sampler')
+                          scale=unconditional_guidance_scale, uc=unconditional_conditioning, desc='DDIM Sampler',
+                          quantize_denoised=quantize_x0)
 
     @torch.no_grad()
     def _loop(self, cond, shape, timesteps, x_T=None, callback=None, img_callback=None, mask=None, x0=None,
-              log_every_t=100, temperature=1., noise_dropout=0., scale=1., uc=None, desc='DDIM Sampler'):
+              log_every_t=100, temperature=1., noise_dropout=0., scale=1., uc=None, desc='DDIM Sampler', quantize_denoised=False):
         device, b, img, cfg, c_in, x_in = self._prepare(cond, shape, x_T, uc, scale)
         time_range = np.flip(timesteps)
         total_steps = timesteps.shape[0]
@@ -253,14 +280,14 @@ class DDIMSamplerHIP(_SamplerBase):
             unet.cache_timesteps([int(t) for t in time_range])
         try:
             img = self._ddim_loop(time_range, total_steps, device, b, img, cfg, c_in, x_in, scale, mask, x0, callback,
-                                  img_callback, log_every_t, temperature, noise_dropout, intermediates, desc)
+                                  img_callback, log_every_t, temperature, noise_dropout, intermediates, desc, quantize_denoised)
         finally:
             if unet is not None:
                 unet.unpin_context()
         return img, intermediates
 
     def _ddim_loop(self, time_range, total_steps, device, b, img, cfg, c_in, x_in, scale, mask, x0, callback,
-                   img_callback, log_every_t, temperature, noise_dropout, intermediates, desc):
+                   img_callback, log_every_t, temperature, noise_dropout, intermediates, desc, quantize=False):
         for i, step in enumerate(tqdm(time_range, desc=desc, total=total_steps)):
             index = total_steps - i - 1
             if mask is not None:
@@ -278,7 +305,7 @@ class DDIMSamplerHIP(_SamplerBase):
             noise = noise.float().contiguous() if float(self._tab['sigmas'][index]) != 0.0 else None
             x_prev = torch.empty_like(img)
             pred_x0 = torch.empty_like(img)
-            self._step(eps, cfg, scale, img, 0, [], index, None, x_prev, pred_x0, noise)
+            pred_x0 = self._step(eps, cfg, scale, img, 0, [], index, None, x_prev, pred_x0, noise, quantize=quantize)
             img = x_prev
             if callback: callback(i)
             if img_callback: img_callback(pred_x0, i)
@@ -308,6 +335,198 @@ class DDIMSamplerHIP(_SamplerBase):
         img, _ = self._loop(cond, tuple(x_latent.shape), self.ddim_timesteps[:t_start], x_T=x_latent,
                             scale=unconditional_guidance_scale, uc=unconditional_conditioning, desc='Decoding image')
         return img
+
+
+# ---- ancestral DDPM sampling: scripts/sample_diffusion.py --vanilla_sample (LatentDiffusion.p_sample_loop, ddpm.py:1165-1214) --------
+DDPM_TABLES = ('betas', 'alphas_cumprod', 'alphas_cumprod_prev', 'sqrt_alphas_cumprod', 'sqrt_one_minus_alphas_cumprod',
+               'log_one_minus_alphas_cumprod', 'sqrt_recip_alphas_cumprod', 'sqrt_recipm1_alphas_cumprod', 'posterior_variance',
+               'posterior_log_variance_clipped', 'posterior_mean_coef1', 'posterior_mean_coef2')
+
+
+def ddpm_tables(betas):
+    """The buffers of DDPM.register_schedule (ddpm.py:117-157, v_posterior = 0) from float64 betas, computed as the reference computes
+    them -- float64 numpy, expression for expression, then float32: {name: fp32 numpy [n]}."""
+    betas = np.asarray(betas, dtype=np.float64)
+    alphas = 1. - betas
+    alphas_cumprod = np.cumprod(alphas, axis=0)
+    alphas_cumprod_prev = np.append(1., alphas_cumprod[:-1])
+    posterior_variance = (1 - 0.) * betas * (1. - alphas_cumprod_prev) / (1. - alphas_cumprod) + 0. * betas
+    t = dict(betas=betas, alphas_cumprod=alphas_cumprod, alphas_cumprod_prev=alphas_cumprod_prev,
+             sqrt_alphas_cumprod=np.sqrt(alphas_cumprod), sqrt_one_minus_alphas_cumprod=np.sqrt(1. - alphas_cumprod),
+             log_one_minus_alphas_cumprod=np.log(1. - alphas_cumprod), sqrt_recip_alphas_cumprod=np.sqrt(1. / alphas_cumprod),
+             sqrt_recipm1_alphas_cumprod=np.sqrt(1. / alphas_cumprod - 1), posterior_variance=posterior_variance,
+             posterior_log_variance_clipped=np.log(np.maximum(posterior_variance, 1e-20)),
+             posterior_mean_coef1=betas * np.sqrt(alphas_cumprod_prev) / (1. - alphas_cumprod),
+             posterior_mean_coef2=(1. - alphas_cumprod_prev) * np.sqrt(alphas) / (1. - alphas_cumprod))
+    return {k: np.asarray(v, dtype=np.float32) for k, v in t.items()}
+
+
+def ddpm_step_std(posterior_log_variance_clipped):
+    """(0.5 * model_log_variance).exp() of p_sample (ddpm.py:1107) for every t: the same two fp32 torch ops on the CPU -> fp32 numpy [n].
+    (The reference runs them on a [b, 1, 1, 1] gather of the table; torch's CPU exp gives an element the same bits in either shape --
+    tests/test_ddpm_host.py holds this against the values a reference run recorded.)"""
+    lv = torch.as_tensor(np.asarray(posterior_log_variance_clipped, dtype=np.float32))
+    return (0.5 * lv).exp().numpy()
+
+
+class DDPMSamplerHIP(_SamplerBase):
+    """The ancestral sampler of LatentDiffusion -- `p_sample_loop` (ddpm.py:1165-1214) and `progressive_denoising` (:1109-1163) over
+    `p_sample` / `p_mean_variance` (:1047-1107) -- for any `model` with betas, alphas_cumprod, num_timesteps and apply_model (the
+    reference's LatentDiffusion over UNetModelHIP included).  Per step: one apply_model, one noise draw and ONE launch (sdmi_ddpm_step:
+    predict_start_from_noise, clamp, q_posterior's mean, the noise term and the mask blend), where the reference issues about a dozen
+    elementwise launches and gathers.  With quantize_denoised the step is two launches around first_stage_model.quantize.
+
+    The schedule tables are the model's own registered buffers where it has them (LatentDiffusion, LatentDiffusionHIP); a model with
+    betas alone gets ddpm_tables(betas) -- from its fp32 betas, so the last bit of a table entry may differ from a reference that
+    started from float64 betas.  No classifier-free guidance: the reference's loop has none."""
+
+    def __init__(self, model, **kwargs):
+        super().__init__(model, **kwargs)
+        if getattr(model, 'parameterization', 'eps') != 'eps':
+            raise NotImplementedError(f"parameterization {model.parameterization!r}: the ancestral step is built for parameterization 'eps' only")
+        if getattr(model, 'shorten_cond_schedule', False):
+            raise NotImplementedError('shorten_cond_schedule (a noised conditioning per step) is not implemented here')
+        have = all(hasattr(model, k) for k in DDPM_TABLES)
+        if have:
+            tab = {k: getattr(model, k).detach().to(torch.float32).cpu().numpy() for k in DDPM_TABLES}
+        else:
+            tab = ddpm_tables(model.betas.detach().cpu().numpy())
+        assert tab['betas'].shape[0] == self.ddpm_num_timesteps, 'betas have to be defined for each timestep'
+        self._tab = tab
+        self._std = ddpm_step_std(tab['posterior_log_variance_clipped'])
+        self.clip_denoised = bool(getattr(model, 'clip_denoised', True))          # DDPM.__init__'s default
+        self.log_every_t = int(getattr(model, 'log_every_t', 100))
+
+    @staticmethod
+    def _q_noise_like(x0):
+        """the draw inside q_sample(x0, ts) of the mask blend (ddpm.py:275); a method of its own for the same reason as _noise_like"""
+        return torch.randn_like(x0)
+
+    def step_scalars(self, t):
+        """(c_recip, c_recipm1, coef1, coef2, s, sa, s1ma) of sdmi_ddpm_step at timestep t; s = nonzero_mask * std (ddpm.py:1100-1107)"""
+        T = self._tab
+        return (float(T['sqrt_recip_alphas_cumprod'][t]), float(T['sqrt_recipm1_alphas_cumprod'][t]), float(T['posterior_mean_coef1'][t]),
+                float(T['posterior_mean_coef2'][t]), float(self._std[t]) if t != 0 else 0.0, float(T['sqrt_alphas_cumprod'][t]),
+                float(T['sqrt_one_minus_alphas_cumprod'][t]))
+
+    def _check(self, cond, quantize_denoised, score_corrector=None):
+        if score_corrector is not None:
+            raise NotImplementedError('score_corrector is not implemented here (the reference ships no corrector)')
+        if isinstance(cond, dict):
+            raise NotImplementedError('dict conditioning (hybrid models) is not implemented in the ancestral loop')
+        if quantize_denoised and not hasattr(getattr(self.model, 'first_stage_model', None), 'quantize'):
+            raise NotImplementedError('quantize_denoised needs a first stage with a codebook: model.first_stage_model.quantize '
+                                      '(VQModelInterfaceHIP)')
+
+    def _apply(self, img, t, cond, unet):
+        ts = torch.full((img.shape[0],), t, device=img.device, dtype=torch.long)
+        if unet is not None:
+            unet.hint_timestep(t)
+        try:
+            out = self.model.apply_model(img, ts, cond)
+        finally:
+            if unet is not None:
+                unet.clear_timestep_hint()
+        return out.float().contiguous()
+
+    def _p_sample(self, img, eps, t, noise, quantize, blend, want_x0):
+        """one ancestral step: (x_prev, x0 or None); blend = (mask, x0_orig, q_noise) or None"""
+        if not img.is_cuda:
+            raise RuntimeError('the HIP sampler step runs on MI355X device tensors only (no CPU fallback)')
+        c_recip, c_recipm1, coef1, coef2, s, sa, s1ma = self.step_scalars(t)
+        if self._lib is None:
+            self._lib = _lib.load()
+        step, n, st = self._lib.sdmi_ddpm_step, img.numel(), _lib.stream_ptr()
+        m, xo, qn = blend if blend is not None else (None, None, None)
+        x_prev = torch.empty_like(img)
+        x0 = torch.empty_like(img) if (want_x0 or quantize) else None
+        clip = int(self.clip_denoised)
+        if quantize:
+            _lib.check(step(eps.data_ptr(), None, img.data_ptr(), c_recip, c_recipm1, clip, coef1, coef2, s, None, None, None, None,
+                            sa, s1ma, x0.data_ptr(), None, n, st))
+            x0 = self.model.first_stage_model.quantize(x0)[0].float().contiguous()
+            _lib.check(step(None, x0.data_ptr(), img.data_ptr(), c_recip, c_recipm1, clip, coef1, coef2, s, noise.data_ptr(), _lib.ptr(m),
+                            _lib.ptr(xo), _lib.ptr(qn), sa, s1ma, None, x_prev.data_ptr(), n, st))
+        else:
+            _lib.check(step(eps.data_ptr(), None, img.data_ptr(), c_recip, c_recipm1, clip, coef1, coef2, s, noise.data_ptr(), _lib.ptr(m),
+                            _lib.ptr(xo), _lib.ptr(qn), sa, s1ma, _lib.ptr(x0), x_prev.data_ptr(), n, st))
+        return x_prev, x0
+
+    def _run(self, cond, shape, x_T, timesteps, mask, x0, quantize_denoised, temperature, noise_dropout, callback, img_callback,
+             log_every_t, verbose, progressive, desc):
+        device = self.model.betas.device
+        img = torch.randn(tuple(shape), device=device) if x_T is None else x_T
+        first = img
+        img = img.detach().float().contiguous()
+        blend0 = None
+        if mask is not None:
+            assert x0 is not None
+            assert x0.shape[2:3] == mask.shape[2:3]  # spatial size has to match
+            blend0 = (mask.detach().float().expand(img.shape).contiguous(), x0.detach().float().expand(img.shape).contiguous())
+        steps = list(reversed(range(0, timesteps)))
+        unet = self._hip_unet()
+        if unet is not None:
+            if torch.is_tensor(cond):
+                unet.pin_context(cond)
+            unet.cache_timesteps(steps)
+        intermediates = [] if progressive else [first]
+        try:
+            for i in (tqdm(steps, desc=desc, total=timesteps) if verbose else steps):
+                eps = self._apply(img, i, cond, unet)
+                temp = temperature[i] if isinstance(temperature, (list, tuple)) else temperature
+                noise = self._noise_like(img.shape, device)        # drawn at t = 0 too, as ddpm.py:1096 does
+                if temp != 1.:
+                    noise = noise * temp
+                if noise_dropout > 0.:
+                    noise = torch.nn.functional.dropout(noise, p=noise_dropout)
+                noise = noise.float().contiguous()
+                blend = None if blend0 is None else blend0 + (self._q_noise_like(blend0[1]).float().contiguous(),)
+                img, x0_partial = self._p_sample(img, eps, i, noise, quantize_denoised, blend, progressive)
+                if i % log_every_t == 0 or i == timesteps - 1:
+                    intermediates.append(x0_partial if progressive else img)
+                if callback: callback(i)
+                if img_callback: img_callback(img, i)
+        finally:
+            if unet is not None:
+                unet.unpin_context()
+        return img, intermediates
+
+    @torch.no_grad()
+    def p_sample_loop(self, cond, shape, return_intermediates=False, x_T=None, verbose=True, callback=None, timesteps=None,
+                      quantize_denoised=False, mask=None, x0=None, img_callback=None, start_T=None, log_every_t=None):
+        """ddpm.py:1165-1214: -> img, or (img, [x_T, ...img at every log_every_t-th t and the first step])."""
+        self._check(cond, quantize_denoised)
+        if not log_every_t:
+            log_every_t = self.log_every_t
+        if timesteps is None:
+            timesteps = self.ddpm_num_timesteps
+        if start_T is not None:
+            timesteps = min(timesteps, start_T)
+        img, intermediates = self._run(cond, shape, x_T, timesteps, mask, x0, quantize_denoised, 1., 0., callback, img_callback,
+                                       log_every_t, verbose, False, 'Sampling t')
+        if return_intermediates:
+            return img, intermediates
+        return img
+
+    @torch.no_grad()
+    def progressive_denoising(self, cond, shape, verbose=True, callback=None, quantize_denoised=False, img_callback=None, mask=None,
+                              x0=None, temperature=1., noise_dropout=0., score_corrector=None, corrector_kwargs=None, batch_size=None,
+                              x_T=None, start_T=None, log_every_t=None):
+        """ddpm.py:1109-1163: -> (img, [the x0 of every log_every_t-th t and the first step]); `temperature` a number or a per-t list."""
+        self._check(cond, quantize_denoised, score_corrector)
+        if not log_every_t:
+            log_every_t = self.log_every_t
+        timesteps = self.ddpm_num_timesteps
+        if batch_size is not None:
+            shape = [batch_size] + list(shape)
+        else:
+            batch_size = shape[0]
+        if cond is not None:
+            cond = [c[:batch_size] for c in cond] if isinstance(cond, list) else cond[:batch_size]
+        if start_T is not None:
+            timesteps = min(timesteps, start_T)
+        return self._run(cond, shape, x_T, timesteps, mask, x0, quantize_denoised, temperature, noise_dropout, callback, img_callback,
+                         log_every_t, verbose, True, 'Progressive Generation')
 
 
 # ---- DPM-Solver++ (2M): scripts/txt2img.py --dpm_solver (SURVEY.md 8 f-3) ----------------------------------------------
