@@ -217,7 +217,8 @@ int sdmi_dpm_solver_step(const float* eps_model, int cfg, float scale, const flo
  * AutoencoderKL.encode (autoencoder.py:324-328) -> Encoder.forward (model.py:427-460). */
 typedef struct sdmi_vae sdmi_vae;
 /* ddconfig of configs/stable-diffusion/v1-inference.yaml:51-65 (attn_resolutions = [], dropout 0, double_z) + embed_dim
- * (attn_resolutions != []: sdmi_vae_create_attn, below; z_channels <= 16, embed_dim <= 16, in_channels <= 16, out_ch <= 8) */
+ * (attn_resolutions != []: sdmi_vae_create_attn, below; z_channels <= 16 (or 32 / 64), embed_dim <= 16 (or 32 / 64), in_channels <= 16,
+ * out_ch <= 8; n_levels <= 8) */
 typedef struct sdmi_vae_cfg {
   int32_t ch;
   int32_t out_ch;
@@ -262,7 +263,13 @@ int sdmi_vae_precision(const sdmi_vae* h);        /* SDMI_PRECISION_*, or -1 for
  * ONE flash launch (sdmi_k_attention's kernels, d = 512 on KL-f16) -> proj_out + residual: no N x N score buffer, any latent size.  In
  * SDMI_PRECISION_FULL the blocks are the split-fp16 ones of sdmi_vae_create_precision.  Every attention width of the handle that its mode has
  * no kernel for (mixed: sdmi_k_attention's head dims; full: sdmi_k_attention_split16's) is refused here, by level.
- * z_channels and embed_dim may be up to 16 (double_z: a 32-channel encoder.conv_out and a 32 -> 32 quant_conv).
+ * z_channels and embed_dim may be up to 16 (double_z: a 32-channel encoder.conv_out and a 32 -> 32 quant_conv), or 32 or 64 (KL-f32 of
+ * models/first_stage_models/kl-f32: ch_mult [1,1,2,2,4,4], z_channels 64, embed_dim 64, attn_resolutions [16, 8] = mask 0b110000; its ends
+ * run sdmi_k_conv_in64 / sdmi_k_conv_out128 / sdmi_k_pointwise_nchw128's launches).  A codebook first stage (ext->n_embed > 0, double_z 0:
+ * VQ-f8 with attn_resolutions [32] = mask 1 << 3, VQ-f16 with [16] = 1 << 4) takes a mask like any other.
+ * In SDMI_PRECISION_MIXED a stage of six or more levels runs its decoder's mid block and its levels >= 4 (1 / 16 of the image resolution and
+ * below) with split-fp16 operands, as SDMI_PRECISION_FULL runs every layer; stages of up to five levels have fp16 operands throughout.
+ * A handle with mask 0 keeps the GEMM / softmax / GEMM mid attention where H * W % 64 == 0 and takes the flash form elsewhere.
  * sdmi_vae_create_precision(cfg, ext, parts, precision, out) = sdmi_vae_create_attn(cfg, ext, parts, precision, 0, out): mask 0 launches
  * exactly what that entry always launched. */
 int sdmi_vae_create_attn(const sdmi_vae_cfg* cfg, const sdmi_vae_ext* ext, int parts, int precision, uint32_t attn_level_mask,
@@ -653,6 +660,18 @@ int sdmi_k_conv_out(const float* h_nhwc, const float* w_ohwi, const float* bias,
  * more than 16 */
 int sdmi_k_conv_out32(const float* h_nhwc, const float* w_ohwi, const float* bias, float* out_nchw, int B, int H, int W,
                       int Cin, int Cout, void* stream);
+/* The wide latent ends of the first stages with 32 / 64 latent channels (KL-f32: decoder.conv_in 64 -> 512, encoder.conv_out 512 -> 128;
+ * additive, fp32 like the entries above).
+ *   sdmi_k_conv_in64     the 3x3 input convolution for up to 64 input channels: per output the bias, then k = ci*9 + ky*3 + kx ascending, an
+ *                        order that depends on Cin alone.  Cin <= 16 launches what sdmi_k_conv_in launches (the same bits); sdmi_k_conv_in
+ *                        keeps refusing more than 16.
+ *   sdmi_k_conv_out128   the 3x3 output convolution for up to 128 outputs at Cin <= 512, Cin % 4 == 0: ceil(Cout / 8) slices of eight outputs
+ *                        in one launch, the 4-pixel form where W % 4 == 0 and the pointers are 16-byte aligned, else one pixel per wave.  Up to
+ *                        32 outputs it launches what sdmi_k_conv_out32 launches, which keeps refusing more than 32. */
+int sdmi_k_conv_in64(const float* x_nchw, const float* w_oihw, const float* bias, float* out_nhwc, int B, int Cin, int H, int W,
+                     int Cout, void* stream);
+int sdmi_k_conv_out128(const float* h_nhwc, const float* w_ohwi, const float* bias, float* out_nchw, int B, int H, int W, int Cin,
+                       int Cout, void* stream);
 int sdmi_k_pack_conv_weight(const float* w_oihw, void* dst_f16, int O, int I, int KH, int KW, void* stream);
 /* ... for A sources that are multiples of 32 channels (c0 + c1 + c2 == I, each % 32 == 0): the 64-channel chunks are numbered per source,
  * and the last chunk of a source of 32 (mod 64) channels is 32 wide (the kernels' half k-tile).  K = KH*KW*I stays dense.  With every source
@@ -668,6 +687,11 @@ int sdmi_k_pack_conv_split3(const float* w_oihw, void* dst_f16, int O, int I, in
  * one kernel, per output: bias, then the input channels ascending); row softmax fp32 -> fp16 */
 int sdmi_k_pointwise_nchw(const float* x, const float* w, const float* bias, float* out, int B, int Cin, int Cout, int HW,
                           float in_scale, void* stream);
+/* ... on up to 128 input channels (KL-f32: quant_conv 128 -> 128, post_quant_conv 64 -> 64): a thread owns a pixel and a block of 16
+ * output accumulators and walks the input channels once -- per output the bias, then the input channels ascending, as above.  Cin <= 32
+ * launches what sdmi_k_pointwise_nchw launches, which keeps refusing more than 32. */
+int sdmi_k_pointwise_nchw128(const float* x, const float* w, const float* bias, float* out, int B, int Cin, int Cout, int HW,
+                             float in_scale, void* stream);
 int sdmi_k_softmax_rows(const float* S, void* P_f16, int rows, int cols, float scale, void* stream);
 /* exact-erf GELU (the BERT encoder's feed-forward activation): fp32 [n] -> fp16 [n], n % 4 == 0 */
 /* The codebook quantizer of VectorQuantizer2 (legacy): per pixel of z' = z_scale * z (z fp32 NCHW [B, D, HW]) the first index of

@@ -449,6 +449,12 @@ int launch_conv_in(const float* x_nchw, const float* w, const float* bias, float
                    const int* gn_cbase = nullptr);
 int launch_conv_out(const float* h_nhwc, const float* w_khwc, const float* bias, float* out_nchw, int B, int H, int W,
                     int Cin, int Cout, hipStream_t s);
+// the wide latent ends of the first stage (KL-f32: 64 latent channels): the launches above up to their limits (16 inputs / 32 outputs), beyond
+// them conv_in64_kernel (Cin <= 64) and the sliced conv_out kernels with up to 16 slices (Cout <= 128, Cin <= 512)
+int launch_conv_in64(const float* x_nchw, const float* w, const float* bias, float* out_nhwc, int B, int Cin, int H, int W, int Cout,
+                     hipStream_t s);
+int launch_conv_out128(const float* h_nhwc, const float* w_khwc, const float* bias, float* out_nchw, int B, int H, int W, int Cin,
+                       int Cout, hipStream_t s);
 
 // DPM-Solver++ multistep step (see sampler.hip)
 struct DpmStepParams {
@@ -492,6 +498,9 @@ int launch_safety_head(const float* image_embeds, const float* concept_embeds, c
 // first-stage (VAE) helpers
 int launch_pointwise_nchw(const float* x_nchw, const float* w, const float* bias, float* out_nchw, int B, int Cin, int Cout,
                           int HW, float in_scale, hipStream_t s);
+// ... and up to 128 input channels (Cin <= 32: the launch above; beyond: pointwise_nchw_wide_kernel)
+int launch_pointwise_nchw128(const float* x_nchw, const float* w, const float* bias, float* out_nchw, int B, int Cin, int Cout,
+                             int HW, float in_scale, hipStream_t s);
 int launch_softmax_rows(const float* S, f16* P, int rows, int cols, int lds, int ldp, float scale, hipStream_t s);
 
 // latent-inpainting model (inpaint.hip)

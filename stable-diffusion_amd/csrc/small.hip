@@ -193,6 +193,48 @@ __global__ void __launch_bounds__(256) conv_in_kernel(const float* x, const floa
   }
 }
 
+// The same convolution for 17 .. 64 input channels (decoder.conv_in of the first stages with 32 / 64 latent channels: KL-f32 is 64 -> 512):
+// conv_in_kernel's loop over a 36 KB patch -- per output the bias, then k = ci*9 + ky*3 + kx ascending over K = 9 * Cin <= 576, an order
+// that depends on Cin alone.  blockIdx.y picks 256 outputs (the patch is built once per block of outputs: a latent has few pixels, and 512
+// outputs in one block would be two serial passes of 576 steps on 32 of the 256 CUs).  No GroupNorm statistics (the UNet's conv_in, which feeds them, has at most 16 input channels).
+constexpr int CI64_MAXK = 9 * 64;
+__global__ void __launch_bounds__(256) conv_in64_kernel(const float* x, const float* w, const float* bias, float* out, int B,
+                                                        int Cin, int H, int W, int Cout) {
+  __shared__ float patch[CI_PIX][CI64_MAXK];
+  const int tid = threadIdx.x;
+  const int K = Cin * 9;
+  const int M = B * H * W;
+  const int m0 = blockIdx.x * CI_PIX;
+  for (int idx = tid; idx < CI_PIX * K; idx += 256) {
+    const int pi = idx / K, k = idx - pi * K;
+    const int m = m0 + pi;
+    float v = 0.f;
+    if (m < M) {
+      const int b = m / (H * W), rem = m - b * H * W, y = rem / W, xx = rem - y * W;
+      const int ci = k / 9, t = k - ci * 9, ky = t / 3, kx = t - ky * 3;
+      const int iy = y + ky - 1, ix = xx + kx - 1;
+      if (iy >= 0 && iy < H && ix >= 0 && ix < W) v = x[(((size_t)b * Cin + ci) * H + iy) * W + ix];
+    }
+    patch[pi][k] = v;
+  }
+  __syncthreads();
+  for (int co = blockIdx.y * 256 + tid; co < Cout; co += 256 * gridDim.y) {   // (one pass: gridDim.y = ceil(Cout / 256))
+    float acc[CI_PIX];
+    const float bv = bias ? bias[co] : 0.f;
+#pragma unroll
+    for (int pi = 0; pi < CI_PIX; ++pi) acc[pi] = bv;
+    const float* wr = w + (size_t)co * K;
+    for (int k = 0; k < K; ++k) {
+      const float wv = wr[k];
+#pragma unroll
+      for (int pi = 0; pi < CI_PIX; ++pi) acc[pi] += wv * patch[pi][k];
+    }
+#pragma unroll
+    for (int pi = 0; pi < CI_PIX; ++pi)
+      if (m0 + pi < M) out[(size_t)(m0 + pi) * Cout + co] = acc[pi];
+  }
+}
+
 constexpr int CO_MAXN = 8;
 // h NHWC fp32 (already GroupNorm+SiLU'd), w [Cout][3][3][Cin] fp32 -> out NCHW fp32; one wave per output pixel
 __global__ void __launch_bounds__(256) conv_out_kernel(const float* h, const float* w, const float* bias, float* out, int B,
@@ -319,7 +361,9 @@ __global__ void __launch_bounds__(256) conv_out4_kernel(const float* h, const fl
 // profiles/kernel_resources_conv_out16.txt, kernel_resources_conv_out32.txt), every weight quad still loaded once per wave and tap; the
 // input rows are read by every slice (the later reads hit L2).  An accumulator sees exactly the terms conv_out_kernel gives it, in its
 // order: taps ascending, channel quads ascending inside a tap, out-of-image taps skipped.
-// Cin <= 512, W % COP == 0, Cout <= 8 * gridDim.y <= 4 * CO_MAXN; outputs n >= Cout of the last slice read weight row 0 and are not stored.
+// Cin <= 512, W % COP == 0, Cout <= 8 * gridDim.y; outputs n >= Cout of the last slice read weight row 0 and are not stored.
+// launch_conv_out stops at four slices (32 outputs); launch_conv_out128 runs the same two kernels with up to sixteen (the 128 moment
+// channels of KL-f32's encoder.conv_out): a slice never looks at another slice's outputs, so nothing in the kernels changes with their count.
 __global__ void __launch_bounds__(256) conv_out4_halves_kernel(const float* h, const float* w, const float* bias, float* out, int B,
                                                                int H, int W, int Cin, int Cout) {
   constexpr int NOUT = CO_MAXN;
@@ -638,6 +682,32 @@ __global__ void __launch_bounds__(256) pointwise_nchw_kernel(const float* x, con
   }
 }
 
+// The same 1x1 conv for 33 .. 128 input channels (KL-f32: quant_conv 128 -> 128, post_quant_conv 64 -> 64).  128 inputs per lane would
+// not stay in registers, so the roles are swapped: a thread owns one pixel and PWW_NOUT output accumulators (blockIdx.y picks the block of
+// outputs), walks the input channels once, ascending, and feeds each loaded input to its accumulators; the weights are wave-uniform.
+// Per output: the bias, then the input channels ascending, each input multiplied by in_scale when it is loaded -- pointwise_nchw_kernel's
+// order.  The input is read once per block of outputs (Cout / 16 times: L2 hits at latent resolution).
+constexpr int PWW_NOUT = 16;
+__global__ void __launch_bounds__(256) pointwise_nchw_wide_kernel(const float* x, const float* w, const float* bias, float* out,
+                                                                  int B, int Cin, int Cout, int HW, float in_scale) {
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (int64_t)B * HW) return;
+  const int b = (int)(idx / HW), pix = (int)(idx - (int64_t)b * HW);
+  const int o0 = blockIdx.y * PWW_NOUT;
+  float acc[PWW_NOUT];
+#pragma unroll
+  for (int o = 0; o < PWW_NOUT; ++o) acc[o] = (bias && o0 + o < Cout) ? bias[o0 + o] : 0.f;
+  const float* xp = x + (size_t)b * Cin * HW + pix;
+  for (int c = 0; c < Cin; ++c) {
+    const float v = xp[(size_t)c * HW] * in_scale;
+#pragma unroll
+    for (int o = 0; o < PWW_NOUT; ++o) acc[o] += w[(size_t)(o0 + o < Cout ? o0 + o : 0) * Cin + c] * v;    // (outputs past Cout: row 0, not stored)
+  }
+#pragma unroll
+  for (int o = 0; o < PWW_NOUT; ++o)
+    if (o0 + o < Cout) out[((size_t)b * Cout + o0 + o) * HW + pix] = acc[o];
+}
+
 // P[r][c] = softmax_c(S[r][c] * scale), fp32 in -> fp16 out; one block per row (AttnBlock, model.py:186-187)
 __global__ void __launch_bounds__(256) softmax_rows_kernel(const float* S, f16* P, int cols, int lds, int ldp, float scale) {
   __shared__ float red[8];
@@ -743,6 +813,35 @@ int launch_conv_in(const float* x, const float* w, const float* bias, float* out
   return 0;
 }
 
+// up to 64 input channels: Cin <= 16 is launch_conv_in's launch (no statistics), above it conv_in64_kernel
+int launch_conv_in64(const float* x, const float* w, const float* bias, float* out, int B, int Cin, int H, int W, int Cout, hipStream_t s) {
+  if (Cin * 9 <= CI_MAXK) return launch_conv_in(x, w, bias, out, B, Cin, H, W, Cout, s);
+  SDMI_CHECK(Cin * 9 <= CI64_MAXK, "conv_in64: in_channels <= 64");
+  SDMI_CHECK(B >= 1 && H >= 1 && W >= 1 && Cout >= 1, "conv_in64: bad shape");
+  ProfScope ps("conv_in64_f32", 2.0 * B * H * W * (double)Cout * Cin * 9, (double)B * H * W * (Cin + Cout) * 4.0, s);
+  SDMI_CHECK(Cout <= 256 * 65535, "conv_in64: out_channels");
+  SDMI_LAUNCH(conv_in64_kernel, dim3(cdiv(B * H * W, CI_PIX), cdiv(Cout, 256)), dim3(256), 0, s, x, w, bias, out, B, Cin, H, W, Cout);
+  SDMI_HIP_OK(hipGetLastError());
+  return 0;
+}
+
+// up to 128 outputs: Cout <= 32 is launch_conv_out's launch, above it the same sliced kernels with 5 .. 16 slices of eight outputs
+int launch_conv_out128(const float* h, const float* w, const float* bias, float* out, int B, int H, int W, int Cin, int Cout,
+                       hipStream_t s) {
+  if (Cout <= 4 * CO_MAXN) return launch_conv_out(h, w, bias, out, B, H, W, Cin, Cout, s);
+  SDMI_CHECK(Cout <= 16 * CO_MAXN && Cin >= 4 && Cin <= 512 && Cin % 4 == 0, "conv_out128: out_channels <= 128, Cin <= 512, Cin % 4 == 0");
+  SDMI_CHECK(B >= 1 && H >= 1 && W >= 1, "conv_out128: bad shape");
+  ProfScope ps("conv_out128_f32", 2.0 * B * H * W * (double)Cout * Cin * 9, (double)B * H * W * (Cin + Cout) * 4.0, s);
+  const bool al = ((((uintptr_t)h | (uintptr_t)w | (uintptr_t)out) & 15) == 0);
+  const int slices = cdiv(Cout, CO_MAXN);
+  if (W % COP == 0 && al)
+    SDMI_LAUNCH(conv_out4_halves_kernel, dim3(cdiv(B * H * (W / COP), 4), slices), dim3(256), 0, s, h, w, bias, out, B, H, W, Cin, Cout);
+  else
+    SDMI_LAUNCH(conv_out_halves_kernel, dim3(cdiv(B * H * W, 4), slices), dim3(256), 0, s, h, w, bias, out, B, H, W, Cin, Cout);
+  SDMI_HIP_OK(hipGetLastError());
+  return 0;
+}
+
 int launch_conv_out(const float* h, const float* w, const float* bias, float* out, int B, int H, int W, int Cin, int Cout,
                     hipStream_t s) {
   SDMI_CHECK(Cout >= 1 && Cout <= 4 * CO_MAXN && Cin % 4 == 0, "conv_out: out_channels <= 32, Cin % 4 == 0");
@@ -821,6 +920,18 @@ int launch_pointwise_nchw(const float* x, const float* w, const float* bias, flo
   const dim3 grid((unsigned)((total + 255) / 256));
   if (Cin <= 16) SDMI_LAUNCH(pointwise_nchw_kernel<16>, grid, dim3(256), 0, s, x, w, bias, out, B, Cin, Cout, HW, in_scale);
   else SDMI_LAUNCH(pointwise_nchw_kernel<32>, grid, dim3(256), 0, s, x, w, bias, out, B, Cin, Cout, HW, in_scale);
+  SDMI_HIP_OK(hipGetLastError());
+  return 0;
+}
+
+// up to 128 input channels: Cin <= 32 is launch_pointwise_nchw's launch, above it pointwise_nchw_wide_kernel
+int launch_pointwise_nchw128(const float* x, const float* w, const float* bias, float* out, int B, int Cin, int Cout, int HW,
+                             float in_scale, hipStream_t s) {
+  if (Cin <= 32) return launch_pointwise_nchw(x, w, bias, out, B, Cin, Cout, HW, in_scale, s);
+  SDMI_CHECK(Cin <= 128 && Cout >= 1 && Cout <= 1024 && B >= 1 && HW >= 1, "pointwise conv 128: 1 <= Cin <= 128, Cout <= 1024");
+  const int64_t total = (int64_t)B * HW;
+  SDMI_LAUNCH(pointwise_nchw_wide_kernel, dim3((unsigned)((total + 255) / 256), cdiv(Cout, PWW_NOUT)), dim3(256), 0, s, x, w, bias, out,
+              B, Cin, Cout, HW, in_scale);
   SDMI_HIP_OK(hipGetLastError());
   return 0;
 }

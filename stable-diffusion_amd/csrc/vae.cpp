@@ -12,7 +12,9 @@
 // d = C = 512 is three GEMMs (q k^T, softmax rows, P v) on the igemm kernel, in query chunks so S stays cache-sized.
 // A handle created with attention at resolution levels (sdmi_vae_create_attn, attn_level_mask != 0: KL-f16 of the retrieval-augmented model,
 // AttnBlocks after every ResBlock of the 16 x 16 level) runs every attention block, level and mid, as one flash launch instead
-// (VFwd::attn_block_flash): no S / P buffers, any token count.
+// (VFwd::attn_block_flash): no S / P buffers, any token count.  A handle without level attention takes that form only at token counts the
+// GEMM form refuses (H W % 64 != 0).  On a mixed handle of six or more levels (KL-f32) the decoder's mid block and its levels >= 4 run with
+// split-fp16 operands, as every layer of a SDMI_PRECISION_FULL handle does (VLayer::split, set in Vae::build).
 //
 // A handle created with SDMI_PRECISION_FULL (sdmi_vae_create_precision) runs the same layers with every MFMA operand as a split-fp16
 // pair, as the UNet's full-precision mode does (unet.cpp: Fwd::res_block / resample / attn_block_full): GroupNorm writes hi | lo, the
@@ -24,6 +26,7 @@
 #include "split16.h"
 
 #include <math.h>
+#include <stdlib.h>
 
 #include <algorithm>
 
@@ -47,9 +50,13 @@ int Vae::build(const sdmi_vae_cfg& c, int parts, const sdmi_vae_ext* ext, int pr
   SDMI_CHECK(c.ch % 64 == 0, "ch must be a multiple of 64 on this path");
   // (z_channels 16 / embed_dim 16 with double_z: encoder.conv_out writes 32 channels, quant_conv reads 32 -- launch_conv_out's and
   // launch_pointwise_nchw's limits; decoder.conv_in reads 16 -- launch_conv_in's)
-  SDMI_CHECK(c.in_channels >= 1 && c.in_channels <= 16 && c.z_channels >= 1 && c.z_channels <= 16 && c.embed_dim >= 1 &&
-                 c.embed_dim <= 16 && c.out_ch >= 1 && c.out_ch <= 8,
-             "in_channels <= 16, z_channels <= 16, embed_dim <= 16, out_ch <= 8 on this path");
+  // ... and 32 or 64 of either (KL-f32: 64 / 64): the wide launches -- decoder.conv_in reads up to 64 (launch_conv_in64), encoder.conv_out
+  // writes up to 128 (launch_conv_out128), the quant convs read up to 128 (launch_pointwise_nchw128).  decode() / encode() call the wide
+  // launchers, which ARE the old launches up to the old limits.
+  auto latent_width = [](int v) { return (v >= 1 && v <= 16) || v == 32 || v == 64; };
+  SDMI_CHECK(c.in_channels >= 1 && c.in_channels <= 16 && latent_width(c.z_channels) && latent_width(c.embed_dim) && c.out_ch >= 1 &&
+                 c.out_ch <= 8,
+             "in_channels <= 16, z_channels <= 16 (or 32 / 64), embed_dim <= 16 (or 32 / 64), out_ch <= 8 on this path");
   const int n = c.n_levels;
   SDMI_CHECK((attn_level_mask >> n) == 0, "attn_level_mask " + std::to_string(attn_level_mask) + " names a level past the last one (" +
              std::to_string(n) + " levels)");
@@ -76,8 +83,6 @@ int Vae::build(const sdmi_vae_cfg& c, int parts, const sdmi_vae_ext* ext, int pr
                  " has no attention kernel (32 / 40 / 64 / 80 / 96 / 128 / 160, and 192 .. 1024 in steps of 64)");
   }
   auto level_attn = [&](int lvl) { return ((attn_level_mask >> lvl) & 1) != 0; };
-  const WKind conv_kind = full() ? W_CONV_SPLIT3 : W_CONV;
-  const WKind lin_kind = full() ? W_SPLIT3 : W_ROWS16;
   auto res = [&](const std::string& p, int ci, int co) { VLayer L; L.kind = V_RES; L.prefix = p; L.cin = ci; L.cout = co; return L; };
   auto one = [&](VKind k, const std::string& p, int ch) { VLayer L; L.kind = k; L.prefix = p; L.cin = ch; L.cout = ch; return L; };
 
@@ -96,6 +101,22 @@ int Vae::build(const sdmi_vae_cfg& c, int parts, const sdmi_vae_ext* ext, int pr
       if (lvl != 0) dec_.push_back(one(V_UP, "decoder.up." + std::to_string(lvl) + ".upsample", bi));
     }
     dec_c_end_ = bi;
+    // Mixed precision on a stage of six levels or more (KL-f32): the decoder's mid block and its levels at 1 / 16 of the image resolution and
+    // below run with split-fp16 operands, as a full-precision handle runs every layer.  A pixel of those maps reaches 16 x 16 .. 32 x 32
+    // image pixels, so an fp16 operand rounding there is a coherent error over a whole patch: with the reference's own arithmetic those
+    // layers carry 1.0e-3 of the decode's 1.3e-3 rms error at fp16 operands (profiles/first_stages_parity.txt), for about 8 % of its MACs.
+    // Stages of up to five levels -- every handle that built before KL-f32 -- keep the allocation they had.
+    if (!full() && n >= 6) {
+      for (auto& L : dec_) {
+        const bool mid = L.prefix.compare(0, 12, "decoder.mid.") == 0;
+        int lvl = -1;
+        if (!mid) lvl = atoi(L.prefix.c_str() + 11);            // "decoder.up.<lvl>."
+        L.split = mid || lvl >= 4;
+        if (L.split && L.kind == V_ATTN)
+          SDMI_CHECK(full_attn_width(L.cin), "first stage: " + L.prefix + " runs with split-fp16 operands and its width " + std::to_string(L.cin) +
+                     " has no split-fp16 attention kernel (64, 128, and 192 .. 1024 in steps of 64)");
+      }
+    }
   }
   if (parts & 2) {
     int bi = c.ch;
@@ -118,6 +139,9 @@ int Vae::build(const sdmi_vae_cfg& c, int parts, const sdmi_vae_ext* ext, int pr
   auto visit = [&](VLayer& L) {
     const std::string& p = L.prefix;
     const int64_t ci = L.cin, co = L.cout;
+    if (full()) L.split = true;
+    const WKind conv_kind = L.split ? W_CONV_SPLIT3 : W_CONV;
+    const WKind lin_kind = L.split ? W_SPLIT3 : W_ROWS16;
     switch (L.kind) {
       case V_RES:
         store_.expect(p + ".norm1.weight", {ci}, W_F32, &L.f32[0]);
@@ -129,7 +153,7 @@ int Vae::build(const sdmi_vae_cfg& c, int parts, const sdmi_vae_ext* ext, int pr
         store_.expect(p + ".conv2.weight", {co, co, 3, 3}, conv_kind, &L.w16[1]);
         store_.expect(p + ".conv2.bias", {co}, W_F32, &L.f32[5]);
         if (ci != co) {
-          store_.expect(p + ".nin_shortcut.weight", {co, ci, 1, 1}, (precise_1x1_ || full()) ? W_SPLIT3 : W_ROWS16, &L.w16[2]);
+          store_.expect(p + ".nin_shortcut.weight", {co, ci, 1, 1}, (precise_1x1_ || L.split) ? W_SPLIT3 : W_ROWS16, &L.w16[2]);
           store_.expect(p + ".nin_shortcut.bias", {co}, W_F32, &L.f32[6]);
         }
         break;
@@ -197,7 +221,7 @@ int Vae::finalize() {
   if (!full()) {
     SDMI_HIP_OK(hipDeviceSynchronize());           // (set_weight packed on the caller's stream)
     for (auto& L : dec_) {
-      if (L.kind != V_UP || L.cin % 64 != 0) continue;
+      if (L.kind != V_UP || L.cin % 64 != 0 || L.split) continue;     // (a split layer's weights are packed [w_hi | w_hi | w_lo])
       if (store_.alloc((void**)&L.w_up_phase, (size_t)16 * L.cout * L.cin * sizeof(f16))) return -1;
       if (launch_up_phase_weights(L.w16[0], L.w_up_phase, L.cout, L.cin, nullptr)) return -1;
     }
@@ -212,7 +236,7 @@ int Vae::finalize() {
 // ------------------------------------------------------------------------------------------------------
 struct VFwd : FwdBase {
   static constexpr float EPS = 1e-6f;        // Normalize(): GroupNorm(32, eps=1e-6)   model.py:37-38
-  bool full = false;                         // the handle's precision (Vae::full())
+  bool full = false;                         // the running layer takes split-fp16 operands (VLayer::split; run_layer sets it)
   bool flash = false;                        // the handle has level attention (Vae::attn_level_mask_ != 0): attn_block_flash, not attn_block
 
   // SDMI_PRECISION_FULL: the 3x3 convs take split-fp16 operands (FwdBase::split3 against weights packed W_CONV_SPLIT3; the `_lo` buffers
@@ -406,9 +430,15 @@ struct VFwd : FwdBase {
   }
 
   Act run_layer(VLayer& L, const Act& x) {
+    full = L.split;                            // (every layer of a full-precision handle; the layers Vae::build names on a mixed one)
     switch (L.kind) {
       case V_RES: return res_block(L, x);
-      case V_ATTN: return full ? attn_block_full(L, x) : (flash ? attn_block_flash(L, x) : attn_block(L, x));
+      case V_ATTN:
+        if (full) return attn_block_full(L, x);
+        // a handle without level attention keeps the GEMM / softmax / GEMM form wherever it runs (H W % 64 == 0: the launches it always
+        // made); a token count it refuses (KL-f4 / VQ-f4 at a 6 x 10 latent: 60 tokens) takes the flash form where the width has a kernel
+        if (flash || ((x.H * x.W) % 64 != 0 && mixed_attn_width(L.cin))) return attn_block_flash(L, x);
+        return attn_block(L, x);
       case V_UP: return resample(L, x, true);
       case V_DOWN: return resample(L, x, false);
     }
@@ -465,10 +495,10 @@ int Vae::decode(const float* z, float z_scale, float* img, int B, int H, int W, 
     float* zc = ext_.n_embed > 0 ? f.P<float>((size_t)B * cfg_.embed_dim * H * W) : nullptr;
     if (!d && quantize) {
       if (launch_vq_quantize(z, z_scale, cb_, cb_norm_, ext_.n_embed, cfg_.embed_dim, zc, nullptr, B, H * W, stream)) return -1;
-      if (launch_pointwise_nchw(zc, pq_w_, pq_b_, zq, B, cfg_.embed_dim, cfg_.z_channels, H * W, 1.0f, stream)) return -1;
-    } else if (!d && launch_pointwise_nchw(z, pq_w_, pq_b_, zq, B, cfg_.embed_dim, cfg_.z_channels, H * W, z_scale, stream)) return -1;
+      if (launch_pointwise_nchw128(zc, pq_w_, pq_b_, zq, B, cfg_.embed_dim, cfg_.z_channels, H * W, 1.0f, stream)) return -1;
+    } else if (!d && launch_pointwise_nchw128(z, pq_w_, pq_b_, zq, B, cfg_.embed_dim, cfg_.z_channels, H * W, z_scale, stream)) return -1;
     Act x; x.p = f.P<float>((size_t)B * H * W * c_in); x.C = c_in; x.H = H; x.W = W;
-    if (!d && launch_conv_in(zq, dci_w_, dci_b_, x.p, B, cfg_.z_channels, H, W, c_in, stream)) return -1;
+    if (!d && launch_conv_in64(zq, dci_w_, dci_b_, x.p, B, cfg_.z_channels, H, W, c_in, stream)) return -1;
     for (auto& L : dec_) x = f.run_layer(L, x);
     if (f.rc) return f.rc;
     float* hn = f.S<float>((size_t)B * x.H * x.W * x.C);
@@ -498,8 +528,8 @@ int Vae::encode(const float* img, float* moments, int B, int H, int W, void* wor
     f.groupnorm(x, nullptr, eno_g_, eno_b_, VFwd::EPS, 1, nullptr, hn, nullptr);
     const int zc2 = enc_zc();
     float* mo = f.S<float>((size_t)B * zc2 * x.H * x.W);
-    if (!d && !f.rc && launch_conv_out(hn, eco_w_, eco_b_, mo, B, x.H, x.W, x.C, zc2, stream)) return -1;
-    if (!d && !f.rc && launch_pointwise_nchw(mo, q_w_, q_b_, moments, B, zc2, enc_ed(), x.H * x.W, 1.0f, stream))
+    if (!d && !f.rc && launch_conv_out128(hn, eco_w_, eco_b_, mo, B, x.H, x.W, x.C, zc2, stream)) return -1;
+    if (!d && !f.rc && launch_pointwise_nchw128(mo, q_w_, q_b_, moments, B, zc2, enc_ed(), x.H * x.W, 1.0f, stream))
       return -1;
     return f.rc;
   });

@@ -20,6 +20,9 @@ struct VLayer {
   // V_UP / V_DOWN: w16 = {conv},                         f32 = {conv.b}
   f16* w16[4] = {nullptr, nullptr, nullptr, nullptr};
   float* f32[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  // every MFMA operand of the layer is a split-fp16 pair and its weights are packed for that: all layers of a SDMI_PRECISION_FULL handle,
+  // and on a mixed handle the decoder layers Vae::build names (the mid block and the levels at 1 / 16 resolution and below of a six-level stage)
+  bool split = false;
   f16* w_up_phase = nullptr;     // V_UP, mixed precision, cin % 64 == 0: [4][cout][4 cin] weights of the conv's four 2x2 phase convs (finalize())
 };
 

@@ -314,3 +314,54 @@ def synthetic_kl_f16_state_dict(seed=0, kwargs=None):
     kw = kwargs or KL_F16_KWARGS
     m = AutoencoderKLHIP(kw['ddconfig'], None, kw['embed_dim'])
     return synthetic_named_state_dict([(k, tuple(v.shape)) for k, v in m.state_dict().items()], seed)
+
+
+# ---- the rest of the first-stage zoo (models/first_stage_models/*, configs/autoencoder/*) ------------------------------------------------
+# KL-f32: six levels, AttnBlocks after every ResBlock of the 16 x 16 and 8 x 8 levels (levels 4 and 5: mask 0b110000, d = 512), 64 latent
+# channels -- decoder.conv_in 64 -> 512, encoder.conv_out 512 -> 128, quant_conv 128 -> 128, post_quant_conv 64 -> 64 (the wide fp32 ends)
+KL_F32_DDCONFIG = dict(double_z=True, z_channels=64, resolution=256, in_channels=3, out_ch=3, ch=128, ch_mult=[1, 1, 2, 2, 4, 4],
+                       num_res_blocks=2, attn_resolutions=[16, 8], dropout=0.0)            # kl-f32/config.yaml:13-31 = autoencoder_kl_8x8x64.yaml
+KL_F32_KWARGS = dict(embed_dim=64, ddconfig=KL_F32_DDCONFIG)                               # yaml:6
+# KL-f4: three levels, no level attention, 3 latent channels (a 6-channel encoder.conv_out and quant_conv)
+KL_F4_DDCONFIG = dict(double_z=True, z_channels=3, resolution=256, in_channels=3, out_ch=3, ch=128, ch_mult=[1, 2, 4], num_res_blocks=2,
+                      attn_resolutions=[], dropout=0.0)                                    # kl-f4/config.yaml:13-26 = autoencoder_kl_64x64x3.yaml
+KL_F4_KWARGS = dict(embed_dim=3, ddconfig=KL_F4_DDCONFIG)                                  # yaml:6
+# VQ-f8 (also the first stage of models/ldm/cin256 and configs/latent-diffusion/cin-ldm-vq-f8.yaml): level attention at 32 x 32 (level 3)
+VQ_F8_DDCONFIG = dict(double_z=False, z_channels=4, resolution=256, in_channels=3, out_ch=3, ch=128, ch_mult=[1, 2, 2, 4], num_res_blocks=2,
+                      attn_resolutions=[32], dropout=0.0)                                  # vq-f8/config.yaml:8-23
+VQ_F8_KWARGS = dict(embed_dim=4, n_embed=16384, ddconfig=VQ_F8_DDCONFIG)                   # yaml:5-6
+VQ_F8_N256_KWARGS = dict(embed_dim=4, n_embed=256, ddconfig=VQ_F8_DDCONFIG)                # vq-f8-n256/config.yaml:5-23 (the same ddconfig)
+# VQ-f16: level attention at 16 x 16 (level 4), an 8-dimensional codebook
+VQ_F16_DDCONFIG = dict(double_z=False, z_channels=8, resolution=256, in_channels=3, out_ch=3, ch=128, ch_mult=[1, 1, 2, 2, 4],
+                       num_res_blocks=2, attn_resolutions=[16], dropout=0.0)               # vq-f16/config.yaml:7-23
+VQ_F16_KWARGS = dict(embed_dim=8, n_embed=16384, ddconfig=VQ_F16_DDCONFIG)                 # yaml:5-6
+# stand-ins for the tests: the yamls at ch 64 (level and mid attention at d = 256), and VQ-f8-n256 at ch 64
+FIRST_STAGES = {'kl_f32': KL_F32_KWARGS, 'kl_f32_thin': dict(embed_dim=64, ddconfig=dict(KL_F32_DDCONFIG, ch=64)),
+                'kl_f4': KL_F4_KWARGS,
+                'vq_f8': VQ_F8_KWARGS, 'vq_f8_thin': dict(VQ_F8_KWARGS, ddconfig=dict(VQ_F8_DDCONFIG, ch=64)),
+                'vq_f8_n256': VQ_F8_N256_KWARGS, 'vq_f8_n256_thin': dict(VQ_F8_N256_KWARGS, ddconfig=dict(VQ_F8_DDCONFIG, ch=64)),
+                'vq_f16': VQ_F16_KWARGS, 'vq_f16_thin': dict(VQ_F16_KWARGS, ddconfig=dict(VQ_F16_DDCONFIG, ch=64))}
+
+
+def make_first_stage(kwargs, hip_precision='mixed'):
+    """AutoencoderKLHIP or VQModelInterfaceHIP from one of the kwargs dicts above."""
+    from .vae import AutoencoderKLHIP, VQModelInterfaceHIP
+    if 'n_embed' in kwargs:
+        return VQModelInterfaceHIP(hip_precision=hip_precision, **kwargs)
+    return AutoencoderKLHIP(kwargs['ddconfig'], None, kwargs['embed_dim'], hip_precision=hip_precision)
+
+
+def synthetic_first_stage_state_dict(seed=0, kwargs=None):
+    """CPU state_dict (reference AutoencoderKL / VQModelInterface key names, without loss.*) of a seeded random first stage."""
+    m = make_first_stage(kwargs or KL_F32_KWARGS)
+    return synthetic_named_state_dict([(k, tuple(v.shape)) for k, v in m.state_dict().items()], seed)
+
+
+# ---- the older class-conditional ImageNet model (models/ldm/cin256/config.yaml) -------------------------------------------------------------
+# many heads of 32 channels (8 / 16 / 32 at 256 / 512 / 1024 channels) over ClassEmbedder's one-token context; VQ-f8 first stage
+CIN256_OLD_UNET_KWARGS = dict(image_size=32, in_channels=4, out_channels=4, model_channels=256, attention_resolutions=[4, 2, 1],
+                              num_res_blocks=2, channel_mult=[1, 2, 4], num_head_channels=32, use_spatial_transformer=True,
+                              transformer_depth=1, context_dim=512)                                        # yaml:17-36
+CIN256_OLD_VQ_KWARGS = VQ_F8_KWARGS                                                                        # yaml:37-57
+CIN256_OLD_CLASS_KWARGS = dict(embed_dim=512, key='class_label')                                           # yaml:60-64 (n_classes: the default 1000)
+CIN256_OLD_SCHEDULE = dict(timesteps=1000, linear_start=0.0015, linear_end=0.0195, conditioning_key='crossattn')   # yaml:5-6,9,15

@@ -80,12 +80,15 @@ def attn_level_mask(ddconfig):
 
 
 def make_vae_cfg(ddconfig, embed_dim, vq=False):
-    """vq: the VQModelInterface family (double_z False, attn_type 'vanilla' or 'none', no attn_resolutions); else the AutoencoderKL one
-    (SD-v1's KL-f8, and KL-f16 with attention at resolution levels: attn_level_mask)."""
+    """vq: the VQModelInterface family (double_z False, attn_type 'vanilla' or 'none'; attn_resolutions with 'vanilla' only: VQ-f8 [32],
+    VQ-f16 [16]); else the AutoencoderKL one (SD-v1's KL-f8, and KL-f16 / KL-f32 with attention at resolution levels: attn_level_mask)."""
     dd = dict(ddconfig)
     unsupported = []
-    if vq and list(dd.get('attn_resolutions', [])): unsupported.append('attn_resolutions=[] (mid-block attention only)')
-    if not vq: attn_level_mask(dd)           # (refuses an entry that names no level)
+    if vq and list(dd.get('attn_resolutions', [])) and dd.get('attn_type', 'vanilla') == 'none':
+        # (make_attn(.., 'none') is an Identity, model.py:205-216: the reference would silently build no attention at the levels named)
+        unsupported.append("attn_resolutions=[] with attn_type='none' (level attention needs attn_type='vanilla')")
+    else:
+        attn_level_mask(dd)                  # (refuses an entry that names no level)
     if dd.get('dropout', 0.0) != 0: unsupported.append('dropout=0')
     if vq:
         if dd.get('double_z', True): unsupported.append('double_z=False')
@@ -153,7 +156,7 @@ class AutoencoderKLHIP(nn.Module):
         """`hip_precision` (not a keyword of the reference AutoencoderKL): 'mixed' (default) = fp16 MFMA operands; 'full' = every MFMA
         operand of the ResBlocks, the resampling convs and the attention blocks is a split-fp16 pair (three MFMA passes), as in
         UNetModelHIP's full mode.  Fixed for the module's lifetime; the state_dict keys are the same in both modes.
-        `ddconfig['attn_resolutions']` (KL-f16: [16]) puts an AttnBlock behind every ResBlock of the levels it names (attn_level_mask)."""
+        `ddconfig['attn_resolutions']` (KL-f16: [16], KL-f32: [16, 8]) puts an AttnBlock behind every ResBlock of the levels it names (attn_level_mask)."""
         super().__init__()
         self.hip_precision = _check_precision(hip_precision)
         self.image_key = image_key
@@ -326,7 +329,9 @@ class VQModelInterfaceHIP(AutoencoderKLHIP):
     encode(x) = quant_conv(encoder(x)) with no quantization (autoencoder.py:269-272); decode(h, force_not_quantize=False) =
     decoder(post_quant_conv(quantize(h))) (:274-283), the quantizer being taming's VectorQuantizer2 in its legacy form: the
     nearest codebook row by sum(z^2) + sum(e^2) - 2 z.e, first index on ties, z_q = z + (e[idx] - z) in fp32 (HIP kernel).
-    Parameter names: encoder.*, decoder.*, quant_conv.*, post_quant_conv.*, quantize.embedding.weight."""
+    Parameter names: encoder.*, decoder.*, quant_conv.*, post_quant_conv.*, quantize.embedding.weight.
+    `ddconfig['attn_resolutions']` (models/first_stage_models/vq-f8: [32], vq-f16: [16]; attn_type 'vanilla') puts an AttnBlock behind
+    every ResBlock of the levels it names, as for AutoencoderKLHIP (attn_level_mask)."""
 
     def __init__(self, embed_dim, ddconfig=None, n_embed=None, lossconfig=None, ckpt_path=None, ignore_keys=[],
                  image_key='image', colorize_nlabels=None, monitor=None, batch_resize_range=None, scheduler_config=None,
@@ -349,7 +354,8 @@ class VQModelInterfaceHIP(AutoencoderKLHIP):
         ext = _lib.VaeExt()
         ext.double_z, ext.mid_attn, ext.n_embed = 0, int(self.ddconfig.get('attn_type', 'vanilla') != 'none'), self.n_embed
         self._parts = 3
-        self._handle = _VaeHandle(self._cfg, 3, ext, hip_precision)
+        self.attn_level_mask = attn_level_mask(ddconfig)      # attn_resolutions as levels (0: mid-block attention only)
+        self._handle = _VaeHandle(self._cfg, 3, ext, hip_precision, self.attn_level_mask)
         self._specs = self._handle.weight_specs()
         self.add_module('quantize', _QuantizerHIP(self._quantize))
         for key, shape in self._specs:
