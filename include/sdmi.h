@@ -210,6 +210,37 @@ int sdmi_dpm_solver_step(const float* eps_model, int cfg, float scale, const flo
                          float sigma_s, float cx, float a, float inv_r0, int order, float* m_out, float* x_next, int64_t n,
                          void* stream);
 
+/* ---- the other DPM-Solver variants (dpm_solver.py: singlestep, order 3, adaptive, thresholding).  fp32, every op rounded on its own
+ * in the reference's order; scalars come from the host, evaluated with the reference's own fp32 ops; -(c v) is passed as (-c) v.
+ *
+ * Model value (:340-346, :386-408): e = classifier-free combine of eps_model (rows [0,n) uncond, [n,2n) cond when cfg);
+ *   predict_x0 == 0: out = e;   else out = (x - sigma_s e) / alpha_s, and with s (device, one per sample of `row` elements):
+ *   out = clamp(out, -s[b], s[b]) / s[b] (:397-398). */
+int sdmi_dpm_model_value(const float* eps_model, int cfg, float scale, const float* x, int predict_x0, float alpha_s, float sigma_s,
+                         const float* s, int64_t row, float* out, int64_t n, void* stream);
+
+/* One update of the reference per launch; c9: nine host floats.
+ *   form 0: out = c0 x + c1 m0                                  dpm_solver_first_update (:530-545), x_s1 (:588-591, :682-685)
+ *   form 1: out = (c0 x + c1 m0) + c2 (c3 (m1 - m2))            singlestep second update and x_s2, singlestep third 'dpm_solver'
+ *                                                               (:594-627, :687-698, :726-737; c3 = 1), multistep second (:783-809; c3 = 1 / r0)
+ *   form 2: singlestep third 'taylor' (:700-709, :739-748): D1_0 = c4 (m1 - m0), D1_1 = c5 (m2 - m0), D1 = (c6 D1_0 - c7 D1_1) / c8,
+ *           D2 = (2 (D1_1 - D1_0)) / c8, out = ((c0 x + c1 m0) + c2 D1) + c3 D2
+ *   form 3: multistep third (:835-856): D1_0 = c4 (m0 - m1), D1_1 = c5 (m1 - m2), dd = D1_0 - D1_1, D1 = D1_0 + c6 dd, D2 = c7 dd,
+ *           out = ((c0 x + c1 m0) + c2 D1) + c3 D2 */
+int sdmi_dpm_update(int form, const float* x, const float* m0, const float* m1, const float* m2, const float* c9, float* out, int64_t n,
+                    void* stream);
+
+/* Dynamic-thresholding scale (:395-397): s_out[b] = max(quantile_0.995(|x0[b]|), max_val) by a radix select per row (no sort, no host
+ * sync, integer atomics only: the same bits for every launch and run); torch.quantile's rank 0.995 (row - 1) in fp32 and its lerp.
+ * A row with a NaN gives NaN.  stats_out (optional, [B, 2]): the two order statistics.  row <= 2^24. */
+int sdmi_dpm_threshold_scale(const float* x0, int B, int64_t row, float max_val, float* s_out, float* stats_out, void* stream);
+
+/* Adaptive error (:952-954): E[0] = max_b sqrt(mean(((x_higher - x_lower) / max(atol, rtol max(|x_lower|, |x_prev|)))^2)), left on the
+ * device; two launches, a summation tree fixed by `row` alone.  ws: at least the _ws_floats floats of device memory. */
+int64_t sdmi_dpm_adaptive_error_ws_floats(int B, int64_t row);
+int sdmi_dpm_adaptive_error(const float* x_higher, const float* x_lower, const float* x_prev, float atol, float rtol, int B, int64_t row,
+                            float* ws, int64_t ws_floats, float* E, void* stream);
+
 /* ---- first stage (AutoencoderKL): SURVEY.md 8 f-1 ---------------------------------------------------------------
  * Replaces instantiate_from_config(first_stage_config) (ddpm.py:462-467) for inference:
  * `decode_first_stage` (ddpm.py:705-763) -> AutoencoderKL.decode (autoencoder.py:330-333) -> Decoder.forward

@@ -101,6 +101,12 @@ _SIGS = {
                                  c_ptr, c_ptr, C.c_float, C.c_float, c_ptr, c_ptr, C.c_int64, c_ptr]),
     'sdmi_dpm_solver_step': (C.c_int, [c_ptr, C.c_int, C.c_float, c_ptr, c_ptr, C.c_float, C.c_float, C.c_float, C.c_float,
                                        C.c_float, C.c_int, c_ptr, c_ptr, C.c_int64, c_ptr]),
+    'sdmi_dpm_model_value': (C.c_int, [c_ptr, C.c_int, C.c_float, c_ptr, C.c_int, C.c_float, C.c_float, c_ptr, C.c_int64, c_ptr,
+                                       C.c_int64, c_ptr]),
+    'sdmi_dpm_update': (C.c_int, [C.c_int, c_ptr, c_ptr, c_ptr, c_ptr, C.POINTER(C.c_float), c_ptr, C.c_int64, c_ptr]),
+    'sdmi_dpm_threshold_scale': (C.c_int, [c_ptr, C.c_int, C.c_int64, C.c_float, c_ptr, c_ptr, c_ptr]),
+    'sdmi_dpm_adaptive_error_ws_floats': (C.c_int64, [C.c_int, C.c_int64]),
+    'sdmi_dpm_adaptive_error': (C.c_int, [c_ptr, c_ptr, c_ptr, C.c_float, C.c_float, C.c_int, C.c_int64, c_ptr, C.c_int64, c_ptr, c_ptr]),
     'sdmi_vae_create': (C.c_int, [C.POINTER(VaeCfg), C.c_int, C.POINTER(c_ptr)]),
     'sdmi_vae_destroy': (C.c_int, [c_ptr]),
     'sdmi_vae_create_ext': (C.c_int, [C.POINTER(VaeCfg), C.POINTER(VaeExt), C.c_int, C.POINTER(c_ptr)]),

@@ -200,6 +200,34 @@ int sdmi_dpm_solver_step(const float* eps_model, int cfg, float scale, const flo
   return launch_dpm_step(p, (hipStream_t)stream);
 }
 
+int sdmi_dpm_model_value(const float* eps_model, int cfg, float scale, const float* x, int predict_x0, float alpha_s, float sigma_s,
+                         const float* s, int64_t row, float* out, int64_t n, void* stream) {
+  DpmModelValueParams p = DpmModelValueParams();
+  p.eps_model = eps_model; p.cfg = cfg; p.scale = scale; p.x = x; p.predict_x0 = predict_x0; p.alpha_s = alpha_s; p.sigma_s = sigma_s;
+  p.s = s; p.row = row; p.out = out; p.n = n;
+  return launch_dpm_model_value(p, (hipStream_t)stream);
+}
+
+int sdmi_dpm_update(int form, const float* x, const float* m0, const float* m1, const float* m2, const float* c9, float* out, int64_t n,
+                    void* stream) {
+  SDMI_CHECK(c9, "dpm_update: null coefficients");
+  DpmUpdateParams p = DpmUpdateParams();
+  p.form = form; p.x = x; p.m0 = m0; p.m1 = m1; p.m2 = m2; p.out = out; p.n = n;
+  for (int i = 0; i < 9; ++i) p.c[i] = c9[i];
+  return launch_dpm_update(p, (hipStream_t)stream);
+}
+
+int sdmi_dpm_threshold_scale(const float* x0, int B, int64_t row, float max_val, float* s_out, float* stats_out, void* stream) {
+  return launch_dpm_threshold_scale(x0, B, row, max_val, s_out, stats_out, (hipStream_t)stream);
+}
+
+int64_t sdmi_dpm_adaptive_error_ws_floats(int B, int64_t row) { return B > 0 && row > 0 ? dpm_error_ws_floats(B, row) : -1; }
+
+int sdmi_dpm_adaptive_error(const float* x_higher, const float* x_lower, const float* x_prev, float atol, float rtol, int B, int64_t row,
+                            float* ws, int64_t ws_floats, float* E, void* stream) {
+  return launch_dpm_adaptive_error(x_higher, x_lower, x_prev, atol, rtol, B, row, ws, ws_floats, E, (hipStream_t)stream);
+}
+
 // ---- first stage --------------------------------------------------------------------------------------
 int sdmi_vae_create(const sdmi_vae_cfg* cfg, int parts, sdmi_vae** out) {
   return sdmi_vae_create_precision(cfg, nullptr, parts, SDMI_PRECISION_MIXED, out);

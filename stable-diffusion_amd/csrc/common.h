@@ -471,6 +471,33 @@ struct DpmStepParams {
 };
 int launch_dpm_step(const DpmStepParams& p, hipStream_t s);
 
+// the other DPM-Solver variants (see dpm.hip)
+struct DpmModelValueParams {
+  const float* eps_model = nullptr;  // as DpmStepParams
+  int cfg = 0; float scale = 1.f;
+  const float* x = nullptr;          // latent the model was evaluated at (predict_x0 only)
+  int predict_x0 = 0;
+  float alpha_s = 1.f, sigma_s = 0.f;
+  const float* s = nullptr;          // optional per-sample thresholding scale [n / row], device memory
+  int64_t row = 0;                   // elements per sample (with s)
+  float* out = nullptr;
+  int64_t n = 0;
+};
+int launch_dpm_model_value(const DpmModelValueParams& p, hipStream_t s);
+struct DpmUpdateParams {
+  int form = 0;                      // 0 LIN, 1 DIFF, 2 SS3T, 3 MS3 (dpm.hip)
+  const float* x = nullptr;
+  const float* m0 = nullptr; const float* m1 = nullptr; const float* m2 = nullptr;
+  float c[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  float* out = nullptr;
+  int64_t n = 0;
+};
+int launch_dpm_update(const DpmUpdateParams& p, hipStream_t s);
+int launch_dpm_threshold_scale(const float* x0, int B, int64_t row, float max_val, float* s_out, float* stats_out, hipStream_t s);
+int64_t dpm_error_ws_floats(int B, int64_t row);
+int launch_dpm_adaptive_error(const float* x_higher, const float* x_lower, const float* x_prev, float atol, float rtol, int B, int64_t row,
+                              float* ws, int64_t ws_floats, float* E, hipStream_t s);
+
 // text-encoder helpers: out[m][:] = tok_emb[ids[m]][:] + pos_emb[m % L][:] (fp32); out16 = fp16(x * sigmoid(1.702 x))
 int launch_embed_tokens(const int64_t* ids, const float* tok_emb, const float* pos_emb, float* out, int M, int L, int C,
                         int vocab, hipStream_t s);

@@ -541,10 +541,23 @@ class _DiscreteVP:
         self.t_array = torch.linspace(0., 1., self.N + 1)[1:]
         self.log_alpha_array = 0.5 * torch.log(ac)
 
+    @staticmethod
+    def _interp(x, xp, yp):
+        """interpolate_fn (dpm_solver.py:1132-1171) for a 1-D x: the segment its sort picks, then the same fp32 expression"""
+        i = torch.clamp(torch.searchsorted(xp, x.contiguous()) - 1, 0, xp.shape[0] - 2)
+        return yp[i] + (x - xp[i]) * (yp[i + 1] - yp[i]) / (xp[i + 1] - xp[i])
+
     def log_alpha(self, t):
         xp, yp = self.t_array, self.log_alpha_array
+        if t.dim() == 1:                    # vector form (the plans of DPMSolverHIP); elementwise the 0-dim form below
+            return self._interp(t, xp, yp)
         i = int(torch.clamp(torch.searchsorted(xp, t.reshape(1)) - 1, 0, self.N - 2))
         return yp[i] + (t - xp[i]) * (yp[i + 1] - yp[i]) / (xp[i + 1] - xp[i])
+
+    def inverse_lambda(self, lamb):
+        """dpm_solver.py:166-169 ('discrete'), lamb 1-D: t of a half-logSNR, through the flipped tables"""
+        log_alpha = -0.5 * torch.logaddexp(torch.zeros((1,)), -2. * lamb)
+        return self._interp(log_alpha, torch.flip(self.log_alpha_array, [0]), torch.flip(self.t_array, [0]))
 
     def alpha(self, t):
         return torch.exp(self.log_alpha(t))
@@ -584,12 +597,459 @@ def dpm_plan(ns, S):
     return plan
 
 
+# ---- the rest of DPM_Solver (dpm_solver.py:351-1124): singlestep, order 3, adaptive, thresholding, either prediction type ---------
+DPM_KEYWORDS = ('steps', 't_start', 't_end', 'order', 'skip_type', 'method', 'lower_order_final', 'denoise_to_zero', 'solver_type', 'atol',
+                'rtol')
+_EVAL, _UPDATE = 0, 1
+_LIN, _DIFF, _SS3T, _MS3 = 0, 1, 2, 3           # the kernel forms of sdmi_dpm_update (csrc/dpm.hip)
+
+
+def _c(v):
+    """a host scalar as the fp32 the reference's tensor op sees: a one-element fp32 tensor's value, or a Python float rounded to fp32
+    (what torch does with a Python scalar operand of an fp32 tensor op)"""
+    return float(v.reshape(-1)[0]) if torch.is_tensor(v) else float(np.float32(v))
+
+
+class DPMPlan:
+    """What a non-adaptive DPM_Solver.sample does, op by op, with every scalar already evaluated:
+    ops  int32 [n, 7]: (kind, form, dst, x, m0, m1, m2) -- slots name tensors, slot 0 is the initial x, -1 is none;
+                       kind 0 = model evaluation at x (form 1: the data prediction whatever predict_x0 is -- denoise_to_zero_fn),
+                       kind 1 = update of form `form` (sdmi_dpm_update)
+    coef fp32 [n, 9]:  evaluation: (t, t_input, alpha_t, sigma_t); update: c0..c8
+    timesteps, orders: the outer time grid and the order of each outer step;  result: the slot of the end point"""
+
+    def __init__(self, ops, coef, timesteps, orders, result):
+        self.ops = np.asarray(ops, dtype=np.int32).reshape(-1, 7)
+        self.coef = np.asarray(coef, dtype=np.float32).reshape(-1, 9)
+        self.timesteps = np.asarray(timesteps, dtype=np.float32)
+        self.orders = np.asarray(orders, dtype=np.int32)
+        self.result = int(result)
+
+    def model_times(self):
+        """t_input of every model evaluation, in order"""
+        return [float(c[1]) for o, c in zip(self.ops, self.coef) if o[0] == _EVAL]
+
+
+class _PlanBuilder:
+    def __init__(self, ns):
+        self.ns, self.ops, self.coef, self.n_slots = ns, [], [], 1
+
+    def _emit(self, kind, form, x, ms, coef):
+        dst = self.n_slots
+        self.n_slots += 1
+        ms = list(ms) + [-1] * (3 - len(ms))
+        self.ops.append((kind, form, dst, x) + tuple(ms))
+        self.coef.append([_c(v) for v in coef] + [0.0] * (9 - len(coef)))
+        return dst
+
+    def eval(self, x, t, data_prediction=False):
+        ns = self.ns
+        return self._emit(_EVAL, int(data_prediction), x, (), (t, (t - 1. / ns.N) * 1000., ns.alpha(t), ns.sigma(t)))
+
+    def update(self, form, x, ms, coef):
+        return self._emit(_UPDATE, form, x, ms, coef)
+
+
+class DPMSolverHIP:
+    """DPM_Solver (dpm_solver.py:351-1124) over a 'discrete' NoiseScheduleVP: `sample` with every keyword and default of the reference
+    (:965-967).  The host evaluates each scalar sub-expression of an update with the reference's own torch ops on one-element fp32
+    CPU tensors, in its order; the device runs one launch per model value and one per update (csrc/dpm.hip), whose bits equal the
+    reference's elementwise expression.  For the non-adaptive methods the whole plan -- times, model-input times, orders, coefficients
+    -- is computed before the loop (`plan`), the adaptive solver reads back its four-byte error once per iteration and nothing else.
+
+    eps_fn(x, t_input) -> the raw model output, fp32 contiguous: [B, ...], or with cfg [2B, ...] = (unconditional, conditional) rows
+    -- the noise_pred_fn of model_wrapper (:289-310, model_type 'noise') without the combine, which the model-value launch does.
+
+    Refused, because the reference itself raises there: method='singlestep' with a skip_type other than 'logSNR'
+    (dpm_solver.py:495), with order=1 and steps > 1 (:1114), and method='multistep', order=3, lower_order_final=True with
+    4 <= steps < 15 (:773)."""
+
+    def __init__(self, eps_fn, noise_schedule, predict_x0=False, thresholding=False, max_val=1., cfg=False, scale=1.):
+        self.eps_fn, self.ns = eps_fn, noise_schedule
+        self.predict_x0, self.thresholding, self.max_val = bool(predict_x0), bool(thresholding), float(max_val)
+        self.cfg, self.scale = bool(cfg), float(scale)
+        self.model_times = []           # t_input of every evaluation of the last run
+        self.adaptive_log = []          # (E, accepted) of every iteration of the last adaptive run
+
+    # ---- time grids (:410-437, :439-496) ----------------------------------------------------------------------------------------
+    def get_time_steps(self, skip_type, t_T, t_0, N):
+        ns = self.ns
+        if skip_type == 'logSNR':
+            lambda_T = ns.lam(torch.tensor([t_T]))
+            lambda_0 = ns.lam(torch.tensor([t_0]))
+            return ns.inverse_lambda(torch.linspace(lambda_T.item(), lambda_0.item(), N + 1))
+        if skip_type == 'time_uniform':
+            return torch.linspace(t_T, t_0, N + 1)
+        if skip_type == 'time_quadratic':
+            t_order = 2
+            return torch.linspace(t_T ** (1. / t_order), t_0 ** (1. / t_order), N + 1).pow(t_order)
+        raise ValueError("Unsupported skip_type {}, need to be 'logSNR' or 'time_uniform' or 'time_quadratic'".format(skip_type))
+
+    def get_orders_and_timesteps_for_singlestep_solver(self, steps, order, skip_type, t_T, t_0):
+        if order == 3:
+            K = steps // 3 + 1
+            if steps % 3 == 0:
+                orders = [3, ] * (K - 2) + [2, 1]
+            elif steps % 3 == 1:
+                orders = [3, ] * (K - 1) + [1]
+            else:
+                orders = [3, ] * (K - 1) + [2]
+        elif order == 2:
+            if steps % 2 == 0:
+                K = steps // 2
+                orders = [2, ] * K
+            else:
+                K = steps // 2 + 1
+                orders = [2, ] * (K - 1) + [1]
+        elif order == 1:
+            K = 1
+            orders = [1, ] * steps
+            if steps > 1:
+                raise ValueError("method='singlestep' with order=1 and steps > 1 raises in the reference (dpm_solver.py:1114: K = 1 gives "
+                                 "two outer timesteps for `steps` steps); use method='singlestep_fixed' or 'multistep'")
+        else:
+            raise ValueError("'order' must be '1' or '2' or '3'.")
+        if skip_type != 'logSNR':
+            raise ValueError(f"method='singlestep' with skip_type={skip_type!r} raises in the reference (dpm_solver.py:495: torch.cumsum "
+                             "without dim); only skip_type='logSNR' runs there")
+        return self.get_time_steps(skip_type, t_T, t_0, K), orders
+
+    # ---- the scalars of each update, transcribed expression for expression; s, t, ...: one-element fp32 tensors --------------------
+    def _first(self, s, t):
+        """dpm_solver_first_update (:518-545) -> (c0, c1) of form LIN"""
+        ns = self.ns
+        h = ns.lam(t) - ns.lam(s)
+        if self.predict_x0:
+            return ns.sigma(t) / ns.sigma(s), -(ns.alpha(t) * torch.expm1(-h))
+        return torch.exp(ns.log_alpha(t) - ns.log_alpha(s)), -(ns.sigma(t) * torch.expm1(h))
+
+    def _ss2(self, s, t, r1, solver_type):
+        """singlestep_dpm_solver_second_update (:568-631) -> s1, (c0, c1) of x_s1 [LIN], (c0, c1, c2, 1) of x_t [DIFF]"""
+        if solver_type not in ['dpm_solver', 'taylor']:
+            raise ValueError("'solver_type' must be either 'dpm_solver' or 'taylor', got {}".format(solver_type))
+        if r1 is None:
+            r1 = 0.5
+        ns = self.ns
+        lambda_s, lambda_t = ns.lam(s), ns.lam(t)
+        h = lambda_t - lambda_s
+        s1 = ns.inverse_lambda(lambda_s + r1 * h)
+        if self.predict_x0:
+            phi_11 = torch.expm1(-r1 * h)
+            phi_1 = torch.expm1(-h)
+            a = (ns.sigma(s1) / ns.sigma(s), -(ns.alpha(s1) * phi_11))
+            c0, c1 = ns.sigma(t) / ns.sigma(s), ns.alpha(t) * phi_1
+            if solver_type == 'dpm_solver':
+                c2 = -((0.5 / r1) * c1)
+            else:
+                c2 = (1. / r1) * (ns.alpha(t) * ((torch.exp(-h) - 1.) / h + 1.))
+        else:
+            phi_11 = torch.expm1(r1 * h)
+            phi_1 = torch.expm1(h)
+            a = (torch.exp(ns.log_alpha(s1) - ns.log_alpha(s)), -(ns.sigma(s1) * phi_11))
+            c0, c1 = torch.exp(ns.log_alpha(t) - ns.log_alpha(s)), ns.sigma(t) * phi_1
+            if solver_type == 'dpm_solver':
+                c2 = -((0.5 / r1) * c1)
+            else:
+                c2 = -((1. / r1) * (ns.sigma(t) * ((torch.exp(h) - 1.) / h - 1.)))
+        return s1, a, (c0, -c1, c2, 1.0)
+
+    def _ss3(self, s, t, r1, r2, solver_type):
+        """singlestep_dpm_solver_third_update (:653-753) -> s1, s2, x_s1 [LIN], x_s2 [DIFF], form and coefficients of x_t"""
+        if solver_type not in ['dpm_solver', 'taylor']:
+            raise ValueError("'solver_type' must be either 'dpm_solver' or 'taylor', got {}".format(solver_type))
+        if r1 is None:
+            r1 = 1. / 3.
+        if r2 is None:
+            r2 = 2. / 3.
+        ns = self.ns
+        lambda_s, lambda_t = ns.lam(s), ns.lam(t)
+        h = lambda_t - lambda_s
+        s1 = ns.inverse_lambda(lambda_s + r1 * h)
+        s2 = ns.inverse_lambda(lambda_s + r2 * h)
+        if self.predict_x0:
+            phi_11 = torch.expm1(-r1 * h)
+            phi_12 = torch.expm1(-r2 * h)
+            phi_1 = torch.expm1(-h)
+            phi_22 = torch.expm1(-r2 * h) / (r2 * h) + 1.
+            phi_2 = phi_1 / h + 1.
+            phi_3 = phi_2 / h - 0.5
+            a = (ns.sigma(s1) / ns.sigma(s), -(ns.alpha(s1) * phi_11))
+            b = (ns.sigma(s2) / ns.sigma(s), -(ns.alpha(s2) * phi_12), r2 / r1 * (ns.alpha(s2) * phi_22), 1.0)
+            c0, c1 = ns.sigma(t) / ns.sigma(s), ns.alpha(t) * phi_1
+            if solver_type == 'dpm_solver':
+                return s1, s2, a, b, _DIFF, (c0, -c1, (1. / r2) * (ns.alpha(t) * phi_2), 1.0)
+            return s1, s2, a, b, _SS3T, (c0, -c1, ns.alpha(t) * phi_2, -(ns.alpha(t) * phi_3), 1. / r1, 1. / r2, r2, r1, r2 - r1)
+        phi_11 = torch.expm1(r1 * h)
+        phi_12 = torch.expm1(r2 * h)
+        phi_1 = torch.expm1(h)
+        phi_22 = torch.expm1(r2 * h) / (r2 * h) - 1.
+        phi_2 = phi_1 / h - 1.
+        phi_3 = phi_2 / h - 0.5
+        a = (torch.exp(ns.log_alpha(s1) - ns.log_alpha(s)), -(ns.sigma(s1) * phi_11))
+        b = (torch.exp(ns.log_alpha(s2) - ns.log_alpha(s)), -(ns.sigma(s2) * phi_12), -(r2 / r1 * (ns.sigma(s2) * phi_22)), 1.0)
+        c0, c1 = torch.exp(ns.log_alpha(t) - ns.log_alpha(s)), ns.sigma(t) * phi_1
+        if solver_type == 'dpm_solver':
+            return s1, s2, a, b, _DIFF, (c0, -c1, -((1. / r2) * (ns.sigma(t) * phi_2)), 1.0)
+        return s1, s2, a, b, _SS3T, (c0, -c1, -(ns.sigma(t) * phi_2), -(ns.sigma(t) * phi_3), 1. / r1, 1. / r2, r2, r1, r2 - r1)
+
+    def _ms2(self, t_prev_1, t_prev_0, t, solver_type):
+        """multistep_dpm_solver_second_update (:769-810) -> (c0, c1, c2, 1 / r0) of form DIFF"""
+        if solver_type not in ['dpm_solver', 'taylor']:
+            raise ValueError("'solver_type' must be either 'dpm_solver' or 'taylor', got {}".format(solver_type))
+        ns = self.ns
+        lambda_prev_1, lambda_prev_0, lambda_t = ns.lam(t_prev_1), ns.lam(t_prev_0), ns.lam(t)
+        h_0 = lambda_prev_0 - lambda_prev_1
+        h = lambda_t - lambda_prev_0
+        r0 = h_0 / h
+        if self.predict_x0:
+            c0, c1 = ns.sigma(t) / ns.sigma(t_prev_0), ns.alpha(t) * (torch.exp(-h) - 1.)
+            c2 = -(0.5 * c1) if solver_type == 'dpm_solver' else ns.alpha(t) * ((torch.exp(-h) - 1.) / h + 1.)
+        else:
+            c0, c1 = torch.exp(ns.log_alpha(t) - ns.log_alpha(t_prev_0)), ns.sigma(t) * (torch.exp(h) - 1.)
+            c2 = -(0.5 * c1) if solver_type == 'dpm_solver' else -(ns.sigma(t) * ((torch.exp(h) - 1.) / h - 1.))
+        return (c0, -c1, c2, 1. / r0)
+
+    def _ms3(self, t_prev_2, t_prev_1, t_prev_0, t):
+        """multistep_dpm_solver_third_update (:826-857) -> c0..c7 of form MS3"""
+        ns = self.ns
+        lambda_prev_2, lambda_prev_1, lambda_prev_0, lambda_t = ns.lam(t_prev_2), ns.lam(t_prev_1), ns.lam(t_prev_0), ns.lam(t)
+        h_1 = lambda_prev_1 - lambda_prev_2
+        h_0 = lambda_prev_0 - lambda_prev_1
+        h = lambda_t - lambda_prev_0
+        r0, r1 = h_0 / h, h_1 / h
+        tail = (1. / r0, 1. / r1, r0 / (r0 + r1), 1. / (r0 + r1))
+        if self.predict_x0:
+            alpha_t = ns.alpha(t)
+            return (ns.sigma(t) / ns.sigma(t_prev_0), -(alpha_t * (torch.exp(-h) - 1.)), alpha_t * ((torch.exp(-h) - 1.) / h + 1.),
+                    -(alpha_t * ((torch.exp(-h) - 1. + h) / h ** 2 - 0.5))) + tail
+        sigma_t = ns.sigma(t)
+        return (torch.exp(ns.log_alpha(t) - ns.log_alpha(t_prev_0)), -(sigma_t * (torch.exp(h) - 1.)),
+                -(sigma_t * ((torch.exp(h) - 1.) / h - 1.)), -(sigma_t * ((torch.exp(h) - 1. - h) / h ** 2 - 0.5))) + tail
+
+    # ---- the plan of a non-adaptive run (:1077-1123) --------------------------------------------------------------------------------
+    def _singlestep(self, pb, x, s, t, order, solver_type, r1, r2):
+        """singlestep_dpm_solver_update (:876-883) as plan ops -> the slot of x_t"""
+        m = pb.eval(x, s)
+        if order == 1:
+            return pb.update(_LIN, x, (m,), self._first(s, t))
+        if order == 2:
+            s1, a, c = self._ss2(s, t, r1, solver_type)
+            m1 = pb.eval(pb.update(_LIN, x, (m,), a), s1)
+            return pb.update(_DIFF, x, (m, m1, m), c)
+        if order == 3:
+            s1, s2, a, b, form, c = self._ss3(s, t, r1, r2, solver_type)
+            m1 = pb.eval(pb.update(_LIN, x, (m,), a), s1)
+            m2 = pb.eval(pb.update(_DIFF, x, (m, m1, m), b), s2)
+            return pb.update(form, x, (m, m2, m) if form == _DIFF else (m, m1, m2), c)
+        raise ValueError("Solver order must be 1 or 2 or 3, got {}".format(order))
+
+    def _multistep(self, pb, x, model_prev_list, t_prev_list, t, order, solver_type):
+        """multistep_dpm_solver_update (:900-907) as a plan op"""
+        if order == 1:
+            return pb.update(_LIN, x, (model_prev_list[-1],), self._first(t_prev_list[-1], t))
+        if order == 2:
+            model_prev_1, model_prev_0 = model_prev_list
+            t_prev_1, t_prev_0 = t_prev_list
+            return pb.update(_DIFF, x, (model_prev_0, model_prev_0, model_prev_1), self._ms2(t_prev_1, t_prev_0, t, solver_type))
+        if order == 3:
+            model_prev_2, model_prev_1, model_prev_0 = model_prev_list
+            return pb.update(_MS3, x, (model_prev_0, model_prev_1, model_prev_2), self._ms3(*t_prev_list, t))
+        raise ValueError("Solver order must be 1 or 2 or 3, got {}".format(order))
+
+    def plan(self, steps=20, t_start=None, t_end=None, order=3, skip_type='time_uniform', method='singlestep', lower_order_final=True,
+             denoise_to_zero=False, solver_type='dpm_solver'):
+        ns = self.ns
+        t_0 = 1. / ns.N if t_end is None else t_end
+        t_T = 1. if t_start is None else t_start
+        pb, x, orders = _PlanBuilder(ns), 0, []
+        if method == 'multistep':
+            assert steps >= order
+            if order == 3 and lower_order_final and 4 <= steps < 15:
+                raise ValueError("method='multistep', order=3, lower_order_final=True with 4 <= steps < 15 raises in the reference "
+                                 "(dpm_solver.py:773: the second-order update unpacks the three-entry history into two); "
+                                 "pass lower_order_final=False or steps >= 15")
+            timesteps = self.get_time_steps(skip_type, t_T, t_0, steps)
+            assert timesteps.shape[0] - 1 == steps
+            tt = [timesteps[k:k + 1] for k in range(steps + 1)]
+            model_prev_list, t_prev_list = [pb.eval(x, tt[0])], [tt[0]]
+            for init_order in range(1, order):
+                x = self._multistep(pb, x, model_prev_list, t_prev_list, tt[init_order], init_order, solver_type)
+                orders.append(init_order)
+                model_prev_list.append(pb.eval(x, tt[init_order]))
+                t_prev_list.append(tt[init_order])
+            for step in range(order, steps + 1):
+                step_order = min(order, steps + 1 - step) if lower_order_final and steps < 15 else order
+                x = self._multistep(pb, x, model_prev_list, t_prev_list, tt[step], step_order, solver_type)
+                orders.append(step_order)
+                for i in range(order - 1):
+                    t_prev_list[i] = t_prev_list[i + 1]
+                    model_prev_list[i] = model_prev_list[i + 1]
+                t_prev_list[-1] = tt[step]
+                if step < steps:
+                    model_prev_list[-1] = pb.eval(x, tt[step])
+        elif method in ['singlestep', 'singlestep_fixed']:
+            if method == 'singlestep':
+                timesteps, orders = self.get_orders_and_timesteps_for_singlestep_solver(steps, order, skip_type, t_T, t_0)
+            else:
+                K = steps // order
+                orders = [order, ] * K
+                timesteps = self.get_time_steps(skip_type, t_T, t_0, K)
+            for i, o in enumerate(orders):
+                t_T_inner, t_0_inner = timesteps[i:i + 1], timesteps[i + 1:i + 2]
+                timesteps_inner = self.get_time_steps(skip_type, t_T_inner.item(), t_0_inner.item(), o)
+                lambda_inner = ns.lam(timesteps_inner)
+                h = lambda_inner[-1] - lambda_inner[0]
+                r1 = None if o <= 1 else (lambda_inner[1] - lambda_inner[0]) / h
+                r2 = None if o <= 2 else (lambda_inner[2] - lambda_inner[0]) / h
+                x = self._singlestep(pb, x, t_T_inner, t_0_inner, o, solver_type, r1, r2)
+        else:
+            raise ValueError(f"method {method!r}: 'singlestep', 'multistep', 'singlestep_fixed' or 'adaptive'")
+        if denoise_to_zero:
+            x = pb.eval(x, torch.ones((1,)) * t_0, data_prediction=True)
+        return DPMPlan(pb.ops, pb.coef, timesteps.numpy(), orders, x)
+
+    # ---- the device side ------------------------------------------------------------------------------------------------------------
+    def _model_value(self, x, t_input, alpha_t, sigma_t, data_prediction):
+        """model_fn (:401-408) / data_prediction_fn: one model call, then the model-value launch (twice around the scale with thresholding)"""
+        if not x.is_cuda:
+            raise RuntimeError('the HIP sampler step runs on MI355X device tensors only (no CPU fallback)')
+        lib = _lib.load()
+        eps = self.eps_fn(x, t_input)
+        self.model_times.append(float(t_input))
+        n, B = x.numel(), x.shape[0]
+        assert eps.is_contiguous() and eps.dtype == torch.float32 and eps.numel() == (2 * n if self.cfg else n)
+        out = torch.empty_like(x)
+        value = lambda s: _lib.check(lib.sdmi_dpm_model_value(eps.data_ptr(), int(self.cfg), self.scale, x.data_ptr(), int(data_prediction),
+                                                              alpha_t, sigma_t, _lib.ptr(s), n // B, out.data_ptr(), n, _lib.stream_ptr()))
+        value(None)
+        if data_prediction and self.thresholding:
+            s = torch.empty((B,), device=x.device, dtype=torch.float32)
+            _lib.check(lib.sdmi_dpm_threshold_scale(out.data_ptr(), B, n // B, self.max_val, s.data_ptr(), None, _lib.stream_ptr()))
+            self.last_scale = s
+            value(s)
+        return out
+
+    def _update(self, form, x, ms, coef):
+        lib = _lib.load()
+        out = torch.empty_like(x)
+        ms = list(ms) + [None] * (3 - len(ms))
+        c9 = (_lib.C.c_float * 9)(*([_c(v) for v in coef] + [0.0] * (9 - len(coef))))
+        _lib.check(lib.sdmi_dpm_update(int(form), x.data_ptr(), ms[0].data_ptr(), _lib.ptr(ms[1]), _lib.ptr(ms[2]), c9, out.data_ptr(),
+                                       x.numel(), _lib.stream_ptr()))
+        return out
+
+    def _error(self, x_higher, x_lower, x_prev, atol, rtol):
+        """E of :952-954 -> 0-dim fp32 CPU tensor: two launches, then the loop's one read-back of four bytes"""
+        lib = _lib.load()
+        B, n = x_higher.shape[0], x_higher.numel()
+        if getattr(self, '_err_ws', None) is None or self._err_ws[0].device != x_higher.device:
+            ws_floats = int(lib.sdmi_dpm_adaptive_error_ws_floats(B, n // B))
+            self._err_ws = (torch.empty((ws_floats,), device=x_higher.device, dtype=torch.float32),
+                            torch.empty((1,), device=x_higher.device, dtype=torch.float32))
+        ws, E = self._err_ws
+        _lib.check(lib.sdmi_dpm_adaptive_error(x_higher.data_ptr(), x_lower.data_ptr(), x_prev.data_ptr(), float(atol), float(rtol), B, n // B,
+                                               ws.data_ptr(), ws.numel(), E.data_ptr(), _lib.stream_ptr()))
+        return E.cpu().reshape(())
+
+    def run_plan(self, x, plan, callback=None):
+        """the loop of a DPMPlan on the device: nothing but model calls and launches"""
+        x = x.detach().float().contiguous()
+        self.model_times = []
+        last_use = {}
+        for k, op in enumerate(plan.ops):
+            for slot in op[3:]:
+                last_use[int(slot)] = k
+        last_use[plan.result] = len(plan.ops)
+        buf = {0: x}
+        for k, (op, c) in enumerate(zip(plan.ops, plan.coef)):
+            kind, form, dst, xs = (int(v) for v in op[:4])
+            if kind == _EVAL:
+                buf[dst] = self._model_value(buf[xs], float(c[1]), float(c[2]), float(c[3]), self.predict_x0 or form == 1)
+                if callback: callback(len(self.model_times) - 1)
+            else:
+                buf[dst] = self._update(form, buf[xs], [buf[int(m)] for m in op[4:] if m >= 0], c)
+            for slot in [s for s, last in last_use.items() if last == k and s in buf]:
+                del buf[slot]
+        return buf[plan.result]
+
+    def dpm_solver_adaptive(self, x, order, t_T, t_0, h_init=0.05, atol=0.0078, rtol=0.05, theta=0.9, t_err=1e-5, solver_type='dpm_solver'):
+        """dpm_solver_adaptive (:931-963).  The step size passes through the host (exp / log of the schedule) at run time; per iteration
+        the device hands back the four bytes of E and nothing else."""
+        if order not in (2, 3):
+            raise ValueError("For adaptive step size solver, order must be 2 or 3, got {}".format(order))
+        ns = self.ns
+        x = x.detach().float().contiguous()
+        B = x.shape[0]
+        self.model_times, self.adaptive_log, self._err_ws = [], [], None
+        value = lambda xx, t: self._model_value(xx, _c((t - 1. / ns.N) * 1000.), _c(ns.alpha(t)), _c(ns.sigma(t)), self.predict_x0)
+        s = t_T * torch.ones((1,))
+        lambda_s = ns.lam(s)
+        lambda_0 = ns.lam(t_0 * torch.ones_like(s))
+        h = h_init * torch.ones_like(s)
+        x_prev = x
+        nfe = 0
+        while torch.abs((s - t_0)).repeat(B).mean() > t_err:
+            t = ns.inverse_lambda(lambda_s + h)
+            model_s = value(x, s)
+            if order == 2:
+                r1 = 0.5
+                x_lower = self._update(_LIN, x, (model_s,), self._first(s, t))
+                s1, a, c = self._ss2(s, t, r1, solver_type)
+                model_s1 = value(self._update(_LIN, x, (model_s,), a), s1)
+                x_higher = self._update(_DIFF, x, (model_s, model_s1, model_s), c)
+            else:
+                r1, r2 = 1. / 3., 2. / 3.
+                s1, a, c = self._ss2(s, t, r1, solver_type)
+                model_s1 = value(self._update(_LIN, x, (model_s,), a), s1)
+                x_lower = self._update(_DIFF, x, (model_s, model_s1, model_s), c)
+                _, s2, _, b, form, c = self._ss3(s, t, r1, r2, solver_type)
+                model_s2 = value(self._update(_DIFF, x, (model_s, model_s1, model_s), b), s2)
+                x_higher = self._update(form, x, (model_s, model_s2, model_s) if form == _DIFF else (model_s, model_s1, model_s2), c)
+            E = self._error(x_higher, x_lower, x_prev, atol, rtol)
+            if torch.isnan(E):
+                raise FloatingPointError('the adaptive error estimate is NaN (the reference would reject every step from here on)')
+            accepted = bool(torch.all(E <= 1.))
+            self.adaptive_log.append((float(E), accepted))
+            if accepted:
+                x = x_higher
+                s = t
+                x_prev = x_lower
+                lambda_s = ns.lam(s)
+            h = torch.min(theta * h * torch.float_power(E, -1. / order).float(), lambda_0 - lambda_s)
+            nfe += order
+        print('adaptive solver nfe', nfe)
+        return x
+
+    @torch.no_grad()
+    def sample(self, x, steps=20, t_start=None, t_end=None, order=3, skip_type='time_uniform', method='singlestep', lower_order_final=True,
+               denoise_to_zero=False, solver_type='dpm_solver', atol=0.0078, rtol=0.05, callback=None):
+        """DPM_Solver.sample (:965-1124)"""
+        if method != 'adaptive':
+            return self.run_plan(x, self.plan(steps, t_start, t_end, order, skip_type, method, lower_order_final, denoise_to_zero,
+                                              solver_type), callback)
+        t_0 = 1. / self.ns.N if t_end is None else t_end
+        t_T = 1. if t_start is None else t_start
+        x = self.dpm_solver_adaptive(x, order=order, t_T=t_T, t_0=t_0, atol=atol, rtol=rtol, solver_type=solver_type)
+        if denoise_to_zero:
+            t = torch.ones((1,)) * t_0
+            x = self._model_value(x, _c((t - 1. / self.ns.N) * 1000.), _c(self.ns.alpha(t)), _c(self.ns.sigma(t)), True)
+        return x
+
+
 class DPMSolverSamplerHIP(_SamplerBase):
-    """dpm_solver/sampler.py:9-82: `sample(...)` returns (x, None)."""
+    """dpm_solver/sampler.py:9-82: `sample(...)` returns (x, None).  Without further keywords it runs what the reference's sampler
+    hard-codes -- DPM-Solver++(2M): multistep, order 2, time_uniform, data prediction -- through the fused sdmi_dpm_solver_step;
+    with any keyword of DPM_Solver / DPM_Solver.sample (method, order, skip_type, predict_x0, thresholding, max_val, t_start, t_end,
+    lower_order_final, denoise_to_zero, solver_type, atol, rtol) it runs DPMSolverHIP with these and the reference sampler's values
+    for the rest (steps = S, predict_x0 = True, method 'multistep', order 2, 'time_uniform', lower_order_final = True)."""
 
     def __init__(self, model, **kwargs):
         super().__init__(model, **kwargs)
         self.alphas_cumprod = model.alphas_cumprod.detach().to(torch.float32)
+
+    def plan(self, S):
+        """the scalars of the default run, one row per model evaluation (dpm_plan)"""
+        return dpm_plan(_DiscreteVP(self.alphas_cumprod), S)
 
     @torch.no_grad()
     def sample(self, S, batch_size, shape, conditioning=None, callback=None, normals_sequence=None, img_callback=None,
@@ -605,9 +1065,23 @@ class DPMSolverSamplerHIP(_SamplerBase):
         device, b, img, cfg, c_in, x_in = self._prepare(conditioning, (batch_size, C, H, W), x_T, uc, scale)
         if not img.is_cuda:
             raise RuntimeError('the HIP sampler step runs on MI355X device tensors only (no CPU fallback)')
-        plan = dpm_plan(_DiscreteVP(self.alphas_cumprod), S)
-        lib = _lib.load()
         unet = self._hip_unet()
+        opts = {k: kwargs[k] for k in DPM_KEYWORDS + ('predict_x0', 'thresholding', 'max_val') if k in kwargs}
+        if opts:
+            solver = DPMSolverHIP(lambda x, t_input: self._model_eps(x_in, x, t_input, c_in, cfg, b, t_dtype=torch.float32),
+                                  _DiscreteVP(self.alphas_cumprod), predict_x0=opts.pop('predict_x0', True),
+                                  thresholding=opts.pop('thresholding', False), max_val=opts.pop('max_val', 1.), cfg=cfg, scale=scale)
+            self.solver = solver                # (model_times / adaptive_log of the run)
+            opts = dict(dict(steps=S, order=2, skip_type='time_uniform', method='multistep', lower_order_final=True), **opts)
+            if unet is not None:
+                unet.pin_context(c_in)
+            try:
+                return solver.sample(img, callback=callback, **opts), None
+            finally:
+                if unet is not None:
+                    unet.unpin_context()
+        plan = self.plan(S)
+        lib = _lib.load()
         if unet is not None:
             unet.pin_context(c_in)
         try:
