@@ -293,11 +293,12 @@ int sdmi_vae_encode(sdmi_vae* h, const float* img, float* moments, int B, int H,
 }
 int sdmi_k_pointwise_nchw(const float* x, const float* w, const float* bias, float* out, int B, int Cin, int Cout, int HW,
                           float in_scale, void* stream) {
+  SDMI_CHECK(Cin <= 32, "pointwise conv: 1 <= Cin <= 32");       // (the limit this entry was published with; sdmi_k_pointwise_nchw128 is the wider one)
   return launch_pointwise_nchw(x, w, bias, out, B, Cin, Cout, HW, in_scale, (hipStream_t)stream);
 }
 int sdmi_k_pointwise_nchw128(const float* x, const float* w, const float* bias, float* out, int B, int Cin, int Cout, int HW,
                              float in_scale, void* stream) {
-  return launch_pointwise_nchw128(x, w, bias, out, B, Cin, Cout, HW, in_scale, (hipStream_t)stream);
+  return launch_pointwise_nchw(x, w, bias, out, B, Cin, Cout, HW, in_scale, (hipStream_t)stream);
 }
 int sdmi_k_softmax_rows(const float* S, void* P_f16, int rows, int cols, float scale, void* stream) {
   return launch_softmax_rows(S, (f16*)P_f16, rows, cols, cols, cols, scale, (hipStream_t)stream);
@@ -781,6 +782,7 @@ int sdmi_k_small_linear(const float* in, int ld_in, const float* w, const float*
 }
 int sdmi_k_conv_in(const float* x, const float* w, const float* bias, float* out, int B, int Cin, int H, int W, int Cout,
                    void* stream) {
+  SDMI_CHECK(Cin <= 16, "conv_in: in_channels <= 16");           // (the limit this entry was published with; sdmi_k_conv_in64 is the wider one)
   return launch_conv_in(x, w, bias, out, B, Cin, H, W, Cout, (hipStream_t)stream);
 }
 int sdmi_k_conv_out(const float* h, const float* w, const float* bias, float* out, int B, int H, int W, int Cin, int Cout,
@@ -791,15 +793,16 @@ int sdmi_k_conv_out(const float* h, const float* w, const float* bias, float* ou
 }
 int sdmi_k_conv_out32(const float* h, const float* w, const float* bias, float* out, int B, int H, int W, int Cin, int Cout,
                       void* stream) {
+  SDMI_CHECK(Cout <= 32, "conv_out: out_channels <= 32, Cin % 4 == 0");     // (sdmi_k_conv_out128 takes up to 128)
   return launch_conv_out(h, w, bias, out, B, H, W, Cin, Cout, (hipStream_t)stream);
 }
 int sdmi_k_conv_in64(const float* x, const float* w, const float* bias, float* out, int B, int Cin, int H, int W, int Cout,
                      void* stream) {
-  return launch_conv_in64(x, w, bias, out, B, Cin, H, W, Cout, (hipStream_t)stream);
+  return launch_conv_in(x, w, bias, out, B, Cin, H, W, Cout, (hipStream_t)stream);
 }
 int sdmi_k_conv_out128(const float* h, const float* w, const float* bias, float* out, int B, int H, int W, int Cin, int Cout,
                        void* stream) {
-  return launch_conv_out128(h, w, bias, out, B, H, W, Cin, Cout, (hipStream_t)stream);
+  return launch_conv_out(h, w, bias, out, B, H, W, Cin, Cout, (hipStream_t)stream);
 }
 int sdmi_k_pack_conv_weight(const float* w, void* dst, int O, int I, int KH, int KW, void* stream) {
   return launch_pack_conv_weight(w, (f16*)dst, O, I, KH, KW, (hipStream_t)stream);

@@ -440,21 +440,17 @@ int launch_cast_f16(const float* x, f16* out, f16* out_lo, int64_t n, hipStream_
 int launch_timestep_embedding(const int64_t* t_i64, const float* t_f32, float* out, int B, int dim, hipStream_t s);
 int launch_small_linear(const float* in, int ld_in, const float* w, const float* bias, float* out, int ld_out,
                         int B, int N, int K, int silu_in, hipStream_t s);
-// gn_*: GroupNorm statistics of the output for up to two consuming GroupNorms (accumulator regions, channels per group, channel offset of
-// this tensor inside the GroupNorm's input: IGemmParams::gn_acc / gn_cpg / gn_cbase); needs H * W % 16 == 0
 // one-token context: ao[(b * ntok + tok) * C + c] = vt[(b * C + c) * ld_v] -- the cross-attention output of every query of sample b (small.hip)
 int launch_ctx1_broadcast(const f16* vt, int ld_v, f16* ao, int B, int ntok, int C, hipStream_t s);
+// the fp32 3x3 ends, each over its whole range: Cin <= 64 (above 16: a 36 KB patch, outputs split over blockIdx.y) resp. Cout <= 128 in
+// slices of eight outputs (above 32 outputs: Cin <= 512).  The narrower limits that C entries were published with are checked in api.cpp.
+// gn_*: GroupNorm statistics of the output for up to two consuming GroupNorms (accumulator regions, channels per group, channel offset of
+// this tensor inside the GroupNorm's input: IGemmParams::gn_acc / gn_cpg / gn_cbase); needs Cin <= 16 and H * W % 16 == 0
 int launch_conv_in(const float* x_nchw, const float* w, const float* bias, float* out_nhwc, int B, int Cin, int H,
                    int W, int Cout, hipStream_t s, int gn_n = 0, long long* const* gn_acc = nullptr, const int* gn_cpg = nullptr,
                    const int* gn_cbase = nullptr);
 int launch_conv_out(const float* h_nhwc, const float* w_khwc, const float* bias, float* out_nchw, int B, int H, int W,
                     int Cin, int Cout, hipStream_t s);
-// the wide latent ends of the first stage (KL-f32: 64 latent channels): the launches above up to their limits (16 inputs / 32 outputs), beyond
-// them conv_in64_kernel (Cin <= 64) and the sliced conv_out kernels with up to 16 slices (Cout <= 128, Cin <= 512)
-int launch_conv_in64(const float* x_nchw, const float* w, const float* bias, float* out_nhwc, int B, int Cin, int H, int W, int Cout,
-                     hipStream_t s);
-int launch_conv_out128(const float* h_nhwc, const float* w_khwc, const float* bias, float* out_nchw, int B, int H, int W, int Cin,
-                       int Cout, hipStream_t s);
 
 // DPM-Solver++ multistep step (see sampler.hip)
 struct DpmStepParams {
@@ -523,11 +519,9 @@ int launch_safety_head(const float* image_embeds, const float* concept_embeds, c
                        hipStream_t s);
 
 // first-stage (VAE) helpers
+// 1x1 conv, Cin <= 128 (up to 32: pointwise_nchw_kernel, the inputs in registers; beyond: pointwise_nchw_wide_kernel, Cout <= 1024)
 int launch_pointwise_nchw(const float* x_nchw, const float* w, const float* bias, float* out_nchw, int B, int Cin, int Cout,
                           int HW, float in_scale, hipStream_t s);
-// ... and up to 128 input channels (Cin <= 32: the launch above; beyond: pointwise_nchw_wide_kernel)
-int launch_pointwise_nchw128(const float* x_nchw, const float* w, const float* bias, float* out_nchw, int B, int Cin, int Cout,
-                             int HW, float in_scale, hipStream_t s);
 int launch_softmax_rows(const float* S, f16* P, int rows, int cols, int lds, int ldp, float scale, hipStream_t s);
 
 // latent-inpainting model (inpaint.hip)
@@ -561,7 +555,9 @@ int launch_ln_fold_prep(const f16* w, int N, int K, int ldw, const float* gamma,
 // split-fp16 weights for the 3-pass 1x1 convs: dst [N][3K] = [hi | hi | lo], lo = fp16(w - float(hi))
 int launch_pack_split3(const float* w, f16* dst, int N, int K, hipStream_t s);
 // ... for A sources that are multiples of 32 channels: K chunk-major PER SOURCE (c0 + c1 + c2 == I), the last chunk of a source of
-// 32 (mod 64) channels 32 wide.  The same bytes as launch_pack_conv_weight when every source is a multiple of 64.
+// 32 (mod 64) channels 32 wide.  One kernel serves the three conv packers: launch_pack_conv_weight is the one-source case (c0 = I), and
+// with every source a multiple of 64 the split does not change the bytes.  launch_pack_conv_split3: three sources of the same I channels,
+// [hi | hi | lo].
 int launch_pack_conv_weight_src(const float* w_oihw, f16* dst, int O, int I, int KH, int KW, int c0, int c1, int c2, hipStream_t s);
 int launch_pack_conv_split3(const float* w, f16* dst, int O, int I, int KH, int KW, hipStream_t s);
 // packed 3x3 weights [N][9 Cin] -> the weights [4][N][4 Cin] of the four 2x2 phase convs of conv3x3(nearest x2 (x)) (small.hip; Cin % 64 == 0)

@@ -10,7 +10,7 @@
 // 160 weight rows x 64 k (20 KB), loader waves that issue nothing else, five compute waves x 64 output columns (two 32 x 32 MFMA tiles),
 // one raw s_barrier per unit.
 //
-// k order = the packed conv weights' (pack_conv_kernel: 64-channel chunk major, the nine taps of a chunk adjacent): per chunk c the taps
+// k order = the packed conv weights' (pack_conv_src_kernel: 64-channel chunk major, the nine taps of a chunk adjacent): per chunk c the taps
 // 0 .. 8, per tap the four k-steps -- conv3halo_kernel's order, so the accumulators (and the outputs) are the bits of GroupNorm-apply +
 // conv3halo / igemm launches with splitk = 1.  Only ONE chunk of the halo is resident (104 pixel rows x 128 B, double buffered): chunk
 // c + 1 is loaded (fp32, registers) at tap 0 of chunk c and normalised into the other buffer at taps 3 / 5 / 7, under the weight stream

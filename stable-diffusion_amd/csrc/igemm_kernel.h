@@ -143,7 +143,7 @@ __global__ void __launch_bounds__(WARPS_M* WARPS_N * 64) igemm_kernel(const IGem
   // load cursor (wave-uniform): next k-tile to issue, its tap and first channel.  It stops on the last k-tile of this
   // split: the NS - 1 surplus issues at the end of the pipeline reload that tile (in bounds, never consumed).
   int ld_kt = kt_begin;
-  // K order is chunk-major: k-tile kt = (chunk, tap), tap fastest (see pack_conv_kernel); the chunks are numbered per source, 64 channels
+  // K order is chunk-major: k-tile kt = (chunk, tap), tap fastest (see pack_conv_src_kernel); the chunks are numbered per source, 64 channels
   // each but for the last one of a source of 32 (mod 64) channels.  ld_cin0 walks PADDED channel coordinates (64 per chunk, pp0 / pp01 =
   // where the second / third source begins in them), ld_boff the dense weight columns (bytes): b_soff accumulates the real widths.
   int ld_tap = K3 ? kt_begin % ntap : 0;

@@ -121,7 +121,16 @@ __global__ void __launch_bounds__(512) small_linear_lds_kernel(const float* in, 
 
 constexpr int CI_PIX = 16;
 constexpr int CI_MAXK = 9 * 16;   // Cin <= 16
-// x NCHW fp32 -> out NHWC fp32, 3x3 pad 1
+constexpr int CI64_MAXK = 9 * 64; // Cin <= 64: a 36 KB patch
+// x NCHW fp32 -> out NHWC fp32, 3x3 pad 1: a block gathers the 3x3 patches of 16 pixels into LDS (MAXK >= 9 * Cin floats per pixel), then a
+// thread owns one output channel of the 16 pixels -- per output the bias, then k = ci*9 + ky*3 + kx ascending over K = 9 * Cin, an order
+// that depends on Cin alone.  Two instantiations:
+//   <CI_MAXK, false>    up to 16 input channels (the UNet's conv_in, encoder.conv_in, decoder.conv_in of the narrow latents): one column of
+//                       blocks, a thread loops over the outputs tid, tid + 256, ...; with the GroupNorm statistics below.
+//   <CI64_MAXK, true>   17 .. 64 input channels (decoder.conv_in of the first stages with 32 / 64 latent channels: KL-f32 is 64 -> 512):
+//                       blockIdx.y picks 256 outputs (the patch is built once per block of outputs: a latent has few pixels, and 512 outputs
+//                       in one block would be two serial passes of 576 steps on 32 of the 256 CUs).  No statistics (the UNet's conv_in,
+//                       which feeds them, has at most 16 input channels) and none of their LDS: at 36 KB four workgroups share a CU.
 // Round 6: the GroupNorm statistics of the output for up to two consuming GroupNorms (ConvInStats; the same fixed-point accumulators the igemm
 // epilogues feed: per thread the {sum, sum of squares} of its channel over the block's 16 pixels, combined per group in LDS as integers, one
 // atomic set per (group, word) and block) -- the two GroupNorms that read conv_in's output (input_blocks.1.0, and output_blocks.<last>.0 through the
@@ -131,12 +140,15 @@ struct ConvInStats {
   long long* acc[2] = {nullptr, nullptr};
   int cpg[2] = {1, 1}, cbase[2] = {0, 0};
 };
+template <int MAXK, bool WIDE>
 __global__ void __launch_bounds__(256) conv_in_kernel(const float* x, const float* w, const float* bias, float* out, int B,
                                                       int Cin, int H, int W, int Cout, const ConvInStats st) {
-  __shared__ float patch[CI_PIX][CI_MAXK];
-  __shared__ unsigned long long s_gn[2][32][GN_WORDS];
-  if (st.n > 0) {
-    for (int i = threadIdx.x; i < 2 * 32 * GN_WORDS; i += 256) (&s_gn[0][0][0])[i] = 0ull;
+  __shared__ float patch[CI_PIX][MAXK];
+  __shared__ unsigned long long s_gn[2][32][GN_WORDS];     // (named under `if constexpr (!WIDE)` only: the wide instantiation has no such LDS)
+  if constexpr (!WIDE) {
+    if (st.n > 0) {
+      for (int i = threadIdx.x; i < 2 * 32 * GN_WORDS; i += 256) (&s_gn[0][0][0])[i] = 0ull;
+    }
   }
   const int tid = threadIdx.x;
   const int K = Cin * 9;
@@ -155,7 +167,9 @@ __global__ void __launch_bounds__(256) conv_in_kernel(const float* x, const floa
     patch[pi][k] = v;
   }
   __syncthreads();
-  for (int co = tid; co < Cout; co += 256) {
+  // (WIDE: one pass, gridDim.y = ceil(Cout / 256).  The step is added in each form's own type, unsigned resp. int: the compiler's address
+  // arithmetic, and with it the register count, follows the type)
+  for (int co = WIDE ? (int)(blockIdx.y * 256 + tid) : tid; co < Cout; co = WIDE ? (int)(co + 256 * gridDim.y) : co + 256) {
     float acc[CI_PIX];
     const float bv = bias ? bias[co] : 0.f;
 #pragma unroll
@@ -169,78 +183,43 @@ __global__ void __launch_bounds__(256) conv_in_kernel(const float* x, const floa
 #pragma unroll
     for (int pi = 0; pi < CI_PIX; ++pi)
       if (m0 + pi < M) out[(size_t)(m0 + pi) * Cout + co] = acc[pi];
-    if (st.n > 0) {
-      float s1 = 0.f, s2 = 0.f;
+    if constexpr (!WIDE) {
+      if (st.n > 0) {
+        float s1 = 0.f, s2 = 0.f;
 #pragma unroll
-      for (int pi = 0; pi < CI_PIX; ++pi)
-        if (m0 + pi < M) { s1 += acc[pi]; s2 += acc[pi] * acc[pi]; }
-      for (int tg = 0; tg < st.n; ++tg) {
-        const int g = (st.cbase[tg] + co) / st.cpg[tg];
-        gn_acc_add(&s_gn[tg][g][0], s1);
-        gn_acc_add(&s_gn[tg][g][2], s2);
+        for (int pi = 0; pi < CI_PIX; ++pi)
+          if (m0 + pi < M) { s1 += acc[pi]; s2 += acc[pi] * acc[pi]; }
+        for (int tg = 0; tg < st.n; ++tg) {
+          const int g = (st.cbase[tg] + co) / st.cpg[tg];
+          gn_acc_add(&s_gn[tg][g][0], s1);
+          gn_acc_add(&s_gn[tg][g][2], s2);
+        }
       }
     }
   }
-  if (st.n > 0) {
-    __syncthreads();
-    const int b = m0 / (H * W), slot = blockIdx.x & (GN_SLOTS - 1);
-    for (int e = tid; e < st.n * 32 * GN_WORDS; e += 256) {
-      const unsigned long long wv = (&s_gn[0][0][0])[e];
-      if (wv == 0ull) continue;
-      const int word = e % GN_WORDS, g = (e / GN_WORDS) % 32, tg = e / (GN_WORDS * 32);
-      atomicAdd((unsigned long long*)st.acc[tg] + ((size_t)(b * 32 + g) * GN_SLOTS + slot) * GN_STRIDE + word, wv);
+  if constexpr (!WIDE) {
+    if (st.n > 0) {
+      __syncthreads();
+      const int b = m0 / (H * W), slot = blockIdx.x & (GN_SLOTS - 1);
+      for (int e = tid; e < st.n * 32 * GN_WORDS; e += 256) {
+        const unsigned long long wv = (&s_gn[0][0][0])[e];
+        if (wv == 0ull) continue;
+        const int word = e % GN_WORDS, g = (e / GN_WORDS) % 32, tg = e / (GN_WORDS * 32);
+        atomicAdd((unsigned long long*)st.acc[tg] + ((size_t)(b * 32 + g) * GN_SLOTS + slot) * GN_STRIDE + word, wv);
+      }
     }
-  }
-}
-
-// The same convolution for 17 .. 64 input channels (decoder.conv_in of the first stages with 32 / 64 latent channels: KL-f32 is 64 -> 512):
-// conv_in_kernel's loop over a 36 KB patch -- per output the bias, then k = ci*9 + ky*3 + kx ascending over K = 9 * Cin <= 576, an order
-// that depends on Cin alone.  blockIdx.y picks 256 outputs (the patch is built once per block of outputs: a latent has few pixels, and 512
-// outputs in one block would be two serial passes of 576 steps on 32 of the 256 CUs).  No GroupNorm statistics (the UNet's conv_in, which feeds them, has at most 16 input channels).
-constexpr int CI64_MAXK = 9 * 64;
-__global__ void __launch_bounds__(256) conv_in64_kernel(const float* x, const float* w, const float* bias, float* out, int B,
-                                                        int Cin, int H, int W, int Cout) {
-  __shared__ float patch[CI_PIX][CI64_MAXK];
-  const int tid = threadIdx.x;
-  const int K = Cin * 9;
-  const int M = B * H * W;
-  const int m0 = blockIdx.x * CI_PIX;
-  for (int idx = tid; idx < CI_PIX * K; idx += 256) {
-    const int pi = idx / K, k = idx - pi * K;
-    const int m = m0 + pi;
-    float v = 0.f;
-    if (m < M) {
-      const int b = m / (H * W), rem = m - b * H * W, y = rem / W, xx = rem - y * W;
-      const int ci = k / 9, t = k - ci * 9, ky = t / 3, kx = t - ky * 3;
-      const int iy = y + ky - 1, ix = xx + kx - 1;
-      if (iy >= 0 && iy < H && ix >= 0 && ix < W) v = x[(((size_t)b * Cin + ci) * H + iy) * W + ix];
-    }
-    patch[pi][k] = v;
-  }
-  __syncthreads();
-  for (int co = blockIdx.y * 256 + tid; co < Cout; co += 256 * gridDim.y) {   // (one pass: gridDim.y = ceil(Cout / 256))
-    float acc[CI_PIX];
-    const float bv = bias ? bias[co] : 0.f;
-#pragma unroll
-    for (int pi = 0; pi < CI_PIX; ++pi) acc[pi] = bv;
-    const float* wr = w + (size_t)co * K;
-    for (int k = 0; k < K; ++k) {
-      const float wv = wr[k];
-#pragma unroll
-      for (int pi = 0; pi < CI_PIX; ++pi) acc[pi] += wv * patch[pi][k];
-    }
-#pragma unroll
-    for (int pi = 0; pi < CI_PIX; ++pi)
-      if (m0 + pi < M) out[(size_t)(m0 + pi) * Cout + co] = acc[pi];
   }
 }
 
 constexpr int CO_MAXN = 8;
-// h NHWC fp32 (already GroupNorm+SiLU'd), w [Cout][3][3][Cin] fp32 -> out NCHW fp32; one wave per output pixel
+// h NHWC fp32 (already GroupNorm+SiLU'd), w [Cout][3][3][Cin] fp32 -> out NCHW fp32; one wave per output pixel and slice of eight outputs
+// n0 = 8 * blockIdx.y (any W, any Cin % 4 == 0; Cout <= 8 * gridDim.y).  Per output: taps ascending, channel quads ascending inside a
+// tap, out-of-image taps skipped.
 __global__ void __launch_bounds__(256) conv_out_kernel(const float* h, const float* w, const float* bias, float* out, int B,
                                                        int H, int W, int Cin, int Cout) {
   const int lane = threadIdx.x & 63;
   const int m = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int n0 = blockIdx.y * CO_MAXN;                     // first output channel of this slice
   const int M = B * H * W;
   if (m >= M) return;
   const int b = m / (H * W), rem = m - b * H * W, y = rem / W, x = rem - y * W;
@@ -257,8 +236,8 @@ __global__ void __launch_bounds__(256) conv_out_kernel(const float* h, const flo
       const f32x4 xv = *(const f32x4*)(src + c);
 #pragma unroll
       for (int n = 0; n < CO_MAXN; ++n) {
-        if (n < Cout) {
-          const f32x4 wv = *(const f32x4*)(w + (size_t)n * K + tap * Cin + c);
+        if (n0 + n < Cout) {
+          const f32x4 wv = *(const f32x4*)(w + (size_t)(n0 + n) * K + tap * Cin + c);
           acc[n] += wv[0] * xv[0] + wv[1] * xv[1] + wv[2] * xv[2] + wv[3] * xv[3];
         }
       }
@@ -266,11 +245,11 @@ __global__ void __launch_bounds__(256) conv_out_kernel(const float* h, const flo
   }
 #pragma unroll
   for (int n = 0; n < CO_MAXN; ++n) {
-    if (n < Cout) {
+    if (n0 + n < Cout) {
       float v = acc[n];
 #pragma unroll
       for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-      if (lane == 0) out[(((size_t)b * Cout + n) * H + y) * W + x] = v + (bias ? bias[n] : 0.f);
+      if (lane == 0) out[(((size_t)b * Cout + n0 + n) * H + y) * W + x] = v + (bias ? bias[n0 + n] : 0.f);
     }
   }
 }
@@ -282,94 +261,22 @@ __global__ void __launch_bounds__(256) conv_out_kernel(const float* h, const flo
 // ascending, channel quads ascending inside a tap, out-of-image taps skipped; the compiler contracts the FMAs differently,
 // so the two kernels agree to a few fp32 ulp, not bit for bit (this is the last operation of the UNet / first stage:
 // nothing downstream rounds the difference up).  UNet `out` head: 41.8 -> 22.9 us (profiles/small_kernels_r02.txt).
-// NOUT = 4 or 8 (>= Cout), Cin <= 512 (two channel passes of 64 lanes x 4), W % COP == 0.
+// Heads of more than 8 outputs (the retrieval-augmented UNet writes 16 latent channels; the encoder.conv_out of KL-f16 / KL-f32 writes the
+// 32 / 128 moment channels of a 16- / 64-channel latent): sixteen outputs in one wave would be 64 accumulators and 32 live weight quads per
+// lane; instead blockIdx.y picks one slice of NOUT = 8 outputs, n0 = 8 * blockIdx.y, up to sixteen slices -- the same register budget (no
+// scratch: profiles/kernel_resources_fp32_ends.txt), every weight quad still loaded once per wave and tap; the input rows are read by every
+// slice (the later reads hit L2).  A slice never looks at another slice's outputs, so nothing in the kernel changes with their count.
+// SLICED = false is the head of up to NOUT outputs, gridDim.y == 1, with n0 = 0 at compile time: always reading blockIdx.y measured
+// +0.6 % / +0.4 % on the UNet `out` head and KL-f8's decoder.conv_out against a spread of 0.07 % (profiles/fp32_ends_refactor_ab.txt (0)).
+// NOUT = 4 or 8, Cout <= NOUT * gridDim.y, Cin <= 512 (two channel passes of 64 lanes x 4), W % COP == 0; outputs n >= Cout of the last
+// slice read weight row 0 and are not stored.
 constexpr int COP = 4;
-template <int NOUT>
+template <int NOUT, bool SLICED>
 __global__ void __launch_bounds__(256) conv_out4_kernel(const float* h, const float* w, const float* bias, float* out, int B,
                                                         int H, int W, int Cin, int Cout) {
   const int lane = threadIdx.x & 63;
   const int g = blockIdx.x * 4 + (threadIdx.x >> 6);       // pixel group
-  const int wq = W / COP;
-  if (g >= B * H * wq) return;
-  const int b = g / (H * wq), rem = g - b * H * wq, y = rem / wq, x0 = (rem - y * wq) * COP;
-  const int K = 9 * Cin;
-  const int c0 = lane * 4, c1 = lane * 4 + 256;
-  const bool v0 = c0 < Cin, v1 = c1 < Cin;
-  float acc[COP][NOUT];
-#pragma unroll
-  for (int p = 0; p < COP; ++p)
-#pragma unroll
-    for (int n = 0; n < NOUT; ++n) acc[p][n] = 0.f;
-  const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int ky = 0; ky < 3; ++ky) {
-    const int iy = y + ky - 1;
-    if (iy < 0 || iy >= H) continue;                       // (wave-uniform)
-    f32x4 xa[COP + 2], xb[COP + 2];                        // input columns x0 - 1 .. x0 + COP of this row, both channel passes
-#pragma unroll
-    for (int j = 0; j < COP + 2; ++j) {
-      const int ix = x0 - 1 + j;
-      const bool in = ix >= 0 && ix < W;
-      const float* src = h + ((size_t)(b * H + iy) * W + (in ? ix : 0)) * Cin;
-      xa[j] = (in && v0) ? *(const f32x4*)(src + c0) : zero;
-      xb[j] = (in && v1) ? *(const f32x4*)(src + c1) : zero;
-    }
-#pragma unroll
-    for (int kx = 0; kx < 3; ++kx) {
-      const int tap = ky * 3 + kx;
-      f32x4 wa[NOUT], wb[NOUT];
-#pragma unroll
-      for (int n = 0; n < NOUT; ++n) {
-        const float* wp = w + (size_t)(n < Cout ? n : 0) * K + tap * Cin;
-        wa[n] = v0 ? *(const f32x4*)(wp + c0) : zero;
-        wb[n] = v1 ? *(const f32x4*)(wp + c1) : zero;
-      }
-#pragma unroll
-      for (int p = 0; p < COP; ++p) {
-        const int ix = x0 + p + kx - 1;
-        if (ix < 0 || ix >= W) continue;                   // (wave-uniform) out-of-image tap: skipped, as in conv_out_kernel
-        const f32x4 xv = xa[p + kx], xw = xb[p + kx];
-        if (v0) {
-#pragma unroll
-          for (int n = 0; n < NOUT; ++n) acc[p][n] += wa[n][0] * xv[0] + wa[n][1] * xv[1] + wa[n][2] * xv[2] + wa[n][3] * xv[3];
-        }
-        if (v1) {
-#pragma unroll
-          for (int n = 0; n < NOUT; ++n) acc[p][n] += wb[n][0] * xw[0] + wb[n][1] * xw[1] + wb[n][2] * xw[2] + wb[n][3] * xw[3];
-        }
-      }
-    }
-  }
-#pragma unroll
-  for (int n = 0; n < NOUT; ++n) {
-    f32x4 r;
-#pragma unroll
-    for (int p = 0; p < COP; ++p) {
-      float v = acc[p][n];
-#pragma unroll
-      for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-      r[p] = v + ((bias && n < Cout) ? bias[n] : 0.f);
-    }
-    if (lane == 0 && n < Cout) *(f32x4*)(out + (((size_t)b * Cout + n) * H + y) * W + x0) = r;
-  }
-}
-
-// Output heads of 9 .. 32 channels (the retrieval-augmented UNet writes 16 latent channels; the KL-f16 encoder's conv_out writes the 32
-// moment channels of a 16-channel latent).  Sixteen outputs on the 4-pixel form would be 64 accumulators and 32 live weight quads per
-// lane; instead blockIdx.y picks one slice of eight outputs -- n0 = 0, 8, 16 or 24; two slices ("halves") up to 16 outputs, up to four
-// above -- and a wave runs conv_out4_kernel<8>'s loop for that slice: the same register budget (no scratch:
-// profiles/kernel_resources_conv_out16.txt, kernel_resources_conv_out32.txt), every weight quad still loaded once per wave and tap; the
-// input rows are read by every slice (the later reads hit L2).  An accumulator sees exactly the terms conv_out_kernel gives it, in its
-// order: taps ascending, channel quads ascending inside a tap, out-of-image taps skipped.
-// Cin <= 512, W % COP == 0, Cout <= 8 * gridDim.y; outputs n >= Cout of the last slice read weight row 0 and are not stored.
-// launch_conv_out stops at four slices (32 outputs); launch_conv_out128 runs the same two kernels with up to sixteen (the 128 moment
-// channels of KL-f32's encoder.conv_out): a slice never looks at another slice's outputs, so nothing in the kernels changes with their count.
-__global__ void __launch_bounds__(256) conv_out4_halves_kernel(const float* h, const float* w, const float* bias, float* out, int B,
-                                                               int H, int W, int Cin, int Cout) {
-  constexpr int NOUT = CO_MAXN;
-  const int lane = threadIdx.x & 63;
-  const int g = blockIdx.x * 4 + (threadIdx.x >> 6);       // pixel group
-  const int n0 = blockIdx.y * NOUT;                        // first output channel of this slice
+  const int n0 = SLICED ? blockIdx.y * NOUT : 0;           // first output channel of this slice
   const int wq = W / COP;
   if (g >= B * H * wq) return;
   const int b = g / (H * wq), rem = g - b * H * wq, y = rem / wq, x0 = (rem - y * wq) * COP;
@@ -436,89 +343,15 @@ __global__ void __launch_bounds__(256) conv_out4_halves_kernel(const float* h, c
   }
 }
 
-// ... and the fallback (any W, any Cin % 4 == 0): conv_out_kernel's loop, one wave per output pixel and slice of eight outputs
-__global__ void __launch_bounds__(256) conv_out_halves_kernel(const float* h, const float* w, const float* bias, float* out, int B,
-                                                              int H, int W, int Cin, int Cout) {
-  const int lane = threadIdx.x & 63;
-  const int m = blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int n0 = blockIdx.y * CO_MAXN;
-  const int M = B * H * W;
-  if (m >= M) return;
-  const int b = m / (H * W), rem = m - b * H * W, y = rem / W, x = rem - y * W;
-  float acc[CO_MAXN];
-#pragma unroll
-  for (int n = 0; n < CO_MAXN; ++n) acc[n] = 0.f;
-  const int K = 9 * Cin;
-  for (int tap = 0; tap < 9; ++tap) {
-    const int ky = tap / 3, kx = tap - ky * 3;
-    const int iy = y + ky - 1, ix = x + kx - 1;
-    if (iy < 0 || iy >= H || ix < 0 || ix >= W) continue;
-    const float* src = h + ((size_t)(b * H + iy) * W + ix) * Cin;
-    for (int c = lane * 4; c < Cin; c += 256) {
-      const f32x4 xv = *(const f32x4*)(src + c);
-#pragma unroll
-      for (int n = 0; n < CO_MAXN; ++n) {
-        if (n0 + n < Cout) {
-          const f32x4 wv = *(const f32x4*)(w + (size_t)(n0 + n) * K + tap * Cin + c);
-          acc[n] += wv[0] * xv[0] + wv[1] * xv[1] + wv[2] * xv[2] + wv[3] * xv[3];
-        }
-      }
-    }
-  }
-#pragma unroll
-  for (int n = 0; n < CO_MAXN; ++n) {
-    if (n0 + n < Cout) {
-      float v = acc[n];
-#pragma unroll
-      for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-      if (lane == 0) out[(((size_t)b * Cout + n0 + n) * H + y) * W + x] = v + (bias ? bias[n0 + n] : 0.f);
-    }
-  }
-}
-
 // ---- packing -------------------------------------------------------------------------------------------
-__global__ void pack_conv_kernel(const float* w, f16* dst, int O, int I, int KH, int KW) {
-  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int64_t total = (int64_t)O * I * KH * KW;
-  if (idx >= total) return;
-  // K order (chunk-major): k = ((i / 64) * KH*KW + ky*KW + kx) * 64 + i % 64 -- all 9 taps of a 64-channel chunk are
-  // adjacent, so a kernel that stages one input-channel chunk (with its halo) consumes 9 consecutive k-tiles.
-  // For 1x1 convs this is the identity order.  3x3 convs need I % 64 == 0 (checked by the GEMM launcher).
-  const int64_t K = (int64_t)I * KH * KW;
-  const int o = (int)(idx / K);
-  const int64_t k = idx - (int64_t)o * K;
-  int i, ky, kx;
-  if (KH * KW == 1) { i = (int)k; ky = kx = 0; }
-  else {
-    const int chunk = (int)(k / (64 * KH * KW));
-    const int rem = (int)(k - (int64_t)chunk * 64 * KH * KW);
-    const int tap = rem / 64;
-    i = chunk * 64 + rem % 64; ky = tap / KW; kx = tap % KW;
-  }
-  dst[idx] = (f16)w[(((int64_t)o * I + i) * KH + ky) * KW + kx];
-}
-// 3x3 conv weights of a 3-pass split-fp16 convolution (UNet: the last ResBlock, round 6): the K-concatenated operand A' = [a_hi | a_lo | a_hi]
-// (three channel blocks of I) meets W' = [w_hi | w_hi | w_lo] -- a virtual [O][3 I][KH][KW] tensor in pack_conv_kernel's chunk-major K order
-__global__ void pack_conv_split3_kernel(const float* w, f16* dst, int O, int I, int KH, int KW) {
-  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int I3 = 3 * I;
-  const int64_t K = (int64_t)I3 * KH * KW;
-  if (idx >= (int64_t)O * K) return;
-  const int o = (int)(idx / K);
-  const int64_t k = idx - (int64_t)o * K;
-  const int chunk = (int)(k / (64 * KH * KW));
-  const int rem = (int)(k - (int64_t)chunk * 64 * KH * KW);
-  const int tap = rem / 64;
-  const int i3 = chunk * 64 + rem % 64, ky = tap / KW, kx = tap % KW;
-  const int part = i3 / I, i = i3 - part * I;
-  const float v = w[(((int64_t)o * I + i) * KH + ky) * KW + kx];
-  const f16 hi = (f16)v;
-  dst[idx] = part < 2 ? hi : (f16)(v - (float)hi);
-}
-// The same K order for A sources that are multiples of 32 channels (igemm_kernel's half k-tile): the chunks are numbered PER SOURCE
-// (c0 | c1 | c2 input channels), 64 channels each but for the last chunk of a source of 32 (mod 64) channels, which is 32 wide -- K stays
-// dense (KH * KW * I columns).  split3: the three sources are the SAME I input channels, [w_hi | w_hi | w_lo] (pack_conv_split3_kernel).
-// With every source a multiple of 64 this writes what pack_conv_kernel / pack_conv_split3_kernel write.
+// Conv weights OIHW fp32 -> fp16 [O][K] in the GEMM family's K order (chunk-major): k = ((i / 64) * KH*KW + ky*KW + kx) * 64 + i % 64 -- all 9
+// taps of a 64-channel chunk are adjacent, so a kernel that stages one input-channel chunk (with its halo) consumes 9 consecutive k-tiles.
+// The A operand may be up to three channel-concatenated sources of c0 | c1 | c2 input channels, each a multiple of 32 (igemm_kernel's half
+// k-tile): the chunks are numbered PER SOURCE, 64 channels each but for the last chunk of a source of 32 (mod 64) channels, which is 32
+// wide -- K stays dense (KH * KW * I columns).  A 1x1 conv (one tap) is the identity order for any I: tap == 0 and ci == ks.
+// split3: the weights of a 3-pass split-fp16 convolution (UNet: the last ResBlock, round 6) -- the K-concatenated operand
+// A' = [a_hi | a_lo | a_hi] meets W' = [w_hi | w_hi | w_lo]: three sources that are the SAME I input channels, the third holding
+// lo = fp16(w - float(hi)).
 __global__ void pack_conv_src_kernel(const float* w, f16* dst, int O, int I, int KH, int KW, int c0, int c1, int c2, int split3) {
   const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int taps = KH * KW;
@@ -614,26 +447,16 @@ __global__ void __launch_bounds__(256) embed_tokens_kernel(const int64_t* ids, c
   *(f32x4*)(out + (size_t)m * C + c) = *(const f32x4*)(tok + (size_t)id * C + c) + *(const f32x4*)(pos + (size_t)(m % L) * C + c);
 }
 
-// quick_gelu (CLIP's hidden_act): x * sigmoid(1.702 x), fp32 in -> fp16 out
-__global__ void __launch_bounds__(256) quick_gelu_kernel(const float* x, f16* out, int64_t n4) {
+// fp32 in -> fp16 out.  quick_gelu (CLIP's hidden_act): x * sigmoid(1.702 x); ERF: the exact-erf GELU (nn.GELU() of the LAION-400M BERT
+// encoder's feed-forward, x_transformer.py:201), the same erf as the UNet's GEGLU epilogue
+template <bool ERF>
+__global__ void __launch_bounds__(256) gelu_kernel(const float* x, f16* out, int64_t n4) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= n4) return;
   const f32x4 v = *(const f32x4*)(x + i * 4);
   f16x4 y;
 #pragma unroll
-  for (int j = 0; j < 4; ++j) y[j] = (f16)(v[j] / (1.0f + __expf(-1.702f * v[j])));
-  *(f16x4*)(out + i * 4) = y;
-}
-
-// exact-erf GELU (nn.GELU() of the LAION-400M BERT encoder's feed-forward, x_transformer.py:201), fp32 in -> fp16 out; the
-// same erf as the UNet's GEGLU epilogue
-__global__ void __launch_bounds__(256) gelu_erf_kernel(const float* x, f16* out, int64_t n4) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n4) return;
-  const f32x4 v = *(const f32x4*)(x + i * 4);
-  f16x4 y;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) y[j] = (f16)gelu_erf(v[j]);
+  for (int j = 0; j < 4; ++j) y[j] = (f16)(ERF ? gelu_erf(v[j]) : v[j] / (1.0f + __expf(-1.702f * v[j])));
   *(f16x4*)(out + i * 4) = y;
 }
 
@@ -798,79 +621,58 @@ int launch_ctx1_broadcast(const f16* vt, int ld_v, f16* ao, int B, int ntok, int
   return 0;
 }
 
+// up to 64 input channels: conv_in_kernel (with the statistics, if asked for) up to 16, the 36 KB-patch instantiation above
 int launch_conv_in(const float* x, const float* w, const float* bias, float* out, int B, int Cin, int H, int W, int Cout,
                    hipStream_t s, int gn_n, long long* const* gn_acc, const int* gn_cpg, const int* gn_cbase) {
-  SDMI_CHECK(Cin * 9 <= CI_MAXK, "conv_in: in_channels <= 16");
+  const bool wide = Cin * 9 > CI_MAXK;
   ConvInStats st = ConvInStats();
   if (gn_n > 0) {
-    SDMI_CHECK(gn_n <= 2 && (H * W) % CI_PIX == 0, "conv_in statistics: at most two GroupNorm targets, H * W % 16 == 0");
+    SDMI_CHECK(!wide && gn_n <= 2 && (H * W) % CI_PIX == 0,
+               "conv_in statistics: in_channels <= 16, at most two GroupNorm targets, H * W % 16 == 0");
     st.n = gn_n;
     for (int i = 0; i < gn_n; ++i) { st.acc[i] = gn_acc[i]; st.cpg[i] = gn_cpg[i]; st.cbase[i] = gn_cbase[i]; }
   }
-  ProfScope ps("conv_in_f32", 2.0 * B * H * W * (double)Cout * Cin * 9, (double)B * H * W * (Cin + Cout) * 4.0, s);
-  SDMI_LAUNCH(conv_in_kernel, dim3(cdiv(B * H * W, CI_PIX)), dim3(256), 0, s, x, w, bias, out, B, Cin, H, W, Cout, st);
+  if (wide) {
+    SDMI_CHECK(Cin * 9 <= CI64_MAXK, "conv_in64: in_channels <= 64");
+    SDMI_CHECK(B >= 1 && H >= 1 && W >= 1 && Cout >= 1, "conv_in64: bad shape");
+    SDMI_CHECK(Cout <= 256 * 65535, "conv_in64: out_channels");
+  }
+  ProfScope ps(wide ? "conv_in64_f32" : "conv_in_f32", 2.0 * B * H * W * (double)Cout * Cin * 9, (double)B * H * W * (Cin + Cout) * 4.0, s);
+  if (wide) SDMI_LAUNCH((conv_in_kernel<CI64_MAXK, true>), dim3(cdiv(B * H * W, CI_PIX), cdiv(Cout, 256)), dim3(256), 0, s, x, w, bias, out, B, Cin, H, W, Cout, st);
+  else SDMI_LAUNCH((conv_in_kernel<CI_MAXK, false>), dim3(cdiv(B * H * W, CI_PIX)), dim3(256), 0, s, x, w, bias, out, B, Cin, H, W, Cout, st);
   SDMI_HIP_OK(hipGetLastError());
   return 0;
 }
 
-// up to 64 input channels: Cin <= 16 is launch_conv_in's launch (no statistics), above it conv_in64_kernel
-int launch_conv_in64(const float* x, const float* w, const float* bias, float* out, int B, int Cin, int H, int W, int Cout, hipStream_t s) {
-  if (Cin * 9 <= CI_MAXK) return launch_conv_in(x, w, bias, out, B, Cin, H, W, Cout, s);
-  SDMI_CHECK(Cin * 9 <= CI64_MAXK, "conv_in64: in_channels <= 64");
-  SDMI_CHECK(B >= 1 && H >= 1 && W >= 1 && Cout >= 1, "conv_in64: bad shape");
-  ProfScope ps("conv_in64_f32", 2.0 * B * H * W * (double)Cout * Cin * 9, (double)B * H * W * (Cin + Cout) * 4.0, s);
-  SDMI_CHECK(Cout <= 256 * 65535, "conv_in64: out_channels");
-  SDMI_LAUNCH(conv_in64_kernel, dim3(cdiv(B * H * W, CI_PIX), cdiv(Cout, 256)), dim3(256), 0, s, x, w, bias, out, B, Cin, H, W, Cout);
-  SDMI_HIP_OK(hipGetLastError());
-  return 0;
-}
-
-// up to 128 outputs: Cout <= 32 is launch_conv_out's launch, above it the same sliced kernels with 5 .. 16 slices of eight outputs
-int launch_conv_out128(const float* h, const float* w, const float* bias, float* out, int B, int H, int W, int Cin, int Cout,
-                       hipStream_t s) {
-  if (Cout <= 4 * CO_MAXN) return launch_conv_out(h, w, bias, out, B, H, W, Cin, Cout, s);
-  SDMI_CHECK(Cout <= 16 * CO_MAXN && Cin >= 4 && Cin <= 512 && Cin % 4 == 0, "conv_out128: out_channels <= 128, Cin <= 512, Cin % 4 == 0");
-  SDMI_CHECK(B >= 1 && H >= 1 && W >= 1, "conv_out128: bad shape");
-  ProfScope ps("conv_out128_f32", 2.0 * B * H * W * (double)Cout * Cin * 9, (double)B * H * W * (Cin + Cout) * 4.0, s);
-  const bool al = ((((uintptr_t)h | (uintptr_t)w | (uintptr_t)out) & 15) == 0);
-  const int slices = cdiv(Cout, CO_MAXN);
-  if (W % COP == 0 && al)
-    SDMI_LAUNCH(conv_out4_halves_kernel, dim3(cdiv(B * H * (W / COP), 4), slices), dim3(256), 0, s, h, w, bias, out, B, H, W, Cin, Cout);
-  else
-    SDMI_LAUNCH(conv_out_halves_kernel, dim3(cdiv(B * H * W, 4), slices), dim3(256), 0, s, h, w, bias, out, B, H, W, Cin, Cout);
-  SDMI_HIP_OK(hipGetLastError());
-  return 0;
-}
-
+// up to 128 outputs in slices of eight (gridDim.y = 1 .. 16); above 32 outputs the rules are those the 128-output entry was published with
 int launch_conv_out(const float* h, const float* w, const float* bias, float* out, int B, int H, int W, int Cin, int Cout,
                     hipStream_t s) {
-  SDMI_CHECK(Cout >= 1 && Cout <= 4 * CO_MAXN && Cin % 4 == 0, "conv_out: out_channels <= 32, Cin % 4 == 0");
-  ProfScope ps("conv_out_f32", 2.0 * B * H * W * (double)Cout * Cin * 9, (double)B * H * W * (Cin + Cout) * 4.0, s);
-  if (Cout > CO_MAXN) {        // 9 .. 32 outputs: slices of 8 in one launch (grid.y = 2, 3 or 4); Cout <= 8 launches what it always did, below
-    const bool al = ((((uintptr_t)h | (uintptr_t)w | (uintptr_t)out) & 15) == 0);
-    const int slices = cdiv(Cout, CO_MAXN);      // (9 .. 16 outputs: 2, the launch they always had)
-    if (W % COP == 0 && Cin <= 512 && al)
-      SDMI_LAUNCH(conv_out4_halves_kernel, dim3(cdiv(B * H * (W / COP), 4), slices), dim3(256), 0, s, h, w, bias, out, B, H, W, Cin, Cout);
-    else
-      SDMI_LAUNCH(conv_out_halves_kernel, dim3(cdiv(B * H * W, 4), slices), dim3(256), 0, s, h, w, bias, out, B, H, W, Cin, Cout);
-    SDMI_HIP_OK(hipGetLastError());
-    return 0;
+  const bool wide = Cout > 4 * CO_MAXN;
+  if (wide) {
+    SDMI_CHECK(Cout <= 16 * CO_MAXN && Cin >= 4 && Cin <= 512 && Cin % 4 == 0, "conv_out128: out_channels <= 128, Cin <= 512, Cin % 4 == 0");
+    SDMI_CHECK(B >= 1 && H >= 1 && W >= 1, "conv_out128: bad shape");
+  } else {
+    SDMI_CHECK(Cout >= 1 && Cin % 4 == 0, "conv_out: out_channels <= 32, Cin % 4 == 0");
   }
+  ProfScope ps(wide ? "conv_out128_f32" : "conv_out_f32", 2.0 * B * H * W * (double)Cout * Cin * 9, (double)B * H * W * (Cin + Cout) * 4.0, s);
   // (an LDS-resident-weights variant, 32 pixels per block, was measured at 169 us vs 64 us: one wave per pixel keeps 1024
   // independent waves in flight, which this latency-bound fp32 kernel needs more than it needs fewer weight re-reads)
-  const char* e_co4 = getenv("SDMI_CONV_OUT4");                  // A/B knob, read per launch (1 per UNet call)
+  const char* e_co4 = getenv("SDMI_CONV_OUT4");                  // A/B knob of the heads of up to 8 outputs, read per launch (1 per UNet call)
   const int env_co4 = e_co4 ? atoi(e_co4) : 1;
   const bool al16 = ((((uintptr_t)h | (uintptr_t)w | (uintptr_t)out) & 15) == 0);
-  if (env_co4 && W % COP == 0 && Cin <= 512 && al16) {       // (out rows of W floats at x0 % 4 == 0: 16-byte aligned stores)
-    const int groups = B * H * (W / COP);
-    if (Cout <= 4) SDMI_LAUNCH(conv_out4_kernel<4>, dim3(cdiv(groups, 4)), dim3(256), 0, s, h, w, bias, out, B, H, W, Cin, Cout);
-    else SDMI_LAUNCH(conv_out4_kernel<8>, dim3(cdiv(groups, 4)), dim3(256), 0, s, h, w, bias, out, B, H, W, Cin, Cout);
+  const int slices = cdiv(Cout, CO_MAXN);
+  if ((env_co4 || slices > 1) && W % COP == 0 && Cin <= 512 && al16) {       // (out rows of W floats at x0 % 4 == 0: 16-byte aligned stores)
+    const dim3 grid(cdiv(B * H * (W / COP), 4), slices);
+    if (Cout <= 4) SDMI_LAUNCH((conv_out4_kernel<4, false>), grid, dim3(256), 0, s, h, w, bias, out, B, H, W, Cin, Cout);
+    else if (slices == 1) SDMI_LAUNCH((conv_out4_kernel<8, false>), grid, dim3(256), 0, s, h, w, bias, out, B, H, W, Cin, Cout);
+    else SDMI_LAUNCH((conv_out4_kernel<8, true>), grid, dim3(256), 0, s, h, w, bias, out, B, H, W, Cin, Cout);
   } else {
-    SDMI_LAUNCH(conv_out_kernel, dim3(cdiv(B * H * W, 4)), dim3(256), 0, s, h, w, bias, out, B, H, W, Cin, Cout);
+    SDMI_LAUNCH(conv_out_kernel, dim3(cdiv(B * H * W, 4), slices), dim3(256), 0, s, h, w, bias, out, B, H, W, Cin, Cout);
   }
   SDMI_HIP_OK(hipGetLastError());
   return 0;
 }
+
 
 
 int launch_embed_tokens(const int64_t* ids, const float* tok_emb, const float* pos_emb, float* out, int M, int L, int C,
@@ -885,14 +687,14 @@ int launch_embed_tokens(const int64_t* ids, const float* tok_emb, const float* p
 
 int launch_quick_gelu(const float* x, f16* out, int64_t n, hipStream_t s) {
   SDMI_CHECK(n % 4 == 0, "quick_gelu: n % 4");
-  SDMI_LAUNCH(quick_gelu_kernel, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, s, x, out, n / 4);
+  SDMI_LAUNCH(gelu_kernel<false>, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, s, x, out, n / 4);
   SDMI_HIP_OK(hipGetLastError());
   return 0;
 }
 
 int launch_gelu_erf(const float* x, f16* out, int64_t n, hipStream_t s) {
   SDMI_CHECK(n % 4 == 0, "gelu_erf: n % 4");
-  SDMI_LAUNCH(gelu_erf_kernel, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, s, x, out, n / 4);
+  SDMI_LAUNCH(gelu_kernel<true>, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, s, x, out, n / 4);
   SDMI_HIP_OK(hipGetLastError());
   return 0;
 }
@@ -913,25 +715,16 @@ int launch_gelu_erf_split(const float* x, f16* out, f16* out_lo, int64_t n, hipS
   return 0;
 }
 
+// up to 128 input channels: the inputs in registers up to 32 (pointwise_nchw_kernel), the outputs in registers above
 int launch_pointwise_nchw(const float* x, const float* w, const float* bias, float* out, int B, int Cin, int Cout, int HW,
                           float in_scale, hipStream_t s) {
-  SDMI_CHECK(Cin >= 1 && Cin <= 32 && Cout >= 1, "pointwise conv: 1 <= Cin <= 32");
+  if (Cin <= 32) SDMI_CHECK(Cin >= 1 && Cout >= 1, "pointwise conv: 1 <= Cin <= 32");
+  else SDMI_CHECK(Cin <= 128 && Cout >= 1 && Cout <= 1024 && B >= 1 && HW >= 1, "pointwise conv 128: 1 <= Cin <= 128, Cout <= 1024");
   const int64_t total = (int64_t)B * HW;
-  const dim3 grid((unsigned)((total + 255) / 256));
+  const dim3 grid((unsigned)((total + 255) / 256), Cin <= 32 ? 1 : cdiv(Cout, PWW_NOUT));
   if (Cin <= 16) SDMI_LAUNCH(pointwise_nchw_kernel<16>, grid, dim3(256), 0, s, x, w, bias, out, B, Cin, Cout, HW, in_scale);
-  else SDMI_LAUNCH(pointwise_nchw_kernel<32>, grid, dim3(256), 0, s, x, w, bias, out, B, Cin, Cout, HW, in_scale);
-  SDMI_HIP_OK(hipGetLastError());
-  return 0;
-}
-
-// up to 128 input channels: Cin <= 32 is launch_pointwise_nchw's launch, above it pointwise_nchw_wide_kernel
-int launch_pointwise_nchw128(const float* x, const float* w, const float* bias, float* out, int B, int Cin, int Cout, int HW,
-                             float in_scale, hipStream_t s) {
-  if (Cin <= 32) return launch_pointwise_nchw(x, w, bias, out, B, Cin, Cout, HW, in_scale, s);
-  SDMI_CHECK(Cin <= 128 && Cout >= 1 && Cout <= 1024 && B >= 1 && HW >= 1, "pointwise conv 128: 1 <= Cin <= 128, Cout <= 1024");
-  const int64_t total = (int64_t)B * HW;
-  SDMI_LAUNCH(pointwise_nchw_wide_kernel, dim3((unsigned)((total + 255) / 256), cdiv(Cout, PWW_NOUT)), dim3(256), 0, s, x, w, bias, out,
-              B, Cin, Cout, HW, in_scale);
+  else if (Cin <= 32) SDMI_LAUNCH(pointwise_nchw_kernel<32>, grid, dim3(256), 0, s, x, w, bias, out, B, Cin, Cout, HW, in_scale);
+  else SDMI_LAUNCH(pointwise_nchw_wide_kernel, grid, dim3(256), 0, s, x, w, bias, out, B, Cin, Cout, HW, in_scale);
   SDMI_HIP_OK(hipGetLastError());
   return 0;
 }
@@ -944,20 +737,26 @@ int launch_softmax_rows(const float* S, f16* P, int rows, int cols, int lds, int
   return 0;
 }
 
-int launch_pack_conv_weight_src(const float* w, f16* dst, int O, int I, int KH, int KW, int c0, int c1, int c2, hipStream_t s) {
-  SDMI_CHECK(c0 > 0 && c1 >= 0 && c2 >= 0 && c0 + c1 + c2 == I && (c2 == 0 || c1 > 0), "conv pack: the source split must add up to the input channels");
-  SDMI_CHECK(c0 % 32 == 0 && c1 % 32 == 0 && c2 % 32 == 0, "conv pack: every A source must be a multiple of 32 channels");
-  const int64_t total = (int64_t)O * I * KH * KW;
-  SDMI_LAUNCH(pack_conv_src_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, w, dst, O, I, KH, KW, c0, c1, c2, 0);
+// the one launch of the three conv weight packers below, which differ in what they check
+static int pack_conv_src(const float* w, f16* dst, int O, int I, int KH, int KW, int c0, int c1, int c2, int split3, hipStream_t s) {
+  const int64_t K = (int64_t)(c0 + c1 + c2) * KH * KW;
+  SDMI_CHECK(K < ((int64_t)1 << 31), "conv pack: a weight row must have fewer than 2^31 columns");     // (the kernel's column index is an int)
+  SDMI_LAUNCH(pack_conv_src_kernel, dim3((unsigned)((O * K + 255) / 256)), dim3(256), 0, s, w, dst, O, I, KH, KW, c0, c1, c2, split3);
   SDMI_HIP_OK(hipGetLastError());
   return 0;
 }
+int launch_pack_conv_weight_src(const float* w, f16* dst, int O, int I, int KH, int KW, int c0, int c1, int c2, hipStream_t s) {
+  SDMI_CHECK(c0 > 0 && c1 >= 0 && c2 >= 0 && c0 + c1 + c2 == I && (c2 == 0 || c1 > 0), "conv pack: the source split must add up to the input channels");
+  SDMI_CHECK(c0 % 32 == 0 && c1 % 32 == 0 && c2 % 32 == 0, "conv pack: every A source must be a multiple of 32 channels");
+  return pack_conv_src(w, dst, O, I, KH, KW, c0, c1, c2, 0, s);
+}
 int launch_pack_conv_weight(const float* w, f16* dst, int O, int I, int KH, int KW, hipStream_t s) {
-  if (KH * KW > 1 && I % 64 != 0) return launch_pack_conv_weight_src(w, dst, O, I, KH, KW, I, 0, 0, s);   // one source that ends in a half chunk
-  const int64_t total = (int64_t)O * I * KH * KW;
-  SDMI_LAUNCH(pack_conv_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, w, dst, O, I, KH, KW);
-  SDMI_HIP_OK(hipGetLastError());
-  return 0;
+  if (KH * KW > 1) return launch_pack_conv_weight_src(w, dst, O, I, KH, KW, I, 0, 0, s);   // one source (it may end in a half chunk)
+  return pack_conv_src(w, dst, O, I, KH, KW, I, 0, 0, 0, s);                                // 1x1 / Linear: the identity order, any I
+}
+int launch_pack_conv_split3(const float* w, f16* dst, int O, int I, int KH, int KW, hipStream_t s) {
+  SDMI_CHECK(I % 32 == 0, "split-fp16 conv pack: input channels % 64 must be 0, or 32 (a half k-tile)");
+  return pack_conv_src(w, dst, O, I, KH, KW, I, I, I, 1, s);       // three sources of the same I channels
 }
 // Weights of the four 2x2 phase convs of conv3x3(nearest x2 (x)) (igemm KIND_2X2), derived from the PACKED fp16 3x3 weights wp[N][9 Cin]:
 // dst[phase = 2 a + c][n][k'], k' = ((i / 64) * 4 + 2 dy + dx) * 64 + i % 64 (the kernel's K order: 64-channel chunk major, tap fastest).  Output pixel
@@ -1008,18 +807,6 @@ int launch_prefetch_lines(const void* ptr, int64_t bytes, hipStream_t s) {
   return 0;
 }
 
-int launch_pack_conv_split3(const float* w, f16* dst, int O, int I, int KH, int KW, hipStream_t s) {
-  SDMI_CHECK(I % 32 == 0, "split-fp16 conv pack: input channels % 64 must be 0, or 32 (a half k-tile)");
-  const int64_t total = (int64_t)O * 3 * I * KH * KW;
-  if (I % 64 != 0) {               // three sources of I channels, each ending in a half chunk
-    SDMI_LAUNCH(pack_conv_src_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, w, dst, O, I, KH, KW, I, I, I, 1);
-    SDMI_HIP_OK(hipGetLastError());
-    return 0;
-  }
-  SDMI_LAUNCH(pack_conv_split3_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, w, dst, O, I, KH, KW);
-  SDMI_HIP_OK(hipGetLastError());
-  return 0;
-}
 int launch_pack_conv_out(const float* w, float* dst, int O, int I, hipStream_t s) {
   const int64_t total = (int64_t)O * I * 9;
   SDMI_LAUNCH(pack_conv_f32_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, w, dst, O, I, 3, 3);

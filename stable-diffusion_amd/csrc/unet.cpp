@@ -1274,6 +1274,7 @@ int UNet::run(const float* x, const int64_t* t_i64, const float* t_f32, const fl
         IGemmParams st = IGemmParams();                                   // (carrier of the statistics targets only)
         f.attach_gn_targets(st, h);
         if (!d) {
+          SDMI_CHECK(cfg_.in_channels <= 16, "conv_in: in_channels <= 16");      // (the UNet's limit; the launcher's own is the first stages' 64)
           TapeCaller tc(Tape::R_X, x);
           int r = launch_conv_in(x, L.w32[0], L.f32[0], h.p, B, cfg_.in_channels, H, W, mc, stream, st.gn_n, st.gn_acc, st.gn_cpg, st.gn_cbase);
           if (r) return r;
@@ -1295,6 +1296,7 @@ int UNet::run(const float* x, const int64_t* t_i64, const float* t_f32, const fl
       float* hn = f.S<float>((size_t)B * H * W * mc);
       f.groupnorm(h, nullptr, out_gamma_, out_beta_, 1e-5f, 1, nullptr, hn, nullptr);
       if (!d && !f.rc) {
+        SDMI_CHECK(cfg_.out_channels <= 32, "conv_out: out_channels <= 32, Cin % 4 == 0");   // (the UNet's limit; the launcher's own is 128)
         TapeCaller tc(Tape::R_OUT, eps_out);
         int r = launch_conv_out(hn, out_w_, out_b_, eps_out, B, H, W, mc, cfg_.out_channels, stream);
         if (r) return r;

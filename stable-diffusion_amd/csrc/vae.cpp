@@ -48,11 +48,8 @@ int Vae::build(const sdmi_vae_cfg& c, int parts, const sdmi_vae_ext* ext, int pr
   SDMI_CHECK(parts >= 1 && parts <= 3, "parts: 1 decoder, 2 encoder, 3 both");
   SDMI_CHECK(c.n_levels >= 1 && c.n_levels <= 8 && c.num_res_blocks >= 1, "bad level / res block count");
   SDMI_CHECK(c.ch % 64 == 0, "ch must be a multiple of 64 on this path");
-  // (z_channels 16 / embed_dim 16 with double_z: encoder.conv_out writes 32 channels, quant_conv reads 32 -- launch_conv_out's and
-  // launch_pointwise_nchw's limits; decoder.conv_in reads 16 -- launch_conv_in's)
-  // ... and 32 or 64 of either (KL-f32: 64 / 64): the wide launches -- decoder.conv_in reads up to 64 (launch_conv_in64), encoder.conv_out
-  // writes up to 128 (launch_conv_out128), the quant convs read up to 128 (launch_pointwise_nchw128).  decode() / encode() call the wide
-  // launchers, which ARE the old launches up to the old limits.
+  // (the latent widths the fp32 ends take: decoder.conv_in reads up to 64 channels (launch_conv_in), encoder.conv_out writes up to 128 with
+  // double_z (launch_conv_out), the quant convs read up to 128 (launch_pointwise_nchw))
   auto latent_width = [](int v) { return (v >= 1 && v <= 16) || v == 32 || v == 64; };
   SDMI_CHECK(c.in_channels >= 1 && c.in_channels <= 16 && latent_width(c.z_channels) && latent_width(c.embed_dim) && c.out_ch >= 1 &&
                  c.out_ch <= 8,
@@ -495,10 +492,10 @@ int Vae::decode(const float* z, float z_scale, float* img, int B, int H, int W, 
     float* zc = ext_.n_embed > 0 ? f.P<float>((size_t)B * cfg_.embed_dim * H * W) : nullptr;
     if (!d && quantize) {
       if (launch_vq_quantize(z, z_scale, cb_, cb_norm_, ext_.n_embed, cfg_.embed_dim, zc, nullptr, B, H * W, stream)) return -1;
-      if (launch_pointwise_nchw128(zc, pq_w_, pq_b_, zq, B, cfg_.embed_dim, cfg_.z_channels, H * W, 1.0f, stream)) return -1;
-    } else if (!d && launch_pointwise_nchw128(z, pq_w_, pq_b_, zq, B, cfg_.embed_dim, cfg_.z_channels, H * W, z_scale, stream)) return -1;
+      if (launch_pointwise_nchw(zc, pq_w_, pq_b_, zq, B, cfg_.embed_dim, cfg_.z_channels, H * W, 1.0f, stream)) return -1;
+    } else if (!d && launch_pointwise_nchw(z, pq_w_, pq_b_, zq, B, cfg_.embed_dim, cfg_.z_channels, H * W, z_scale, stream)) return -1;
     Act x; x.p = f.P<float>((size_t)B * H * W * c_in); x.C = c_in; x.H = H; x.W = W;
-    if (!d && launch_conv_in64(zq, dci_w_, dci_b_, x.p, B, cfg_.z_channels, H, W, c_in, stream)) return -1;
+    if (!d && launch_conv_in(zq, dci_w_, dci_b_, x.p, B, cfg_.z_channels, H, W, c_in, stream)) return -1;
     for (auto& L : dec_) x = f.run_layer(L, x);
     if (f.rc) return f.rc;
     float* hn = f.S<float>((size_t)B * x.H * x.W * x.C);
@@ -528,8 +525,8 @@ int Vae::encode(const float* img, float* moments, int B, int H, int W, void* wor
     f.groupnorm(x, nullptr, eno_g_, eno_b_, VFwd::EPS, 1, nullptr, hn, nullptr);
     const int zc2 = enc_zc();
     float* mo = f.S<float>((size_t)B * zc2 * x.H * x.W);
-    if (!d && !f.rc && launch_conv_out128(hn, eco_w_, eco_b_, mo, B, x.H, x.W, x.C, zc2, stream)) return -1;
-    if (!d && !f.rc && launch_pointwise_nchw128(mo, q_w_, q_b_, moments, B, zc2, enc_ed(), x.H * x.W, 1.0f, stream))
+    if (!d && !f.rc && launch_conv_out(hn, eco_w_, eco_b_, mo, B, x.H, x.W, x.C, zc2, stream)) return -1;
+    if (!d && !f.rc && launch_pointwise_nchw(mo, q_w_, q_b_, moments, B, zc2, enc_ed(), x.H * x.W, 1.0f, stream))
       return -1;
     return f.rc;
   });

@@ -2,7 +2,7 @@
 weights verified unmodified; every output judged per element against the worst-case bound of one fp32 accumulator chain (the bounds
 tests/test_kl_f16_kernels_gpu.py derives):
 
-* sdmi_k_conv_in64, 17 .. 64 input channels (conv_in64_kernel): 9 Cin 2^-24 sum |w x| (+ |bias|); one pixel row, a block of 16 pixels that
+* sdmi_k_conv_in64, 17 .. 64 input channels (the 36 KB-patch form of conv_in_kernel): 9 Cin 2^-24 sum |w x| (+ |bias|); one pixel row, a block of 16 pixels that
   is not full, more than one block; and the accumulation order depends on Cin alone -- two equal images of 15 pixels, whose pixels sit at
   different places of different blocks, give the same bits;
 * sdmi_k_conv_out128, 33 .. 128 outputs (the sliced kernels with 5 .. 16 slices): 9 Cin 2^-24 sum |w x| (+ |bias|), on the one-pixel form
