@@ -463,6 +463,40 @@ int sdmi_k_safety_head(const float* image_embeds, const float* concept_embeds, c
                        const float* concept_thresholds, const float* special_care_thresholds, int32_t* has_nsfw, float* concept_scores,
                        float* special_care_scores, int B, int Nc, int Ns, int E, void* stream);
 
+/* ---- the safety checker's feature extractor (scripts/txt2img.py:26-29, 88-90) --------------------------------------------
+ * CLIPFeatureExtractor on the device: numpy_to_pil's uint8 conversion, PIL's 8-bit bicubic Image.resize of the shortest side to `size`
+ * (the other side int(size * long / short)), the centre crop (top = (rh - crop) / 2, left = (rw - crop) / 2), / 255 and (x - mean) / std.
+ * The resized uint8 image equals Pillow's bit for bit; the float stage is three correctly rounded fp32 operations.
+ * Additive entry points: no existing struct or call changes, SDMI_ABI_VERSION stays as it is.
+ *
+ * Host side (no GPU): Pillow's coefficient tables of one axis in -> out, computed in double in Pillow's evaluation order.
+ * sdmi_fe_ksize: taps per output index, (int)ceil(2 max(in / out, 1)) * 2 + 1, or -1 for sizes below 1.  sdmi_fe_coeffs fills
+ * bounds [out][2] = {xmin, xmax} (the taps of output index xx read source indices xmin .. xmin + xmax - 1, all inside [0, in)) and
+ * kk [out][ksize], the bicubic (a = -0.5) weights normalised to sum 1 and rounded to 22 fraction bits; entries x >= xmax are 0. */
+int sdmi_fe_ksize(int in, int out);
+int sdmi_fe_coeffs(int in, int out, int32_t* bounds, int32_t* kk);
+int sdmi_fe_output_size(int H, int W, int size, int* rh, int* rw);
+/* Source kinds of sdmi_k_clip_feature_extract.  Values outside a kind's range are clamped: a float becomes
+ * clamp(rint(x * 255), 0, 255) (fp32 multiply, round half to even: numpy_to_pil's (x * 255).round().astype(uint8) wherever that is defined);
+ * the raw kind applies clamp((x + 1) / 2, 0, 1) first, in the fp32 operation order of scripts/txt2img.py:314. */
+#define SDMI_FE_SRC_U8_NHWC 0       /* uint8 [B, H, W, 3] */
+#define SDMI_FE_SRC_F32_NHWC 1      /* fp32 [B, H, W, 3] in [0, 1] (the script's x_image) */
+#define SDMI_FE_SRC_F32_NCHW 2      /* fp32 [B, 3, H, W] in [0, 1] */
+#define SDMI_FE_SRC_F32_NCHW_RAW 3  /* fp32 [B, 3, H, W] in [-1, 1]: the decode_first_stage output itself */
+/* bytes of the horizontal pass's uint8 rows (0 when the width does not change), or -1 with the error set */
+int64_t sdmi_fe_workspace_bytes(int B, int H, int W, int size, int crop);
+/* One batch of equal-sized device images -> pixel_values fp32 [B, 3, crop, crop] and, when out_u8_or_null is given, the resized and cropped
+ * uint8 image [B, crop, crop, 3].  h_* : the device copies of sdmi_fe_coeffs(W, rw), v_* : of sdmi_fe_coeffs(H, rh), (rh, rw) =
+ * sdmi_fe_output_size(H, W, size); the tables of an axis that keeps its size are not read and may be NULL.  mean3 / std3: host arrays.
+ * At most two launches (horizontal; vertical + crop + normalise), no atomics, the source is only read.  Only the crop window is computed:
+ * its columns, and the source rows its vertical pass reads.  Refused, launching nothing, each with a message that names it: crop > size
+ * (the processor's padding), C != 3, sizes below 1, tables whose ksize is not sdmi_fe_ksize of the sizes given, a horizontal ksize above
+ * 255, a workspace smaller than sdmi_fe_workspace_bytes. */
+int sdmi_k_clip_feature_extract(const void* src, int src_kind, int B, int C, int H, int W, int size, int crop, const int32_t* h_bounds,
+                                const int32_t* h_kk, int h_ksize, const int32_t* v_bounds, const int32_t* v_kk, int v_ksize,
+                                const float* mean3, const float* std3, void* workspace, int64_t workspace_bytes, float* pixel_values,
+                                void* out_u8_or_null, void* stream);
+
 /* ---- exact k-nearest-neighbour search (retrieval conditioning) -------------------------------------------------------
  * Replaces `Searcher.search` of scripts/knn2img.py (scann's score_brute_force with dot_product between L2-normalised vectors): an exact
  * maximum-cosine search over a database of raw fp32 embeddings kept on the device, one copy of the rows plus one inverse norm per row.

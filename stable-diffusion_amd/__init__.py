@@ -36,7 +36,7 @@ from .ldm_shim import LatentDiffusionHIP, DiffusionWrapperHIP  # noqa: F401
 from .superres import SuperResolutionHIP  # noqa: F401
 from .rescaler import SpatialRescalerHIP  # noqa: F401
 from .semantic import SemanticSynthesisHIP  # noqa: F401
-from .vision import CLIPVisionHIP, StableDiffusionSafetyCheckerHIP, FrozenClipImageEmbedderHIP  # noqa: F401
+from .vision import CLIPVisionHIP, StableDiffusionSafetyCheckerHIP, FrozenClipImageEmbedderHIP, CLIPFeatureExtractorHIP  # noqa: F401
 from .retrieval import SearcherHIP  # noqa: F401
 from . import debug, postprocess  # noqa: F401
 

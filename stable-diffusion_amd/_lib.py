@@ -165,6 +165,12 @@ _SIGS = {
     'sdmi_k_vit_embed': (C.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, C.c_int, C.c_int, C.c_int, c_ptr]),
     'sdmi_k_vit_preprocess': (C.c_int, [c_ptr, c_ptr, C.c_int, C.c_int, C.c_int, C.c_int, c_ptr]),
     'sdmi_k_safety_head': (C.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, C.c_int, C.c_int, C.c_int, C.c_int, c_ptr]),
+    'sdmi_fe_ksize': (C.c_int, [C.c_int, C.c_int]),
+    'sdmi_fe_coeffs': (C.c_int, [C.c_int, C.c_int, c_ptr, c_ptr]),
+    'sdmi_fe_output_size': (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    'sdmi_fe_workspace_bytes': (C.c_int64, [C.c_int] * 5),
+    'sdmi_k_clip_feature_extract': (C.c_int, [c_ptr] + [C.c_int] * 7 + [c_ptr, c_ptr, C.c_int, c_ptr, c_ptr, C.c_int, C.POINTER(C.c_float),
+                                              C.POINTER(C.c_float), c_ptr, C.c_int64, c_ptr, c_ptr, c_ptr]),
     'sdmi_knn_create': (C.c_int, [C.c_int, C.c_int64, C.POINTER(c_ptr)]),
     'sdmi_knn_destroy': (C.c_int, [c_ptr]),
     'sdmi_knn_set_rows': (C.c_int, [c_ptr, C.c_int64, C.c_int64, c_ptr, c_ptr]),

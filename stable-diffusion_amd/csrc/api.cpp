@@ -10,6 +10,8 @@
 #include "clip.h"
 #include "knn.h"
 #include "rescale.h"
+#include "fe_coeffs.h"
+#include "feature_extractor.h"
 
 namespace sdmi {
 static thread_local std::string g_err;
@@ -460,6 +462,36 @@ int sdmi_k_safety_head(const float* image_embeds, const float* concept_embeds, c
                        float* special_care_scores, int B, int Nc, int Ns, int E, void* stream) {
   return launch_safety_head(image_embeds, concept_embeds, special_care_embeds, concept_thresholds, special_care_thresholds, (int*)has_nsfw,
                             concept_scores, special_care_scores, B, Nc, Ns, E, (hipStream_t)stream);
+}
+// ---- the safety checker's feature extractor ------------------------------------------------------------------------------
+int sdmi_fe_ksize(int in, int out) {
+  if (in < 1 || out < 1) { fail("fe_ksize: sizes below 1"); return -1; }
+  return fe_ksize(in, out);
+}
+int sdmi_fe_coeffs(int in, int out, int32_t* bounds, int32_t* kk) {
+  SDMI_CHECK(in >= 1 && out >= 1, "fe_coeffs: sizes below 1");
+  SDMI_CHECK(bounds && kk, "fe_coeffs: null table");
+  return fe_coeffs(in, out, bounds, kk);
+}
+int sdmi_fe_output_size(int H, int W, int size, int* rh, int* rw) {
+  SDMI_CHECK(H >= 1 && W >= 1 && size >= 1 && rh && rw, "fe_output_size: sizes below 1, or a null output");
+  SDMI_CHECK((int64_t)size * std::max(H, W) / std::min(H, W) <= 0x7fffffff, "fe_output_size: the resized side does not fit an int");
+  fe_output_size(H, W, size, rh, rw);
+  return 0;
+}
+int64_t sdmi_fe_workspace_bytes(int B, int H, int W, int size, int crop) { return fe_workspace_bytes(B, H, W, size, crop); }
+int sdmi_k_clip_feature_extract(const void* src, int src_kind, int B, int C, int H, int W, int size, int crop, const int32_t* h_bounds,
+                                const int32_t* h_kk, int h_ksize, const int32_t* v_bounds, const int32_t* v_kk, int v_ksize,
+                                const float* mean3, const float* std3, void* workspace, int64_t workspace_bytes, float* pixel_values,
+                                void* out_u8_or_null, void* stream) {
+  SDMI_CHECK(C == 3, "feature_extract: a channel count other than 3 (RGB images only), got " + std::to_string(C));
+  SDMI_CHECK(mean3 && std3, "feature_extract: null mean or std");
+  FeParams p;
+  p.src = src; p.kind = src_kind; p.B = B; p.H = H; p.W = W; p.size = size; p.crop = crop;
+  p.hb = h_bounds; p.hk = h_kk; p.h_ksize = h_ksize; p.vb = v_bounds; p.vk = v_kk; p.v_ksize = v_ksize;
+  for (int c = 0; c < 3; ++c) { p.mean[c] = mean3[c]; p.std[c] = std3[c]; }
+  p.ws = workspace; p.ws_bytes = workspace_bytes; p.pixel_values = pixel_values; p.out_u8 = (unsigned char*)out_u8_or_null;
+  return launch_feature_extract(p, (hipStream_t)stream);
 }
 // ---- exact k-NN search -----------------------------------------------------------------------------------------------
 int sdmi_knn_create(int D, int64_t capacity_rows, sdmi_knn** out) {

@@ -7,7 +7,13 @@
     put_watermark(img, wm_encoder)                      -> `put_watermark` (needs the optional `imwatermark` package)
 
 The safety checker is built as well: `stable_diffusion_amd.vision.StableDiffusionSafetyCheckerHIP` (its CLIP ViT-L/14 vision tower and the
-concept head in libsdmi).  Its feature extractor (PIL resize and crop) stays the reference's host call.
+concept head in libsdmi), and so is its feature extractor (`vision.CLIPFeatureExtractorHIP`: numpy_to_pil's uint8 conversion and PIL's
+bicubic resize and crop, bit for bit, on the device).  `check_safety` below is txt2img.py:314-317 from the raw decode output to the checked images
+and the flags, without the image leaving the GPU:
+
+    x = torch.clamp((x + 1.0) / 2.0, min=0.0, max=1.0)  \\
+    x = x.cpu().permute(0, 2, 3, 1).numpy()              } `check_safety`: the same clamp, then extractor -> tower -> head on the device;
+    x_checked, has_nsfw = check_safety(x)               /  one small device-to-host copy (the flags)
 """
 import numpy as np
 import torch
@@ -26,6 +32,19 @@ def to_uint8_images(x_samples):
     out = torch.empty((B, H, W, C), dtype=torch.uint8, device=x.device)
     _lib.check(_lib.load().sdmi_image_to_uint8(x.data_ptr(), out.data_ptr(), B, C, H, W, _lib.stream_ptr()))
     return out
+
+
+@torch.no_grad()
+def check_safety(x_samples, checker, extractor=None):
+    """scripts/txt2img.py:314-317 on the device.  `x_samples`: the raw decode_first_stage output [B, 3, H, W] (cuda); `checker`: a
+    StableDiffusionSafetyCheckerHIP; `extractor`: a CLIPFeatureExtractorHIP (default: the checker's own, at the tower's image size).
+    -> (images fp32 [B, 3, H, W] in [0, 1] with the flagged ones zeroed, has_nsfw_concepts): `images.permute(0, 2, 3, 1)` is the script's
+    x_checked_image, still on the device (`to_uint8_images` itself takes the raw decode output: for the unflagged images its bytes are
+    those of `(255. * images)` truncated, txt2img.py:323)."""
+    if not x_samples.is_cuda:
+        raise RuntimeError('check_safety runs on MI355X device tensors only (no CPU fallback)')
+    x = torch.clamp((x_samples.detach().float() + 1.0) / 2.0, min=0.0, max=1.0)
+    return checker.check_images(x, extractor=extractor, layout='NCHW', value_range=(0, 1))
 
 
 def put_watermark(img, wm_encoder=None):

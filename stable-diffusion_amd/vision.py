@@ -7,8 +7,13 @@
 
 The tower (patch embedding, 24 pre-norm encoder layers, post-LayerNorm, projection) runs in libsdmi.so behind the `sdmi_vit_*` handle, the concept
 head in `sdmi_k_safety_head`, the embedder's bicubic preprocess in `sdmi_k_vit_preprocess`.  Mixed precision only: fp16 MFMA operands, fp32
-accumulation and residual stream.  The feature extractor (PIL resize and crop) stays the reference's host call, as the tokenizer does.  No CPU /
-PyTorch fallback.
+accumulation and residual stream.  No CPU / PyTorch fallback.
+
+    CLIPFeatureExtractorHIP         <- transformers.CLIPFeatureExtractor as AutoFeatureExtractor builds it for the checker (scripts/txt2img.py:28)
+
+The checker's feature extractor (numpy_to_pil's uint8 conversion, PIL's 8-bit bicubic resize, centre crop, / 255, mean / std) runs in
+`sdmi_k_clip_feature_extract`, its uint8 stage bit-equal to PIL's; `StableDiffusionSafetyCheckerHIP.check_images` chains it with the tower and the
+head on device images.
 """
 import ctypes as C
 import json
@@ -191,6 +196,198 @@ def safety_head(image_embeds, concept_embeds, special_care_embeds, concept_thres
     return has, cs, ss
 
 
+CLIP_IMAGE_MEAN = (0.48145466, 0.4578275, 0.40821073)
+CLIP_IMAGE_STD = (0.26862954, 0.26130258, 0.27577711)
+PIL_BICUBIC = 3                                       # PIL.Image.BICUBIC, the `resample` of the shipped preprocessor_config.json
+# (dtype is uint8, layout, value_range) -> SDMI_FE_SRC_*
+_FE_KINDS = {(True, 'NHWC', None): 0, (False, 'NHWC', (0.0, 1.0)): 1, (False, 'NCHW', (0.0, 1.0)): 2, (False, 'NCHW', (-1.0, 1.0)): 3}
+
+
+def _fe_int(v, keys, what):
+    """`size` / `crop_size` as transformers writes them: an int, or a dict ({'shortest_edge': n} / {'height': n, 'width': n})"""
+    if isinstance(v, dict):
+        vals = {int(v[k]) for k in keys if k in v}
+        if len(vals) != 1:
+            raise NotImplementedError(f'CLIPFeatureExtractorHIP: {what}={v!r} is not supported (one number: {" / ".join(keys)})')
+        return vals.pop()
+    return int(v)
+
+
+class FeatureBatch(dict):
+    """What the extractor returns: `.pixel_values`, also by key (transformers' BatchFeature, as far as the scripts use it)."""
+
+    def __getattr__(self, name):
+        try:
+            return self[name]
+        except KeyError:
+            raise AttributeError(name) from None
+
+    def to(self, *a, **k):
+        return FeatureBatch({key: (v.to(*a, **k) if torch.is_tensor(v) else v) for key, v in self.items()})
+
+
+class CLIPFeatureExtractorHIP:
+    """transformers' CLIPFeatureExtractor / CLIPImageProcessor of the safety checker (scripts/txt2img.py:26-29, 88-90) on the MI355X: numpy_to_pil's
+    uint8 conversion, PIL's bicubic resize of the shortest side to `size`, the centre crop to `crop_size`, / 255, mean / std -- two launches of
+    `sdmi_k_clip_feature_extract`, the resized uint8 image bit-equal to PIL's.  `__call__(images, return_tensors='pt')` -> an object with
+    `.pixel_values`, a device fp32 [B, 3, crop, crop] tensor.  `images`:
+
+      * a device tensor, [B, ...] or one image: uint8 [H, W, 3]; or float, by `layout` ('NHWC', the default: the script's x_image; or 'NCHW')
+        and `value_range` ((0, 1), the default; or (-1, 1) with 'NCHW': the raw decode_first_stage output, clamp((x + 1) / 2, 0, 1) applied
+        inside).  Values outside the range are clamped.
+      * a uint8 numpy array [H, W, 3] / [B, H, W, 3], or a list of PIL RGB images / uint8 arrays: uploaded as uint8 in one copy per image size.
+
+    Bicubic, RGB and crop_size <= size only; everything else is refused by name.  A CPU float tensor is refused: there is no CPU path."""
+
+    model_input_names = ['pixel_values']
+
+    def __init__(self, size=224, crop_size=224, image_mean=CLIP_IMAGE_MEAN, image_std=CLIP_IMAGE_STD, resample=PIL_BICUBIC, do_resize=True,
+                 do_center_crop=True, do_normalize=True, do_rescale=True, rescale_factor=1 / 255, device=None):
+        if int(resample) != PIL_BICUBIC:
+            raise NotImplementedError(f'CLIPFeatureExtractorHIP: resample={resample!r} is not built (bicubic, PIL.Image.BICUBIC = 3, only)')
+        for name, v in (('do_resize', do_resize), ('do_center_crop', do_center_crop), ('do_normalize', do_normalize), ('do_rescale', do_rescale)):
+            if not v:
+                raise NotImplementedError(f'CLIPFeatureExtractorHIP: {name}=False is not built (resize, centre crop, / 255 and normalise always run)')
+        if abs(float(rescale_factor) - 1 / 255) > 1e-12:
+            raise NotImplementedError(f'CLIPFeatureExtractorHIP: rescale_factor={rescale_factor!r} is not built (1 / 255 only)')
+        self.size = _fe_int(size, ('shortest_edge',), 'size')
+        self.crop_size = _fe_int(crop_size, ('height', 'width'), 'crop_size')
+        if self.size < 1 or self.crop_size < 1:
+            raise ValueError('CLIPFeatureExtractorHIP: size and crop_size must be at least 1')
+        if self.crop_size > self.size:
+            raise NotImplementedError(f'CLIPFeatureExtractorHIP: crop_size > size ({self.crop_size} > {self.size}) is not built '
+                                      '(the processor would pad the image)')
+        self.image_mean, self.image_std = tuple(float(v) for v in image_mean), tuple(float(v) for v in image_std)
+        if len(self.image_mean) != 3 or len(self.image_std) != 3:
+            raise NotImplementedError('CLIPFeatureExtractorHIP: a channel count other than 3 (RGB images only)')
+        self.resample = PIL_BICUBIC
+        self.device = device
+        self._mean = (C.c_float * 3)(*self.image_mean)
+        self._std = (C.c_float * 3)(*self.image_std)
+        self._tables = {}
+
+    @classmethod
+    def from_pretrained(cls, local_dir, **kwargs):
+        """A LOCAL directory holding preprocessor_config.json; never reaches for a hub."""
+        path = os.path.join(local_dir, 'preprocessor_config.json')
+        if not os.path.isdir(local_dir) or not os.path.exists(path):
+            raise FileNotFoundError(f'{local_dir!r}: no local preprocessor_config.json (CLIPFeatureExtractorHIP.from_pretrained loads local '
+                                    'files only; nothing is downloaded)')
+        with open(path) as f:
+            cfg = json.load(f)
+        known = ('size', 'crop_size', 'image_mean', 'image_std', 'resample', 'do_resize', 'do_center_crop', 'do_normalize', 'do_rescale',
+                 'rescale_factor')
+        args = {k: cfg[k] for k in known if cfg.get(k) is not None}
+        args.update(kwargs)
+        return cls(**args)
+
+    def output_size(self, H, W):
+        """(rh, rw) of the resize: the shortest side becomes `size`, the other int(size * long / short)"""
+        rh, rw = C.c_int(), C.c_int()
+        _lib.check(_lib.load().sdmi_fe_output_size(int(H), int(W), self.size, C.byref(rh), C.byref(rw)))
+        return rh.value, rw.value
+
+    def tables(self, H, W):
+        """Host tables of an (H, W) image, numpy int32: {'h': (ksize, bounds [rw, 2], kk [rw, ksize]) or None, 'v': ... or None}; an axis
+        that keeps its size has none.  No GPU involved."""
+        lib = _lib.load()
+        rh, rw = self.output_size(H, W)
+        out = {}
+        for name, n_in, n_out in (('h', W, rw), ('v', H, rh)):
+            if n_in == n_out:
+                out[name] = None
+                continue
+            ks = lib.sdmi_fe_ksize(n_in, n_out)
+            if ks < 0:
+                _lib.check(-1)
+            bounds, kk = np.empty((n_out, 2), np.int32), np.empty((n_out, ks), np.int32)
+            _lib.check(lib.sdmi_fe_coeffs(n_in, n_out, bounds.ctypes.data, kk.ctypes.data))
+            out[name] = (ks, bounds, kk)
+        return out
+
+    def _device_tables(self, H, W, device):
+        key = (H, W, str(device))
+        t = self._tables.get(key)
+        if t is None:               # one upload per image size and device; the entries are never written again
+            t = {name: (None if v is None else (v[0], torch.from_numpy(v[1]).to(device), torch.from_numpy(v[2]).to(device)))
+                 for name, v in self.tables(H, W).items()}
+            self._tables[key] = t
+        return t
+
+    @torch.no_grad()
+    def extract(self, x, layout='NHWC', value_range=(0, 1), return_uint8=False):
+        """One device batch of equal-sized images -> pixel_values (and the resized, cropped uint8 image [B, crop, crop, 3])."""
+        if not torch.is_tensor(x) or not x.is_cuda:
+            raise RuntimeError('CLIPFeatureExtractorHIP runs on MI355X device tensors only (no CPU fallback)')
+        is_u8 = x.dtype == torch.uint8
+        if not is_u8 and not x.is_floating_point():
+            raise TypeError(f'CLIPFeatureExtractorHIP: images must be uint8 or float, got {x.dtype}')
+        kind = _FE_KINDS.get((is_u8, layout, None if is_u8 else tuple(float(v) for v in value_range)))
+        if kind is None:
+            raise NotImplementedError(f'CLIPFeatureExtractorHIP: dtype {x.dtype} with layout={layout!r}, value_range={value_range!r} is not a '
+                                      "source kind (uint8 'NHWC'; float 'NHWC' (0, 1); float 'NCHW' (0, 1) or (-1, 1))")
+        if x.dim() == 3:
+            x = x[None]
+        if x.dim() != 4:
+            raise ValueError(f'CLIPFeatureExtractorHIP: images must be [B, H, W, 3] or [B, 3, H, W], got {tuple(x.shape)}')
+        x = (x if is_u8 else x.detach().float()).contiguous()
+        B, (H, W, Cc) = x.shape[0], ((x.shape[1], x.shape[2], x.shape[3]) if layout == 'NHWC' else (x.shape[2], x.shape[3], x.shape[1]))
+        lib = _lib.load()
+        S, Cr = self.size, self.crop_size
+        t = self._device_tables(H, W, x.device) if Cc == 3 else {'h': None, 'v': None}       # (C != 3: the library refuses it by name)
+        need = lib.sdmi_fe_workspace_bytes(B, H, W, S, Cr)
+        if need < 0:
+            _lib.check(-1)
+        ws = torch.empty(max(int(need), 1), dtype=torch.uint8, device=x.device)
+        pv = torch.empty((B, 3, Cr, Cr), dtype=torch.float32, device=x.device)
+        u8 = torch.empty((B, Cr, Cr, 3), dtype=torch.uint8, device=x.device) if return_uint8 else None
+        hks, hb, hk = t['h'] or (0, None, None)
+        vks, vb, vk = t['v'] or (0, None, None)
+        _lib.check(lib.sdmi_k_clip_feature_extract(x.data_ptr(), kind, B, Cc, H, W, S, Cr, _lib.ptr(hb), _lib.ptr(hk), hks, _lib.ptr(vb), _lib.ptr(vk),
+                                                   vks, self._mean, self._std, ws.data_ptr(), ws.numel(), pv.data_ptr(), _lib.ptr(u8),
+                                                   _lib.stream_ptr()))
+        return (pv, u8) if return_uint8 else pv
+
+    def _upload_groups(self, arrays):
+        """uint8 host images -> [(indices, device batch)] with one upload per image size"""
+        dev = self.device if self.device is not None else 'cuda'
+        groups = {}
+        for i, a in enumerate(arrays):
+            if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3:
+                raise NotImplementedError(f'CLIPFeatureExtractorHIP: host images must be uint8 RGB [H, W, 3], got {a.dtype} {a.shape}')
+            groups.setdefault(a.shape, []).append(i)
+        return [(idx, torch.from_numpy(np.stack([arrays[i] for i in idx])).to(dev)) for idx in groups.values()]
+
+    def __call__(self, images, return_tensors='pt', layout='NHWC', value_range=(0, 1)):
+        if return_tensors != 'pt':
+            raise NotImplementedError(f"CLIPFeatureExtractorHIP: return_tensors={return_tensors!r} is not built ('pt' only)")
+        if torch.is_tensor(images):
+            return FeatureBatch(pixel_values=self.extract(images, layout, value_range))
+        if isinstance(images, np.ndarray):
+            if images.dtype != np.uint8:
+                raise RuntimeError('CLIPFeatureExtractorHIP: a host float image has no path here (no CPU fallback); pass uint8, or a device tensor')
+            arrays = [images] if images.ndim == 3 else list(images)
+        else:
+            arrays = []
+            for im in (images if isinstance(images, (list, tuple)) else [images]):
+                if torch.is_tensor(im):
+                    raise NotImplementedError('CLIPFeatureExtractorHIP: a list of tensors is not a source kind (stack them into one device tensor)')
+                if not isinstance(im, np.ndarray):          # a PIL image
+                    if getattr(im, 'mode', 'RGB') != 'RGB':
+                        raise NotImplementedError(f'CLIPFeatureExtractorHIP: image mode {im.mode!r} is not built (RGB only)')
+                    im = np.asarray(im)
+                arrays.append(im)
+        if not arrays:
+            raise ValueError('CLIPFeatureExtractorHIP: no images')
+        groups = self._upload_groups(arrays)
+        if len(groups) == 1:
+            return FeatureBatch(pixel_values=self.extract(groups[0][1]))
+        pv = torch.empty((len(arrays), 3, self.crop_size, self.crop_size), dtype=torch.float32, device=groups[0][1].device)
+        for idx, batch in groups:
+            pv[torch.tensor(idx, device=pv.device)] = self.extract(batch)
+        return FeatureBatch(pixel_values=pv)
+
+
 def _read_checkpoint(local_dir):
     """state dict of a local `model.safetensors` or `pytorch_model.bin`; local files only"""
     st = os.path.join(local_dir, 'model.safetensors')
@@ -265,6 +462,32 @@ class StableDiffusionSafetyCheckerHIP(nn.Module):
             if flagged:
                 images[i] = torch.zeros_like(images[i]) if torch.is_tensor(images[i]) else np.zeros(images[i].shape)   # (the checker's black image)
         return images, has_nsfw_concepts
+
+    @torch.no_grad()
+    def check_images(self, x, extractor=None, layout='NHWC', value_range=(0, 1)):
+        """scripts/txt2img.py:check_safety without the image leaving the GPU: device images of any source kind of CLIPFeatureExtractorHIP
+        (`layout` / `value_range` as there) -> the extractor, the tower, the head.  Flagged images are zeroed in place on the device; returns
+        (x, has_nsfw_concepts) as `forward(clip_input=extractor(x).pixel_values, images=x)` does -- the same launches -- with one small
+        device-to-host copy, of the flags."""
+        S = self._tower[0]._cfg.image_size
+        if extractor is None:
+            if getattr(self, '_extractor', None) is None:
+                self._extractor = CLIPFeatureExtractorHIP(size=S, crop_size=S)
+            extractor = self._extractor
+        if extractor.crop_size != S:
+            raise ValueError(f"check_images: the extractor's crop_size {extractor.crop_size} differs from the tower's image_size {S}")
+        dev = self.concept_embeds.device
+        if dev.type != 'cuda':
+            raise RuntimeError('StableDiffusionSafetyCheckerHIP parameters must live on the GPU (call .cuda() first); there is no CPU implementation')
+        if not torch.is_tensor(x) or not x.is_cuda or x.dim() != 4:
+            raise RuntimeError('check_images takes one device batch [B, H, W, 3] / [B, 3, H, W] (no CPU fallback)')
+        embeds = self._tower[0](extractor.extract(x, layout, value_range))[0]
+        has, cs, ss = safety_head(embeds, self.concept_embeds.detach().float().contiguous(), self.special_care_embeds.detach().float().contiguous(),
+                                  self.concept_embeds_weights.detach().float().contiguous(),
+                                  self.special_care_embeds_weights.detach().float().contiguous())
+        self.last_scores = dict(concept_scores=cs, special_scores=ss)
+        x.masked_fill_((has != 0).view(-1, 1, 1, 1), 0)               # (the checker's black image)
+        return x, [bool(v) for v in has.cpu().tolist()]
 
 
 # ---- OpenAI `clip` naming -> transformers naming ----------------------------------------------------------------------------------------

@@ -91,7 +91,7 @@ def _warn(msg):
     print('\n' + '!' * 100 + f'\n!! run_reference_script: {msg}\n' + '!' * 100 + '\n', file=sys.stderr, flush=True)
 
 
-def install_stubs(have_gpu, offline_stubs=False, real_ckpt=False, hip_safety=None):
+def install_stubs(have_gpu, offline_stubs=False, real_ckpt=False, hip_safety=None, hip_feature_extractor=None):
     import yaml
     import transformers          # before the stand-ins: it probes optional packages (torchvision, ...) via find_spec
 
@@ -257,7 +257,18 @@ def install_stubs(have_gpu, offline_stubs=False, real_ckpt=False, hip_safety=Non
                                           num_attention_heads=12, max_position_embeddings=77, hidden_act='quick_gelu')
         torch.manual_seed(1234)
         return transformers.CLIPTextModel(cfg)
-    _try_real('AutoFeatureExtractor', 'the safety feature extractor', _FeatureExtractor)
+    if hip_feature_extractor:
+        # --hip-feature-extractor: CLIPFeatureExtractorHIP where the reference builds the checker's extractor (scripts/txt2img.py:28)
+        def _hip_feature_extractor_from_pretrained(cls, *a, **k):
+            from stable_diffusion_amd.vision import CLIPFeatureExtractorHIP
+            if hip_feature_extractor != 'default' and os.path.exists(os.path.join(hip_feature_extractor, 'preprocessor_config.json')):
+                print(f'run_reference_script: feature extractor = CLIPFeatureExtractorHIP.from_pretrained({hip_feature_extractor!r})', flush=True)
+                return CLIPFeatureExtractorHIP.from_pretrained(hip_feature_extractor)
+            print('run_reference_script: feature extractor = CLIPFeatureExtractorHIP() (size 224, crop 224, CLIP mean / std)', flush=True)
+            return CLIPFeatureExtractorHIP()
+        transformers.AutoFeatureExtractor.from_pretrained = classmethod(_hip_feature_extractor_from_pretrained)
+    else:
+        _try_real('AutoFeatureExtractor', 'the safety feature extractor', _FeatureExtractor)
     _try_real('CLIPTokenizer', 'the CLIP tokenizer', _Tokenizer)
     _try_real('CLIPTextModel', 'the CLIP text model weights', _clip_text)
 
@@ -457,6 +468,10 @@ def main():
                          'Off by default.')
     ap.add_argument('--hip-safety-dir', default=None, metavar='DIR',
                     help='a local copy of the shipped checker (config.json + model.safetensors / pytorch_model.bin); implies --hip-safety')
+    ap.add_argument('--hip-feature-extractor', action='store_true',
+                    help="CLIPFeatureExtractorHIP in place of the safety checker's feature extractor (needs the MI355X).  Its configuration comes "
+                         'from --hip-safety-dir when that directory holds a preprocessor_config.json; otherwise size 224, crop 224 and '
+                         "CLIP's mean / std.  Off by default.")
     ap.add_argument('script', choices=['txt2img', 'img2img'])
     ap.add_argument('rest', nargs=argparse.REMAINDER)
     args = ap.parse_args()
@@ -492,7 +507,10 @@ def main():
     hip_safety = args.hip_safety_dir or ('synthetic' if args.hip_safety else None)
     if hip_safety and not have_gpu:
         raise SystemExit('--hip-safety needs the MI355X (the HIP path has no CPU fallback)')
-    install_stubs(have_gpu, offline_stubs=args.offline_stubs, real_ckpt=real_ckpt, hip_safety=hip_safety)
+    hip_fe = (args.hip_safety_dir or 'default') if args.hip_feature_extractor else None
+    if hip_fe and not have_gpu:
+        raise SystemExit('--hip-feature-extractor needs the MI355X (the HIP path has no CPU fallback)')
+    install_stubs(have_gpu, offline_stubs=args.offline_stubs, real_ckpt=real_ckpt, hip_safety=hip_safety, hip_feature_extractor=hip_fe)
     patch_torch_load()
 
     import ldm.models.diffusion.ddim as ddim
