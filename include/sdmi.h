@@ -186,6 +186,34 @@ int sdmi_sampler_step_x0(const float* eps_model, int cfg, float scale, const flo
 int sdmi_sampler_step_from_x0(const float* pred_x0, const float* ep, float a_prev, float sigma, const float* noise, float* x_prev,
                               int64_t n, void* stream);
 
+/* ---- the same step for rows at different steps of different schedules: one launch for up to SDMI_SAMPLER_MAX_SLOTS latents -----------
+ * What lets requests that arrive one after another share a UNet call (SamplerPoolHIP): each slot is one latent of n elements with its
+ * own table entries, history and destinations.  Per slot the arithmetic is sdmi_sampler_step's, op for op, and the host scalars come
+ * from the same code: e_t_out, pred_x0 and x_prev are the bits of a lone sdmi_sampler_step call with the slot's arguments.
+ *   eps_u, eps_c     two rows of the UNet output; cfg == 0: eps_u alone is read
+ *   x, old0..old2, noise, scale, mode, a_t, a_prev, sigma, sqrt_1m_at: as sdmi_sampler_step
+ *   outputs, each optional (at least one): e_t_out; x_state_out (x_prev; may be x itself); pred_x0; unet_dst0 / unet_dst1 (the same
+ *     x_prev, written where the NEXT UNet call reads this slot's row(s): a guided slot feeds an unconditional and a conditional row);
+ *     t_dst0 / t_dst1 receive t_next, the slot's entry in the next call's int64 timestep tensor
+ * A slot whose pointers are all 16-byte aligned, with n % 4 == 0, is moved 16 bytes per lane, any other one element by element.
+ * The first PLMS step is two slot operations, one per UNet call: mode 0 writing e_t_out and unet_dst* only, then mode 4 with old0 = that
+ * e_t.  Additive: no existing struct or call changes, SDMI_ABI_VERSION stays as it is.
+ * Refused before anything is launched: n_slots > SDMI_SAMPLER_MAX_SLOTS, n <= 0, a missing pointer, a mode outside 0..4, missing history. */
+#define SDMI_SAMPLER_MAX_SLOTS 8
+typedef struct sdmi_sampler_slot {
+  const float* eps_u; const float* eps_c; const float* x;
+  const float* old0; const float* old1; const float* old2;
+  const float* noise;
+  float* e_t_out; float* x_state_out; float* pred_x0;
+  float* unet_dst0; float* unet_dst1;
+  int64_t* t_dst0; int64_t* t_dst1;
+  int64_t t_next;
+  int32_t cfg; int32_t mode;
+  float scale; float a_t; float a_prev; float sigma; float sqrt_1m_at;
+  int32_t reserved;                 /* 0 */
+} sdmi_sampler_slot;                /* 152 bytes */
+int sdmi_sampler_step_rows(const sdmi_sampler_slot* slots, int n_slots, int64_t n, void* stream);
+
 /* ---- ancestral DDPM step: LatentDiffusion.p_mean_variance + p_sample (ddpm.py:1047-1107) and the mask blend of p_sample_loop /
  * progressive_denoising (:1203-1205, :1154-1157) in one launch; fp32, each op rounded on its own in the reference's order:
  *   x0 = c_recip x - c_recipm1 eps;  clip != 0: x0 = clamp(x0, -1, 1) (a NaN stays NaN);  mean = coef1 x0 + coef2 x;

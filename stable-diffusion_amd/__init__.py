@@ -8,6 +8,7 @@ this package is the host-side mirror of the reference's interfaces for that path
     DDIMSamplerHIP    <- ldm.models.diffusion.ddim.DDIMSampler
     DPMSolverSamplerHIP <- ldm.models.diffusion.dpm_solver.sampler.DPMSolverSampler
     DPMSolverHIP      <- ldm.models.diffusion.dpm_solver.dpm_solver.DPM_Solver (every method, order, skip type and solver type)
+    SamplerPoolHIP    <- no counterpart: DDIM / PLMS requests that arrive one after another share UNet calls (sampler_pool.py)
     DDPMSamplerHIP    <- LatentDiffusion.p_sample_loop / progressive_denoising (scripts/sample_diffusion.py --vanilla_sample)
     AutoencoderKLHIP  <- ldm.models.autoencoder.AutoencoderKL (decode / encode)
     VQModelInterfaceHIP <- ldm.models.autoencoder.VQModelInterface (the latent-inpainting model's first stage)
@@ -28,6 +29,7 @@ Importable as `stable_diffusion_amd` (see stable_diffusion_amd.py at the repo ro
 from . import _lib  # noqa: F401
 from .unet import UNetModelHIP  # noqa: F401
 from .samplers import PLMSSamplerHIP, DDIMSamplerHIP, DPMSolverSamplerHIP, DDPMSamplerHIP, DPMSolverHIP  # noqa: F401
+from .sampler_pool import SamplerPoolHIP, plan_calls  # noqa: F401
 from .vae import AutoencoderKLHIP, VQModelInterfaceHIP  # noqa: F401
 from .clip import FrozenCLIPEmbedderHIP, FrozenCLIPTextEmbedderHIP  # noqa: F401
 from .bert import BERTEmbedderHIP  # noqa: F401
@@ -40,4 +42,4 @@ from .vision import CLIPVisionHIP, StableDiffusionSafetyCheckerHIP, FrozenClipIm
 from .retrieval import SearcherHIP  # noqa: F401
 from . import debug, postprocess  # noqa: F401
 
-__all__ = ['UNetModelHIP', 'AutoencoderKLHIP', 'VQModelInterfaceHIP', 'FrozenCLIPEmbedderHIP', 'BERTEmbedderHIP', 'ClassEmbedderHIP', 'PLMSSamplerHIP', 'DDIMSamplerHIP', 'DPMSolverSamplerHIP', 'DPMSolverHIP', 'DDPMSamplerHIP', 'LatentDiffusionHIP', 'DiffusionWrapperHIP', 'SuperResolutionHIP', 'SpatialRescalerHIP', 'SemanticSynthesisHIP', 'CLIPVisionHIP', 'StableDiffusionSafetyCheckerHIP', 'FrozenClipImageEmbedderHIP', 'FrozenCLIPTextEmbedderHIP', 'SearcherHIP']
+__all__ = ['UNetModelHIP', 'AutoencoderKLHIP', 'VQModelInterfaceHIP', 'FrozenCLIPEmbedderHIP', 'BERTEmbedderHIP', 'ClassEmbedderHIP', 'PLMSSamplerHIP', 'DDIMSamplerHIP', 'DPMSolverSamplerHIP', 'DPMSolverHIP', 'DDPMSamplerHIP', 'SamplerPoolHIP', 'LatentDiffusionHIP', 'DiffusionWrapperHIP', 'SuperResolutionHIP', 'SpatialRescalerHIP', 'SemanticSynthesisHIP', 'CLIPVisionHIP', 'StableDiffusionSafetyCheckerHIP', 'FrozenClipImageEmbedderHIP', 'FrozenCLIPTextEmbedderHIP', 'SearcherHIP']

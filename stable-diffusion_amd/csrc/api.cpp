@@ -12,6 +12,7 @@
 #include "rescale.h"
 #include "fe_coeffs.h"
 #include "feature_extractor.h"
+#include "sampler_rows.h"
 
 namespace sdmi {
 static thread_local std::string g_err;
@@ -179,6 +180,10 @@ int sdmi_sampler_step_x0(const float* eps_model, int cfg, float scale, const flo
 int sdmi_sampler_step_from_x0(const float* pred_x0, const float* ep, float a_prev, float sigma, const float* noise, float* x_prev,
                               int64_t n, void* stream) {
   return launch_sampler_step_from_x0(pred_x0, ep, a_prev, sigma, noise, x_prev, n, (hipStream_t)stream);
+}
+
+int sdmi_sampler_step_rows(const sdmi_sampler_slot* slots, int n_slots, int64_t n, void* stream) {
+  return launch_sampler_step_rows(slots, n_slots, n, (hipStream_t)stream);
 }
 
 int sdmi_ddpm_step(const float* eps, const float* x0_in, const float* x, float c_recip, float c_recipm1, int clip, float coef1,

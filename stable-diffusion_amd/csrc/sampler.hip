@@ -7,6 +7,7 @@
 // the PLMS / DDIM step split at pred_x0 for quantize_x0.
 #include "common.h"
 #include "prof.h"
+#include "sampler_rows.h"
 #include <math.h>
 
 // every product / sum below must round on its own, exactly like the reference's separate torch ops
@@ -15,48 +16,72 @@
 namespace sdmi {
 namespace {
 
+// plms.py:201-213, ddim.py:189-199: a_t.sqrt(), a_prev.sqrt(), (1 - a_prev - sigma_t**2).sqrt() -- fp32 tensor ops there, the host's
+// fp32 ops here; the one place every launcher of the step takes them from
+struct StepScalars { float sqrt_at, sqrt_aprev, dir_coef; };
+inline StepScalars step_scalars(float a_t, float a_prev, float sigma) {
+  return {sqrtf(a_t), sqrtf(a_prev), sqrtf((1.0f - a_prev) - sigma * sigma)};
+}
+
+// The arithmetic of one element, shared by every kernel of the step (the whole launch, its two halves, the per-slot launch): each helper
+// is one expression of the reference, op by op.
+__device__ __forceinline__ float cfg_combine(float eu, float ec, float scale) {
+#pragma clang fp contract(off)
+  const float d = ec - eu;
+  const float sd = scale * d;
+  return eu + sd;                                    // e_u + s * (e_c - e_u)
+}
+
+__device__ __forceinline__ float multistep_eps(int mode, float e_t, float o0, float o1, float o2) {
+#pragma clang fp contract(off)
+  switch (mode) {
+    case 1: { const float a = 3.f * e_t; const float b = a - o0; return b / 2.f; }
+    case 2: {
+      const float a = 23.f * e_t, b = 16.f * o0, c = 5.f * o1;
+      const float ab = a - b; const float abc = ab + c; return abc / 12.f;
+    }
+    case 3: {
+      const float a = 55.f * e_t, b = 59.f * o0, c = 37.f * o1, d = 9.f * o2;
+      const float ab = a - b; const float abc = ab + c; const float abcd = abc - d; return abcd / 24.f;
+    }
+    case 4: { const float a = o0 + e_t; return a / 2.f; }
+    default: return e_t;
+  }
+}
+
+__device__ __forceinline__ float pred_x0_of(float x, float ep, float sqrt_1m_at, float sqrt_at) {
+#pragma clang fp contract(off)
+  const float t1 = sqrt_1m_at * ep;
+  const float t2 = x - t1;
+  return t2 / sqrt_at;
+}
+
+// nz: sigma * noise, or 0 without noise
+__device__ __forceinline__ float x_prev_of(float pred, float ep, float sqrt_aprev, float dir_coef, float nz) {
+#pragma clang fp contract(off)
+  const float t3 = sqrt_aprev * pred;
+  const float t4 = dir_coef * ep;
+  const float xp = t3 + t4;
+  return xp + nz;
+}
+
 __global__ void __launch_bounds__(256) sampler_step_kernel(SamplerStepParams p, float sqrt_at, float sqrt_aprev,
                                                            float dir_coef) {
 #pragma clang fp contract(off)
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= p.n) return;
-  float e_t;
-  if (p.cfg) {
-    const float eu = p.eps_model[i], ec = p.eps_model[p.n + i];
-    const float d = ec - eu;
-    const float sd = p.scale * d;
-    e_t = eu + sd;                                   // e_u + s * (e_c - e_u)
-  } else {
-    e_t = p.eps_model[i];
-  }
+  const float e_t = p.cfg ? cfg_combine(p.eps_model[i], p.eps_model[p.n + i], p.scale) : p.eps_model[i];
   if (p.e_t_out) p.e_t_out[i] = e_t;
-  float ep;
-  switch (p.mode) {
-    case 1: { const float a = 3.f * e_t; const float b = a - p.old0[i]; ep = b / 2.f; break; }
-    case 2: {
-      const float a = 23.f * e_t, b = 16.f * p.old0[i], c = 5.f * p.old1[i];
-      const float ab = a - b; const float abc = ab + c; ep = abc / 12.f; break;
-    }
-    case 3: {
-      const float a = 55.f * e_t, b = 59.f * p.old0[i], c = 37.f * p.old1[i], d = 9.f * p.old2[i];
-      const float ab = a - b; const float abc = ab + c; const float abcd = abc - d; ep = abcd / 24.f; break;
-    }
-    case 4: { const float a = p.old0[i] + e_t; ep = a / 2.f; break; }
-    default: ep = e_t; break;
-  }
+  const float o0 = p.mode != 0 ? p.old0[i] : 0.f;
+  const float o1 = p.mode == 2 || p.mode == 3 ? p.old1[i] : 0.f;
+  const float o2 = p.mode == 3 ? p.old2[i] : 0.f;
+  const float ep = multistep_eps(p.mode, e_t, o0, o1, o2);
   if (p.ep_out) p.ep_out[i] = ep;
-  const float x = p.x[i];
-  const float t1 = p.sqrt_1m_at * ep;
-  const float t2 = x - t1;
-  const float pred = t2 / sqrt_at;
+  const float pred = pred_x0_of(p.x[i], ep, p.sqrt_1m_at, sqrt_at);
   if (p.pred_x0) p.pred_x0[i] = pred;
   if (!p.x_prev) return;                             // first half of the split step: a quantizer runs on pred_x0 next
-  const float t3 = sqrt_aprev * pred;
-  const float t4 = dir_coef * ep;
-  float xp = t3 + t4;
   const float nz = p.noise ? p.sigma * p.noise[i] : 0.f;
-  xp = xp + nz;
-  p.x_prev[i] = xp;
+  p.x_prev[i] = x_prev_of(pred, ep, sqrt_aprev, dir_coef, nz);
 }
 
 // Second half of the split PLMS / DDIM step (quantize_x0: ddim.py:195-204, plms.py:207-216): from a given pred_x0 -- the codebook rows
@@ -68,12 +93,87 @@ __global__ void __launch_bounds__(256) sampler_step_from_x0_kernel(const float* 
 #pragma clang fp contract(off)
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const float t3 = sqrt_aprev * pred_x0[i];
-  const float t4 = dir_coef * ep[i];
-  float xp = t3 + t4;
   const float nz = noise ? sigma * noise[i] : 0.f;
-  xp = xp + nz;
-  x_prev[i] = xp;
+  x_prev[i] = x_prev_of(pred_x0[i], ep[i], sqrt_aprev, dir_coef, nz);
+}
+
+// The PLMS / DDIM step of sampler_step_kernel for up to SDMI_SAMPLER_MAX_SLOTS independent latents in one launch: rows of one UNet call
+// that stand at different steps of different schedules (sdmi_sampler_step_rows).  blockIdx.y selects the slot, so every field of its
+// descriptor is wave-uniform and comes out of the kernel arguments with scalar loads; there is no device-side table.  A slot whose
+// pointers are all 16-byte aligned, with n % 4 == 0, moves four elements per lane (`vec`, decided on the host), any other one.
+// At 16 K floats per slot this is launch- and latency-bound: no LDS, no atomics, nothing staged.
+struct RowSlot {
+  sdmi_sampler_slot d;
+  float sqrt_at, sqrt_aprev, dir_coef;               // step_scalars() of the slot's table entries
+  int vec;
+};
+struct RowsParams {
+  RowSlot slot[SDMI_SAMPLER_MAX_SLOTS];
+  int64_t n;
+};
+
+template <int V> __device__ __forceinline__ void load_elems(const float* p, int64_t i, float (&v)[V]) {
+  if constexpr (V == 4) {
+    const float4 q = *reinterpret_cast<const float4*>(p + i);
+    v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+  } else {
+    v[0] = p[i];
+  }
+}
+
+template <int V> __device__ __forceinline__ void store_elems(float* p, int64_t i, const float (&v)[V]) {
+  if constexpr (V == 4) *reinterpret_cast<float4*>(p + i) = make_float4(v[0], v[1], v[2], v[3]);
+  else p[i] = v[0];
+}
+
+// elements [i, i + V) of one slot; every input is read before the first output is written, so x_state_out may be x
+template <int V> __device__ __forceinline__ void rows_elems(const RowSlot& r, int64_t i) {
+#pragma clang fp contract(off)
+  const sdmi_sampler_slot& d = r.d;
+  float e_t[V], x[V], o0[V] = {}, o1[V] = {}, o2[V] = {}, nz[V] = {};
+  load_elems<V>(d.eps_u, i, e_t);
+  if (d.cfg) {
+    float ec[V];
+    load_elems<V>(d.eps_c, i, ec);
+#pragma unroll
+    for (int k = 0; k < V; ++k) e_t[k] = cfg_combine(e_t[k], ec[k], d.scale);
+  }
+  if (d.mode != 0) load_elems<V>(d.old0, i, o0);
+  if (d.mode == 2 || d.mode == 3) load_elems<V>(d.old1, i, o1);
+  if (d.mode == 3) load_elems<V>(d.old2, i, o2);
+  load_elems<V>(d.x, i, x);
+  const bool want_x_prev = d.x_state_out || d.unet_dst0 || d.unet_dst1;
+  if (want_x_prev && d.noise) {
+    load_elems<V>(d.noise, i, nz);
+#pragma unroll
+    for (int k = 0; k < V; ++k) nz[k] = d.sigma * nz[k];
+  }
+  float pred[V], xp[V];
+#pragma unroll
+  for (int k = 0; k < V; ++k) {
+    const float ep = multistep_eps(d.mode, e_t[k], o0[k], o1[k], o2[k]);
+    pred[k] = pred_x0_of(x[k], ep, d.sqrt_1m_at, r.sqrt_at);
+    xp[k] = x_prev_of(pred[k], ep, r.sqrt_aprev, r.dir_coef, nz[k]);
+  }
+  if (d.e_t_out) store_elems<V>(d.e_t_out, i, e_t);
+  if (d.pred_x0) store_elems<V>(d.pred_x0, i, pred);
+  if (d.x_state_out) store_elems<V>(d.x_state_out, i, xp);
+  if (d.unet_dst0) store_elems<V>(d.unet_dst0, i, xp);      // the slot's row(s) of the next UNet call's input
+  if (d.unet_dst1) store_elems<V>(d.unet_dst1, i, xp);
+}
+
+__global__ void __launch_bounds__(256) sampler_step_rows_kernel(RowsParams p) {
+  const RowSlot& r = p.slot[blockIdx.y];
+  const int64_t lane = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (lane == 0) {                                   // the slot's timestep in the next call's timestep tensor: one lane, plain stores
+    if (r.d.t_dst0) *r.d.t_dst0 = r.d.t_next;
+    if (r.d.t_dst1) *r.d.t_dst1 = r.d.t_next;
+  }
+  if (r.vec) {
+    if (lane * 4 < p.n) rows_elems<4>(r, lane * 4);
+  } else {
+    if (lane < p.n) rows_elems<1>(r, lane);
+  }
 }
 
 // Ancestral DDPM step: LatentDiffusion.p_mean_variance + p_sample (ldm/models/diffusion/ddpm.py:1047-1107) and the loop's mask blend
@@ -207,10 +307,9 @@ int launch_ddpm_step(const DdpmStepParams& p, hipStream_t s) {
 int launch_sampler_step_from_x0(const float* pred_x0, const float* ep, float a_prev, float sigma, const float* noise, float* x_prev,
                                 int64_t n, hipStream_t s) {
   SDMI_CHECK(n > 0 && pred_x0 && ep && x_prev, "sampler_step_from_x0: missing pointer");
-  const float sqrt_aprev = sqrtf(a_prev);                                    // (as launch_sampler_step)
-  const float dir_coef = sqrtf((1.0f - a_prev) - sigma * sigma);
+  const StepScalars c = step_scalars(1.0f, a_prev, sigma);                   // (a_t belongs to the first half)
   ProfScope ps("sampler_step_from_x0", 0.0, (double)n * 4.0 * 4.0, s);
-  SDMI_LAUNCH(sampler_step_from_x0_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, pred_x0, ep, sqrt_aprev, dir_coef, sigma,
+  SDMI_LAUNCH(sampler_step_from_x0_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, pred_x0, ep, c.sqrt_aprev, c.dir_coef, sigma,
               noise, x_prev, n);
   SDMI_HIP_OK(hipGetLastError());
   return 0;
@@ -222,13 +321,46 @@ int launch_sampler_step(const SamplerStepParams& p, hipStream_t s) {
   SDMI_CHECK(p.mode == 0 || p.old0, "sampler_step: history missing");
   SDMI_CHECK(p.mode != 2 && p.mode != 3 || p.old1, "sampler_step: history missing");
   SDMI_CHECK(p.mode != 3 || p.old2, "sampler_step: history missing");
-  // plms.py:201-213: a_t.sqrt(), a_prev.sqrt(), (1 - a_prev - sigma_t**2).sqrt()  -- fp32 tensor ops
-  const float sqrt_at = sqrtf(p.a_t);
-  const float sqrt_aprev = sqrtf(p.a_prev);
-  const float dir_coef = sqrtf((1.0f - p.a_prev) - p.sigma * p.sigma);
+  const StepScalars c = step_scalars(p.a_t, p.a_prev, p.sigma);
   ProfScope ps("sampler_step", 0.0, (double)p.n * 4.0 * 6.0, s);
-  SDMI_LAUNCH(sampler_step_kernel, dim3((unsigned)((p.n + 255) / 256)), dim3(256), 0, s, p, sqrt_at, sqrt_aprev,
-                     dir_coef);
+  SDMI_LAUNCH(sampler_step_kernel, dim3((unsigned)((p.n + 255) / 256)), dim3(256), 0, s, p, c.sqrt_at, c.sqrt_aprev,
+                     c.dir_coef);
+  SDMI_HIP_OK(hipGetLastError());
+  return 0;
+}
+
+int launch_sampler_step_rows(const sdmi_sampler_slot* slots, int n_slots, int64_t n, hipStream_t s) {
+  SDMI_CHECK(slots && n_slots >= 1, "sampler_step_rows: no slots");
+  SDMI_CHECK(n_slots <= SDMI_SAMPLER_MAX_SLOTS, "sampler_step_rows: more than SDMI_SAMPLER_MAX_SLOTS (8) slots");
+  SDMI_CHECK(n > 0 && n <= (int64_t)0x7fffffff * 256, "sampler_step_rows: n");
+  RowsParams p = RowsParams();
+  p.n = n;
+  bool all_vec = true;
+  for (int k = 0; k < n_slots; ++k) {
+    const sdmi_sampler_slot& d = slots[k];
+    const std::string at = " (slot " + std::to_string(k) + ")";
+    SDMI_CHECK(d.eps_u && d.x && (!d.cfg || d.eps_c), "sampler_step_rows: missing pointer" + at);
+    SDMI_CHECK(d.e_t_out || d.x_state_out || d.pred_x0 || d.unet_dst0 || d.unet_dst1, "sampler_step_rows: missing pointer: no output" + at);
+    SDMI_CHECK(d.mode >= 0 && d.mode <= 4, "sampler_step_rows: mode" + at);
+    SDMI_CHECK(d.mode == 0 || d.old0, "sampler_step_rows: history missing" + at);
+    SDMI_CHECK(d.mode != 2 && d.mode != 3 || d.old1, "sampler_step_rows: history missing" + at);
+    SDMI_CHECK(d.mode != 3 || d.old2, "sampler_step_rows: history missing" + at);
+    RowSlot& r = p.slot[k];
+    r.d = d;
+    r.d.reserved = 0;
+    if (!d.cfg) r.d.eps_c = nullptr;                 // (eps_u alone is read)
+    const StepScalars c = step_scalars(d.a_t, d.a_prev, d.sigma);
+    r.sqrt_at = c.sqrt_at; r.sqrt_aprev = c.sqrt_aprev; r.dir_coef = c.dir_coef;
+    const void* ptrs[] = {r.d.eps_u, r.d.eps_c, d.x, d.old0, d.old1, d.old2, d.noise, d.e_t_out, d.x_state_out, d.pred_x0, d.unet_dst0,
+                          d.unet_dst1};
+    uintptr_t bits = (uintptr_t)(n % 4);
+    for (const void* q : ptrs) bits |= (uintptr_t)q & 15;    // (a null pointer is aligned)
+    r.vec = bits == 0;
+    all_vec = all_vec && r.vec;
+  }
+  const int64_t lanes = all_vec ? n / 4 : n;         // one grid for all slots: a 16-byte slot's surplus blocks return at once
+  ProfScope ps("sampler_step_rows", 0.0, (double)n * 4.0 * 7.0 * n_slots, s);
+  SDMI_LAUNCH(sampler_step_rows_kernel, dim3((unsigned)((lanes + 255) / 256), (unsigned)n_slots), dim3(256), 0, s, p);
   SDMI_HIP_OK(hipGetLastError());
   return 0;
 }
