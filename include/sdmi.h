@@ -703,6 +703,10 @@ int sdmi_k_ln_fold_prep(const void* w_f16, int N, int K, int ldw, const float* g
  * contract (sdmi_k_igemm mode 2 into a cleared buffer, sdmi_k_split_heads kind 1 writes the pad tokens as zeros). */
 int sdmi_k_attention(const void* q, const void* k, const void* vt, void* out, int BH, int heads, int nq, int nkv,
                      int nkv_pad, int d, float scale, void* stream);
+/* The routing of sdmi_k_attention between its ring kernel and the one-pass kernel for at most 256 keys (csrc/attn_small.hip; d = 80 / 160,
+ * non-causal): the one-pass kernel's waves per workgroup (1, 2 or 4) for this shape, or 0 where the ring kernel runs.  knob = the value of
+ * SDMI_ATTN_SMALL: 0 the ring kernel everywhere, 1 the measured routing table (the default), 2 the one-pass kernel wherever it exists.  Host only. */
+int sdmi_attn_small_takes(int d, int nq, int nkv, int causal, int knob);
 /* split-fp16 attention (the full-precision mode): q / k / vt and their low halves q_lo / k_lo / vt_lo in the layouts above,
  * out / out_lo fp16 [BH/heads, nq, heads*d] = hi / lo of the fp32 result; d in {24, 32, 40, 48, 64, 80, 96, 128, 160} (csrc/attn_split16.hip)
  * or 192 .. 1024 in steps of 64 (csrc/attn_wide_split16.hip: four waves split d and sum their partial scores in a fixed order; like the

@@ -760,6 +760,7 @@ int sdmi_k_attention(const void* q, const void* k, const void* vt, void* out, in
   if (const char* e = getenv("SDMI_ATTN_NW")) a.nw = atoi(e);     // test / tuning knob
   return launch_attention(a, (hipStream_t)stream);
 }
+int sdmi_attn_small_takes(int d, int nq, int nkv, int causal, int knob) { return attn_small_takes(d, nq, nkv, causal, knob); }
 int sdmi_k_attention_split16(const void* q, const void* q_lo, const void* k, const void* k_lo, const void* vt, const void* vt_lo, void* out,
                              void* out_lo, int BH, int heads, int nq, int nkv, int nkv_pad, int d, float scale, void* stream) {
   AttnSplitParams a = AttnSplitParams();

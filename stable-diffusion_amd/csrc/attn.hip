@@ -603,6 +603,17 @@ int launch_d(const AttnParams& p, hipStream_t stream) {
   static const std::string pname_long = std::string("attn_d") + std::to_string(D) + "_self";
   static const std::string pname_short = std::string("attn_d") + std::to_string(D) + "_ctx";
   ProfScope ps((p.nkv >= 256 ? pname_long : pname_short).c_str(), 4.0 * p.BH * (double)p.nq * p.nkv * D, 2.0 * p.BH * D * (2.0 * p.nq + 2.0 * p.nkv), stream);
+  // at most 256 keys: the one-pass kernel of attn_small.hip where the routing table (attn_small_takes, below) has it ahead.
+  // SDMI_ATTN_SMALL=0 keeps the ring kernel everywhere, =2 takes the one-pass kernel wherever it is instantiated (A/B; read per launch);
+  // SDMI_ATTN_SMALL_NW=<1,2,4> overrides its waves per workgroup (tuning).  An explicit p.nw asks for the ring kernel's workgroup.
+  if constexpr (D == 80 || D == 160) {
+    const int small_env = getenv("SDMI_ATTN_SMALL") ? atoi(getenv("SDMI_ATTN_SMALL")) : 1;
+    int snw = (p.nw <= 0 || small_env == 2) ? attn_small_takes(D, p.nq, p.nkv, p.causal, small_env) : 0;
+    if (snw) {
+      if (const char* e = getenv("SDMI_ATTN_SMALL_NW")) snw = atoi(e);
+      return launch_attention_small(p, snw, stream);
+    }
+  }
   constexpr int DNS = (D > 128) ? 3 : 4;                        // LDS-DMA ring depth (D = 160: 3 x 44 KB)
   // round 6: the key range split over two 8-wave groups of ONE 16-wave workgroup (attn_dma_kernel KVS = 2): d = 40 self-attention of the
   // 64 x 64 level (an even number of 64-key tiles, 16 .. 32 of them per group: 2048 .. 4096 keys).  Same-box A/B (profiles/attn_kvsplit_r06.txt): 78.0 -> 73.9 us
@@ -648,6 +659,27 @@ int launch_d(const AttnParams& p, hipStream_t stream) {
 }
 
 }  // namespace
+
+// Routing table of the one-pass kernel (attn_small.hip).  A class (d, nq range, nkv range) is listed only where the kernel's in-situ event
+// time -- inside the UNet call, tapes on, knob 0 against knob 2 on one box -- is at least 3 % ahead of the ring kernel's, the margin and
+// method of the phase-conv rule (profiles/up_phase_ab.txt §1); the measured pairs stand beside each row (profiles/attn_small_ab.txt).
+// nw = waves per workgroup over the same head.  knob: SDMI_ATTN_SMALL (0 never, 1 the table, 2 wherever the kernel is instantiated).
+namespace {
+struct AttnSmallRule { int d, nq_lo, nq_hi, nkv_lo, nkv_hi, nw; };
+const AttnSmallRule kAttnSmallRules[] = {
+    //  d   queries      keys     nw     ring -> one-pass, us per launch in situ (SD-v1 UNet call, CFG batch 2; other nw beside it)
+    {160,    1,  256,   1,  256,  1},  // 64 x 64 latents: attn_d160_ctx (16 x 16 and 8 x 8, 64 / 77 keys) 13.30 -> 7.57 (nw 2: 8.95, nw 4: 10.99),
+                                       //   attn_d160_self (256 x 256) 15.98 -> 12.56 (14.48, 21.48); 32 x 32 latents: attn_d160_ctx (8 x 8, 4 x 4) 10.69 -> 6.90
+    { 80,    1,  256,   1,  256,  1},  // 32 x 32 latents: attn_d80_ctx (256 x 77) 9.67 -> 6.71 (7.02, 8.16), attn_d80_self (256 x 256) 11.27 -> 8.64 (9.78, 12.51)
+    { 80,  257, 1024,   1,  128,  2},  // 64 x 64 latents: attn_d80_ctx (1024 x 77) 10.50 -> 7.75 (nw 1: 7.93, nw 4: 8.65)
+};
+}  // namespace
+int attn_small_takes(int d, int nq, int nkv, int causal, int knob) {
+  if (knob == 0 || !attn_small_supported(d, nq, nkv, causal)) return 0;
+  for (const AttnSmallRule& r : kAttnSmallRules)
+    if (d == r.d && nq >= r.nq_lo && nq <= r.nq_hi && nkv >= r.nkv_lo && nkv <= r.nkv_hi) return r.nw;
+  return knob == 2 ? (nq > 256 ? 2 : 1) : 0;
+}
 
 static int launch_attention_impl(const AttnParams& p, hipStream_t stream);
 int launch_attention(const AttnParams& p, hipStream_t stream) {

@@ -398,6 +398,11 @@ struct AttnParams {
 int launch_attention(const AttnParams& p, hipStream_t stream);
 // head dims 192 .. 1024 in steps of 64, non-causal (attn_wide.hip); launch_attention dispatches to it by d
 int launch_attention_wide(const AttnParams& p, hipStream_t stream);
+// the one-pass kernel for at most 256 keys (attn_small.hip), nw = 1, 2 or 4 waves per workgroup; launch_attention routes to it by
+// attn_small_takes (attn.hip: the routing table and the SDMI_ATTN_SMALL knob)
+bool attn_small_supported(int d, int nq, int nkv, int causal);
+int launch_attention_small(const AttnParams& p, int nw, hipStream_t stream);
+int attn_small_takes(int d, int nq, int nkv, int causal, int knob);    // waves per workgroup, or 0 = the ring kernel
 
 // GroupNorm(32) (+SiLU) over fp32 NHWC, channel-concat of two sources, fp16 or fp32 output
 struct GroupNormParams {
