@@ -214,6 +214,44 @@ typedef struct sdmi_sampler_slot {
 } sdmi_sampler_slot;                /* 152 bytes */
 int sdmi_sampler_step_rows(const sdmi_sampler_slot* slots, int n_slots, int64_t n, void* stream);
 
+/* ---- one launch for up to SDMI_SAMPLER_MAX_SLOTS latents of two kinds: that step, or one evaluation of a DPM-Solver plan -----------------
+ * What lets DPM-Solver requests share UNet calls with one another and with PLMS / DDIM requests (SamplerPoolHIP(timesteps='float32')):
+ * the next call's timestep tensor is fp32 -- sdmi_unet_forward embeds (float)t_i64[b] or t_f32[b], the same bits for an integer t.
+ *   kind 0   the PLMS / DDIM step: eps_u, eps_c, cfg, scale, x, mode, old0..old2, noise, a_t, a_prev, sigma, sqrt_1m_at, e_t_out, pred_x0,
+ *            x_state_out, unet_dst0 / 1 exactly as in sdmi_sampler_slot, the same arithmetic from the same code: the bits of
+ *            sdmi_sampler_step_rows with these fields.  The fields of kind 1 are ignored.
+ *   kind 1   one model evaluation of a DPMPlan and the update that follows it (sdmi_dpm_model_value, then sdmi_dpm_update):
+ *            e = eps_u, or with cfg eps_u + scale (eps_c - eps_u);  m = e, or with data_prediction (x - sigma_t e) / alpha_t, x being the
+ *            latent the model was evaluated at;  m_out (optional) receives m.
+ *            form 0..3: the update of that form over x_base, m0, m1, m2 and c9[9], as sdmi_dpm_update defines them; m_self is a mask of
+ *            the operands that ARE the m just computed (bit j: m_j) -- they come from registers and their pointers are not read.
+ *            form -1: no update (the last evaluation of denoise_to_zero); the slot's result is m.
+ *            x_state_out (may be x_base or x) and unet_dst0 / 1 receive the result.  The fields of kind 0 are ignored.
+ *   both     tf_dst0 / tf_dst1 receive t_next, the slot's entry in the next call's fp32 timestep tensor: a kind 0 slot's integer timestep
+ *            as float (exact below 2^24), a kind 1 slot's next model-input time.  At least one output other than tf_dst* is required.
+ * Every input of a slot is read before its first output is written.  A slot whose pointers are all 16-byte aligned, with n % 4 == 0, is
+ * moved 16 bytes per lane, any other one element by element.  There is no thresholding inside a slot: its per-sample quantile sits
+ * between the model value and the update.  Additive: no existing struct or call changes, SDMI_ABI_VERSION stays as it is.
+ * Refused before anything is launched: n_slots > SDMI_SAMPLER_MAX_SLOTS, n <= 0, a kind other than 0 / 1, a missing pointer the kind /
+ * form needs, a mode outside 0..4, missing history, a form outside -1..3, an m_self bit on an operand the form does not read. */
+typedef struct sdmi_sampler_plan_slot {
+  const float* eps_u; const float* eps_c; const float* x;
+  const float* old0; const float* old1; const float* old2; const float* noise;     /* kind 0 */
+  const float* x_base; const float* m0; const float* m1; const float* m2;           /* kind 1 */
+  float* e_t_out; float* pred_x0;                                                   /* kind 0 */
+  float* m_out;                                                                     /* kind 1 */
+  float* x_state_out; float* unet_dst0; float* unet_dst1;
+  float* tf_dst0; float* tf_dst1;
+  int32_t kind; int32_t cfg;
+  int32_t mode;                                                                     /* kind 0 */
+  int32_t form; int32_t m_self; int32_t data_prediction;                            /* kind 1 */
+  float scale; float t_next;
+  float a_t; float a_prev; float sigma; float sqrt_1m_at;                           /* kind 0 */
+  float alpha_t; float sigma_t; float c9[9];                                        /* kind 1 */
+  int32_t reserved;                 /* 0 */
+} sdmi_sampler_plan_slot;           /* 248 bytes */
+int sdmi_sampler_plan_rows(const sdmi_sampler_plan_slot* slots, int n_slots, int64_t n, void* stream);
+
 /* ---- ancestral DDPM step: LatentDiffusion.p_mean_variance + p_sample (ddpm.py:1047-1107) and the mask blend of p_sample_loop /
  * progressive_denoising (:1203-1205, :1154-1157) in one launch; fp32, each op rounded on its own in the reference's order:
  *   x0 = c_recip x - c_recipm1 eps;  clip != 0: x0 = clamp(x0, -1, 1) (a NaN stays NaN);  mean = coef1 x0 + coef2 x;

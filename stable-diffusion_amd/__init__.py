@@ -8,7 +8,7 @@ this package is the host-side mirror of the reference's interfaces for that path
     DDIMSamplerHIP    <- ldm.models.diffusion.ddim.DDIMSampler
     DPMSolverSamplerHIP <- ldm.models.diffusion.dpm_solver.sampler.DPMSolverSampler
     DPMSolverHIP      <- ldm.models.diffusion.dpm_solver.dpm_solver.DPM_Solver (every method, order, skip type and solver type)
-    SamplerPoolHIP    <- no counterpart: DDIM / PLMS requests that arrive one after another share UNet calls (sampler_pool.py)
+    SamplerPoolHIP    <- no counterpart: DDIM / PLMS / DPM-Solver requests that arrive one after another share UNet calls (sampler_pool.py)
     DDPMSamplerHIP    <- LatentDiffusion.p_sample_loop / progressive_denoising (scripts/sample_diffusion.py --vanilla_sample)
     AutoencoderKLHIP  <- ldm.models.autoencoder.AutoencoderKL (decode / encode)
     VQModelInterfaceHIP <- ldm.models.autoencoder.VQModelInterface (the latent-inpainting model's first stage)

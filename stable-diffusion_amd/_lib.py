@@ -80,6 +80,17 @@ class SamplerSlot(C.Structure):
                 ('reserved', C.c_int32)]
 
 
+class SamplerPlanSlot(C.Structure):
+    """sdmi_sampler_plan_slot (include/sdmi.h): one latent of an sdmi_sampler_plan_rows launch"""
+    _fields_ = [('eps_u', c_ptr), ('eps_c', c_ptr), ('x', c_ptr), ('old0', c_ptr), ('old1', c_ptr), ('old2', c_ptr), ('noise', c_ptr),
+                ('x_base', c_ptr), ('m0', c_ptr), ('m1', c_ptr), ('m2', c_ptr), ('e_t_out', c_ptr), ('pred_x0', c_ptr), ('m_out', c_ptr),
+                ('x_state_out', c_ptr), ('unet_dst0', c_ptr), ('unet_dst1', c_ptr), ('tf_dst0', c_ptr), ('tf_dst1', c_ptr),
+                ('kind', C.c_int32), ('cfg', C.c_int32), ('mode', C.c_int32), ('form', C.c_int32), ('m_self', C.c_int32),
+                ('data_prediction', C.c_int32), ('scale', C.c_float), ('t_next', C.c_float), ('a_t', C.c_float), ('a_prev', C.c_float),
+                ('sigma', C.c_float), ('sqrt_1m_at', C.c_float), ('alpha_t', C.c_float), ('sigma_t', C.c_float), ('c9', C.c_float * 9),
+                ('reserved', C.c_int32)]
+
+
 _SIGS = {
     'sdmi_last_error': (C.c_char_p, []),
     'sdmi_abi_version': (C.c_int, []),
@@ -110,6 +121,7 @@ _SIGS = {
                                        c_ptr, c_ptr, C.c_int64, c_ptr]),
     'sdmi_sampler_step_from_x0': (C.c_int, [c_ptr, c_ptr, C.c_float, C.c_float, c_ptr, c_ptr, C.c_int64, c_ptr]),
     'sdmi_sampler_step_rows': (C.c_int, [C.POINTER(SamplerSlot), C.c_int, C.c_int64, c_ptr]),
+    'sdmi_sampler_plan_rows': (C.c_int, [C.POINTER(SamplerPlanSlot), C.c_int, C.c_int64, c_ptr]),
     'sdmi_ddpm_step': (C.c_int, [c_ptr, c_ptr, c_ptr, C.c_float, C.c_float, C.c_int, C.c_float, C.c_float, C.c_float, c_ptr, c_ptr,
                                  c_ptr, c_ptr, C.c_float, C.c_float, c_ptr, c_ptr, C.c_int64, c_ptr]),
     'sdmi_dpm_solver_step': (C.c_int, [c_ptr, C.c_int, C.c_float, c_ptr, c_ptr, C.c_float, C.c_float, C.c_float, C.c_float,

@@ -186,6 +186,10 @@ int sdmi_sampler_step_rows(const sdmi_sampler_slot* slots, int n_slots, int64_t 
   return launch_sampler_step_rows(slots, n_slots, n, (hipStream_t)stream);
 }
 
+int sdmi_sampler_plan_rows(const sdmi_sampler_plan_slot* slots, int n_slots, int64_t n, void* stream) {
+  return launch_sampler_plan_rows(slots, n_slots, n, (hipStream_t)stream);
+}
+
 int sdmi_ddpm_step(const float* eps, const float* x0_in, const float* x, float c_recip, float c_recipm1, int clip, float coef1,
                    float coef2, float s, const float* noise, const float* mask, const float* x0_orig, const float* q_noise, float sa,
                    float s1ma, float* x0_out, float* x_prev, int64_t n, void* stream) {

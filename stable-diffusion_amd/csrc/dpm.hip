@@ -6,6 +6,7 @@
 // them with the reference's own torch ops (samplers.py); a subtraction of c * v arrives as the addition of (-c) * v, which is exact.
 #include "common.h"
 #include "prof.h"
+#include "step_math.h"
 #include <math.h>
 
 #pragma clang fp contract(off)
@@ -21,19 +22,9 @@ __global__ void __launch_bounds__(256) dpm_model_value_kernel(DpmModelValueParam
 #pragma clang fp contract(off)
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= p.n) return;
-  float e;
-  if (p.cfg) {
-    const float eu = p.eps_model[i], ec = p.eps_model[p.n + i];
-    const float d = ec - eu;
-    const float sd = p.scale * d;
-    e = eu + sd;                                     // e_u + s * (e_c - e_u)
-  } else {
-    e = p.eps_model[i];
-  }
+  const float e = p.cfg ? cfg_combine(p.eps_model[i], p.eps_model[p.n + i], p.scale) : p.eps_model[i];
   if (!p.predict_x0) { p.out[i] = e; return; }
-  const float se = p.sigma_s * e;
-  const float num = p.x[i] - se;
-  float x0 = num / p.alpha_s;
+  float x0 = dpm_data_prediction(p.x[i], e, p.sigma_s, p.alpha_s);
   if (p.s) {
     const float sv = p.s[i / p.row];
     const float lo = -sv;
@@ -63,40 +54,9 @@ __global__ void __launch_bounds__(256) dpm_update_kernel(DpmUpdateParams p) {
 #pragma clang fp contract(off)
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= p.n) return;
-  const float m0 = p.m0[i];
-  const float t0 = p.c[0] * p.x[i];
-  const float t1 = p.c[1] * m0;
-  float xt = t0 + t1;
-  if (p.form == 1) {
-    const float d = p.m1[i] - p.m2[i];
-    const float D = p.c[3] * d;
-    const float t2 = p.c[2] * D;
-    xt = xt + t2;
-  } else if (p.form == 2) {
-    const float a = p.m1[i] - m0, b = p.m2[i] - m0;
-    const float d10 = p.c[4] * a, d11 = p.c[5] * b;
-    const float u = p.c[6] * d10, v = p.c[7] * d11;
-    const float uv = u - v;
-    const float D1 = uv / p.c[8];
-    const float w = d11 - d10;
-    const float w2 = 2.f * w;
-    const float D2 = w2 / p.c[8];
-    const float t2 = p.c[2] * D1, t3 = p.c[3] * D2;
-    xt = xt + t2;
-    xt = xt + t3;
-  } else if (p.form == 3) {
-    const float m1 = p.m1[i];
-    const float a = m0 - m1, b = m1 - p.m2[i];
-    const float d10 = p.c[4] * a, d11 = p.c[5] * b;
-    const float dd = d10 - d11;
-    const float q = p.c[6] * dd;
-    const float D1 = d10 + q;
-    const float D2 = p.c[7] * dd;
-    const float t2 = p.c[2] * D1, t3 = p.c[3] * D2;
-    xt = xt + t2;
-    xt = xt + t3;
-  }
-  p.out[i] = xt;
+  const float m1 = p.form != 0 ? p.m1[i] : 0.f;
+  const float m2 = p.form != 0 ? p.m2[i] : 0.f;
+  p.out[i] = dpm_update_of(p.form, p.c, p.x[i], p.m0[i], m1, m2);
 }
 
 // Dynamic-thresholding scale (:395-397): s[b] = max(quantile_0.995(|x0[b]|), max_val).  The two order statistics k_lo <= k_hi the

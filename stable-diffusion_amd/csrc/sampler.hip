@@ -8,6 +8,7 @@
 #include "common.h"
 #include "prof.h"
 #include "sampler_rows.h"
+#include "step_math.h"
 #include <math.h>
 
 // every product / sum below must round on its own, exactly like the reference's separate torch ops
@@ -24,14 +25,7 @@ inline StepScalars step_scalars(float a_t, float a_prev, float sigma) {
 }
 
 // The arithmetic of one element, shared by every kernel of the step (the whole launch, its two halves, the per-slot launch): each helper
-// is one expression of the reference, op by op.
-__device__ __forceinline__ float cfg_combine(float eu, float ec, float scale) {
-#pragma clang fp contract(off)
-  const float d = ec - eu;
-  const float sd = scale * d;
-  return eu + sd;                                    // e_u + s * (e_c - e_u)
-}
-
+// is one expression of the reference, op by op (cfg_combine: step_math.h).
 __device__ __forceinline__ float multistep_eps(int mode, float e_t, float o0, float o1, float o2) {
 #pragma clang fp contract(off)
   switch (mode) {
@@ -127,9 +121,9 @@ template <int V> __device__ __forceinline__ void store_elems(float* p, int64_t i
 }
 
 // elements [i, i + V) of one slot; every input is read before the first output is written, so x_state_out may be x
-template <int V> __device__ __forceinline__ void rows_elems(const RowSlot& r, int64_t i) {
+// (D: sdmi_sampler_slot, or the descriptor of sdmi_sampler_plan_rows, whose kind 0 has the same fields)
+template <int V, class D> __device__ __forceinline__ void rows_elems(const D& d, float sqrt_at, float sqrt_aprev, float dir_coef, int64_t i) {
 #pragma clang fp contract(off)
-  const sdmi_sampler_slot& d = r.d;
   float e_t[V], x[V], o0[V] = {}, o1[V] = {}, o2[V] = {}, nz[V] = {};
   load_elems<V>(d.eps_u, i, e_t);
   if (d.cfg) {
@@ -152,8 +146,8 @@ template <int V> __device__ __forceinline__ void rows_elems(const RowSlot& r, in
 #pragma unroll
   for (int k = 0; k < V; ++k) {
     const float ep = multistep_eps(d.mode, e_t[k], o0[k], o1[k], o2[k]);
-    pred[k] = pred_x0_of(x[k], ep, d.sqrt_1m_at, r.sqrt_at);
-    xp[k] = x_prev_of(pred[k], ep, r.sqrt_aprev, r.dir_coef, nz[k]);
+    pred[k] = pred_x0_of(x[k], ep, d.sqrt_1m_at, sqrt_at);
+    xp[k] = x_prev_of(pred[k], ep, sqrt_aprev, dir_coef, nz[k]);
   }
   if (d.e_t_out) store_elems<V>(d.e_t_out, i, e_t);
   if (d.pred_x0) store_elems<V>(d.pred_x0, i, pred);
@@ -170,9 +164,82 @@ __global__ void __launch_bounds__(256) sampler_step_rows_kernel(RowsParams p) {
     if (r.d.t_dst1) *r.d.t_dst1 = r.d.t_next;
   }
   if (r.vec) {
-    if (lane * 4 < p.n) rows_elems<4>(r, lane * 4);
+    if (lane * 4 < p.n) rows_elems<4>(r.d, r.sqrt_at, r.sqrt_aprev, r.dir_coef, lane * 4);
   } else {
-    if (lane < p.n) rows_elems<1>(r, lane);
+    if (lane < p.n) rows_elems<1>(r.d, r.sqrt_at, r.sqrt_aprev, r.dir_coef, lane);
+  }
+}
+
+// The same launch shape for slots of two kinds (sdmi_sampler_plan_rows): kind 0 is the step above, field for field; kind 1 is one model
+// evaluation of a DPM-Solver plan with the update that follows it -- the model value of dpm_model_value_kernel, then one form of
+// dpm_update_kernel whose operands named in m_self are that value, taken from registers.  Both kinds hand the next call its timestep as
+// fp32, so PLMS / DDIM and DPM-Solver rows share one call.  The arithmetic is the helpers' the lone kernels call: nothing is restated.
+struct PlanSlot {
+  sdmi_sampler_plan_slot d;
+  float sqrt_at, sqrt_aprev, dir_coef;               // kind 0: step_scalars() of the slot's table entries
+  int vec;
+};
+struct PlanParams {
+  PlanSlot slot[SDMI_SAMPLER_MAX_SLOTS];
+  int64_t n;
+};
+static_assert(sizeof(PlanParams) <= 4096, "sampler_plan_rows: the descriptors travel in the kernel arguments (HIP's limit is 4096 bytes)");
+
+// elements [i, i + V) of a kind 1 slot; every input is read before the first output is written, so x_state_out may be x_base or x
+template <int V> __device__ __forceinline__ void plan_dpm_elems(const sdmi_sampler_plan_slot& d, int64_t i) {
+#pragma clang fp contract(off)
+  float m[V], xb[V] = {}, m0[V] = {}, m1[V] = {}, m2[V] = {};
+  load_elems<V>(d.eps_u, i, m);
+  if (d.cfg) {
+    float ec[V];
+    load_elems<V>(d.eps_c, i, ec);
+#pragma unroll
+    for (int k = 0; k < V; ++k) m[k] = cfg_combine(m[k], ec[k], d.scale);
+  }
+  if (d.data_prediction) {
+    float x[V];
+    load_elems<V>(d.x, i, x);
+#pragma unroll
+    for (int k = 0; k < V; ++k) m[k] = dpm_data_prediction(x[k], m[k], d.sigma_t, d.alpha_t);
+  }
+  if (d.form >= 0) {
+    load_elems<V>(d.x_base, i, xb);
+    if (!(d.m_self & 1)) load_elems<V>(d.m0, i, m0);
+    if (d.form != 0) {
+      if (!(d.m_self & 2)) load_elems<V>(d.m1, i, m1);
+      if (!(d.m_self & 4)) load_elems<V>(d.m2, i, m2);
+    }
+  }
+  float out[V];
+#pragma unroll
+  for (int k = 0; k < V; ++k) {
+    const float a0 = (d.m_self & 1) ? m[k] : m0[k];
+    const float a1 = (d.m_self & 2) ? m[k] : m1[k];
+    const float a2 = (d.m_self & 4) ? m[k] : m2[k];
+    out[k] = d.form >= 0 ? dpm_update_of(d.form, d.c9, xb[k], a0, a1, a2) : m[k];     // no update: the slot's result is the model value
+  }
+  if (d.m_out) store_elems<V>(d.m_out, i, m);
+  if (d.x_state_out) store_elems<V>(d.x_state_out, i, out);
+  if (d.unet_dst0) store_elems<V>(d.unet_dst0, i, out);     // the slot's row(s) of the next UNet call's input
+  if (d.unet_dst1) store_elems<V>(d.unet_dst1, i, out);
+}
+
+template <int V> __device__ __forceinline__ void plan_elems(const PlanSlot& r, int64_t i) {
+  if (r.d.kind == 0) rows_elems<V>(r.d, r.sqrt_at, r.sqrt_aprev, r.dir_coef, i);
+  else plan_dpm_elems<V>(r.d, i);
+}
+
+__global__ void __launch_bounds__(256) sampler_plan_rows_kernel(PlanParams p) {
+  const PlanSlot& r = p.slot[blockIdx.y];
+  const int64_t lane = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (lane == 0) {                                   // the slot's timestep in the next call's fp32 timestep tensor: one lane, plain stores
+    if (r.d.tf_dst0) *r.d.tf_dst0 = r.d.t_next;
+    if (r.d.tf_dst1) *r.d.tf_dst1 = r.d.t_next;
+  }
+  if (r.vec) {
+    if (lane * 4 < p.n) plan_elems<4>(r, lane * 4);
+  } else {
+    if (lane < p.n) plan_elems<1>(r, lane);
   }
 }
 
@@ -361,6 +428,66 @@ int launch_sampler_step_rows(const sdmi_sampler_slot* slots, int n_slots, int64_
   const int64_t lanes = all_vec ? n / 4 : n;         // one grid for all slots: a 16-byte slot's surplus blocks return at once
   ProfScope ps("sampler_step_rows", 0.0, (double)n * 4.0 * 7.0 * n_slots, s);
   SDMI_LAUNCH(sampler_step_rows_kernel, dim3((unsigned)((lanes + 255) / 256), (unsigned)n_slots), dim3(256), 0, s, p);
+  SDMI_HIP_OK(hipGetLastError());
+  return 0;
+}
+
+int launch_sampler_plan_rows(const sdmi_sampler_plan_slot* slots, int n_slots, int64_t n, hipStream_t s) {
+  SDMI_CHECK(slots && n_slots >= 1, "sampler_plan_rows: no slots");
+  SDMI_CHECK(n_slots <= SDMI_SAMPLER_MAX_SLOTS, "sampler_plan_rows: more than SDMI_SAMPLER_MAX_SLOTS (8) slots");
+  SDMI_CHECK(n > 0 && n <= (int64_t)0x7fffffff * 256, "sampler_plan_rows: n");
+  PlanParams p = PlanParams();
+  p.n = n;
+  bool all_vec = true;
+  for (int k = 0; k < n_slots; ++k) {
+    const sdmi_sampler_plan_slot& d = slots[k];
+    const std::string at = " (slot " + std::to_string(k) + ")";
+    PlanSlot& r = p.slot[k];
+    r.d = d;
+    r.d.reserved = 0;
+    sdmi_sampler_plan_slot& q = r.d;                 // what the kernel reads: the pointers the slot's kind and form do not read are cleared
+    SDMI_CHECK(d.kind == 0 || d.kind == 1, "sampler_plan_rows: kind" + at);
+    SDMI_CHECK(d.eps_u && (!d.cfg || d.eps_c), "sampler_plan_rows: missing pointer" + at);
+    if (!d.cfg) q.eps_c = nullptr;                   // (eps_u alone is read)
+    if (d.kind == 0) {
+      SDMI_CHECK(d.x, "sampler_plan_rows: missing pointer" + at);
+      SDMI_CHECK(d.e_t_out || d.x_state_out || d.pred_x0 || d.unet_dst0 || d.unet_dst1, "sampler_plan_rows: missing pointer: no output" + at);
+      SDMI_CHECK(d.mode >= 0 && d.mode <= 4, "sampler_plan_rows: mode" + at);
+      SDMI_CHECK(d.mode == 0 || d.old0, "sampler_plan_rows: history missing" + at);
+      SDMI_CHECK(d.mode != 2 && d.mode != 3 || d.old1, "sampler_plan_rows: history missing" + at);
+      SDMI_CHECK(d.mode != 3 || d.old2, "sampler_plan_rows: history missing" + at);
+      const StepScalars c = step_scalars(d.a_t, d.a_prev, d.sigma);
+      r.sqrt_at = c.sqrt_at; r.sqrt_aprev = c.sqrt_aprev; r.dir_coef = c.dir_coef;
+      q.x_base = q.m0 = q.m1 = q.m2 = nullptr; q.m_out = nullptr;
+      q.form = -1; q.m_self = 0; q.data_prediction = 0;
+    } else {
+      SDMI_CHECK(d.form >= -1 && d.form <= 3, "sampler_plan_rows: form" + at);
+      SDMI_CHECK(!d.data_prediction || d.x, "sampler_plan_rows: missing pointer: the data prediction needs x" + at);
+      const int reads = d.form < 0 ? 0 : (d.form == 0 ? 1 : 7);       // the operands of m0..m2 the form reads, as a mask
+      SDMI_CHECK(d.m_self >= 0 && (d.m_self & ~reads) == 0, "sampler_plan_rows: m_self names an operand the form does not read" + at);
+      SDMI_CHECK(d.form < 0 || d.x_base, "sampler_plan_rows: missing pointer: x_base" + at);
+      const float* const ms[3] = {d.m0, d.m1, d.m2};
+      for (int j = 0; j < 3; ++j)
+        SDMI_CHECK(!((reads & ~d.m_self) >> j & 1) || ms[j], "sampler_plan_rows: missing pointer: a model value of the update" + at);
+      SDMI_CHECK(d.m_out || d.x_state_out || d.unet_dst0 || d.unet_dst1, "sampler_plan_rows: missing pointer: no output" + at);
+      if (!d.data_prediction) q.x = nullptr;
+      if (d.form < 0) q.x_base = nullptr;
+      if (!((reads & ~d.m_self) & 1)) q.m0 = nullptr;
+      if (!((reads & ~d.m_self) & 2)) q.m1 = nullptr;
+      if (!((reads & ~d.m_self) & 4)) q.m2 = nullptr;
+      q.old0 = q.old1 = q.old2 = q.noise = nullptr; q.e_t_out = q.pred_x0 = nullptr;
+      q.mode = 0;
+    }
+    const void* ptrs[] = {q.eps_u, q.eps_c, q.x, q.old0, q.old1, q.old2, q.noise, q.x_base, q.m0, q.m1, q.m2, q.e_t_out, q.pred_x0, q.m_out,
+                          q.x_state_out, q.unet_dst0, q.unet_dst1};
+    uintptr_t bits = (uintptr_t)(n % 4);
+    for (const void* v : ptrs) bits |= (uintptr_t)v & 15;    // (a null pointer is aligned)
+    r.vec = bits == 0;
+    all_vec = all_vec && r.vec;
+  }
+  const int64_t lanes = all_vec ? n / 4 : n;         // one grid for all slots: a 16-byte slot's surplus blocks return at once
+  ProfScope ps("sampler_plan_rows", 0.0, (double)n * 4.0 * 7.0 * n_slots, s);
+  SDMI_LAUNCH(sampler_plan_rows_kernel, dim3((unsigned)((lanes + 255) / 256), (unsigned)n_slots), dim3(256), 0, s, p);
   SDMI_HIP_OK(hipGetLastError());
   return 0;
 }

@@ -7,4 +7,6 @@
 
 namespace sdmi {
 int launch_sampler_step_rows(const sdmi_sampler_slot* slots, int n_slots, int64_t n, hipStream_t s);
+// ... and for slots of two kinds, that step or one evaluation of a DPM-Solver plan with its update, the next timestep written as fp32
+int launch_sampler_plan_rows(const sdmi_sampler_plan_slot* slots, int n_slots, int64_t n, hipStream_t s);
 }  // namespace sdmi

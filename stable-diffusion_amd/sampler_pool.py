@@ -10,12 +10,16 @@ is the UNet call plus one launch with no host-to-device copy; which rows the nex
 deterministic (`plan_calls`).
 
 Per slot the arithmetic is `sdmi_sampler_step`'s, so a request's samples and intermediates are, with a model whose rows are independent
-(every UNet here), the bits of the same request run alone -- up to what the UNet's own kernels make of another row count."""
+(every UNet here), the bits of the same request run alone -- up to what the UNet's own kernels make of another row count.
+
+`SamplerPoolHIP(..., timesteps='float32')` is a pool whose calls carry fp32 timesteps -- the UNet embeds (float)t either way, so an integer
+timestep handed over as fp32 gives the same bits -- and whose launch is `sdmi_sampler_plan_rows`: a slot is that PLMS / DDIM step, or one
+model evaluation of a DPM-Solver plan (`DPMSolverHIP.plan`) with the update that follows it.  Such a pool also takes `sampler='dpm'`."""
 import numpy as np
 import torch
 
 from . import _lib
-from .samplers import make_ddim_timesteps, make_tables, plms_plan
+from .samplers import DPMSolverHIP, _DiscreteVP, make_ddim_timesteps, make_tables, plms_plan
 
 
 # ---- the plan: pure host code, no GPU and no library ------------------------------------------------------------------------------
@@ -26,10 +30,59 @@ def request_timesteps(S, num_timesteps=1000, ddim_discretize='uniform', t_start=
     return ts if t_start is None else ts[:t_start]
 
 
-def request_evals(sampler, timesteps):
+DPM_POOL_KEYWORDS = ('method', 'order', 'skip_type', 'predict_x0', 't_start', 't_end', 'lower_order_final', 'denoise_to_zero', 'solver_type')
+
+
+def dpm_request_plan(alphas_cumprod, S, plan=None, **kw):
+    """-> (DPMPlan, predict_x0) of a sampler='dpm' request: the given `plan`, or DPMSolverHIP.plan with the keywords of
+    DPMSolverSamplerHIP.sample and its values for the rest (steps = S, predict_x0 = True, 'multistep', order 2, 'time_uniform',
+    lower_order_final).  Refused: what has no plan (adaptive), what sits between a model value and its update (thresholding), and whatever
+    DPMSolverHIP.plan refuses."""
+    if kw.get('method') == 'adaptive':
+        raise NotImplementedError("method='adaptive': its number of evaluations depends on the data, so there is no plan to share calls by")
+    if kw.pop('thresholding', False):
+        raise NotImplementedError('thresholding=True: the per-sample quantile sits between the model value and the update of one slot')
+    unknown = sorted(k for k in kw if k not in DPM_POOL_KEYWORDS)
+    if unknown:
+        raise TypeError(f"sampler='dpm' takes {', '.join(DPM_POOL_KEYWORDS)} and plan; got {', '.join(unknown)}")
+    predict_x0 = bool(kw.pop('predict_x0', True))
+    if plan is not None:
+        if any(v is not None for v in kw.values()):
+            raise TypeError(f'plan= is a whole run: it goes with predict_x0 alone, not with {", ".join(sorted(kw))}')
+        return plan, predict_x0
+    if alphas_cumprod is None:
+        raise ValueError("a sampler='dpm' request without a plan needs the schedule: pass alphas_cumprod")
+    opts = dict(steps=int(S), order=2, skip_type='time_uniform', method='multistep', lower_order_final=True)
+    opts.update({k: v for k, v in kw.items() if not (k in ('t_start', 't_end') and v is None)})
+    ac = alphas_cumprod if torch.is_tensor(alphas_cumprod) else torch.as_tensor(np.asarray(alphas_cumprod))
+    return DPMSolverHIP(None, _DiscreteVP(ac), predict_x0=predict_x0).plan(**opts), predict_x0
+
+
+def dpm_plan_pairs(plan):
+    """[(k, k + 1 or None)]: every model evaluation of a DPMPlan with the index of the update that follows it (None after the last
+    evaluation of denoise_to_zero).  A plan alternates evaluation, update, ...; each evaluation but the first is at the state the update
+    before it wrote -- what lets one slot run the pair and feed the next call."""
+    ops, pairs, k = plan.ops, [], 0
+    while k < len(ops):
+        upd = k + 1 if k + 1 < len(ops) else None
+        if int(ops[k][0]) != 0 or (upd is not None and int(ops[upd][0]) != 1):
+            raise ValueError(f'the plan does not alternate evaluation and update at op {k}')
+        if pairs and int(ops[k][3]) != int(ops[k - 1][2]):
+            raise ValueError(f'the evaluation at op {k} is not at the state the update before it wrote')
+        pairs.append((k, upd))
+        k += 2
+    if not pairs:
+        raise ValueError('the plan has no model evaluation')
+    return pairs
+
+
+def request_evals(sampler, timesteps, plan=None):
     """[(t, mode, index, phase)], one per UNet evaluation of a request: the DDIM time range (ddim.py:141-146, mode 0), or plms_plan with
     its first step as the two evaluations it is -- the Euler predictor (t, 0, index, 0), which only feeds the next call, and the corrector
-    (t_next, 4, index, 1) (plms.py:218-226)."""
+    (t_next, 4, index, 1) (plms.py:218-226).  sampler='dpm' (timesteps unused): the evaluations of the DPMPlan `plan`, each
+    (t_input, form of the update that follows or -1, evaluation number, 0)."""
+    if sampler == 'dpm':
+        return [(float(plan.coef[k][1]), -1 if u is None else int(plan.ops[u][1]), j, 0) for j, (k, u) in enumerate(dpm_plan_pairs(plan))]
     timesteps = np.asarray(timesteps)
     if sampler == 'plms':
         out = []
@@ -84,11 +137,12 @@ class _Queue:
         return left
 
 
-def plan_calls(requests, max_rows=8, num_timesteps=1000):
+def plan_calls(requests, max_rows=8, num_timesteps=1000, alphas_cumprod=None):
     """The UNet calls a pool of `max_rows` rows makes for `requests`, each a dict(ticket, S, sampler='ddim', samples=1, guided=False,
     ddim_discretize='uniform', t_start=None, arrival=0); `arrival` is the number of calls the pool had made when the request was
     submitted (a request submitted to an idle pool arrives at once).  -> one list per call of (ticket, sample, t, mode, index, phase), a
-    guided sample's row twice ([uncond, cond])."""
+    guided sample's row twice ([uncond, cond]).  A sampler='dpm' request carries `plan` (a DPMPlan), or S and the keywords of
+    dpm_request_plan over `alphas_cumprod`; its rows are (ticket, sample, t_input, form of the following update or -1, evaluation, 0)."""
     pending = sorted(((int(r.get('arrival', 0)), k, r) for k, r in enumerate(requests)), key=lambda a: a[:2])
     q, calls = _Queue(max_rows), []
     while pending or q.waiting or q.active:
@@ -96,8 +150,13 @@ def plan_calls(requests, max_rows=8, num_timesteps=1000):
             pending[0] = (len(calls),) + pending[0][1:]           # the pool idles until the next request
         while pending and pending[0][0] <= len(calls):
             r = pending.pop(0)[2]
-            ts = request_timesteps(r['S'], num_timesteps, r.get('ddim_discretize', 'uniform'), r.get('t_start'))
-            e = _Entry(r['ticket'], r.get('samples', 1), r.get('guided', False), request_evals(r.get('sampler', 'ddim'), ts))
+            if r.get('sampler', 'ddim') == 'dpm':
+                plan = dpm_request_plan(alphas_cumprod, r.get('S'), r.get('plan'), **{k: r[k] for k in DPM_POOL_KEYWORDS + ('thresholding',) if k in r})[0]
+                evals = request_evals('dpm', None, plan)
+            else:
+                ts = request_timesteps(r['S'], num_timesteps, r.get('ddim_discretize', 'uniform'), r.get('t_start'))
+                evals = request_evals(r.get('sampler', 'ddim'), ts)
+            e = _Entry(r['ticket'], r.get('samples', 1), r.get('guided', False), evals)
             if e.rows > max_rows:
                 raise ValueError(f'request {e.ticket!r} needs {e.rows} rows, the pool has {max_rows}: it can never fit')
             q.waiting.append(e)
@@ -109,8 +168,8 @@ def plan_calls(requests, max_rows=8, num_timesteps=1000):
 
 # ---- the pool -------------------------------------------------------------------------------------------------------------------------
 class SamplerPoolHIP(object):
-    """SamplerPoolHIP(model, shape=(C, H, W), max_rows=UNetModelHIP.MAX_ROWS) over the `model` the samplers take (apply_model,
-    alphas_cumprod, betas, num_timesteps).
+    """SamplerPoolHIP(model, shape=(C, H, W), max_rows=UNetModelHIP.MAX_ROWS, timesteps='int64') over the `model` the samplers take
+    (apply_model, alphas_cumprod, betas, num_timesteps).
 
         ticket = pool.submit(S=50, conditioning=c, unconditional_conditioning=uc, unconditional_guidance_scale=7.5)
         pool.step()                 # one UNet evaluation of every active request: one apply_model, one sdmi_sampler_step_rows launch
@@ -118,9 +177,14 @@ class SamplerPoolHIP(object):
         samples, intermediates = pool.result(ticket)       # as sample() returns them
 
     A request without a `generator` gets one of its own, seeded from torch's default generator at submit: what its neighbours in a call
-    draw never changes its draws."""
+    draw never changes its draws.
 
-    def __init__(self, model, shape, max_rows=None):
+    timesteps='float32': every call carries fp32 timesteps and every step is one sdmi_sampler_plan_rows launch; 'ddim' and 'plms' requests
+    run as in the default pool, and sampler='dpm' is taken too -- S model evaluations of DPM-Solver++(2M) by default, or what the keywords of
+    DPMSolverSamplerHIP.sample (DPM_POOL_KEYWORDS; t_start is DPM-Solver's float time there) or a ready `plan=` say; result() gives
+    (x, None), an img_callback receives the model value and the evaluation number.  The dtype is the pool's for good, like its shape."""
+
+    def __init__(self, model, shape, max_rows=None, timesteps='int64'):
         from .unet import UNetModelHIP
         self.model = model
         self.shape = tuple(int(s) for s in shape)
@@ -129,6 +193,10 @@ class SamplerPoolHIP(object):
         self.max_rows = int(UNetModelHIP.MAX_ROWS if max_rows is None else max_rows)
         if self.max_rows < 1:
             raise ValueError('max_rows must be at least 1')
+        if timesteps not in ('int64', 'float32'):
+            raise ValueError(f"timesteps={timesteps!r}: 'int64' or 'float32'")
+        self.timesteps = timesteps
+        self._float = timesteps == 'float32'
         self.n = int(np.prod(self.shape))
         self._q = _Queue(self.max_rows)
         self._ac = None
@@ -161,7 +229,7 @@ class SamplerPoolHIP(object):
     # ---- submit -------------------------------------------------------------------------------------------------------------------------
     def submit(self, S, conditioning, unconditional_conditioning=None, unconditional_guidance_scale=1., eta=0., x_T=None, sampler='ddim',
                ddim_discretize='uniform', t_start=None, generator=None, img_callback=None, log_every_t=100, mask=None, x0=None,
-               quantize_x0=False, score_corrector=None):
+               quantize_x0=False, score_corrector=None, plan=None, **dpm_keywords):
         if mask is not None or x0 is not None:
             raise NotImplementedError('mask / x0 (the inpainting blend draws q_sample noise between the steps) is not implemented in the pool')
         if quantize_x0:
@@ -170,10 +238,17 @@ class SamplerPoolHIP(object):
             raise NotImplementedError('score_corrector is not implemented here (the reference ships no corrector)')
         if isinstance(conditioning, dict) or isinstance(unconditional_conditioning, dict):
             raise NotImplementedError('dict conditioning (hybrid models) is not implemented in the pool')
-        if sampler == 'dpm':
+        if sampler == 'dpm' and not self._float:
             raise NotImplementedError("sampler='dpm': DPM-Solver's float timesteps cannot share a call with integer ones")
-        if sampler not in ('ddim', 'plms'):
-            raise NotImplementedError(f"sampler={sampler!r}: 'ddim' or 'plms'")
+        if sampler not in ('ddim', 'plms', 'dpm'):
+            raise NotImplementedError(f"sampler={sampler!r}: 'ddim' or 'plms'" + (" or 'dpm'" if self._float else ''))
+        if sampler != 'dpm' and (plan is not None or dpm_keywords):
+            raise TypeError(f"{', '.join(sorted(dpm_keywords) or ['plan'])}: keywords of sampler='dpm'")
+        if sampler == 'dpm' and eta != 0:
+            raise ValueError('eta must be 0 for DPM-Solver')
+        dpm = None
+        if sampler == 'dpm':             # (refuses adaptive, thresholding and what DPMSolverHIP.plan refuses: host code only)
+            dpm = dpm_request_plan(self.model.alphas_cumprod, S, plan, t_start=t_start, **dpm_keywords)
         if sampler == 'plms' and eta != 0:
             raise ValueError('eta must be 0 for PLMS')
         if sampler == 'plms' and t_start is not None:
@@ -187,7 +262,7 @@ class SamplerPoolHIP(object):
             raise ValueError(f'unconditional_conditioning {tuple(uc.shape)} does not match conditioning {tuple(conditioning.shape)}')
         if x_T is not None and tuple(x_T.shape) != (b,) + self.shape:
             raise ValueError(f'shape {tuple(x_T.shape)} is not the pool\'s: x_T must be [{b}, {", ".join(map(str, self.shape))}]')
-        if t_start is not None and x_T is None:
+        if t_start is not None and x_T is None and sampler != 'dpm':
             raise ValueError('t_start decodes a given latent: pass it as x_T')
         tokens = tuple(int(s) for s in conditioning.shape[1:])
         if self._tokens is not None and tokens != tuple(self._tokens):
@@ -195,10 +270,14 @@ class SamplerPoolHIP(object):
         rows = b * (2 if guided else 1)
         if rows > self.max_rows:
             raise ValueError(f'the request needs {rows} rows, the pool has {self.max_rows}: it can never fit')
-        ddim_timesteps = make_ddim_timesteps(S, self.model.num_timesteps, ddim_discretize)
-        timesteps = ddim_timesteps if t_start is None else ddim_timesteps[:t_start]
-        if timesteps.shape[0] < 1:
-            raise ValueError('the request has no steps')
+        if dpm is None:
+            ddim_timesteps = make_ddim_timesteps(S, self.model.num_timesteps, ddim_discretize)
+            timesteps = ddim_timesteps if t_start is None else ddim_timesteps[:t_start]
+            if timesteps.shape[0] < 1:
+                raise ValueError('the request has no steps')
+            evals = request_evals(sampler, timesteps)
+        else:
+            evals = request_evals('dpm', None, dpm[0])
         self._check_device([conditioning, self.model.betas] + ([uc] if guided else []) + ([x_T] if x_T is not None else []))
         device = self.model.betas.device
 
@@ -206,10 +285,12 @@ class SamplerPoolHIP(object):
             ac = self.model.alphas_cumprod
             assert ac.shape[0] == self.model.num_timesteps, 'alphas have to be defined for each timestep'
             self._ac = ac.detach().to(torch.float32).cpu().numpy()
-        r = _Entry(self._next_ticket, b, guided, request_evals(sampler, timesteps))
+        r = _Entry(self._next_ticket, b, guided, evals)
         self._next_ticket += 1
-        r.sampler, r.scale, r.eta, r.total = sampler, scale, float(eta), int(timesteps.shape[0])
-        r.tab = make_tables(self._ac, ddim_timesteps, eta)            # exactly the tables of _SamplerBase._tables
+        r.sampler, r.scale, r.eta, r.total = sampler, scale, float(eta), len(evals)
+        if dpm is None:
+            r.total = int(timesteps.shape[0])
+            r.tab = make_tables(self._ac, ddim_timesteps, eta)        # exactly the tables of _SamplerBase._tables
         if generator is None and (eta != 0 or x_T is None):
             generator = torch.Generator(device=device)
             generator.manual_seed(int(torch.randint(0, 2 ** 62, (1,)).item()))
@@ -223,6 +304,16 @@ class SamplerPoolHIP(object):
         r.c_rows = torch.stack([uc.detach().float(), cond], dim=1).reshape((2 * b,) + tokens).contiguous() if guided else cond.contiguous()
         r.img_callback, r.log_every_t = img_callback, int(log_every_t)
         r.old, r.ring, r.e_pred, r.noise = [], None, None, None
+        if dpm is not None:              # the plan's tensor slots are the request's state; slot 0 is the initial latent
+            r.plan, r.predict_x0 = dpm
+            r.pairs = dpm_plan_pairs(r.plan)
+            r.buf = {0: r.state}
+            r.last_use = {}
+            for k, op in enumerate(r.plan.ops):
+                for slot in op[3:]:
+                    r.last_use[int(slot)] = k
+            r.last_use[r.plan.result] = len(r.plan.ops)
+            r.intermediates = None
         self._tokens = tokens
         self._q.waiting.append(r)
         return r.ticket
@@ -231,7 +322,7 @@ class SamplerPoolHIP(object):
     def _allocate(self, device):
         self._lib = _lib.load()
         self._X = torch.zeros((self.max_rows,) + self.shape, device=device, dtype=torch.float32)
-        self._T = torch.zeros((self.max_rows,), device=device, dtype=torch.long)
+        self._T = torch.zeros((self.max_rows,), device=device, dtype=torch.float32 if self._float else torch.long)
         self._ctx = torch.zeros((self.max_rows,) + tuple(self._tokens), device=device, dtype=torch.float32)
 
     def _row_starts(self, active):
@@ -269,6 +360,56 @@ class SamplerPoolHIP(object):
                 e.ring = [torch.empty_like(e.state) for _ in range(4)]      # e_t history: three old ones and the one being written
         return entered
 
+    def _dpm_slots(self, e, eps, nxt_row, after):
+        """the kind 1 slots of a DPM request's current evaluation, one per sample: the model value at plan op k and the update at k + 1.
+        eps: the request's first row of the UNet output; nxt_row: its first row in the next call, None after its last evaluation"""
+        nb = self.n * 4
+        X, T = self._X.data_ptr(), self._T.data_ptr()
+        plan, per = e.plan, (2 if e.guided else 1)
+        k, u = e.pairs[e.cursor]
+        dst, xs = int(plan.ops[k][2]), int(plan.ops[k][3])
+        data = e.predict_x0 or int(plan.ops[k][1]) == 1
+        x_eval = e.buf[xs]
+        new = torch.empty_like(x_eval)
+        if u is None:                    # the slot's result is the model value itself
+            form, m_self, operands, m = -1, 0, [None] * 4, new
+            e.buf[dst] = new
+        else:
+            form, udst = int(plan.ops[u][1]), int(plan.ops[u][2])
+            names = [int(v) for v in plan.ops[u][3:]]
+            m_self = sum(1 << j for j, v in enumerate(names[1:]) if v == dst)
+            operands = [None if (v < 0 or v == dst) else e.buf[v] for v in names]
+            m = torch.empty_like(x_eval) if (e.last_use.get(dst, -1) > u or e.img_callback) else None
+            if e.last_use.get(dst, -1) > u:
+                e.buf[dst] = m
+            e.buf[udst] = new
+        out = []
+        for j in range(e.samples):
+            off = j * nb
+            at = lambda t: None if t is None else t.data_ptr() + off
+            s = _lib.SamplerPlanSlot()
+            s.kind, s.cfg, s.scale = 1, int(e.guided), e.scale
+            s.eps_u = eps + per * j * nb
+            s.eps_c = eps + (per * j + 1) * nb if e.guided else None
+            s.x, s.data_prediction = (at(x_eval) if data else None), int(data)
+            s.alpha_t, s.sigma_t = float(plan.coef[k][2]), float(plan.coef[k][3])
+            s.form, s.m_self = form, m_self
+            s.x_base, s.m0, s.m1, s.m2 = (at(t) for t in operands)
+            if u is not None:
+                s.c9 = (_lib.C.c_float * 9)(*[float(v) for v in plan.coef[u]])
+            s.m_out, s.x_state_out = at(None if m is new else m), at(new)
+            if nxt_row is not None:
+                d = nxt_row + per * j
+                s.t_next = e.evals[e.cursor + 1][0]
+                s.unet_dst0, s.tf_dst0 = X + d * nb, T + d * 4
+                if e.guided:
+                    s.unet_dst1, s.tf_dst1 = X + (d + 1) * nb, T + (d + 1) * 4
+            out.append(s)
+        ops = (k,) if u is None else (k, u)
+        freed = [slot for slot, last in e.last_use.items() if last in ops and slot in e.buf]
+        after.append((e, m, e.evals[e.cursor][2], freed))
+        return out
+
     # ---- one UNet evaluation of every active request ---------------------------------------------------------------------------------------
     @torch.no_grad()
     def step(self):
@@ -296,8 +437,14 @@ class SamplerPoolHIP(object):
                 r0 += e.rows
         n, nb = self.n, self.n * 4
         X, T, o = self._X.data_ptr(), self._T.data_ptr(), out.data_ptr()
-        slots, after, row = [], [], 0
+        Slot, t_bytes = (_lib.SamplerPlanSlot, 4) if self._float else (_lib.SamplerSlot, 8)
+        t_dst0, t_dst1 = ('tf_dst0', 'tf_dst1') if self._float else ('t_dst0', 't_dst1')
+        slots, after, after_dpm, row = [], [], [], 0
         for e in q.active:
+            if e.sampler == 'dpm':
+                slots += self._dpm_slots(e, o + row * nb, None if e.cursor + 1 == len(e.evals) else nxt[e.ticket], after_dpm)
+                row += e.rows
+                continue
             t, mode, index, phase = e.evals[e.cursor]
             per = 2 if e.guided else 1
             predictor = e.sampler == 'plms' and mode == 0
@@ -318,7 +465,7 @@ class SamplerPoolHIP(object):
             new_state = torch.empty_like(e.state) if log else e.own        # a logged x_prev is a tensor of its own
             pred = torch.empty_like(e.state) if (log or (e.img_callback and not predictor)) else None
             for j in range(e.samples):
-                s = _lib.SamplerSlot()
+                s = Slot()               # (a plan slot of kind 0 has these fields under these names)
                 off = j * nb
                 s.eps_u = o + (row + per * j) * nb
                 s.eps_c = o + (row + per * j + 1) * nb if e.guided else None
@@ -333,18 +480,21 @@ class SamplerPoolHIP(object):
                 s.pred_x0 = None if pred is None else pred.data_ptr() + off
                 if not last:
                     d = nxt[e.ticket] + per * j
-                    s.t_next = e.evals[e.cursor + 1][0]
-                    s.unet_dst0, s.t_dst0 = X + d * nb, T + d * 8
+                    s.t_next = e.evals[e.cursor + 1][0]                   # (an fp32 pool: float(int), exact below 2^24)
+                    s.unet_dst0 = X + d * nb
+                    setattr(s, t_dst0, T + d * t_bytes)
                     if e.guided:
-                        s.unet_dst1, s.t_dst1 = X + (d + 1) * nb, T + (d + 1) * 8
+                        s.unet_dst1 = X + (d + 1) * nb
+                        setattr(s, t_dst1, T + (d + 1) * t_bytes)
                 slots.append(s)
             after.append((e, predictor, mode, index, log, new_state, pred, e_out))
             row += e.rows
         stream = _lib.stream_ptr()
+        launch = self._lib.sdmi_sampler_plan_rows if self._float else self._lib.sdmi_sampler_step_rows
         for k in range(0, len(slots), _lib.SAMPLER_MAX_SLOTS):
             chunk = slots[k:k + _lib.SAMPLER_MAX_SLOTS]
-            arr = (_lib.SamplerSlot * len(chunk))(*chunk)
-            _lib.check(self._lib.sdmi_sampler_step_rows(arr, len(chunk), n, stream))
+            arr = (Slot * len(chunk))(*chunk)
+            _lib.check(launch(arr, len(chunk), n, stream))
 
         for (e, predictor, mode, index, log, new_state, pred, e_out) in after:
             if predictor:
@@ -359,9 +509,14 @@ class SamplerPoolHIP(object):
             if log:
                 e.intermediates['x_inter'].append(e.state)
                 e.intermediates['pred_x0'].append(pred)
+        for (e, m, number, freed) in after_dpm:
+            if e.img_callback:
+                e.img_callback(m, number)
+            for slot in freed:           # by last use, as DPMSolverHIP.run_plan frees them (the launch is queued on this stream)
+                del e.buf[slot]
         for e in q.advance():
-            self._results[e.ticket] = (e.state, e.intermediates)
-            e.ring = e.old = e.e_pred = e.noise = None
+            self._results[e.ticket] = (e.buf[e.plan.result], None) if e.sampler == 'dpm' else (e.state, e.intermediates)
+            e.ring = e.old = e.e_pred = e.noise = e.buf = None
         if not q.active:                 # idle: the next request finds no pinned K/V of rows that are gone
             self._layout = self._views = None
             unet = self._hip_unet()
